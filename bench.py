@@ -1,7 +1,15 @@
 #!/usr/bin/env python3
 """Benchmark of the Gibbs hot path: Gibbs samples/s (all chains) at N_obs=10000, K=32.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints one JSON line (``ms_per_step`` is
+the wall time of one timed step).  ``--dump-outputs DIR`` also writes the last timed step's
+pooled samples to DIR/samples.npy; the inputs and chain seeds are fixed, so two builds run
+with the same arguments can be compared output for output.  ``--full`` (one GPU) adds what
+the headline does not need: the CPU baseline of the reference loop and the ``extra`` block
+(more chains, the reference's own sizes, C4 / C5 sizes, single kernels, the reference surface
+end to end).
 
 A "step" is one complete pass of the hot path over the synthetic workload: every
 chain of this rank runs ``--iters`` (default 50000) Gibbs iterations -- on-device
@@ -44,9 +52,16 @@ def parse_args(argv=None):
     ap.add_argument("--chains-per-gpu", type=int, default=1)
     ap.add_argument("--n-obs", type=int, default=10000)
     ap.add_argument("--k", type=int, default=32)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what it does not need (one GPU only): "
+                         "the CPU baseline and the extras (more chains, other sizes and "
+                         "precisions, single kernels, the reference surface end to end)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the pooled samples of the last timed step to DIR/samples.npy "
+                         "(float64; a fixed, seeded subset of the iterations beyond 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-budget-s", type=float, default=12.0)
-    ap.add_argument("--no-extra", action="store_true")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the extras")
     ap.add_argument("--groups", type=int, default=0)
     ap.add_argument("--waves", type=int, default=0)
     ap.add_argument("--rank-timeout-s", type=float, default=1500.0,
@@ -60,7 +75,10 @@ def parse_args(argv=None):
     ap.add_argument("--dry-run-cpu", action="store_true",
                     help="rehearse the launch / rendezvous / pooling plumbing on the CPU with "
                          "gloo and a stand-in for the sampler; measures nothing")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 # ------------------------------------------------------------------------- launching
@@ -228,6 +246,24 @@ def cpu_baseline(problem, budget_s=12.0, chunk=1000):
     return out
 
 
+def dump_samples(pooled, out_dir, limit_bytes=64 * 10 ** 6):
+    """--dump-outputs: the pooled draws of the last timed step ([chains, iterations, k+1], what
+    a caller of the timed path receives) as out_dir/samples.npy in float64.  Beyond
+    ``limit_bytes`` only a fixed subset of the iterations is written (seed 0, in order), so that
+    two builds run with the same arguments still write the same elements."""
+    import torch
+    n_chains, T, k1 = pooled.shape
+    keep = min(T, limit_bytes // (n_chains * k1 * 8))
+    if keep < 1:
+        raise SystemExit(f"--dump-outputs: one iteration of {n_chains} chains exceeds {limit_bytes} bytes")
+    if keep < T:
+        idx = np.sort(np.random.default_rng(0).choice(T, keep, replace=False))
+        pooled = pooled.index_select(1, torch.from_numpy(idx).to(pooled.device))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "samples.npy"),
+            np.ascontiguousarray(pooled.cpu().numpy(), dtype=np.float64))
+
+
 class DryRunCtx:
     """--dry-run-cpu only: stands where pybmc_amd._lib.Context stands so that the launch,
     rendezvous and pooling code of this file and of pybmc_amd.chains can be rehearsed on a
@@ -367,6 +403,8 @@ def rank_main(args):
         infos = [None] * world
         dist.all_gather_object(infos, mine_info)
 
+    if rank == 0 and args.dump_outputs:
+        dump_samples(pooled, args.dump_outputs)
     if dry:
         # the pooled block must hold every global chain's stand-in values, in chain order
         want = chain_seeds(1, list(range(n_chains)))
@@ -411,14 +449,14 @@ def rank_main(args):
         }
         if not dry:
             line["roofline"] = roofline_entry(st, avg_loop_ms, float(np.mean(bytes_moved)), N, K, T)
-            if world == 1 and not args.no_extra:
+            if world == 1 and args.full and not args.no_extra:
                 line["extra"] = extras(ctx, torch, dev, local_rank, N, K, T)
                 # the kernel BASELINE.json's north_star names for the HBM roofline (>= 40 %): the
                 # residual reduction at the C4 size, as a roofline block of its own
                 rc4 = line["extra"].pop("residual_rss_c4", None)
                 if rc4 and "error" not in rc4:
                     line["roofline_residual_c4"] = residual_roofline(rc4)
-            if world == 1 and not args.no_cpu_baseline:
+            if world == 1 and args.full and not args.no_cpu_baseline:
                 cb = cpu_baseline(prob, budget_s=args.cpu_budget_s)
                 line["cpu_baseline"] = cb
                 line["gpu_over_cpu_best"] = value / cb["best_value"]
@@ -797,6 +835,8 @@ def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     args = parse_args(argv)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        if args.dump_outputs:    # (the rank children run in ROOT: hand them the caller's DIR)
+            argv += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
         raise SystemExit(spawn_ranks(args, argv))
     rank_main(args)
 

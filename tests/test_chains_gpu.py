@@ -55,3 +55,29 @@ def test_bench_rccl_leg_with_one_rank():
     assert line["rccl"]["backend"] == "nccl" and line["rccl"]["world"] == 1
     assert line["rccl"]["allgather_ms"] > 0 and line["rccl"]["allgather_bytes_per_rank"] == 3000 * 33 * 8
     assert line["value"] > 1e5 and line["n_gpus"] == 1 and line["roofline"]["bound"] == "latency"
+
+
+def test_bench_plain_run_is_lean_and_its_dump_repeats(tmp_path):
+    """A plain `bench.py --gpus 1` times the headline only (no CPU baseline, no extras: those
+    are --full) and --dump-outputs writes the last step's samples; a second run with the same
+    arguments writes the same array (fixed inputs and chain seeds)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items()
+           if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    dumps = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1",
+                            "--steps", "3", "--warmup", "1", "--iters", "3000",
+                            "--dump-outputs", str(tmp_path / run)],
+                           env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 1e5
+        assert "extra" not in line and "cpu_baseline" not in line
+        dumps.append(np.load(tmp_path / run / "samples.npy", allow_pickle=False))
+    assert dumps[0].dtype == np.float64 and dumps[0].shape == (1, 3000, 33)
+    assert np.isfinite(dumps[0]).all() and np.array_equal(dumps[0], dumps[1])

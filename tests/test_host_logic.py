@@ -196,3 +196,27 @@ def test_run_on_devices_splits_chains_like_ranks(monkeypatch):
     made[1] = Boom(1)
     with pytest.raises(np.linalg.LinAlgError):      # a worker's exception reaches the caller
         chains.run_on_devices(y, X, 5, prior, 7, seeds, [0, 1, 2])
+
+
+def test_bench_dump_keeps_a_fixed_subset_beyond_the_limit(tmp_path):
+    """bench.py's dump_samples: whole block under the size limit; beyond it, the same sorted
+    subset of iterations on every call, within the limit."""
+    import importlib
+    import os
+    import sys
+    import torch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if root not in sys.path:
+        sys.path.insert(0, root)
+    bench = importlib.import_module("bench")
+    block = torch.arange(2 * 100 * 3, dtype=torch.float64).reshape(2, 100, 3)
+    bench.dump_samples(block, str(tmp_path / "all"))
+    assert np.array_equal(np.load(tmp_path / "all" / "samples.npy"), block.numpy())
+    limit = 2 * 3 * 8 * 10                                        # room for 10 iterations
+    for d in ("a", "b"):
+        bench.dump_samples(block, str(tmp_path / d), limit_bytes=limit)
+    a, b = (np.load(tmp_path / d / "samples.npy") for d in ("a", "b"))
+    assert a.dtype == np.float64 and a.shape == (2, 10, 3) and a.nbytes <= limit
+    assert np.array_equal(a, b)
+    rows = a[0, :, 0] / 3                                          # iteration index of each row kept
+    assert np.all(np.diff(rows) > 0) and np.array_equal(a, block.numpy()[:, rows.astype(int)])

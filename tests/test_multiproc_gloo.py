@@ -179,3 +179,23 @@ def test_bench_parent_fails_fast_when_a_rank_dies():
     assert took < 120, f"the parent waited {took:.0f} s for a rank that was already dead"
     assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert "rank 1 exited with status 3" in r.stderr and "--fail-rank test hook" in r.stderr
+
+
+def test_bench_dumps_the_pooled_samples_of_the_last_step(tmp_path):
+    """--dump-outputs DIR: rank 0 writes the pooled block of the LAST timed step (every rank's
+    chains, in global chain order) as DIR/samples.npy, float64.  A relative DIR is the caller's,
+    not the directory the rank children run in."""
+    env = {k: v for k, v in os.environ.items()
+           if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2",
+                        "--warmup", "1", "--iters", "8", "--k", "3", "--dry-run-cpu",
+                        "--rank-timeout-s", "240", "--dump-outputs", "dump"],
+                       env=env, cwd=str(tmp_path), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    got = np.load(out / "samples.npy", allow_pickle=False)
+    assert got.dtype == np.float64 and got.shape == (2, 8, 4)
+    # the stand-in sampler's block for the third call (warmup 1 + steps 2), chain by chain
+    base = np.array([(int(s) % 1000003) * 1e-3 for s in chain_seeds(1, [0, 1])])
+    want = base[:, None, None] + np.arange(8)[None, :, None] + 1e-3 * np.arange(4) + 2
+    assert np.allclose(got, want, rtol=0, atol=1e-9)
