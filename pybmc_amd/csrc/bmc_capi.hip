@@ -16,13 +16,12 @@
 
 #include "../../include/pybmc_amd.h"
 #include "bmc_launch.h"
+#include "bmc_plan.h"
 #include "host_linalg.hpp"
 
 using namespace bmc;
 
 namespace {
-
-constexpr size_t LDS_LIMIT = 160 * 1024;
 
 struct DevBuf {
     void* p = nullptr;
@@ -229,23 +228,6 @@ Panels panels_of(const bmc_ctx* c, const void* X) {
     return P;
 }
 
-// rows per lane: one row per lane whenever the whole matrix can stay in the chip's VGPRs
-// (256 CUs x 8 waves x ppw panels of 64 rows); otherwise wide (16-byte) reads once there
-// are enough panels to occupy the chip, narrower panels for small N.
-int choose_vec(int64_t n, int32_t k, int f32) {
-    // register residency: the narrowest panel that lets every panel have its own wave (more
-    // waves = shorter serial FMA phase); two rows per lane (wider reads for the streaming
-    // kernels that share the layout) once one row per lane would need two panels per wave
-    const int64_t waves_chip = 256 * 8;   // sized for the full chip; geometry re-checks the fit
-    if (gibbs_reg_capacity(k, f32, 1) && (n + 63) / 64 <= waves_chip) return 1;
-    if (gibbs_reg_capacity(k, f32, 2) && (n + 127) / 128 <= waves_chip) return 2;
-    for (int ppw : {2, 4})
-        if (gibbs_reg_capacity(k, f32, ppw) && (n + 63) / 64 <= waves_chip * ppw) return 1;
-    int vec = f32 ? 4 : 2;
-    while (vec > 1 && (n + 64 * vec - 1) / (64 * vec) < 1024) vec >>= 1;
-    return vec;
-}
-
 int finish_problem(bmc_ctx* c);
 
 int set_problem_common(bmc_ctx* c, const void* dX, const void* dy, int64_t n, int32_t k,
@@ -330,197 +312,9 @@ int rss_on_raw(bmc_ctx* c, const double* coef_host, int32_t nb, double* out_host
     return BMC_OK;
 }
 
-struct Geometry {
-    int chains_per_launch, G, waves, ppg, mode, ppw, nslot;
-    int one_wave;   // the chain runs in ONE wave (gibbs_wave_kernel)
-};
-
-constexpr int RES_AUTO = 0, RES_REG = 1, RES_STREAM = 3;  // 2 = LDS
-// one-wave chains: register-resident FMAs per iteration (rows per lane x columns, padded) up to
-// which one wave beats the workgroup form.  Same-box, us per iteration, wave / workgroup:
-// 12 x 4 (N = 629, K = 3) 0.351 / 0.629, 16 x 4 0.394 / 0.636, 12 x 8 0.469 / 0.633,
-// 2 x 32 0.521 / 0.545; 16 x 8 0.675 / 0.636, 8 x 16 0.657 / 0.562, 4 x 32 0.739 / 0.550
-// (gpurun_out/r3_wave_ab3.log)
-constexpr int ONE_WAVE_MAX_FMAS = 96;
-// Chip shape from the device properties (MI355X in SPX mode: 256 CUs = 8 XCDs x 32; a
-// partitioned device exposes fewer CUs, and the co-residency bound must follow it).
-struct Chip {
-    int groups_max;   // one resident workgroup per CU
-    int xcds;         // slots: blocks b and b + xcds share an XCD (observed round-robin)
-    int cu_per_xcd;
-};
+Shape shape_of(const bmc_ctx* c) { return Shape{c->n, c->k, c->f32, c->vec, c->npanels}; }
 Chip chip_of(const bmc_ctx* c) {
-    Chip ch;
-    ch.groups_max = c->n_cu > 0 ? c->n_cu : 256;
-    // bmc_tuning.cu_limit: fewer CUs can hold this context's persistent workgroups than the
-    // device reports (CU-masked queue, a GPU shared with another process)
-    const int cu_limit = c->tune.cu_limit > 0 ? c->tune.cu_limit : c->env_cu_limit;
-    if (cu_limit > 0 && cu_limit < ch.groups_max) ch.groups_max = cu_limit;
-    if (ch.groups_max > 256) ch.groups_max = 256;   // the gather holds 2 x 256 granules
-    ch.xcds = ch.groups_max >= 64 ? ch.groups_max / 32 : 1;
-    ch.cu_per_xcd = ch.groups_max / ch.xcds;
-    return ch;
-}
-
-// Pick the launch geometry.  Preference order: row panels in VGPRs with each chain on
-// one XCD (8 slots x <= 32 groups), then panels pinned in LDS, then streaming.
-Geometry choose_geometry(const bmc_ctx* c, int n_chains, bool allow_one_wave = false,
-                         int max_waves = 1) {
-    const Chip chip = chip_of(c);
-    const int MAX_GROUPS_PER_LAUNCH = chip.groups_max, XCD_COUNT = chip.xcds,
-              CU_PER_XCD = chip.cu_per_xcd;
-    const int RP = 64 * c->vec;
-    const size_t es = c->f32 ? 4 : 8;
-    const size_t panel_bytes = (size_t)(c->k + 1) * RP * es;
-    // u slices for up to 8 chains per pass + partial sums + control words + alignment slack
-    const size_t fixed = (size_t)((c->k + 63) / 64 * 64) * 8 * 8 + (512 + 8) * 8 + 64;
-    const int NP = c->npanels;
-    const bmc_tuning& tu = c->tune;
-    auto lds_fits = [&](int G) {
-        const int ppg = (NP + G - 1) / G;
-        return fixed + (size_t)ppg * panel_bytes <= LDS_LIMIT;
-    };
-    Geometry g{};
-    g.ppw = 1;
-    // ---- register residency: G <= 32 groups of <= 8 waves, 1/2/4 panels per wave ----
-    // ---- small problem: ONE workgroup holds the whole chain in registers -------------------
-    // No inter-workgroup exchange, no co-residency requirement (measured 0.85 us/iteration at
-    // N = 629 against 1.4 with ten single-wave groups), and every chain is an independent
-    // workgroup, so hundreds of chains run side by side in one launch.
-    // Smaller still (the reference's data set, 629 x 3): the chain in ONE wave, rows and columns
-    // in its registers, no hand-over of any kind inside an iteration (gibbs_wave_kernel; measured
-    // at N = 629, K = 3: see DESIGN.md 4.1).  waves_per_group = 1 asks for it, > 1 or an
-    // explicit panels_per_wave keep the workgroup form.
-    if (allow_one_wave && (tu.residency == RES_AUTO || tu.residency == RES_REG) && c->vec == 1 &&
-        tu.groups_per_chain <= 1 && tu.waves_per_group <= 1 && tu.panels_per_wave <= 0) {
-        // 1, 2, 4 (one per SIMD) or 8 waves: the fewest that keep a wave's FMAs per iteration
-        // within the measured crossover
-        int nw = 0, fmas = 0;
-        for (int w : {1, 2, 4, 8}) {
-            if (w > 1 && (w > max_waves || tu.waves_per_group == 1)) break;
-            const int f = bmc::gibbs_wave_capacity(c->k, (int)((NP + w - 1) / w));
-            if (w == 8 && f > 64) break;   // (8 waves: 256 registers each, shapes up to 64 FMAs)
-            if (f > 0 && (f <= ONE_WAVE_MAX_FMAS || tu.waves_per_group == 1)) { nw = w; fmas = f; break; }
-        }
-        if (nw > 0 && fmas > 0) {
-            g.mode = 0;
-            g.ppw = (int)((NP + nw - 1) / nw);
-            g.G = 1;
-            g.waves = nw;
-            g.ppg = (int)NP;
-            g.chains_per_launch = n_chains < 2048 ? n_chains : 2048;
-            g.nslot = g.chains_per_launch;
-            g.one_wave = 1;
-            return g;
-        }
-    }
-    if ((tu.residency == RES_AUTO || tu.residency == RES_REG) && c->vec == 1 &&
-        tu.groups_per_chain <= 1) {
-        for (int want : {4, 8}) {
-            for (int ppw : {1, 2, 4}) {
-                if (tu.panels_per_wave > 0 && tu.panels_per_wave != ppw) continue;
-                if (!gibbs_reg_capacity(c->k, c->f32, ppw)) continue;
-                const int waves = (NP + ppw - 1) / ppw;
-                if (waves > want || (tu.waves_per_group > 0 && waves > tu.waves_per_group)) continue;
-                g.mode = 0;
-                g.ppw = ppw;
-                g.G = 1;
-                g.waves = tu.waves_per_group > 0 ? tu.waves_per_group : waves;
-                g.ppg = NP;
-                g.chains_per_launch = n_chains < 2048 ? n_chains : 2048;
-                g.nslot = g.chains_per_launch;
-                return g;
-            }
-        }
-    }
-    if ((tu.residency == RES_AUTO || tu.residency == RES_REG) && c->vec <= 2) {
-        // Prefer the fewest panels per wave that keep the chain on ONE XCD (32 groups x 8 waves):
-        // its exchange is a single hop through that XCD's L2 (~0.4 us) where a chain spread over
-        // the chip pays two levels (~1.3 us), which outweighs one or three more panels per wave
-        // (~0.2 us each at K = 32); N = 30000, K = 32: 2.1 -> 1.5 us per iteration, and 8 chains
-        // then run side by side, one per XCD.
-        int first_ppw = 1;
-        if (tu.panels_per_wave <= 0 && tu.groups_per_chain <= 0 && c->vec == 1)
-            for (int ppw : {1, 2, 4})
-                if (gibbs_reg_capacity(c->k, c->f32, ppw) && (int64_t)CU_PER_XCD * 8 * ppw >= NP) {
-                    first_ppw = ppw;
-                    break;
-                }
-        for (int ppw : {1, 2, 4}) {
-            if (ppw < first_ppw) continue;
-            if (tu.panels_per_wave > 0 && tu.panels_per_wave != ppw) continue;
-            if (c->vec == 2 && ppw != 1) continue;
-            if (!gibbs_reg_capacity(c->k, c->f32, ppw * c->vec)) continue;
-            // one XCD (32 CUs) per chain while the panels fit there (measured: 32 groups x 5
-            // waves beats 20 x 8 at C2); otherwise the whole chip serves one chain at a time
-            int G = tu.groups_per_chain;
-            if (G <= 0) {
-                G = NP < CU_PER_XCD ? NP : CU_PER_XCD;
-                if ((int64_t)G * 8 * ppw < NP) {
-                    G = (int)((NP + 8 * ppw - 1) / (8 * ppw));
-                    if (G > MAX_GROUPS_PER_LAUNCH) continue;
-                }
-            }
-            if (G > MAX_GROUPS_PER_LAUNCH) continue;
-            // a chain over several XCDs: whole teams (groups g mod 8), so that the kernel can
-            // put team j on XCD j whichever XCD the launch starts on
-            if (tu.groups_per_chain <= 0 && G > CU_PER_XCD && XCD_COUNT == 8 &&
-                ((G + 7) & ~7) <= MAX_GROUPS_PER_LAUNCH)
-                G = (G + 7) & ~7;
-            const int ppg_reg = (NP + G - 1) / G;
-            int waves = tu.waves_per_group > 0 ? tu.waves_per_group : (ppg_reg + ppw - 1) / ppw;
-            if (waves > 8 || (int64_t)G * waves * ppw < NP) continue;
-            g.mode = 0;
-            g.ppw = ppw;
-            g.G = G;
-            g.waves = waves;
-            if (G <= CU_PER_XCD) {
-                // one chain per XCD (run_common widens this when more chains fit side by side)
-                g.nslot = XCD_COUNT;
-                g.chains_per_launch = n_chains < XCD_COUNT ? n_chains : XCD_COUNT;
-            } else {
-                g.chains_per_launch = MAX_GROUPS_PER_LAUNCH / G;
-                if (g.chains_per_launch > n_chains) g.chains_per_launch = n_chains;
-                g.nslot = g.chains_per_launch;
-            }
-            g.ppg = (NP + G - 1) / G;
-            return g;
-        }
-    }
-    // ---- LDS residency or streaming ------------------------------------------------------
-    const int t_waves = tu.waves_per_group;
-    int cpl = n_chains < XCD_COUNT ? n_chains : XCD_COUNT;
-    int G;
-    if (tu.groups_per_chain > 0) {
-        G = tu.groups_per_chain;
-        if (G > MAX_GROUPS_PER_LAUNCH) G = MAX_GROUPS_PER_LAUNCH;
-        if (cpl > MAX_GROUPS_PER_LAUNCH / G) cpl = MAX_GROUPS_PER_LAUNCH / G;
-        if (cpl < 1) cpl = 1;
-    } else {
-        // fewer chains per launch until the panels fit in LDS (or one chain is left)
-        while (cpl > 1 && !lds_fits(MAX_GROUPS_PER_LAUNCH / cpl)) --cpl;
-        const int gmax = MAX_GROUPS_PER_LAUNCH / cpl;
-        const int want_waves = t_waves > 0 ? t_waves : 4;
-        G = (NP + want_waves - 1) / want_waves;
-        if (G > gmax) G = gmax;
-        if (G < 1) G = 1;
-        if (!lds_fits(G) && lds_fits(gmax))
-            while (!lds_fits(G)) ++G;
-        if (G > CU_PER_XCD && XCD_COUNT == 8 && ((G + 7) & ~7) <= gmax) G = (G + 7) & ~7;   // whole teams
-    }
-    if (G > NP) G = NP;
-    g.G = G;
-    g.chains_per_launch = cpl;
-    g.ppg = (NP + G - 1) / G;
-    const bool want_stream = tu.residency == RES_STREAM;
-    g.mode = (!want_stream && lds_fits(G)) ? 1 : 2;
-    int waves = t_waves > 0 ? t_waves : (g.ppg < 4 ? g.ppg : (g.mode == 1 ? (g.ppg < 8 ? g.ppg : 8) : 8));
-    if (waves > 8) waves = 8;   // 512-thread workgroups: 256 VGPRs per lane, no spills
-    if (waves < 1) waves = 1;
-    g.waves = waves;
-    // one slot per XCD while a chain's groups fit one XCD's CUs; otherwise any placement
-    g.nslot = (G <= CU_PER_XCD) ? XCD_COUNT : cpl;
-    return g;
+    return bmc::chip_of(c->n_cu, c->tune.cu_limit > 0 ? c->tune.cu_limit : c->env_cu_limit);
 }
 
 // rss_mode 1: upload G, u0, g0 and take rss(u0) from ONE residual pass over the rotated panels
@@ -611,23 +405,10 @@ int run_common(bmc_ctx* c, int32_t n_chains, int64_t iters, const uint64_t* seed
         d_samples = (double*)c->samples.p;
     }
     if ((rc = check_tuning_fits(c))) return rc;
-    Geometry geo = choose_geometry(c, n_chains, true, 8);
-    // One-XCD register residency with more than 8 chains.
-    // (a) 16 chains or more: the register-resident panels of an XCD's 32 groups serve a BUNDLE of
-    //     2 / 4 / 8 chains per pass (gibbs_multi_kernel, one bundle per XCD: 16 .. 64 chains in one
-    //     launch); every chain bit-identical to its solo run.
-    // (b) 9 .. 15 chains left: chains c and c + 8 share XCD c % 8, two workgroups per CU side by
-    //     side.  That needs 4 waves per SIMD (two 5-wave groups must fit whatever SIMDs their
-    //     waves land on), i.e. the kernel variant held to 128 VGPRs, which exists for light
-    //     shapes only.  (Three or four per XCD are not used: measured, the launch then stalls.)
-    const int xcds = chip_of(c).xcds;
-    const bool one_xcd_reg = geo.mode == 0 && geo.G > 1 && geo.nslot == xcds && xcds > 1 &&
-                             geo.G <= chip_of(c).cu_per_xcd && c->tune.groups_per_chain <= 0;
-    const bool xcd_bundles = one_xcd_reg && geo.ppw == 1 && c->vec == 1 && geo.G <= 32 &&
-                             c->tune.chains_per_pass != 1 &&
-                             bmc::gibbs_reg_multi_cap(c->k, c->f32 != 0, c->vec) >= 2;
-    int pack_ok = 0;
-    if (one_xcd_reg && n_chains > geo.nslot && 2 * geo.waves <= 16) {
+    const Chip chip = chip_of(c);
+    const Geometry geo = choose_geometry(shape_of(c), c->tune, chip, n_chains, true, 8);
+    bool pack_ok = false;
+    if (gibbs_pack_candidate(geo, chip, c->tune, n_chains)) {
         int32_t regs = 0;
         GibbsArgs q{};
         q.P = panels_of(c, c->Xrot.p);
@@ -641,15 +422,11 @@ int run_common(bmc_ctx* c, int32_t n_chains, int64_t iters, const uint64_t* seed
         qo.query_occupancy = &per_cu;
         if (launch_gibbs(q, c->stream) == hipSuccess && regs > 0 && regs <= 128 &&
             launch_gibbs(qo, c->stream) == hipSuccess && per_cu >= 2)
-            pack_ok = 1;
+            pack_ok = true;
     }
-    // the most chains one launch can hold (sizes the exchange words)
-    int max_per_launch = geo.chains_per_launch;
-    if (pack_ok) max_per_launch = 2 * geo.nslot;
-    if (xcd_bundles) max_per_launch = 8 * xcds;
-    if (max_per_launch < 8) max_per_launch = 8;
+    const GibbsPlan plan = plan_gibbs(geo, shape_of(c), c->tune, chip, n_chains, pack_ok);
     const int gran_stride = bmc::gran_slot_words(geo.G);
-    if ((rc = ensure(c, c->gran, (size_t)max_per_launch * 3 * gran_stride * 8))) return rc;
+    if ((rc = ensure(c, c->gran, (size_t)plan.max_per_launch * 3 * gran_stride * 8))) return rc;
     if ((rc = ensure(c, c->status, C * sizeof(int32_t)))) return rc;
     if ((rc = ensure(c, c->placement, C * sizeof(int32_t)))) return rc;
     HIPCHK(c, hipMemsetAsync(c->placement.p, 0, C * sizeof(int32_t), c->stream));
@@ -683,10 +460,8 @@ int run_common(bmc_ctx* c, int32_t n_chains, int64_t iters, const uint64_t* seed
     a.gran_stride = gran_stride;
     a.iters = iters;
     a.G = geo.G;
-    a.waves = geo.waves;
     a.mode = geo.mode;
     a.reg_ppw = geo.ppw;
-    a.nslot = geo.nslot;
     a.force_agent_scope = c->tune.force_agent_scope;
     a.panels_per_group = geo.ppg;
     a.one_wave = geo.one_wave;
@@ -701,36 +476,14 @@ int run_common(bmc_ctx* c, int32_t n_chains, int64_t iters, const uint64_t* seed
     }
     a.dbg = nullptr;
     a.query_regs = nullptr;
-    a.pack = 0;
 #ifdef BMC_STAMPS
     if ((rc = ensure(c, c->dbg, 12 * sizeof(long long)))) return rc;
     HIPCHK(c, hipMemsetAsync(c->dbg.p, 0, 12 * sizeof(long long), c->stream));
     a.dbg = (long long*)c->dbg.p;
 #endif
-    // chains per pass: when the panels are NOT register-resident one read of X can serve up to
-    // 8 chains (one leader wave per chain); 0 = automatic, 1 = off
-    int cpp_max = 1, waves_multi = geo.waves;
-    // (register residency: only the whole-chip form, one chain bundle per launch, one panel per
-    // wave; the one-XCD-per-chain form already runs 8 chains side by side)
-    const bool reg_multi_ok = geo.mode == 0 && geo.nslot < 8 && geo.G > 1 && geo.ppw == 1;
-    if ((geo.mode != 0 || reg_multi_ok) && n_chains > 1 && c->tune.chains_per_pass != 1) {
-        // every chain of a pass needs a leader wave: widen the workgroup if the panels alone
-        // would ask for fewer waves (the extra waves own no panel, they only lead a chain)
-        int want = n_chains >= 8 ? 8 : n_chains >= 4 ? 4 : 2;
-        if (c->tune.chains_per_pass > 1 && c->tune.chains_per_pass < want)
-            want = c->tune.chains_per_pass >= 4 ? 4 : 2;
-        if (a.waves < want && c->tune.waves_per_group <= 0) a.waves = want;
-        waves_multi = a.waves;
-        cpp_max = a.waves >= 8 ? 8 : a.waves >= 4 ? 4 : a.waves >= 2 ? 2 : 1;
-        if (cpp_max > want) cpp_max = want;
-        if (reg_multi_ok) {
-            const int cap = bmc::gibbs_reg_multi_cap(K, a.P.f32 != 0, a.P.vec);
-            if (cpp_max > cap) cpp_max = cap < 2 ? 1 : cap;
-        }
-    }
-    const int waves_single = geo.waves;
-    int launches = 0, cpp_used = 1, waves_used = 0;
+    int launches = 0;
     const bool gram_mode = c->tune.rss_mode == 1;
+    const bool loop = !gram_mode && iters > 0;
     if (gram_mode && iters > 0) {
         if ((rc = gram_device_setup(c))) return rc;
         GramArgs ga;
@@ -745,78 +498,28 @@ int run_common(bmc_ctx* c, int32_t n_chains, int64_t iters, const uint64_t* seed
         HIPCHK(c, launch_gibbs_gram(ga, c->stream));
         launches = 1;
     }
-    int64_t passes = 0;
-    for (int c0 = 0; !gram_mode && iters > 0 && c0 < n_chains;) {
-        const int left = n_chains - c0;
-        int cpp = 1, m, resident;
-        a.bundle_slots = 0;
-        a.bundle_bal = 0;
-        a.pack = 0;
-        a.nslot = geo.nslot;
-        // bundles pay from 4 chains per XCD on (measured at C2, us per iteration for all chains:
-        // 16 chains 1.37 as bundles of 2 against 1.05 packed two per XCD; 32 chains 1.81 as
-        // bundles of 4 against 2 x 1.05; 64 chains 2.33 as bundles of 8); with fewer they are
-        // used when asked for (chains_per_pass = 2) or when the shape has no packed variant
-        if (xcd_bundles && left >= 2 * xcds &&
-            (left >= 4 * xcds || !pack_ok || c->tune.chains_per_pass > 1)) {
-            // one bundle per XCD: as many chains per bundle as keep all XCDs busy
-            int cap = bmc::gibbs_reg_multi_cap(K, a.P.f32 != 0, a.P.vec);
-            if (c->tune.chains_per_pass > 1 && c->tune.chains_per_pass < cap) cap = c->tune.chains_per_pass;
-            cpp = 2;
-            while (cpp * 2 <= cap && cpp * 2 * xcds <= left) cpp *= 2;
-            // 40 .. 63 chains: bundles of 8 on 5 .. 7 XCDs in one launch (2.3 us per iteration at C2)
-            // rather than bundles of 4 on all 8 (1.8 us for 32 of them) plus a second launch
-            if (cap >= 8 && cpp == 4 && left >= 5 * 8) cpp = 8;
-            const int bundles = left / cpp < xcds ? left / cpp : xcds;
-            m = bundles * cpp;
-            a.bundle_slots = xcds;
-            a.waves = waves_single > cpp ? waves_single : cpp;   // a leader wave per chain
-            // bundles of 8 on 8 waves, at most 5 panels per group, two panels of K columns in a
-            // wave's registers: the balanced layout (4 chains of panel w % 4 + 1 chain of the
-            // fifth panel per wave instead of 8 chains of one panel on waves 0 .. 3)
-#ifndef BMC_NO_BAL
-            // (panels_per_wave = 1 asked for explicitly keeps the one-panel layout: the A/B knob)
-            a.bundle_bal = (cpp == 8 && a.waves == 8 && geo.ppg <= 5 && K > 8 &&
-                            c->tune.panels_per_wave != 1 &&
-                            bmc::gibbs_reg_capacity(K, a.P.f32 != 0, 2)) ? 1 : 0;
-#endif
-            resident = bundles * a.G;
-            passes += (int64_t)bundles * iters;
-        } else if (cpp_max > 1 && left >= 2) {
-            while (cpp * 2 <= left && cpp * 2 <= cpp_max) cpp *= 2;
-            m = cpp;
-            a.waves = waves_multi;
-            resident = a.G;
-            passes += iters;
-        } else {
-            a.waves = waves_single;
-            if (pack_ok && left > geo.nslot) {
-                a.pack = 1;
-                a.nslot = 2 * geo.nslot;
-            }
-            const int cap = a.pack ? a.nslot : geo.chains_per_launch;
-            m = left < cap ? left : cap;
-            resident = m * a.G;
-            passes += (int64_t)m * iters;
-        }
-        a.n_chains = m;
-        a.chains_per_pass = cpp;
+    for (size_t i = 0; loop && i < plan.launches.size(); ++i) {
+        const GibbsLaunch& l = plan.launches[i];
+        a.n_chains = l.n_chains;
+        a.chains_per_pass = l.chains_per_pass;
+        a.waves = l.waves;
+        a.nslot = l.nslot;
+        a.pack = l.pack;
+        a.bundle_slots = l.bundle_slots;
+        a.bundle_bal = l.bundle_bal;
         a.epoch0 = launch_nonce(c, (uint64_t)iters);
-        if (cpp > cpp_used) cpp_used = cpp;
-        if (a.waves > waves_used) waves_used = a.waves;
-        a.xi = (const double*)c->xi.p + (size_t)c0 * T * K;
-        a.gam = (const double*)c->gam.p + (size_t)c0 * T;
-        a.uout = (double*)c->uout.p + (size_t)c0 * T * (K + 1);
-        a.status = (int32_t*)c->status.p + c0;
-        a.placement = (int32_t*)c->placement.p + c0;
-        HIPCHK(c, hipMemsetAsync(c->gran.p, 0, (size_t)m * 3 * gran_stride * 8, c->stream));
+        a.xi = (const double*)c->xi.p + (size_t)l.c0 * T * K;
+        a.gam = (const double*)c->gam.p + (size_t)l.c0 * T;
+        a.uout = (double*)c->uout.p + (size_t)l.c0 * T * (K + 1);
+        a.status = (int32_t*)c->status.p + l.c0;
+        a.placement = (int32_t*)c->placement.p + l.c0;
+        HIPCHK(c, hipMemsetAsync(c->gran.p, 0, (size_t)l.n_chains * 3 * gran_stride * 8, c->stream));
         if (gibbs_lds_bytes(a) > LDS_LIMIT) return fail(c, BMC_EINVAL, "LDS plan exceeds 160 KiB");
-        if (a.G > 1 || cpp > 1)   // (a single-workgroup chain waits for nobody)
-            if ((rc = check_residency(c, a, resident, launch_gibbs, "persistent Gibbs kernel")))
+        if (a.G > 1 || l.chains_per_pass > 1)   // (a single-workgroup chain waits for nobody)
+            if ((rc = check_residency(c, a, l.resident, launch_gibbs, "persistent Gibbs kernel")))
                 return rc;
         HIPCHK(c, launch_gibbs(a, c->stream));
         ++launches;
-        c0 += m;
     }
     HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
     if (iters > 0)
@@ -843,14 +546,14 @@ int run_common(bmc_ctx* c, int32_t n_chains, int64_t iters, const uint64_t* seed
         stats->n_chains = n_chains;
         stats->launches = launches;
         stats->groups_per_chain = geo.G;
-        stats->waves_per_group = waves_used ? waves_used : geo.waves;   // widened for leader waves
-        stats->chains_per_pass = cpp_used;
+        stats->waves_per_group = loop ? plan.waves_per_group : geo.waves;   // widened for leader waves
+        stats->chains_per_pass = loop ? plan.chains_per_pass : 1;
         stats->residency = gram_mode ? 4 : geo.mode + 1;
         stats->xcd_local_chains = 0;
         for (size_t i = 0; i < C; ++i) stats->xcd_local_chains += place[i] ? 1 : 0;
         stats->bytes_per_pass = ((int64_t)c->n * K + c->n) * (c->f32 ? 4 : 8);
         // a pass that serves several chains counts once
-        stats->passes = gram_mode ? 0 : passes;
+        stats->passes = loop ? plan.passes * iters : 0;
         if (gram_mode) { stats->groups_per_chain = 1; stats->waves_per_group = 1; }
     }
     for (size_t i = 0; i < C; ++i)
@@ -1405,7 +1108,7 @@ int bmc_simplex_run(bmc_ctx* c, const double* Vt_hat, int32_t Km, const double* 
     std::vector<double> step(K);
     for (int j = 0; j < K; ++j) step[j] = std::sqrt(S_hat[j] * S_hat[j] * stepsize * stepsize);  // :80
     if ((rc = check_tuning_fits(c))) return rc;
-    const Geometry geo = choose_geometry(c, 1, Km <= 64, 4);   // (a model per lane)
+    const Geometry geo = choose_geometry(shape_of(c), c->tune, chip_of(c), 1, Km <= 64, 4);   // (a model per lane)
     const int gran_stride = bmc::gran_slot_words(geo.G);
     if ((rc = ensure(c, c->gran, (size_t)3 * gran_stride * 8))) return rc;
     HIPCHK(c, hipMemsetAsync(c->gran.p, 0, (size_t)3 * gran_stride * 8, c->stream));

@@ -182,10 +182,6 @@ struct GramArgs {
     int32_t n_chains;
 };
 hipError_t launch_gibbs_gram(const GramArgs& a, hipStream_t s);
-// register-resident FMAs per iteration of the one-wave-per-chain kernel for k columns and
-// npanels panels of 64 rows PER WAVE (f64 or f32 storage, one row per lane), 0 = no such kernel;
-// a chain runs in 1, 2 or 4 such waves (GibbsArgs.waves)
-int gibbs_wave_capacity(int k, int npanels);
 
 struct SimplexArgs {
     Panels P;               // UN-rotated panels (the simplex sampler proposes beta itself)
@@ -217,8 +213,6 @@ hipError_t launch_simplex(const SimplexArgs& a, hipStream_t s);
 hipError_t launch_uniform_fill(uint64_t seed, int64_t n, double* out, hipStream_t s);
 
 size_t gibbs_lds_bytes(const GibbsArgs& a);
-int gibbs_reg_capacity(int k, int f32, int rows_per_lane);  // 1 if that many rows of k columns fit in VGPRs
-int gibbs_reg_multi_cap(int k, bool f32, int vec);  // most chains per pass in register residency
 hipError_t launch_gibbs(const GibbsArgs& a, hipStream_t s);
 
 }  // namespace bmc

@@ -5,12 +5,11 @@
 
 #include "bmc_dev.h"
 #include "bmc_launch.h"
+#include "bmc_plan.h"
 
 namespace bmc {
 
-constexpr int MAX_KCH = 4;        // K <= 256 columns (64 per lane-chunk)
 constexpr int RED_DOUBLES = 512;  // LDS doubles of the group-level sum (group_allreduce)
-constexpr int MAX_GROUPS = 256;   // 8 teams of <= 32 groups (exchange_sum)
 constexpr unsigned long long SPIN_TIMEOUT_TICKS = 400000000ull;  // 4 s of s_memrealtime (100 MHz)
 
 enum { MODE_REG = 0, MODE_LDS = 1, MODE_STREAM = 2 };

@@ -1,0 +1,423 @@
+// Launch planning of the Gibbs and simplex loops: which kernel, which geometry, how the chains
+// are split over launches.  Plain C++17 (no HIP): the dispatcher of kernels_gibbs.hip builds
+// its instantiations from the same capacity rules the host plans with, and
+// tests/launch_plan_check.cpp runs the planner on the CPU.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <initializer_list>
+#include <vector>
+
+#include "../../include/pybmc_amd.h"
+
+namespace bmc {
+
+constexpr size_t LDS_LIMIT = 160 * 1024;
+constexpr int MAX_KCH = 4;        // K <= 256 columns (64 per lane-chunk)
+constexpr int MAX_GROUPS = 256;   // 8 teams of <= 32 groups (exchange_sum)
+
+// ---- capacity rules (host plan and kernel instantiations) ------------------------------------
+constexpr int reg_kmax(int k) { return k <= 8 ? 8 : k <= 16 ? 16 : k <= 32 ? 32 : k <= 64 ? 64 : 0; }
+
+// 1 if rows_per_lane (panels per wave x rows per lane of a panel) rows of k columns fit the 128
+// data VGPRs per lane that keep the register-resident loop spill-free (f64: two per element)
+constexpr bool gibbs_reg_capacity(int k, bool f32, int rows_per_lane) {
+    return reg_kmax(k) > 0 && rows_per_lane * reg_kmax(k) * (f32 ? 1 : 2) <= 128;
+}
+
+// register residency with several chains per pass: one panel per wave (PPW = 1).  The panel
+// (KMAX*VEC values) plus two blocks of u plus the leaders' state must fit 256 VGPRs: the most
+// chains per pass that hipcc compiles without scratch, per (columns, storage type, rows per lane)
+constexpr int gibbs_reg_multi_cap(int k, bool f32, int vec) {
+    if (reg_kmax(k) == 0) return 0;
+    if (vec == 1) return 8;
+    if (vec == 2) return reg_kmax(k) * (f32 ? 4 : 8) >= 256 ? 4 : 8;   // 128 VGPRs of panel: 4 chains
+    return 0;
+}
+
+// PACK: the loop kernel held to 128 VGPRs (4 waves per SIMD), so that two 5-wave groups of
+// different chains fit a CU side by side.  It exists only for shapes with one panel of at most 64
+// data VGPRs per wave (e.g. K = 32 doubles).
+constexpr bool gibbs_packable(int k, bool f32, int vec, int ppw) {
+    return ppw == 1 && vec == 1 && reg_kmax(k) > 0 && reg_kmax(k) * (f32 ? 1 : 2) <= 64 &&
+           !(f32 && reg_kmax(k) == 64);   // (f32, 64 columns spills at 128)
+}
+
+// bundles of 8 chains in the balanced two-panels-per-wave layout (PanelStore::partial_rss_reg_bal)
+constexpr bool gibbs_bundle_bal_shape(int k, bool f32, int vec, int chains_per_pass) {
+    return vec == 1 && chains_per_pass == 8 && reg_kmax(k) >= 16 && gibbs_reg_capacity(k, f32, 2);
+}
+
+// one-wave-per-chain kernels (gibbs_wave_kernel, simplex_wave_kernel): row panels x columns a
+// wave keeps, RMAX * KMAX <= 128 (and at most 16 panels = 1024 rows)
+constexpr int wave_kmax(int k) { return k <= 4 ? 4 : k <= 8 ? 8 : k <= 16 ? 16 : k <= 32 ? 32 : 0; }
+constexpr int wave_rmax(int np) { return np <= 2 ? 2 : np <= 4 ? 4 : np <= 8 ? 8 : np <= 12 ? 12 : np <= 16 ? 16 : 0; }
+// register-resident FMAs per iteration for k columns and npanels panels of 64 rows PER WAVE,
+// 0 = no such kernel; a chain runs in 1, 2, 4 or 8 such waves
+constexpr int gibbs_wave_capacity(int k, int npanels) {
+    const int km = wave_kmax(k), rm = wave_rmax(npanels);
+    return (km > 0 && rm > 0 && km * rm <= 128) ? km * rm : 0;
+}
+// 8 waves: two per SIMD, 256 registers each -- shapes up to 64 FMAs (12 x 8 spills at 256)
+constexpr bool gibbs_wave_fits(int fmas, int waves) { return waves <= 4 || fmas <= 64; }
+
+// ---- argument checks of launch_gibbs / launch_simplex ---------------------------------------
+constexpr bool geometry_ok(int k, int G, int waves, int nslot) {
+    return k <= 64 * MAX_KCH && G <= MAX_GROUPS && G >= 1 && waves >= 1 && waves <= 8 && nslot >= 1 &&
+           nslot <= 2048;
+}
+// chains of one gibbs_loop_kernel launch (chains_per_pass <= 1) or of one gibbs_multi_kernel launch
+// (bundles of chains_per_pass chains, one or one per slot; a leader wave per chain)
+constexpr bool gibbs_chains_ok(int n_chains, int chains_per_pass, int waves, int nslot, int bundle_slots,
+                               int G, int mode) {
+    if (chains_per_pass <= 1) return n_chains >= 1 && n_chains <= nslot;
+    return waves >= chains_per_pass && n_chains >= chains_per_pass && n_chains % chains_per_pass == 0 &&
+           bundle_slots >= 0 && n_chains / chains_per_pass <= (bundle_slots > 0 ? bundle_slots : 1) &&
+           !(bundle_slots > 0 && (G > 32 || mode != 0));
+}
+
+// ---- the plan ----------------------------------------------------------------------------
+struct Shape {
+    int64_t n;
+    int k, f32, vec, npanels;   // vec: rows per lane of a panel (choose_vec)
+};
+
+// Chip shape from the device properties (MI355X in SPX mode: 256 CUs = 8 XCDs x 32; a
+// partitioned device exposes fewer CUs, and the co-residency bound must follow it).
+struct Chip {
+    int groups_max;   // one resident workgroup per CU
+    int xcds;         // slots: blocks b and b + xcds share an XCD (observed round-robin)
+    int cu_per_xcd;
+};
+// cu_limit (bmc_tuning.cu_limit, or its environment default; 0 = none): fewer CUs can hold this
+// context's persistent workgroups than the device reports (CU-masked queue, a GPU shared with
+// another process)
+inline Chip chip_of(int n_cu, int cu_limit) {
+    Chip ch;
+    ch.groups_max = n_cu > 0 ? n_cu : 256;
+    if (cu_limit > 0 && cu_limit < ch.groups_max) ch.groups_max = cu_limit;
+    if (ch.groups_max > 256) ch.groups_max = 256;   // the gather holds 2 x 256 granules
+    ch.xcds = ch.groups_max >= 64 ? ch.groups_max / 32 : 1;
+    ch.cu_per_xcd = ch.groups_max / ch.xcds;
+    return ch;
+}
+
+// rows per lane: one row per lane whenever the whole matrix can stay in the chip's VGPRs
+// (256 CUs x 8 waves x ppw panels of 64 rows); otherwise wide (16-byte) reads once there
+// are enough panels to occupy the chip, narrower panels for small N.
+inline int choose_vec(int64_t n, int32_t k, int f32) {
+    // register residency: the narrowest panel that lets every panel have its own wave (more
+    // waves = shorter serial FMA phase); two rows per lane (wider reads for the streaming
+    // kernels that share the layout) once one row per lane would need two panels per wave
+    const int64_t waves_chip = 256 * 8;   // sized for the full chip; geometry re-checks the fit
+    if (gibbs_reg_capacity(k, f32, 1) && (n + 63) / 64 <= waves_chip) return 1;
+    if (gibbs_reg_capacity(k, f32, 2) && (n + 127) / 128 <= waves_chip) return 2;
+    for (int ppw : {2, 4})
+        if (gibbs_reg_capacity(k, f32, ppw) && (n + 63) / 64 <= waves_chip * ppw) return 1;
+    int vec = f32 ? 4 : 2;
+    while (vec > 1 && (n + 64 * vec - 1) / (64 * vec) < 1024) vec >>= 1;
+    return vec;
+}
+
+struct Geometry {
+    int chains_per_launch, G, waves, ppg, mode, ppw, nslot;
+    int one_wave;   // the chain runs in ONE wave (gibbs_wave_kernel)
+};
+
+constexpr int RES_AUTO = 0, RES_REG = 1, RES_STREAM = 3;  // 2 = LDS
+// one-wave chains: register-resident FMAs per iteration (rows per lane x columns, padded) up to
+// which one wave beats the workgroup form.  Same-box, us per iteration, wave / workgroup:
+// 12 x 4 (N = 629, K = 3) 0.351 / 0.629, 16 x 4 0.394 / 0.636, 12 x 8 0.469 / 0.633,
+// 2 x 32 0.521 / 0.545; 16 x 8 0.675 / 0.636, 8 x 16 0.657 / 0.562, 4 x 32 0.739 / 0.550
+constexpr int ONE_WAVE_MAX_FMAS = 96;
+
+// Pick the launch geometry.  Preference order: row panels in VGPRs with each chain on
+// one XCD (8 slots x <= 32 groups), then panels pinned in LDS, then streaming.
+inline Geometry choose_geometry(const Shape& s, const bmc_tuning& tu, const Chip& chip, int n_chains,
+                                bool allow_one_wave = false, int max_waves = 1) {
+    const int MAX_GROUPS_PER_LAUNCH = chip.groups_max, XCD_COUNT = chip.xcds,
+              CU_PER_XCD = chip.cu_per_xcd;
+    const int RP = 64 * s.vec;
+    const size_t es = s.f32 ? 4 : 8;
+    const size_t panel_bytes = (size_t)(s.k + 1) * RP * es;
+    // u slices for up to 8 chains per pass + partial sums + control words + alignment slack.
+    // (An upper bound that decides the residency, not lds_plan: the launch itself checks
+    // gibbs_lds_bytes against LDS_LIMIT.)
+    const size_t fixed = (size_t)((s.k + 63) / 64 * 64) * 8 * 8 + (512 + 8) * 8 + 64;
+    const int NP = s.npanels;
+    auto lds_fits = [&](int G) {
+        const int ppg = (NP + G - 1) / G;
+        return fixed + (size_t)ppg * panel_bytes <= LDS_LIMIT;
+    };
+    Geometry g{};
+    g.ppw = 1;
+    // ---- register residency: G <= 32 groups of <= 8 waves, 1/2/4 panels per wave ----
+    // ---- small problem: ONE workgroup holds the whole chain in registers -------------------
+    // No inter-workgroup exchange, no co-residency requirement (measured 0.85 us/iteration at
+    // N = 629 against 1.4 with ten single-wave groups), and every chain is an independent
+    // workgroup, so hundreds of chains run side by side in one launch.
+    // Smaller still (the reference's data set, 629 x 3): the chain in ONE wave, rows and columns
+    // in its registers, no hand-over of any kind inside an iteration (gibbs_wave_kernel; measured
+    // at N = 629, K = 3: see DESIGN.md 4.1).  waves_per_group = 1 asks for it, > 1 or an
+    // explicit panels_per_wave keep the workgroup form.
+    if (allow_one_wave && (tu.residency == RES_AUTO || tu.residency == RES_REG) && s.vec == 1 &&
+        tu.groups_per_chain <= 1 && tu.waves_per_group <= 1 && tu.panels_per_wave <= 0) {
+        // 1, 2, 4 (one per SIMD) or 8 waves: the fewest that keep a wave's FMAs per iteration
+        // within the measured crossover
+        int nw = 0, fmas = 0;
+        for (int w : {1, 2, 4, 8}) {
+            if (w > 1 && (w > max_waves || tu.waves_per_group == 1)) break;
+            const int f = gibbs_wave_capacity(s.k, (int)((NP + w - 1) / w));
+            if (!gibbs_wave_fits(f, w)) break;
+            if (f > 0 && (f <= ONE_WAVE_MAX_FMAS || tu.waves_per_group == 1)) { nw = w; fmas = f; break; }
+        }
+        if (nw > 0 && fmas > 0) {
+            g.mode = 0;
+            g.ppw = (int)((NP + nw - 1) / nw);
+            g.G = 1;
+            g.waves = nw;
+            g.ppg = (int)NP;
+            g.chains_per_launch = n_chains < 2048 ? n_chains : 2048;
+            g.nslot = g.chains_per_launch;
+            g.one_wave = 1;
+            return g;
+        }
+    }
+    if ((tu.residency == RES_AUTO || tu.residency == RES_REG) && s.vec == 1 &&
+        tu.groups_per_chain <= 1) {
+        for (int want : {4, 8}) {
+            for (int ppw : {1, 2, 4}) {
+                if (tu.panels_per_wave > 0 && tu.panels_per_wave != ppw) continue;
+                if (!gibbs_reg_capacity(s.k, s.f32, ppw)) continue;
+                const int waves = (NP + ppw - 1) / ppw;
+                if (waves > want || (tu.waves_per_group > 0 && waves > tu.waves_per_group)) continue;
+                g.mode = 0;
+                g.ppw = ppw;
+                g.G = 1;
+                g.waves = tu.waves_per_group > 0 ? tu.waves_per_group : waves;
+                g.ppg = NP;
+                g.chains_per_launch = n_chains < 2048 ? n_chains : 2048;
+                g.nslot = g.chains_per_launch;
+                return g;
+            }
+        }
+    }
+    if ((tu.residency == RES_AUTO || tu.residency == RES_REG) && s.vec <= 2) {
+        // Prefer the fewest panels per wave that keep the chain on ONE XCD (32 groups x 8 waves):
+        // its exchange is a single hop through that XCD's L2 (~0.4 us) where a chain spread over
+        // the chip pays two levels (~1.3 us), which outweighs one or three more panels per wave
+        // (~0.2 us each at K = 32); N = 30000, K = 32: 2.1 -> 1.5 us per iteration, and 8 chains
+        // then run side by side, one per XCD.
+        int first_ppw = 1;
+        if (tu.panels_per_wave <= 0 && tu.groups_per_chain <= 0 && s.vec == 1)
+            for (int ppw : {1, 2, 4})
+                if (gibbs_reg_capacity(s.k, s.f32, ppw) && (int64_t)CU_PER_XCD * 8 * ppw >= NP) {
+                    first_ppw = ppw;
+                    break;
+                }
+        for (int ppw : {1, 2, 4}) {
+            if (ppw < first_ppw) continue;
+            if (tu.panels_per_wave > 0 && tu.panels_per_wave != ppw) continue;
+            if (s.vec == 2 && ppw != 1) continue;
+            if (!gibbs_reg_capacity(s.k, s.f32, ppw * s.vec)) continue;
+            // one XCD (32 CUs) per chain while the panels fit there (measured: 32 groups x 5
+            // waves beats 20 x 8 at C2); otherwise the whole chip serves one chain at a time
+            int G = tu.groups_per_chain;
+            if (G <= 0) {
+                G = NP < CU_PER_XCD ? NP : CU_PER_XCD;
+                if ((int64_t)G * 8 * ppw < NP) {
+                    G = (int)((NP + 8 * ppw - 1) / (8 * ppw));
+                    if (G > MAX_GROUPS_PER_LAUNCH) continue;
+                }
+            }
+            if (G > MAX_GROUPS_PER_LAUNCH) continue;
+            // a chain over several XCDs: whole teams (groups g mod 8), so that the kernel can
+            // put team j on XCD j whichever XCD the launch starts on
+            if (tu.groups_per_chain <= 0 && G > CU_PER_XCD && XCD_COUNT == 8 &&
+                ((G + 7) & ~7) <= MAX_GROUPS_PER_LAUNCH)
+                G = (G + 7) & ~7;
+            const int ppg_reg = (NP + G - 1) / G;
+            int waves = tu.waves_per_group > 0 ? tu.waves_per_group : (ppg_reg + ppw - 1) / ppw;
+            if (waves > 8 || (int64_t)G * waves * ppw < NP) continue;
+            g.mode = 0;
+            g.ppw = ppw;
+            g.G = G;
+            g.waves = waves;
+            if (G <= CU_PER_XCD) {
+                // one chain per XCD (plan_gibbs widens this when more chains fit side by side)
+                g.nslot = XCD_COUNT;
+                g.chains_per_launch = n_chains < XCD_COUNT ? n_chains : XCD_COUNT;
+            } else {
+                g.chains_per_launch = MAX_GROUPS_PER_LAUNCH / G;
+                if (g.chains_per_launch > n_chains) g.chains_per_launch = n_chains;
+                g.nslot = g.chains_per_launch;
+            }
+            g.ppg = (NP + G - 1) / G;
+            return g;
+        }
+    }
+    // ---- LDS residency or streaming ------------------------------------------------------
+    const int t_waves = tu.waves_per_group;
+    int cpl = n_chains < XCD_COUNT ? n_chains : XCD_COUNT;
+    int G;
+    if (tu.groups_per_chain > 0) {
+        G = tu.groups_per_chain;
+        if (G > MAX_GROUPS_PER_LAUNCH) G = MAX_GROUPS_PER_LAUNCH;
+        if (cpl > MAX_GROUPS_PER_LAUNCH / G) cpl = MAX_GROUPS_PER_LAUNCH / G;
+        if (cpl < 1) cpl = 1;
+    } else {
+        // fewer chains per launch until the panels fit in LDS (or one chain is left)
+        while (cpl > 1 && !lds_fits(MAX_GROUPS_PER_LAUNCH / cpl)) --cpl;
+        const int gmax = MAX_GROUPS_PER_LAUNCH / cpl;
+        const int want_waves = t_waves > 0 ? t_waves : 4;
+        G = (NP + want_waves - 1) / want_waves;
+        if (G > gmax) G = gmax;
+        if (G < 1) G = 1;
+        if (!lds_fits(G) && lds_fits(gmax))
+            while (!lds_fits(G)) ++G;
+        if (G > CU_PER_XCD && XCD_COUNT == 8 && ((G + 7) & ~7) <= gmax) G = (G + 7) & ~7;   // whole teams
+    }
+    if (G > NP) G = NP;
+    g.G = G;
+    g.chains_per_launch = cpl;
+    g.ppg = (NP + G - 1) / G;
+    const bool want_stream = tu.residency == RES_STREAM;
+    g.mode = (!want_stream && lds_fits(G)) ? 1 : 2;
+    int waves = t_waves > 0 ? t_waves : (g.ppg < 4 ? g.ppg : (g.mode == 1 ? (g.ppg < 8 ? g.ppg : 8) : 8));
+    if (waves > 8) waves = 8;   // 512-thread workgroups: 256 VGPRs per lane, no spills
+    if (waves < 1) waves = 1;
+    g.waves = waves;
+    // one slot per XCD while a chain's groups fit one XCD's CUs; otherwise any placement
+    g.nslot = (G <= CU_PER_XCD) ? XCD_COUNT : cpl;
+    return g;
+}
+
+// One-XCD register residency: each chain on the groups of one XCD, one chain per XCD.  With more
+// chains than XCDs, the packed variant's queries (VGPRs <= 128, two groups per CU) decide whether
+// chains c and c + xcds may share XCD c % xcds; they are worth asking only when
+// gibbs_pack_candidate holds.
+inline bool gibbs_one_xcd_reg(const Geometry& geo, const Chip& chip, const bmc_tuning& tu) {
+    return geo.mode == 0 && geo.G > 1 && geo.nslot == chip.xcds && chip.xcds > 1 &&
+           geo.G <= chip.cu_per_xcd && tu.groups_per_chain <= 0;
+}
+inline bool gibbs_pack_candidate(const Geometry& geo, const Chip& chip, const bmc_tuning& tu, int n_chains) {
+    return gibbs_one_xcd_reg(geo, chip, tu) && n_chains > geo.nslot && 2 * geo.waves <= 16;
+}
+
+// One launch of the persistent Gibbs loop: chains c0 .. c0 + n_chains - 1.
+struct GibbsLaunch {
+    int c0, n_chains, chains_per_pass, waves, nslot, pack, bundle_slots, bundle_bal;
+    int resident;   // workgroups that stay in the loop (the residency check)
+};
+struct GibbsPlan {
+    std::vector<GibbsLaunch> launches;
+    int max_per_launch;        // the most chains one launch holds (sizes the exchange words)
+    int64_t passes = 0;        // X passes per iteration (a pass serving several chains counts once)
+    int chains_per_pass = 1;   // the largest of the launches
+    int waves_per_group = 0;   // the largest of the launches (geo.waves without any)
+};
+
+// Split n_chains over launches of the geometry.  pack_ok: the packed variant exists for this
+// geometry and two of its groups fit a CU (the device's answer; only used where
+// gibbs_pack_candidate holds).
+inline GibbsPlan plan_gibbs(const Geometry& geo, const Shape& s, const bmc_tuning& tu, const Chip& chip,
+                            int n_chains, bool pack_ok) {
+    // One-XCD register residency with more than 8 chains.
+    // (a) 16 chains or more: the register-resident panels of an XCD's 32 groups serve a BUNDLE of
+    //     2 / 4 / 8 chains per pass (gibbs_multi_kernel, one bundle per XCD: 16 .. 64 chains in one
+    //     launch); every chain bit-identical to its solo run.
+    // (b) 9 .. 15 chains left: chains c and c + 8 share XCD c % 8, two workgroups per CU side by
+    //     side.  That needs 4 waves per SIMD (two 5-wave groups must fit whatever SIMDs their
+    //     waves land on), i.e. the kernel variant held to 128 VGPRs, which exists for light
+    //     shapes only.  (Three or four per XCD are not used: measured, the launch then stalls.)
+    const int xcds = chip.xcds, K = s.k;
+    const bool xcd_bundles = gibbs_one_xcd_reg(geo, chip, tu) && geo.ppw == 1 && s.vec == 1 && geo.G <= 32 &&
+                             tu.chains_per_pass != 1 && gibbs_reg_multi_cap(K, s.f32, s.vec) >= 2;
+    pack_ok = pack_ok && gibbs_pack_candidate(geo, chip, tu, n_chains);
+    GibbsPlan p;
+    p.max_per_launch = geo.chains_per_launch;
+    if (pack_ok) p.max_per_launch = 2 * geo.nslot;
+    if (xcd_bundles) p.max_per_launch = 8 * xcds;
+    if (p.max_per_launch < 8) p.max_per_launch = 8;
+    // chains per pass: when the panels are NOT register-resident one read of X can serve up to
+    // 8 chains (one leader wave per chain); 0 = automatic, 1 = off
+    int cpp_max = 1, waves_multi = geo.waves;
+    // (register residency: only the whole-chip form, one chain bundle per launch, one panel per
+    // wave; the one-XCD-per-chain form already runs 8 chains side by side)
+    const bool reg_multi_ok = geo.mode == 0 && geo.nslot < 8 && geo.G > 1 && geo.ppw == 1;
+    if ((geo.mode != 0 || reg_multi_ok) && n_chains > 1 && tu.chains_per_pass != 1) {
+        // every chain of a pass needs a leader wave: widen the workgroup if the panels alone
+        // would ask for fewer waves (the extra waves own no panel, they only lead a chain)
+        int want = n_chains >= 8 ? 8 : n_chains >= 4 ? 4 : 2;
+        if (tu.chains_per_pass > 1 && tu.chains_per_pass < want) want = tu.chains_per_pass >= 4 ? 4 : 2;
+        if (waves_multi < want && tu.waves_per_group <= 0) waves_multi = want;
+        cpp_max = waves_multi >= 8 ? 8 : waves_multi >= 4 ? 4 : waves_multi >= 2 ? 2 : 1;
+        if (cpp_max > want) cpp_max = want;
+        if (reg_multi_ok) {
+            const int cap = gibbs_reg_multi_cap(K, s.f32, s.vec);
+            if (cpp_max > cap) cpp_max = cap < 2 ? 1 : cap;
+        }
+    }
+    for (int c0 = 0; c0 < n_chains;) {
+        const int left = n_chains - c0;
+        GibbsLaunch l{};
+        l.c0 = c0;
+        l.chains_per_pass = 1;
+        l.nslot = geo.nslot;
+        // bundles pay from 4 chains per XCD on (measured at C2, us per iteration for all chains:
+        // 16 chains 1.37 as bundles of 2 against 1.05 packed two per XCD; 32 chains 1.81 as
+        // bundles of 4 against 2 x 1.05; 64 chains 2.33 as bundles of 8); with fewer they are
+        // used when asked for (chains_per_pass = 2) or when the shape has no packed variant
+        if (xcd_bundles && left >= 2 * xcds && (left >= 4 * xcds || !pack_ok || tu.chains_per_pass > 1)) {
+            // one bundle per XCD: as many chains per bundle as keep all XCDs busy
+            int cap = gibbs_reg_multi_cap(K, s.f32, s.vec);
+            if (tu.chains_per_pass > 1 && tu.chains_per_pass < cap) cap = tu.chains_per_pass;
+            int cpp = 2;
+            while (cpp * 2 <= cap && cpp * 2 * xcds <= left) cpp *= 2;
+            // 40 .. 63 chains: bundles of 8 on 5 .. 7 XCDs in one launch (2.3 us per iteration at C2)
+            // rather than bundles of 4 on all 8 (1.8 us for 32 of them) plus a second launch
+            if (cap >= 8 && cpp == 4 && left >= 5 * 8) cpp = 8;
+            const int bundles = left / cpp < xcds ? left / cpp : xcds;
+            l.chains_per_pass = cpp;
+            l.n_chains = bundles * cpp;
+            l.bundle_slots = xcds;
+            l.waves = geo.waves > cpp ? geo.waves : cpp;   // a leader wave per chain
+            // bundles of 8 on 8 waves, at most 5 panels per group, two panels of K columns in a
+            // wave's registers: the balanced layout (4 chains of panel w % 4 + 1 chain of the
+            // fifth panel per wave instead of 8 chains of one panel on waves 0 .. 3)
+#ifndef BMC_NO_BAL
+            // (panels_per_wave = 1 asked for explicitly keeps the one-panel layout: the A/B knob)
+            l.bundle_bal = gibbs_bundle_bal_shape(K, s.f32, s.vec, cpp) && l.waves == 8 && geo.ppg <= 5 &&
+                           tu.panels_per_wave != 1;
+#endif
+            l.resident = bundles * geo.G;
+            p.passes += bundles;
+        } else if (cpp_max > 1 && left >= 2) {
+            int cpp = 1;
+            while (cpp * 2 <= left && cpp * 2 <= cpp_max) cpp *= 2;
+            l.chains_per_pass = cpp;
+            l.n_chains = cpp;
+            l.waves = waves_multi;
+            l.resident = geo.G;
+            p.passes += 1;
+        } else {
+            l.waves = geo.waves;
+            if (pack_ok && left > geo.nslot) {
+                l.pack = 1;
+                l.nslot = 2 * geo.nslot;
+            }
+            const int cap = l.pack ? l.nslot : geo.chains_per_launch;
+            l.n_chains = left < cap ? left : cap;
+            l.resident = l.n_chains * geo.G;
+            p.passes += l.n_chains;
+        }
+        if (l.chains_per_pass > p.chains_per_pass) p.chains_per_pass = l.chains_per_pass;
+        if (l.waves > p.waves_per_group) p.waves_per_group = l.waves;
+        p.launches.push_back(l);
+        c0 += l.n_chains;
+    }
+    if (p.waves_per_group == 0) p.waves_per_group = geo.waves;   // widened for leader waves
+    return p;
+}
+
+}  // namespace bmc

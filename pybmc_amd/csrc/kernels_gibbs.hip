@@ -87,13 +87,11 @@ __device__ __forceinline__ double draw_u(double lam, double c1, double c2, doubl
 
 // PACK: the same kernel held to 128 VGPRs (4 waves per SIMD), so that two 5-wave groups of
 // different chains fit a CU side by side whatever SIMDs their waves land on -- used when more
-// than 8 chains share a launch (two per XCD).  It exists only for shapes with one panel of at
-// most 64 data VGPRs per wave (e.g. K = 32 doubles); at 136 VGPRs the unpacked kernel is 3 %
-// faster per iteration, so a single chain keeps that one.
+// than 8 chains share a launch (two per XCD).  It exists only for the shapes of gibbs_packable;
+// at 136 VGPRs the unpacked kernel is 3 % faster per iteration, so a single chain keeps that one.
 template <typename T, int VEC, int MODE, int KMAX, int PPW>
 constexpr bool loop_can_pack() {
-    return MODE == MODE_REG && PPW == 1 && VEC == 1 && KMAX * (int)(sizeof(T) / 4) <= 64 &&
-           !(sizeof(T) == 4 && KMAX == 64);   // (f32, 64 columns spills at 128)
+    return MODE == MODE_REG && gibbs_packable(KMAX, sizeof(T) == 4, VEC, PPW);
 }
 
 // SMALLG: the host promises G <= 32 (one-level exchange); the loop then exists in two copies,
@@ -1101,20 +1099,21 @@ static hipError_t launch_one(SimplexTag, const SimplexArgs& a, hipStream_t s) {
 
 template <typename Tag, typename Args, typename T, int KMAX>
 static hipError_t launch_reg(const Args& a, hipStream_t s) {
-    // rows per lane (PPW * VEC) * KMAX * (registers per element) <= 128 data VGPRs keeps the
-    // kernel spill-free; VEC = 2 panels are supported with one panel per wave
+    // rows per lane (PPW * VEC) within gibbs_reg_capacity keeps the kernel spill-free; VEC = 2
+    // panels are supported with one panel per wave
+    constexpr bool f32 = sizeof(T) == 4;
     if (a.P.vec == 2) {
-        if constexpr (KMAX * sizeof(T) <= 256)
+        if constexpr (gibbs_reg_capacity(KMAX, f32, 2))
             if (a.reg_ppw == 1) return launch_one<T, 2, MODE_REG, KMAX, 1>(Tag{}, a, s);
         return hipErrorInvalidValue;
     }
     switch (a.reg_ppw) {
         case 1: return launch_one<T, 1, MODE_REG, KMAX, 1>(Tag{}, a, s);
         case 2:
-            if constexpr (KMAX * sizeof(T) <= 256) return launch_one<T, 1, MODE_REG, KMAX, 2>(Tag{}, a, s);
+            if constexpr (gibbs_reg_capacity(KMAX, f32, 2)) return launch_one<T, 1, MODE_REG, KMAX, 2>(Tag{}, a, s);
             break;
         case 4:
-            if constexpr (KMAX * sizeof(T) <= 128) return launch_one<T, 1, MODE_REG, KMAX, 4>(Tag{}, a, s);
+            if constexpr (gibbs_reg_capacity(KMAX, f32, 4)) return launch_one<T, 1, MODE_REG, KMAX, 4>(Tag{}, a, s);
             break;
     }
     return hipErrorInvalidValue;
@@ -1142,20 +1141,6 @@ static hipError_t launch_t(const Args& a, hipStream_t s) {
     }
 #undef BMC_MEM
     return hipErrorInvalidValue;
-}
-
-int gibbs_reg_capacity(int k, int f32, int rows_per_lane) {
-    // data VGPRs per lane: f64 panels take two registers per element, f32 panels one;
-    // rows_per_lane = panels per wave x rows per lane of a panel
-    if (k > 64) return 0;
-    const int kmax = k <= 8 ? 8 : k <= 16 ? 16 : k <= 32 ? 32 : 64;
-    return rows_per_lane * kmax * (f32 ? 1 : 2) <= 128 ? 1 : 0;
-}
-
-template <typename Args>
-static bool geometry_ok(const Args& a) {
-    return a.P.k <= 64 * MAX_KCH && a.G <= MAX_GROUPS && a.G >= 1 && a.waves >= 1 &&
-           a.waves <= 8 && a.nslot >= 1 && a.nslot <= 2048;
 }
 
 template <typename T, int VEC, int MODE>
@@ -1189,26 +1174,13 @@ static hipError_t launch_multi_t(const GibbsArgs& a, hipStream_t s) {
     return hipErrorInvalidValue;
 }
 
-// register residency with several chains per pass: one panel per wave (PPW = 1).  The panel
-// (KMAX*VEC values) plus two blocks of u plus the leaders' state must fit 256 VGPRs: the most
-// chains per pass that hipcc compiles without scratch, per (columns, storage type, rows per lane)
-static constexpr int reg_multi_cap(int kmax, bool f32, int vec) {
-    if (vec == 1) return 8;
-    if (vec == 2) return kmax * (f32 ? 4 : 8) >= 256 ? 4 : 8;   // 128 VGPRs of panel: 4 chains
-    return 0;
-}
-int gibbs_reg_multi_cap(int k, bool f32, int vec) {
-    const int kmax = k <= 8 ? 8 : k <= 16 ? 16 : k <= 32 ? 32 : k <= 64 ? 64 : 0;
-    return kmax ? reg_multi_cap(kmax, f32, vec) : 0;
-}
-
 // register residency with several chains per pass: one panel per wave (PPW = 1)
 template <typename T, int VEC, int KMAX>
 static hipError_t launch_multi_reg_k(const GibbsArgs& a, hipStream_t s) {
     const size_t lds = gibbs_lds_bytes(a);
 #define BMC_MR(C)                                                                            \
     do {                                                                                         \
-        if constexpr (VEC == 1 && C == 8 && KMAX >= 16 && KMAX * sizeof(T) <= 256) {             \
+        if constexpr (gibbs_bundle_bal_shape(KMAX, sizeof(T) == 4, VEC, C)) {                   \
             if (a.bundle_slots > 0 && a.bundle_bal)                                              \
                 return launch_or_query(                                                          \
                     (const void*)gibbs_multi_kernel<T, VEC, MODE_REG, C, KMAX, 2, true, true>,     \
@@ -1226,7 +1198,7 @@ static hipError_t launch_multi_reg_k(const GibbsArgs& a, hipStream_t s) {
                                dim3(a.G), dim3(64 * a.waves), lds, s, a, a.query_occupancy);     \
     } while (0)
     // only the combinations that fit the 256-VGPR budget without spilling are built
-    constexpr int CMAX = reg_multi_cap(KMAX, sizeof(T) == 4, VEC);
+    constexpr int CMAX = gibbs_reg_multi_cap(KMAX, sizeof(T) == 4, VEC);
     switch (a.chains_per_pass) {
         case 2: if constexpr (CMAX >= 2) BMC_MR(2); break;
         case 4: if constexpr (CMAX >= 4) BMC_MR(4); break;
@@ -1375,18 +1347,10 @@ __global__ __launch_bounds__(MANY ? 256 : 64) void simplex_wave_kernel(SimplexAr
     }
 }
 
-// row panels x columns a wave keeps: RMAX * KMAX <= 128 (and at most 16 panels = 1024 rows)
-static constexpr int wave_kmax(int k) { return k <= 4 ? 4 : k <= 8 ? 8 : k <= 16 ? 16 : k <= 32 ? 32 : 0; }
-static constexpr int wave_rmax(int np) { return np <= 2 ? 2 : np <= 4 ? 4 : np <= 8 ? 8 : np <= 12 ? 12 : np <= 16 ? 16 : 0; }
-int gibbs_wave_capacity(int k, int npanels) {   // npanels: per WAVE
-    const int km = wave_kmax(k), rm = wave_rmax(npanels);
-    return (km > 0 && rm > 0 && km * rm <= 128) ? km * rm : 0;
-}
-
 template <typename T, int RMAX, int KM>
 static const void* wave_kernel_of(GibbsTag, int waves) {
-    if (waves > 4) {   // 8 waves: two per SIMD, 256 registers each -- the shapes that fit them
-        if constexpr (RMAX * KM <= 64) return (const void*)gibbs_wave_kernel<T, RMAX, KM, 8>;   // (12 x 8 spills at 256)
+    if (waves > 4) {
+        if constexpr (gibbs_wave_fits(RMAX * KM, 8)) return (const void*)gibbs_wave_kernel<T, RMAX, KM, 8>;
         return nullptr;
     }
     return waves > 1 ? (const void*)gibbs_wave_kernel<T, RMAX, KM, 4> : (const void*)gibbs_wave_kernel<T, RMAX, KM, 1>;
@@ -1402,7 +1366,7 @@ template <typename Tag, typename T, int RMAX, typename Args>
 static hipError_t launch_wave_r(const Args& a, int n_blocks, hipStream_t s) {
     const dim3 grid((unsigned)n_blocks), block(64 * (a.waves > 1 ? a.waves : 1));
 #define BMC_WV(KM)                                                                              \
-    if constexpr (RMAX * KM <= 128) {                                                           \
+    if constexpr (gibbs_wave_capacity(KM, RMAX) > 0) {                                          \
         const void* fn = wave_kernel_of<T, RMAX, KM>(Tag{}, a.waves);                           \
         if (!fn) return hipErrorInvalidValue;                                                   \
         return launch_or_query(fn, grid, block, 0, s, a, a.query_occupancy);                    \
@@ -1441,19 +1405,15 @@ hipError_t launch_gibbs(const GibbsArgs& a, hipStream_t s) {
         return a.P.f32 ? launch_wave<GibbsTag, float>(a, a.n_chains, s)
                        : launch_wave<GibbsTag, double>(a, a.n_chains, s);
     }
-    if (a.chains_per_pass > 1) {
+    if (!geometry_ok(a.P.k, a.G, a.waves, a.nslot) ||
+        !gibbs_chains_ok(a.n_chains, a.chains_per_pass, a.waves, a.nslot, a.bundle_slots, a.G, a.mode))
+        return hipErrorInvalidValue;
+    if (a.chains_per_pass > 1) {   // bundles of chains_per_pass chains (one, or one per slot)
         if (a.query_regs) return hipErrorInvalidValue;
-        // bundles of chains_per_pass chains (one, or one per slot); a leader wave per chain
-        if (!geometry_ok(a) || a.waves < a.chains_per_pass || a.n_chains < a.chains_per_pass ||
-            a.n_chains % a.chains_per_pass != 0 || a.bundle_slots < 0 ||
-            a.n_chains / a.chains_per_pass > (a.bundle_slots > 0 ? a.bundle_slots : 1) ||
-            (a.bundle_slots > 0 && (a.G > 32 || a.mode != MODE_REG)))
-            return hipErrorInvalidValue;
         if (a.mode == MODE_REG)
             return a.P.f32 ? launch_multi_reg<float>(a, s) : launch_multi_reg<double>(a, s);
         return a.P.f32 ? launch_multi_t<float>(a, s) : launch_multi_t<double>(a, s);
     }
-    if (!geometry_ok(a) || a.n_chains < 1 || a.n_chains > a.nslot) return hipErrorInvalidValue;
     return a.P.f32 ? launch_t<GibbsTag, GibbsArgs, float>(a, s)
                    : launch_t<GibbsTag, GibbsArgs, double>(a, s);
 }
@@ -1463,7 +1423,7 @@ hipError_t launch_simplex(const SimplexArgs& a, hipStream_t s) {
         if (a.Km < 1 || a.Km > 64) return hipErrorInvalidValue;
         return a.P.f32 ? launch_wave<SimplexTag, float>(a, 1, s) : launch_wave<SimplexTag, double>(a, 1, s);
     }
-    if (!geometry_ok(a) || a.Km < 1) return hipErrorInvalidValue;
+    if (!geometry_ok(a.P.k, a.G, a.waves, a.nslot) || a.Km < 1) return hipErrorInvalidValue;
     return a.P.f32 ? launch_t<SimplexTag, SimplexArgs, float>(a, s)
                    : launch_t<SimplexTag, SimplexArgs, double>(a, s);
 }

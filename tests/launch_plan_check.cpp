@@ -1,0 +1,202 @@
+// CPU check of pybmc_amd/csrc/bmc_plan.h, the launch planner of the Gibbs loop.
+//   (no argument)  one line per named case: the shape, the geometry and every launch of the plan;
+//                  tests/test_launch_plan.py compares them with the plans of the parent commit.
+//   sweep          plans over a grid of shapes x chain counts x cu_limit x tunings; every plan
+//                  must cover its chains once and in order, fit its exchange words, and pass the
+//                  argument checks of launch_gibbs.  Prints "sweep <plans> <failures>" last.
+#include "../pybmc_amd/csrc/bmc_plan.h"
+
+#include <cstdio>
+#include <cstring>
+
+using namespace bmc;
+
+struct Case {
+    const char* name;
+    int64_t n;
+    int k, f32, n_chains, cu_limit;
+    int groups, waves, residency, ppw, cpp;   // bmc_tuning fields (0: automatic)
+    int pack_ok;                              // what the device queries of run_common answer
+};
+
+static const Case CASES[] = {
+    // name                 n       k   f32 chains cu  G   W  res ppw cpp pack
+    {"ref629x3",            629,    3,  0,  1,     0,  0,  0, 0,  0,  0,  0},
+    {"ref629x3_256ch",      629,    3,  0,  256,   0,  0,  0, 0,  0,  0,  0},
+    {"ref629x3_f32",        629,    3,  1,  1,     0,  0,  0, 0,  0,  0,  0},
+    {"n2500x8_4waves",      2500,   8,  0,  1,     0,  0,  0, 0,  0,  0,  0},
+    {"n2500x8_256ch",       2500,   8,  0,  256,   0,  0,  0, 0,  0,  0,  0},
+    {"n8000x4_8waves",      8000,   4,  0,  1,     0,  0,  0, 0,  0,  0,  0},
+    {"golden64x8",          64,     8,  0,  1,     0,  0,  0, 0,  0,  0,  0},
+    {"golden3x2",           3,      2,  0,  1,     0,  0,  0, 0,  0,  0,  0},
+    {"c2_1",                10000,  32, 0,  1,     0,  0,  0, 0,  0,  0,  0},
+    {"c2_1_pack",           10000,  32, 0,  1,     0,  0,  0, 0,  0,  0,  1},
+    {"c2_8",                10000,  32, 0,  8,     0,  0,  0, 0,  0,  0,  0},
+    {"c2_8_pack",           10000,  32, 0,  8,     0,  0,  0, 0,  0,  0,  1},
+    {"c2_9",                10000,  32, 0,  9,     0,  0,  0, 0,  0,  0,  0},
+    {"c2_9_pack",           10000,  32, 0,  9,     0,  0,  0, 0,  0,  0,  1},
+    {"c2_15",               10000,  32, 0,  15,    0,  0,  0, 0,  0,  0,  0},
+    {"c2_15_pack",          10000,  32, 0,  15,    0,  0,  0, 0,  0,  0,  1},
+    {"c2_16",               10000,  32, 0,  16,    0,  0,  0, 0,  0,  0,  0},
+    {"c2_16_pack",          10000,  32, 0,  16,    0,  0,  0, 0,  0,  0,  1},
+    {"c2_32",               10000,  32, 0,  32,    0,  0,  0, 0,  0,  0,  0},
+    {"c2_32_pack",          10000,  32, 0,  32,    0,  0,  0, 0,  0,  0,  1},
+    {"c2_40",               10000,  32, 0,  40,    0,  0,  0, 0,  0,  0,  0},
+    {"c2_40_pack",          10000,  32, 0,  40,    0,  0,  0, 0,  0,  0,  1},
+    {"c2_63",               10000,  32, 0,  63,    0,  0,  0, 0,  0,  0,  0},
+    {"c2_63_pack",          10000,  32, 0,  63,    0,  0,  0, 0,  0,  0,  1},
+    {"c2_64",               10000,  32, 0,  64,    0,  0,  0, 0,  0,  0,  0},
+    {"c2_64_pack",          10000,  32, 0,  64,    0,  0,  0, 0,  0,  0,  1},
+    {"c2_130_pack",         10000,  32, 0,  130,   0,  0,  0, 0,  0,  0,  1},
+    {"c2_cu128_1",          10000,  32, 0,  1,     128, 0, 0, 0,  0,  0,  0},
+    {"c2_cu128_16_pack",    10000,  32, 0,  16,    128, 0, 0, 0,  0,  0,  1},
+    {"c2_cu32_1",           10000,  32, 0,  1,     32, 0,  0, 0,  0,  0,  0},
+    {"c2_cu32_8",           10000,  32, 0,  8,     32, 0,  0, 0,  0,  0,  0},
+    {"c4_1",                200000, 64, 1,  1,     0,  0,  0, 0,  0,  0,  0},
+    {"c4_8",                200000, 64, 1,  8,     0,  0,  0, 0,  0,  0,  0},
+    {"c5_1",                50000,  256, 0, 1,     0,  0,  0, 0,  0,  0,  0},
+    {"c5_8",                50000,  256, 0, 8,     0,  0,  0, 0,  0,  0,  0},
+    {"hbm410mb_1",          400000, 256, 1, 1,     0,  0,  0, 0,  0,  0,  0},
+    // the tuning knobs the GPU tests set
+    {"ref629x4_w1",         629,    4,  0,  2,     0,  0,  1, 0,  0,  0,  0},
+    {"ref629x4_g10_w1",     629,    4,  0,  2,     0,  10, 1, 0,  0,  0,  0},
+    {"n1000x4_g1_w4",       1000,   4,  0,  2,     0,  1,  4, 0,  0,  0,  0},
+    {"n8000x4_w8",          8000,   4,  0,  2,     0,  0,  8, 0,  0,  0,  0},
+    {"n3000x8_res3_8ch",    3000,   8,  0,  8,     0,  0,  0, 3,  0,  0,  0},
+    {"n3000x8_res3_cpp1",   3000,   8,  0,  8,     0,  0,  0, 3,  0,  1,  0},
+    {"n3000x8_res2_5ch",    3000,   8,  0,  5,     0,  0,  0, 2,  0,  0,  0},
+    {"n700x130_res3_3ch",   700,    130, 0, 3,     0,  0,  0, 3,  0,  0,  0},
+    {"n3000x8_g3_w2_res2",  3000,   8,  0,  2,     0,  3,  2, 2,  0,  0,  0},
+    {"c2_19_cpp2_pack",     10000,  32, 0,  19,    0,  0,  0, 0,  0,  2,  1},
+    {"c2_40_cpp4_pack",     10000,  32, 0,  40,    0,  0,  0, 0,  0,  4,  1},
+    {"c2_64_cpp1_pack",     10000,  32, 0,  64,    0,  0,  0, 0,  0,  1,  1},
+    {"c2_64_ppw1",          10000,  32, 0,  64,    0,  0,  0, 0,  1,  0,  0},
+    {"n9000x16f32_64ch",    9000,   16, 1,  64,    0,  0,  0, 0,  0,  0,  0},
+    {"n9000x16f32_64ch_ppw1", 9000, 16, 1,  64,    0,  0,  0, 0,  1,  0,  0},
+    {"c2_res3_8ch",         10000,  32, 0,  8,     0,  0,  0, 3,  0,  0,  0},
+    {"n100000x32_4ch",      100000, 32, 0,  4,     0,  0,  0, 0,  0,  0,  0},
+};
+
+static Shape shape_of(int64_t n, int k, int f32) {
+    const int vec = choose_vec(n, k, f32);
+    return Shape{n, k, f32, vec, (int)((n + 64 * vec - 1) / (64 * vec))};
+}
+
+static bmc_tuning tuning(int groups, int waves, int residency, int ppw, int cpp, int cu_limit) {
+    bmc_tuning t;
+    std::memset(&t, 0, sizeof t);
+    t.groups_per_chain = groups;
+    t.waves_per_group = waves;
+    t.residency = residency;
+    t.panels_per_wave = ppw;
+    t.chains_per_pass = cpp;
+    t.cu_limit = cu_limit;
+    return t;
+}
+
+static void print_case(const Case& c) {
+    const Shape s = shape_of(c.n, c.k, c.f32);
+    const bmc_tuning tu = tuning(c.groups, c.waves, c.residency, c.ppw, c.cpp, c.cu_limit);
+    const Chip chip = chip_of(256, c.cu_limit);
+    const Geometry g = choose_geometry(s, tu, chip, c.n_chains, true, 8);
+    const GibbsPlan p = plan_gibbs(g, s, tu, chip, c.n_chains, c.pack_ok != 0);
+    std::printf("%s: vec=%d np=%d | G=%d waves=%d ppg=%d mode=%d ppw=%d nslot=%d cpl=%d one_wave=%d | "
+                "max=%d passes=%lld cpp=%d wpg=%d |",
+                c.name, s.vec, s.npanels, g.G, g.waves, g.ppg, g.mode, g.ppw, g.nslot, g.chains_per_launch,
+                g.one_wave, p.max_per_launch, (long long)p.passes, p.chains_per_pass, p.waves_per_group);
+    // c0+chains cpp/waves/nslot/pack/bundle_slots/bundle_bal/resident
+    for (const GibbsLaunch& l : p.launches)
+        std::printf(" %d+%d:%d/%d/%d/%d/%d/%d/%d", l.c0, l.n_chains, l.chains_per_pass, l.waves, l.nslot, l.pack,
+                    l.bundle_slots, l.bundle_bal, l.resident);
+    std::printf("\n");
+}
+
+static long failures = 0;
+static void fail(const char* what, const Shape& s, const bmc_tuning& tu, int n_chains, bool pack) {
+    if (++failures <= 20)
+        std::printf("FAIL %s: n=%lld k=%d f32=%d chains=%d cu_limit=%d G=%d W=%d res=%d ppw=%d cpp=%d pack=%d\n",
+                    what, (long long)s.n, s.k, s.f32, n_chains, tu.cu_limit, tu.groups_per_chain,
+                    tu.waves_per_group, tu.residency, tu.panels_per_wave, tu.chains_per_pass, (int)pack);
+}
+
+static long sweep() {
+    const int64_t ns[] = {1, 3, 64, 100, 629, 1000, 2500, 4000, 8000, 10000, 16000, 30000, 65000,
+                          100000, 200000, 400000, 1000000};
+    const int ks[] = {1, 3, 4, 8, 12, 16, 24, 32, 48, 64, 65, 128, 256};
+    const int cu_limits[] = {0, 128, 64, 32, 16};
+    const int chains[] = {1, 2, 3, 4, 5, 7, 8, 9, 12, 15, 16, 17, 19, 24, 31, 32, 33, 37, 40, 45, 48,
+                          63, 64, 65, 100, 130, 256, 300, 2048, 3000};
+    const int knobs[][5] = {{0, 0, 0, 0, 0}, {0, 1, 0, 0, 0}, {0, 2, 0, 0, 0}, {0, 4, 0, 0, 0}, {0, 8, 0, 0, 0},
+                            {1, 0, 0, 0, 0}, {10, 0, 0, 0, 0}, {32, 0, 0, 0, 0}, {10, 1, 0, 0, 0},
+                            {1, 4, 0, 0, 0}, {3, 2, 2, 0, 0}, {0, 0, 1, 0, 0}, {0, 0, 2, 0, 0},
+                            {0, 0, 3, 0, 0}, {0, 0, 3, 0, 1}, {0, 0, 1, 0, 1}, {0, 0, 0, 0, 1},
+                            {0, 0, 0, 0, 2}, {0, 0, 0, 0, 4}, {0, 0, 0, 0, 8}, {0, 0, 0, 1, 0},
+                            {0, 0, 0, 2, 0}, {0, 0, 0, 4, 0}};
+    long plans = 0;
+    for (int64_t n : ns)
+        for (int k : ks)
+            for (int f32 : {0, 1}) {
+                const Shape s = shape_of(n, k, f32);
+                for (const auto& kn : knobs)
+                    for (int cl : cu_limits) {
+                        const bmc_tuning tu = tuning(kn[0], kn[1], kn[2], kn[3], kn[4], cl);
+                        const Chip chip = chip_of(256, cl);
+                        if (tu.groups_per_chain > chip.groups_max) continue;   // run_common: BMC_EINVAL
+                        for (int nc : chains) {
+                            const Geometry g = choose_geometry(s, tu, chip, nc, true, 8);
+                            for (bool flag : {false, true}) {
+                                // the device queries answer yes only for a shape the packed kernel exists for
+                                const bool pack_ok = flag && gibbs_packable(s.k, s.f32, s.vec, g.ppw);
+                                const GibbsPlan p = plan_gibbs(g, s, tu, chip, nc, pack_ok);
+                                ++plans;
+                                int next = 0;
+                                for (const GibbsLaunch& l : p.launches) {
+                                    if (l.c0 != next || l.n_chains < 1) fail("chains not covered in order", s, tu, nc, pack_ok);
+                                    next = l.c0 + l.n_chains;
+                                    if (l.n_chains > p.max_per_launch) fail("exceeds max_per_launch", s, tu, nc, pack_ok);
+                                    if (l.chains_per_pass > p.chains_per_pass || l.waves > p.waves_per_group)
+                                        fail("summary", s, tu, nc, pack_ok);
+                                    if (g.one_wave) {
+                                        const int rpw = (s.npanels + l.waves - 1) / l.waves;
+                                        const int f = gibbs_wave_capacity(s.k, rpw);
+                                        if (s.vec != 1 || f == 0 || !gibbs_wave_fits(f, l.waves) || l.chains_per_pass != 1 ||
+                                            (l.waves != 1 && l.waves != 2 && l.waves != 4 && l.waves != 8) ||
+                                            l.n_chains > l.nslot || l.nslot > 2048)
+                                            fail("no one-wave kernel", s, tu, nc, pack_ok);
+                                        continue;
+                                    }
+                                    if (!geometry_ok(s.k, g.G, l.waves, l.nslot) ||
+                                        !gibbs_chains_ok(l.n_chains, l.chains_per_pass, l.waves, l.nslot,
+                                                         l.bundle_slots, g.G, g.mode))
+                                        fail("launch_gibbs argument checks", s, tu, nc, pack_ok);
+                                    if (g.mode == 0 && !gibbs_reg_capacity(s.k, s.f32, g.ppw * s.vec))
+                                        fail("register capacity", s, tu, nc, pack_ok);
+                                    if (g.mode == 0 && l.chains_per_pass > gibbs_reg_multi_cap(s.k, s.f32, s.vec) &&
+                                        l.chains_per_pass > 1)
+                                        fail("chains per pass in registers", s, tu, nc, pack_ok);
+                                    if (l.bundle_bal && (!gibbs_bundle_bal_shape(s.k, s.f32, s.vec, l.chains_per_pass) ||
+                                                         l.bundle_slots < 1))
+                                        fail("balanced bundle", s, tu, nc, pack_ok);
+                                    if (l.pack && !gibbs_packable(s.k, s.f32, s.vec, g.ppw))
+                                        fail("packed variant", s, tu, nc, pack_ok);
+                                    if ((g.G > 1 || l.chains_per_pass > 1) &&
+                                        l.resident > chip.groups_max * (l.pack ? 2 : 1))
+                                        fail("co-resident workgroups", s, tu, nc, pack_ok);
+                                }
+                                if (next != nc) fail("chains not all covered", s, tu, nc, pack_ok);
+                            }
+                        }
+                    }
+            }
+    return plans;
+}
+
+int main(int argc, char** argv) {
+    if (argc > 1 && std::strcmp(argv[1], "sweep") == 0) {
+        const long plans = sweep();
+        std::printf("sweep %ld %ld\n", plans, failures);
+        return failures != 0;
+    }
+    for (const Case& c : CASES) print_case(c);
+    return 0;
+}
