@@ -258,6 +258,30 @@ int bmc_comm_init(bmc_ctx* ctx, int32_t world, int32_t rank, const char id[BMC_C
 int bmc_allgather(bmc_ctx* ctx, const void* d_send, void* d_recv, int64_t count_per_rank);
 int bmc_comm_destroy(bmc_ctx* ctx);
 
+/* ---- convergence diagnostics of sampled chains (a capability the reference lacks) ------------
+ * Classic split R-hat and "mean" ESS of Vehtari, Gelman, Simpson, Carpenter & Buerkner (2021),
+ * as Stan and ArviZ (method="split" / "mean") define them; the estimator is written out in
+ * INTEGRATION.md section 6.  samples is [n_chains][iters][ld] f64 (the layout bmc_gibbs_run*
+ * write), column j < n_cols.  The first `burn` draws of each chain are dropped and the
+ * T' = iters - burn kept ones split into two halves of n = T'/2 draws (2 n_chains sequences).
+ * Per column (every output is [n_cols]; any may be NULL):
+ *   mean_out, sd_out   over all kept draws (sd with ddof 1; the middle draw of an odd T' counts)
+ *   rhat_out           split R-hat;   ess_out  effective sample size;   mcse_out  sd / sqrt(ess)
+ *   max_lag_out        the largest autocovariance lag the ESS scan read
+ * A column with W = 0 (constant within every half) or any non-finite value gets NaN r-hat, ess
+ * and mcse (max_lag 0): a value, not an error.  BMC_EINVAL when n < 4, ld < n_cols,
+ * n_chains < 1, burn < 0, or n_chains / n_cols > 65536.  Results are deterministic (no atomics).
+ * bmc_chain_diagnostics stages the host array on the device itself; the _device form reads
+ * caller-owned DEVICE memory on the context's stream (the caller orders its producer before). */
+int bmc_chain_diagnostics(bmc_ctx* ctx, const double* samples, int32_t n_chains, int64_t iters,
+                          int32_t n_cols, int64_t ld, int64_t burn, double* mean_out,
+                          double* sd_out, double* rhat_out, double* ess_out, double* mcse_out,
+                          int64_t* max_lag_out);
+int bmc_chain_diagnostics_device(bmc_ctx* ctx, const void* d_samples, int32_t n_chains,
+                                 int64_t iters, int32_t n_cols, int64_t ld, int64_t burn,
+                                 double* mean_out, double* sd_out, double* rhat_out,
+                                 double* ess_out, double* mcse_out, int64_t* max_lag_out);
+
 /* ---- on-device variates (exposed so the generator itself can be tested) ----
  * normals_out [count_normal] ~ N(0,1); gammas_out [count_gamma] ~ Gamma(shape,1). */
 int bmc_rng_fill(bmc_ctx* ctx, uint64_t seed, int64_t count_normal, double* normals_out,

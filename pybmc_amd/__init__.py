@@ -5,6 +5,7 @@ nonexistent ``Model`` of its ``__all__`` is dropped.
 """
 from .bmc import BayesianModelCombination
 from .data import Dataset
+from .diagnostics import chain_diagnostics
 from .inference_utils import gibbs_sampler, gibbs_sampler_simplex, USVt_hat_extraction
 from .sampling_utils import coverage, rndm_m_random_calculator
 
@@ -16,4 +17,5 @@ __all__ = [
     "USVt_hat_extraction",
     "coverage",
     "rndm_m_random_calculator",
+    "chain_diagnostics",
 ]

@@ -82,6 +82,11 @@ PROTOTYPES = {
                               C.c_uint64, _D, C.POINTER(C.c_int32), _D, C.c_int32, _D,
                               C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, _D, _D,
                               C.POINTER(C.c_int64)]),
+    "bmc_chain_diagnostics": (C.c_int, [_P, _D, C.c_int32, C.c_int64, C.c_int32, C.c_int64,
+                                        C.c_int64, _D, _D, _D, _D, _D, C.POINTER(C.c_int64)]),
+    "bmc_chain_diagnostics_device": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int64,
+                                               C.c_int64, _D, _D, _D, _D, _D,
+                                               C.POINTER(C.c_int64)]),
     "bmc_rng_fill": (C.c_int, [_P, C.c_uint64, C.c_int64, _D, C.c_double, C.c_int64, _D]),
     "bmc_philox_raw": (C.c_int, [_P, C.c_uint64, C.c_uint32, C.c_int64, C.POINTER(C.c_uint32)]),
 }
@@ -447,6 +452,29 @@ class Context:
         self._last_predict = (M, S)
         cov = None if hits is None else [int(h) / M * 100 for h in hits]
         return (self.predict_draws(draws_order) if want_draws else None), bands, cov
+
+    # -- convergence diagnostics ------------------------------------------------------------
+    def _diag_call(self, fn, ptr, n_chains, iters, n_cols, ld, burn):
+        out = {k: np.empty(n_cols) for k in ("mean", "sd", "r_hat", "ess", "mcse_mean")}
+        lag = np.empty(n_cols, dtype=np.int64)
+        self._check(fn(self._h, ptr, int(n_chains), int(iters), int(n_cols), int(ld), int(burn),
+                       _dptr(out["mean"]), _dptr(out["sd"]), _dptr(out["r_hat"]),
+                       _dptr(out["ess"]), _dptr(out["mcse_mean"]),
+                       lag.ctypes.data_as(C.POINTER(C.c_int64))))
+        out["max_lag"] = lag
+        return out
+
+    def chain_diagnostics(self, samples, n_chains, iters, n_cols, ld, burn=0):
+        """Split R-hat / ESS of a HOST f64 array whose element (c, t, j) is at
+        c*iters*ld + t*ld + j (bmc_chain_diagnostics).  Returns a dict of [n_cols] arrays."""
+        return self._diag_call(self._lib.bmc_chain_diagnostics, samples.ctypes.data_as(_D),
+                               n_chains, iters, n_cols, ld, burn)
+
+    def chain_diagnostics_device(self, d_ptr, n_chains, iters, n_cols, ld, burn=0):
+        """The same on DEVICE memory (bmc_chain_diagnostics_device), read on the context's
+        stream: the caller orders its producer before the call."""
+        return self._diag_call(self._lib.bmc_chain_diagnostics_device, _P(d_ptr), n_chains, iters,
+                               n_cols, ld, burn)
 
     # -- variates -----------------------------------------------------------------------
     def rng_fill(self, seed, n_normal=0, shape=1.0, n_gamma=0):

@@ -40,6 +40,7 @@ class BayesianModelCombination:
         self.truth_column_name = truth_column_name
         self.device = device
         self.samples = None
+        self.n_chains = None
         self.current_property = None
         self.centered_experiment_train = None
         self.U_hat = self.S_hat = self.Vt_hat = self.Vt_hat_normalized = None
@@ -133,6 +134,7 @@ class BayesianModelCombination:
             self.samples = gibbs_sampler_simplex(
                 self.centered_experiment_train, self.U_hat, self.Vt_hat, self.S_hat,
                 iterations, [nu0, sigma20], burn=burn, stepsize=stepsize, device=self.device)
+            self.n_chains = 1
         else:
             dtype = opts.get("dtype")
             if dtype is not None and np.dtype(dtype) not in (np.dtype(np.float32),
@@ -160,6 +162,27 @@ class BayesianModelCombination:
             self.last_stats = stats
             # several chains are pooled along the sample axis
             self.samples = res if res.ndim == 2 else res.reshape(-1, res.shape[-1])
+            self.n_chains = n_chains
+
+    # ------------------------------------------------------------- diagnostics
+    def diagnostics(self, burn=0):
+        """Convergence diagnostics of the last ``train()`` (not in the reference): split R-hat,
+        ESS, Monte-Carlo standard error, mean and sd of every coefficient ``beta_i``, of
+        ``sigma`` and of every model weight ``beta Vt_hat + 1/K`` (the numbers a BMC user reads),
+        computed on the GPU (``pybmc_amd.diagnostics``).  The pooled ``samples`` are split back
+        into their ``n_chains`` chains; ``burn`` more draws are dropped from the start of each.
+        Returns a DataFrame indexed by ``beta_0 .. beta_{k-1}``, ``sigma`` and the model names,
+        with columns ``mean``, ``sd``, ``mcse_mean``, ``ess``, ``r_hat``, ``max_lag``."""
+        if self.samples is None or self.Vt_hat is None:
+            raise ValueError("Must call `orthogonalize()` and `train()` before computing diagnostics.")
+        s = np.asarray(self.samples)
+        k1 = s.shape[-1]
+        chains = int(self.n_chains or 1)
+        s = s.reshape(chains, -1, k1)
+        d = _series_diagnostics(s, self.Vt_hat, burn, self.device)
+        index = [f"beta_{i}" for i in range(k1 - 1)] + ["sigma"] + list(self.models)
+        from .diagnostics import KEYS
+        return pd.DataFrame({key: np.asarray(d[key]) for key in KEYS}, index=index)
 
     # ----------------------------------------------------------------- predict
     def _require_trained(self):
@@ -234,3 +257,18 @@ class BayesianModelCombination:
         return predictive_coverage(np.arange(0, 101, 5), df[self.models].to_numpy(), self.samples,
                                    self.Vt_hat, df[self.truth_column_name].to_numpy(),
                                    device=self.device)
+
+
+def _series_diagnostics(samples, Vt_hat, burn, device):
+    """Diagnostics of [beta, sigma, weights] per draw: ONE upload of the (C, T, k+1) samples, the
+    weights beta Vt_hat + 1/K formed next to them on the device (torch matmul), and the
+    ``chain_diagnostics`` kernels on the concatenated (C, T, k+1+K) tensor."""
+    import torch
+
+    from .diagnostics import chain_diagnostics
+
+    dev = torch.device("cuda", device)
+    s = torch.as_tensor(np.ascontiguousarray(samples, dtype=np.float64), device=dev)
+    V = torch.as_tensor(np.ascontiguousarray(Vt_hat, dtype=np.float64), device=dev)
+    w = torch.matmul(s[..., :-1], V) + 1.0 / V.shape[1]
+    return chain_diagnostics(torch.cat([s, w], dim=-1), burn=burn, device=device)

@@ -215,4 +215,28 @@ hipError_t launch_uniform_fill(uint64_t seed, int64_t n, double* out, hipStream_
 size_t gibbs_lds_bytes(const GibbsArgs& a);
 hipError_t launch_gibbs(const GibbsArgs& a, hipStream_t s);
 
+// ---- chain diagnostics (kernels_diag.hip) -------------------------------------------
+// Samples [C][iters][ld] f64, column j < P.  Each chain drops `burn` draws and splits the
+// T' = iters - burn kept ones into two halves of n = T'/2 draws: sequence 2c + h starts at
+// row burn + h * half_off (half_off = T' - n).  Sequences 2C .. 3C-1 exist when T' is odd: the
+// middle draw of each chain, for the pooled mean and sd only.
+struct DiagShape {
+    const double* x;
+    int64_t iters, ld, burn, n, half_off;
+    int32_t C, P, n_seq;
+};
+// mean[m][j] = mean of (x - shift_j), m2[m][j] = sum (x - mean)^2 of sequence m < n_seq, and
+// mean[n_seq][j] = shift_j, the column's first kept draw of chain 0 (device, [n_seq + 1][P] and
+// [n_seq][P]); scratch >= diag_moments_scratch() bytes
+size_t diag_moments_scratch(const DiagShape& d);
+hipError_t launch_diag_moments(const DiagShape& d, double* scratch, double* mean, double* m2,
+                               hipStream_t s);
+// acov_out[a][lc*64 + l] = mean over the 2C halves of (1/n) sum_i d_i d_{i+t}, t = t0 + lc*64 + l,
+// for column cols[a], a < n_active, lags t0 .. t0 + n_lags (rounded up to 64; lags >= n give 0).
+// acov_out is [n_active][ceil(n_lags/64)*64]; scratch >= diag_acov_scratch() bytes.
+size_t diag_acov_scratch(const DiagShape& d, int32_t n_active, int64_t n_lags);
+hipError_t launch_diag_acov(const DiagShape& d, const double* mean, const int32_t* cols,
+                            int32_t n_active, int64_t t0, int64_t n_lags, double* scratch,
+                            double* acov_out, hipStream_t s);
+
 }  // namespace bmc
