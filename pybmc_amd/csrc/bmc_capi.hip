@@ -349,11 +349,12 @@ int gram_device_setup(bmc_ctx* c) {
 // until the bounded spins expire, 4 s): ask the runtime how many workgroups of exactly this
 // kernel, block size and LDS footprint one CU admits and compare with what the launch keeps
 // resident.  `resident` = workgroups that stay in the loop (unused slots leave at once).
-template <typename Args, typename Launch>
-int check_residency(bmc_ctx* c, Args a, int resident, Launch launch, const char* what) {
-    int32_t per_cu = 0;
-    a.query_occupancy = &per_cu;
-    const hipError_t e = launch(a, c->stream);
+// (hipFuncSetAttribute first: the occupancy answer depends on the dynamic LDS the kernel admits)
+int check_residency(bmc_ctx* c, const LoopKernel& k, int resident, const char* what) {
+    int per_cu = 0;
+    hipError_t e = k.fn ? hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds)
+                        : hipErrorInvalidValue;
+    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k.fn, (int)k.block.x, k.lds);
     if (e != hipSuccess)
         return fail(c, e == hipErrorInvalidValue ? BMC_EINVAL : BMC_EHIP,
                     std::string(what) + ": no kernel for this geometry (" + hipGetErrorString(e) + ")");
@@ -410,21 +411,22 @@ int run_common(bmc_ctx* c, int32_t n_chains, int64_t iters, const uint64_t* seed
     const Chip chip = chip_of(c);
     const Geometry geo = choose_geometry(shape_of(c), c->tune, chip, n_chains, true, 8);
     bool pack_ok = false;
-    if (gibbs_pack_candidate(geo, chip, c->tune, n_chains)) {
-        int32_t regs = 0;
+    GibbsLaunch lp{};
+    lp.n_chains = 1; lp.chains_per_pass = 1; lp.waves = geo.waves; lp.nslot = geo.nslot; lp.pack = 1;
+    if (gibbs_pack_candidate(geo, chip, c->tune, n_chains) && gibbs_kernel_key(shape_of(c), geo, lp).pack) {
+        // the packed variant exists for this shape: its VGPRs (<= 128) and two groups per CU?
         GibbsArgs q{};
         q.P = panels_of(c, c->Xrot.p);
         q.G = geo.G; q.waves = geo.waves; q.mode = geo.mode; q.reg_ppw = geo.ppw;
         q.nslot = geo.nslot; q.n_chains = 1; q.chains_per_pass = 1; q.panels_per_group = geo.ppg;
-        q.query_regs = &regs;
-        int32_t per_cu = 0;
-        GibbsArgs qo = q;
-        qo.query_regs = nullptr;
-        qo.pack = 1;
-        qo.query_occupancy = &per_cu;
-        if (launch_gibbs(q, c->stream) == hipSuccess && regs > 0 && regs <= 128 &&
-            launch_gibbs(qo, c->stream) == hipSuccess && per_cu >= 2)
-            pack_ok = true;
+        q.pack = 1;
+        const LoopKernel k = gibbs_kernel(q);
+        hipFuncAttributes at;
+        int per_cu = 0;
+        pack_ok = k.fn && hipFuncGetAttributes(&at, k.fn) == hipSuccess && at.numRegs > 0 && at.numRegs <= 128 &&
+                  hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds) == hipSuccess &&
+                  hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k.fn, (int)k.block.x, k.lds) == hipSuccess &&
+                  per_cu >= 2;
     }
     const GibbsPlan plan = plan_gibbs(geo, shape_of(c), c->tune, chip, n_chains, pack_ok);
     const int gran_stride = bmc::gran_slot_words(geo.G);
@@ -477,7 +479,6 @@ int run_common(bmc_ctx* c, int32_t n_chains, int64_t iters, const uint64_t* seed
         if (total > budget) a.P.stream_keep = (int32_t)((double)geo.ppg * budget / total);
     }
     a.dbg = nullptr;
-    a.query_regs = nullptr;
 #ifdef BMC_STAMPS
     if ((rc = ensure(c, c->dbg, 12 * sizeof(long long)))) return rc;
     HIPCHK(c, hipMemsetAsync(c->dbg.p, 0, 12 * sizeof(long long), c->stream));
@@ -518,7 +519,7 @@ int run_common(bmc_ctx* c, int32_t n_chains, int64_t iters, const uint64_t* seed
         HIPCHK(c, hipMemsetAsync(c->gran.p, 0, (size_t)l.n_chains * 3 * gran_stride * 8, c->stream));
         if (gibbs_lds_bytes(a) > LDS_LIMIT) return fail(c, BMC_EINVAL, "LDS plan exceeds 160 KiB");
         if (a.G > 1 || l.chains_per_pass > 1)   // (a single-workgroup chain waits for nobody)
-            if ((rc = check_residency(c, a, l.resident, launch_gibbs, "persistent Gibbs kernel")))
+            if ((rc = check_residency(c, gibbs_kernel(a), l.resident, "persistent Gibbs kernel")))
                 return rc;
         HIPCHK(c, launch_gibbs(a, c->stream));
         ++launches;
@@ -1366,7 +1367,7 @@ int bmc_simplex_run(bmc_ctx* c, const double* Vt_hat, int32_t Km, const double* 
     if (simplex_lds_bytes(a) > LDS_LIMIT) return fail(c, BMC_EINVAL, "LDS plan exceeds 160 KiB");
     if (Tt > 0) {
         if (a.G > 1 &&
-            (rc = check_residency(c, a, a.G, launch_simplex, "persistent simplex kernel")))
+            (rc = check_residency(c, simplex_kernel(a), a.G, "persistent simplex kernel")))
             return rc;
         HIPCHK(c, launch_simplex(a, c->stream));
     }

@@ -1,4 +1,6 @@
-// Host-callable launchers of the gfx950 kernels (one per kernel family).
+// Host-callable launchers of the gfx950 kernels (one per kernel family).  The loop kernels of
+// launch_gibbs / launch_simplex are chosen on the host (bmc_plan.h, gibbs_kernel_key); gibbs_kernel /
+// simplex_kernel below return the chosen instantiation for the residency and packing queries.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -154,15 +156,9 @@ struct GibbsArgs {
     int32_t* placement;     // [C] out: 1 = chain verified on one XCD (L2-local exchange)
     int32_t panels_per_group;  // max panels a group owns
     long long* dbg;         // diagnostic builds only (-DBMC_STAMPS); NULL otherwise
-    int32_t* query_regs;    // host pointer; when set launch_gibbs launches nothing and reports the
-                            // VGPR count of the packed (<= 128 VGPR) variant of the kernel it
-                            // would have launched, 0 if that shape has none
+    // (host-only from here on: no kernel reads the fields below)
     int32_t pack;           // 1: launch the packed variant (two chains per XCD)
     int32_t one_wave = 0;   // 1: gibbs_wave_kernel, one wave per chain (gibbs_wave_capacity() > 0)
-    int32_t* query_occupancy = nullptr;  // host pointer; when set launch_gibbs launches nothing and
-                            // reports how many workgroups of the kernel / block size / LDS bytes it
-                            // would have launched ONE CU admits (hipOccupancyMaxActiveBlocksPer
-                            // Multiprocessor): the persistent kernels need every group resident
 };
 // rss from sufficient statistics (bmc_tuning.rss_mode = 1): one wave per chain, K <= 64
 struct GramArgs {
@@ -204,8 +200,7 @@ struct SimplexArgs {
     int64_t iters, burn;
     int32_t G, waves, mode, reg_ppw, nslot, force_agent_scope, panels_per_group;
     uint32_t epoch0 = 0;    // as in GibbsArgs
-    int32_t* query_occupancy = nullptr;  // as in GibbsArgs
-    int32_t one_wave = 0;   // 1: simplex_wave_kernel (gibbs_wave_capacity() > 0, Km <= 64)
+    int32_t one_wave = 0;   // host-only. 1: simplex_wave_kernel (gibbs_wave_capacity() > 0, Km <= 64)
 };
 size_t simplex_lds_bytes(const SimplexArgs& a);
 hipError_t launch_simplex(const SimplexArgs& a, hipStream_t s);
@@ -214,6 +209,19 @@ hipError_t launch_uniform_fill(uint64_t seed, int64_t n, double* out, hipStream_
 
 size_t gibbs_lds_bytes(const GibbsArgs& a);
 hipError_t launch_gibbs(const GibbsArgs& a, hipStream_t s);
+
+// The kernel that launch_gibbs / launch_simplex would launch for these arguments: the
+// instantiation of bmc_plan.h's gibbs_kernel_key / simplex_kernel_key, its grid, block and dynamic
+// LDS bytes.  fn = nullptr when the arguments fail the launcher's checks or no such kernel is
+// compiled (the launcher then returns hipErrorInvalidValue).  The host asks the runtime about fn
+// itself: occupancy before a persistent launch (check_residency), registers of the packed variant.
+struct LoopKernel {
+    const void* fn;
+    dim3 grid, block;
+    size_t lds;
+};
+LoopKernel gibbs_kernel(const GibbsArgs& a);
+LoopKernel simplex_kernel(const SimplexArgs& a);
 
 // ---- chain diagnostics (kernels_diag.hip) -------------------------------------------
 // Samples [C][iters][ld] f64, column j < P.  Each chain drops `burn` draws and splits the

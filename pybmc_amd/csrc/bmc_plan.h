@@ -1,11 +1,15 @@
-// Launch planning of the Gibbs and simplex loops: which kernel, which geometry, how the chains
-// are split over launches.  Plain C++17 (no HIP): the dispatcher of kernels_gibbs.hip builds
-// its instantiations from the same capacity rules the host plans with, and
-// tests/launch_plan_check.cpp runs the planner on the CPU.
+// Launch planning of the Gibbs and simplex loops: which geometry, how the chains are split over
+// launches, and which compiled kernel each launch runs.  Plain C++17 (no HIP): the capacity rules
+// below decide both what the host plans and which instantiations exist.  A launch's KernelKey
+// (gibbs_kernel_key / simplex_kernel_key) names one instantiation; kernel_compiled() says whether
+// it is built, and kernels_gibbs.hip instantiates exactly the keys of loop_kernel_keys(), one
+// table entry each.  tests/launch_plan_check.cpp runs the planner and the selection on the CPU.
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <cstdio>
 #include <initializer_list>
+#include <string>
 #include <vector>
 
 #include "../../include/pybmc_amd.h"
@@ -41,6 +45,10 @@ constexpr int gibbs_reg_multi_cap(int k, bool f32, int vec) {
 constexpr bool gibbs_packable(int k, bool f32, int vec, int ppw) {
     return ppw == 1 && vec == 1 && reg_kmax(k) > 0 && reg_kmax(k) * (f32 ? 1 : 2) <= 64 &&
            !(f32 && reg_kmax(k) == 64);   // (f32, 64 columns spills at 128)
+}
+// (at 136 VGPRs the unpacked kernel is 3 % faster per iteration, so a single chain keeps that one)
+constexpr bool loop_can_pack(bool f32, int vec, int mode, int kmax, int ppw) {
+    return mode == 0 && gibbs_packable(kmax, f32, vec, ppw);
 }
 
 // bundles of 8 chains in the balanced two-panels-per-wave layout (PanelStore::partial_rss_reg_bal)
@@ -418,6 +426,187 @@ inline GibbsPlan plan_gibbs(const Geometry& geo, const Shape& s, const bmc_tunin
     }
     if (p.waves_per_group == 0) p.waves_per_group = geo.waves;   // widened for leader waves
     return p;
+}
+
+// ---- which compiled kernel a launch runs ----------------------------------------------------
+// One key per instantiation of the loop kernels of kernels_gibbs.hip (T = f32 ? float : double):
+//   KF_LOOP          gibbs_loop_kernel<T, vec, mode, kmax, ppw, single, pack, smallg>
+//   KF_MULTI         gibbs_multi_kernel<T, vec, mode, cpp, kmax, ppw, slotted, bal>
+//   KF_WAVE          gibbs_wave_kernel<T, rmax, kmax, nw>
+//   KF_SIMPLEX_LOOP  simplex_loop_kernel<T, vec, mode, kmax, ppw, single>
+//   KF_SIMPLEX_WAVE  simplex_wave_kernel<T, rmax, kmax, nw > 1>   (MANY)
+enum KernelFamily { KF_NONE, KF_LOOP, KF_MULTI, KF_WAVE, KF_SIMPLEX_LOOP, KF_SIMPLEX_WAVE };
+struct KernelKey {
+    int family = KF_NONE, f32 = 0;
+    int vec = 0, mode = 0, kmax = 0, ppw = 0, cpp = 0, rmax = 0, nw = 0;
+    bool single = false, pack = false, smallg = false, slotted = false, bal = false;
+};
+constexpr bool operator==(const KernelKey& a, const KernelKey& b) {
+    return a.family == b.family && a.f32 == b.f32 && a.vec == b.vec && a.mode == b.mode && a.kmax == b.kmax &&
+           a.ppw == b.ppw && a.cpp == b.cpp && a.rmax == b.rmax && a.nw == b.nw && a.single == b.single &&
+           a.pack == b.pack && a.smallg == b.smallg && a.slotted == b.slotted && a.bal == b.bal;
+}
+
+// The instantiation rules.  LDS / streaming (mode 1, 2): one kernel per rows per lane (4 for f32
+// only).  Registers: kmax = reg_kmax, rows per lane (ppw x vec; vec 2: one panel per wave) within
+// gibbs_reg_capacity; the single-chain loop as the general kernel, SINGLE (G = 1), SMALLG
+// (G <= 32) and, where packable, PACK; bundles of cpp <= gibbs_reg_multi_cap chains, SLOTTED
+// (one bundle per XCD) for one row per lane, BAL for gibbs_bundle_bal_shape.  One wave per chain:
+// rmax x kmax within gibbs_wave_capacity on 1, 2 / 4 (nw 4) or, if gibbs_wave_fits, 8 waves;
+// the simplex sampler has no 8-wave kernel.
+constexpr bool kernel_compiled(const KernelKey& k) {
+    const bool mem_vec = k.vec == 1 || k.vec == 2 || (k.vec == 4 && k.f32);
+    const bool reg_ok = k.kmax > 0 && reg_kmax(k.kmax) == k.kmax && (k.vec == 1 || k.vec == 2);
+    switch (k.family) {
+        case KF_LOOP:
+        case KF_SIMPLEX_LOOP:
+            if (k.mode != 0)
+                return (k.mode == 1 || k.mode == 2) && mem_vec && k.kmax == 0 && k.ppw == 0 && !k.single &&
+                       !k.pack && !k.smallg;
+            if (!reg_ok || !(k.ppw == 1 || k.ppw == 2 || k.ppw == 4) || (k.vec == 2 && k.ppw != 1) ||
+                !gibbs_reg_capacity(k.kmax, k.f32, k.ppw * k.vec))
+                return false;
+            if (k.family == KF_SIMPLEX_LOOP) return !k.pack && !k.smallg;
+            return k.pack ? k.smallg && !k.single && loop_can_pack(k.f32, k.vec, k.mode, k.kmax, k.ppw)
+                          : !(k.single && k.smallg);
+        case KF_MULTI:
+            if (k.cpp != 2 && k.cpp != 4 && k.cpp != 8) return false;
+            if (k.mode != 0)
+                return (k.mode == 1 || k.mode == 2) && mem_vec && k.kmax == 0 && k.ppw == 0 && !k.slotted && !k.bal;
+            if (!reg_ok || !gibbs_reg_capacity(k.kmax, k.f32, k.vec) || k.cpp > gibbs_reg_multi_cap(k.kmax, k.f32, k.vec))
+                return false;
+            if (k.bal) return k.slotted && k.ppw == 2 && gibbs_bundle_bal_shape(k.kmax, k.f32, k.vec, k.cpp);
+            return k.ppw == 1 && (!k.slotted || k.vec == 1);
+        case KF_WAVE:
+        case KF_SIMPLEX_WAVE:
+            if (wave_kmax(k.kmax) != k.kmax || wave_rmax(k.rmax) != k.rmax || gibbs_wave_capacity(k.kmax, k.rmax) == 0)
+                return false;
+            return k.nw == 1 || k.nw == 4 || (k.family == KF_WAVE && k.nw == 8 && gibbs_wave_fits(k.rmax * k.kmax, 8));
+    }
+    return false;
+}
+
+// Every compiled key, in a fixed order: the key space enumerated once, filtered by kernel_compiled
+struct KernelKeys {
+    KernelKey key[512];
+    int n = 0;
+};
+constexpr KernelKeys loop_kernel_keys() {
+    KernelKeys ks{};
+    auto add = [&ks](const KernelKey& k) {
+        if (kernel_compiled(k)) ks.key[ks.n++] = k;
+    };
+    for (int f32 = 0; f32 < 2; ++f32) {
+        for (int vec : {1, 2, 4})
+            for (int mode : {0, 1, 2})
+                for (int kmax : {0, 8, 16, 32, 64})
+                    for (int ppw : {0, 1, 2, 4})
+                        for (int v = 0; v < 8; ++v) {
+                            const bool b0 = v & 1, b1 = v & 2, b2 = v & 4;
+                            add({KF_LOOP, f32, vec, mode, kmax, ppw, 0, 0, 0, b0, b1, b2, false, false});
+                            add({KF_SIMPLEX_LOOP, f32, vec, mode, kmax, ppw, 0, 0, 0, b0, b1, b2, false, false});
+                            for (int cpp : {2, 4, 8})
+                                if (v < 4) add({KF_MULTI, f32, vec, mode, kmax, ppw, cpp, 0, 0, false, false, false, b0, b1});
+                        }
+        for (int rmax : {2, 4, 8, 12, 16})
+            for (int kmax : {4, 8, 16, 32})
+                for (int nw : {1, 4, 8}) {
+                    add({KF_WAVE, f32, 0, 0, kmax, 0, 0, rmax, nw, false, false, false, false, false});
+                    add({KF_SIMPLEX_WAVE, f32, 0, 0, kmax, 0, 0, rmax, nw, false, false, false, false, false});
+                }
+    }
+    return ks;
+}
+
+// The one-wave kernels: rmax x kmax of the panels a wave keeps, 1 / 4 / 8 waves (KF_NONE: none)
+inline KernelKey wave_kernel_key(int family, const Shape& s, int waves, int n_blocks) {
+    const int nw = waves > 1 ? waves : 1;
+    const int rpw = (s.npanels + nw - 1) / nw;
+    if (s.vec != 1 || !gibbs_wave_capacity(s.k, rpw) || n_blocks < 1 || (nw != 1 && nw != 2 && nw != 4 && nw != 8))
+        return KernelKey{};
+    KernelKey key;
+    key.family = family;
+    key.f32 = s.f32 != 0;
+    key.kmax = wave_kmax(s.k);
+    key.rmax = wave_rmax(rpw);
+    key.nw = nw > 4 ? 8 : nw > 1 ? 4 : 1;
+    return key;
+}
+
+// The single-chain loop kernels of both samplers: registers (kmax, ppw; SINGLE for one workgroup)
+// or LDS / streaming
+inline KernelKey loop_kernel_key(int family, const Shape& s, const Geometry& g) {
+    KernelKey key;
+    key.family = family;
+    key.f32 = s.f32 != 0;
+    key.vec = s.vec;
+    key.mode = g.mode == 0 ? 0 : g.mode == 1 ? 1 : 2;
+    if (key.mode == 0) {
+        key.kmax = reg_kmax(s.k);
+        key.ppw = g.ppw;
+        key.single = g.G == 1;
+    }
+    return key;
+}
+
+// The kernel of one launch of a Gibbs plan (launch_gibbs).  The key may name a kernel that is not
+// compiled: check kernel_compiled().
+inline KernelKey gibbs_kernel_key(const Shape& s, const Geometry& g, const GibbsLaunch& l) {
+    if (g.one_wave) return wave_kernel_key(KF_WAVE, s, l.waves, l.n_chains);
+    KernelKey key = loop_kernel_key(KF_LOOP, s, g);
+    if (l.chains_per_pass > 1) {   // bundles of chains: registers with one panel per wave (BAL: two)
+        key.family = KF_MULTI;
+        key.cpp = l.chains_per_pass;
+        key.single = false;
+        if (key.mode == 0) {
+            if (g.ppw != 1) return KernelKey{};
+            key.slotted = l.bundle_slots > 0;
+            key.bal = l.bundle_bal != 0;
+            key.ppw = key.bal ? 2 : 1;
+        }
+    } else if (key.mode == 0 && g.G > 1) {
+        // PACK where the packed variant exists (two chains per XCD: SMALLG), else SMALLG for the
+        // one-level exchange
+        key.pack = l.pack && loop_can_pack(key.f32, key.vec, key.mode, key.kmax, key.ppw);
+        key.smallg = key.pack || g.G <= 32;
+    }
+    return key;
+}
+
+// The kernel of the simplex sampler's launch (launch_simplex)
+inline KernelKey simplex_kernel_key(const Shape& s, const Geometry& g) {
+    if (g.one_wave) return wave_kernel_key(KF_SIMPLEX_WAVE, s, g.waves, 1);
+    return loop_kernel_key(KF_SIMPLEX_LOOP, s, g);
+}
+
+// The key as the demangled kernel name, e.g. gibbs_loop_kernel<double, 1, 0, 32, 1, false, false, true>
+inline std::string kernel_name(const KernelKey& k) {
+    const char* T = k.f32 ? "float" : "double";
+    auto b = [](bool x) { return x ? "true" : "false"; };
+    char buf[128];
+    switch (k.family) {
+        case KF_LOOP:
+            std::snprintf(buf, sizeof buf, "gibbs_loop_kernel<%s, %d, %d, %d, %d, %s, %s, %s>", T, k.vec, k.mode,
+                          k.kmax, k.ppw, b(k.single), b(k.pack), b(k.smallg));
+            break;
+        case KF_MULTI:
+            std::snprintf(buf, sizeof buf, "gibbs_multi_kernel<%s, %d, %d, %d, %d, %d, %s, %s>", T, k.vec, k.mode,
+                          k.cpp, k.kmax, k.ppw, b(k.slotted), b(k.bal));
+            break;
+        case KF_WAVE:
+            std::snprintf(buf, sizeof buf, "gibbs_wave_kernel<%s, %d, %d, %d>", T, k.rmax, k.kmax, k.nw);
+            break;
+        case KF_SIMPLEX_LOOP:
+            std::snprintf(buf, sizeof buf, "simplex_loop_kernel<%s, %d, %d, %d, %d, %s>", T, k.vec, k.mode, k.kmax,
+                          k.ppw, b(k.single));
+            break;
+        case KF_SIMPLEX_WAVE:
+            std::snprintf(buf, sizeof buf, "simplex_wave_kernel<%s, %d, %d, %s>", T, k.rmax, k.kmax, b(k.nw > 1));
+            break;
+        default:
+            return "none";
+    }
+    return buf;
 }
 
 }  // namespace bmc

@@ -38,6 +38,9 @@
 // every group leaves the loop.
 #include "bmc_loop.h"
 
+#include <type_traits>
+#include <utility>
+
 #ifndef BMC_LEADER_PRIO
 #define BMC_LEADER_PRIO 3      // s_setprio of the leader wave of a group (0: leave it alone)
 #endif
@@ -87,13 +90,8 @@ __device__ __forceinline__ double draw_u(double lam, double c1, double c2, doubl
 
 // PACK: the same kernel held to 128 VGPRs (4 waves per SIMD), so that two 5-wave groups of
 // different chains fit a CU side by side whatever SIMDs their waves land on -- used when more
-// than 8 chains share a launch (two per XCD).  It exists only for the shapes of gibbs_packable;
-// at 136 VGPRs the unpacked kernel is 3 % faster per iteration, so a single chain keeps that one.
-template <typename T, int VEC, int MODE, int KMAX, int PPW>
-constexpr bool loop_can_pack() {
-    return MODE == MODE_REG && gibbs_packable(KMAX, sizeof(T) == 4, VEC, PPW);
-}
-
+// than 8 chains share a launch (two per XCD).  It exists only for the shapes of loop_can_pack
+// (bmc_plan.h).
 // SMALLG: the host promises G <= 32 (one-level exchange); the loop then exists in two copies,
 // one per exchange scope, chosen once after the placement check (exchange_sum, TEAMS / LOCAL).
 template <typename T, int VEC, int MODE, int KMAX, int PPW, bool SINGLE = false, bool PACK = false,
@@ -1015,218 +1013,6 @@ __global__ __launch_bounds__(512) void simplex_loop_kernel(SimplexArgs a) {
     }
 }
 
-size_t gibbs_lds_bytes(const GibbsArgs& a) {
-    const int cpp = a.chains_per_pass > 1 ? a.chains_per_pass : 1;
-    // (several chains per pass in register residency with one row per lane: lane-wise group sum)
-    const bool lanewise_multi = cpp > 1 && a.mode == MODE_REG && a.P.vec == 1;
-    return lds_plan(a.P.k, a.P.f32 ? 4 : 8, 64 * a.P.vec, a.panels_per_group, a.mode == MODE_LDS, 0,
-                    cpp, lanewise_multi ? cpp : 1).total;
-}
-size_t simplex_lds_bytes(const SimplexArgs& a) {
-    return lds_plan(a.P.k, a.P.f32 ? 4 : 8, 64 * a.P.vec, a.panels_per_group, a.mode == MODE_LDS,
-                    a.vt_in_lds ? a.P.k * a.Km : 0).total;
-}
-
-// ---- dispatch over <T, VEC, MODE, KMAX, PPW>: one table for both kernels ----------------
-struct GibbsTag {};
-struct SimplexTag {};
-
-// Launch `fn` -- or, when `occ` is set, launch nothing and report how many workgroups of this
-// block size and LDS footprint one CU admits (the persistent kernels spin on each other, so the
-// host checks residency before it launches: bmc_capi.hip, check_residency).
-template <typename Args>
-static hipError_t launch_or_query(const void* fn, dim3 grid, dim3 block, size_t lds, hipStream_t s,
-                                  const Args& a, int32_t* occ) {
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    if (occ) {
-        int nb = 0;
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, (int)block.x, lds);
-        *occ = nb;
-        return e;
-    }
-    Args copy = a;
-    void* params[] = {&copy};
-    e = hipLaunchKernel(fn, grid, block, params, lds, s);
-    return e != hipSuccess ? e : hipGetLastError();
-}
-
-template <typename T, int VEC, int MODE, int KMAX, int PPW>
-static hipError_t launch_one(GibbsTag, const GibbsArgs& a, hipStream_t s) {
-    const size_t lds = gibbs_lds_bytes(a);
-    if (a.query_regs) {   // report the packed variant's VGPR count (0: none), do not launch
-        *a.query_regs = 0;
-        if constexpr (loop_can_pack<T, VEC, MODE, KMAX, PPW>()) {
-            hipFuncAttributes at;
-            const hipError_t e = hipFuncGetAttributes(
-                &at, (const void*)gibbs_loop_kernel<T, VEC, MODE, KMAX, PPW, false, true, true>);
-            if (e != hipSuccess) return e;
-            *a.query_regs = at.numRegs;
-        }
-        return hipSuccess;
-    }
-    const dim3 grid(a.nslot * a.G), block(64 * a.waves);
-    if constexpr (loop_can_pack<T, VEC, MODE, KMAX, PPW>()) {
-        if (a.pack && a.G > 1)   // (two chains per XCD implies G <= 32)
-            return launch_or_query(
-                (const void*)gibbs_loop_kernel<T, VEC, MODE, KMAX, PPW, false, true, true>, grid, block,
-                lds, s, a, a.query_occupancy);
-    }
-    if constexpr (MODE == MODE_REG) {
-        if (a.G == 1)   // the chain fits one workgroup: no exchange code at all
-            return launch_or_query((const void*)gibbs_loop_kernel<T, VEC, MODE, KMAX, PPW, true>,
-                                   grid, block, lds, s, a, a.query_occupancy);
-        if (a.G <= 32)  // one-level exchange, known at compile time (SMALLG)
-            return launch_or_query(
-                (const void*)gibbs_loop_kernel<T, VEC, MODE, KMAX, PPW, false, false, true>, grid, block,
-                lds, s, a, a.query_occupancy);
-    }
-    return launch_or_query((const void*)gibbs_loop_kernel<T, VEC, MODE, KMAX, PPW>, grid, block,
-                           lds, s, a, a.query_occupancy);
-}
-template <typename T, int VEC, int MODE, int KMAX, int PPW>
-static hipError_t launch_one(SimplexTag, const SimplexArgs& a, hipStream_t s) {
-    if constexpr (MODE == MODE_REG) {
-        if (a.G == 1)
-            return launch_or_query((const void*)simplex_loop_kernel<T, VEC, MODE, KMAX, PPW, true>,
-                                   dim3(a.nslot * a.G), dim3(64 * a.waves), simplex_lds_bytes(a), s, a,
-                                   a.query_occupancy);
-    }
-    return launch_or_query((const void*)simplex_loop_kernel<T, VEC, MODE, KMAX, PPW>,
-                           dim3(a.nslot * a.G), dim3(64 * a.waves), simplex_lds_bytes(a), s, a,
-                           a.query_occupancy);
-}
-
-template <typename Tag, typename Args, typename T, int KMAX>
-static hipError_t launch_reg(const Args& a, hipStream_t s) {
-    // rows per lane (PPW * VEC) within gibbs_reg_capacity keeps the kernel spill-free; VEC = 2
-    // panels are supported with one panel per wave
-    constexpr bool f32 = sizeof(T) == 4;
-    if (a.P.vec == 2) {
-        if constexpr (gibbs_reg_capacity(KMAX, f32, 2))
-            if (a.reg_ppw == 1) return launch_one<T, 2, MODE_REG, KMAX, 1>(Tag{}, a, s);
-        return hipErrorInvalidValue;
-    }
-    switch (a.reg_ppw) {
-        case 1: return launch_one<T, 1, MODE_REG, KMAX, 1>(Tag{}, a, s);
-        case 2:
-            if constexpr (gibbs_reg_capacity(KMAX, f32, 2)) return launch_one<T, 1, MODE_REG, KMAX, 2>(Tag{}, a, s);
-            break;
-        case 4:
-            if constexpr (gibbs_reg_capacity(KMAX, f32, 4)) return launch_one<T, 1, MODE_REG, KMAX, 4>(Tag{}, a, s);
-            break;
-    }
-    return hipErrorInvalidValue;
-}
-
-template <typename Tag, typename Args, typename T>
-static hipError_t launch_t(const Args& a, hipStream_t s) {
-    if (a.mode == MODE_REG) {
-        if (a.P.vec != 1 && a.P.vec != 2) return hipErrorInvalidValue;
-        if (a.P.k <= 8) return launch_reg<Tag, Args, T, 8>(a, s);
-        if (a.P.k <= 16) return launch_reg<Tag, Args, T, 16>(a, s);
-        if (a.P.k <= 32) return launch_reg<Tag, Args, T, 32>(a, s);
-        if (a.P.k <= 64) return launch_reg<Tag, Args, T, 64>(a, s);
-        return hipErrorInvalidValue;
-    }
-#define BMC_MEM(V)                                                                   \
-    (a.mode == MODE_LDS ? launch_one<T, V, MODE_LDS, 0, 0>(Tag{}, a, s)               \
-                        : launch_one<T, V, MODE_STREAM, 0, 0>(Tag{}, a, s))
-    switch (a.P.vec) {
-        case 1: return BMC_MEM(1);
-        case 2: return BMC_MEM(2);
-        case 4:
-            if constexpr (sizeof(T) == 4) return BMC_MEM(4);
-            break;
-    }
-#undef BMC_MEM
-    return hipErrorInvalidValue;
-}
-
-template <typename T, int VEC, int MODE>
-static hipError_t launch_multi_cpp(const GibbsArgs& a, hipStream_t s) {
-    const size_t lds = gibbs_lds_bytes(a);
-#define BMC_MULTI(C)                                                                        \
-    return launch_or_query((const void*)gibbs_multi_kernel<T, VEC, MODE, C>, dim3(a.G),     \
-                           dim3(64 * a.waves), lds, s, a, a.query_occupancy)
-    switch (a.chains_per_pass) {
-        case 2: BMC_MULTI(2);
-        case 4: BMC_MULTI(4);
-        case 8: BMC_MULTI(8);
-    }
-#undef BMC_MULTI
-    return hipErrorInvalidValue;
-}
-
-template <typename T>
-static hipError_t launch_multi_t(const GibbsArgs& a, hipStream_t s) {
-#define BMC_MM(V)                                                         \
-    (a.mode == MODE_LDS ? launch_multi_cpp<T, V, MODE_LDS>(a, s)           \
-                        : launch_multi_cpp<T, V, MODE_STREAM>(a, s))
-    switch (a.P.vec) {
-        case 1: return BMC_MM(1);
-        case 2: return BMC_MM(2);
-        case 4:
-            if constexpr (sizeof(T) == 4) return BMC_MM(4);
-            break;
-    }
-#undef BMC_MM
-    return hipErrorInvalidValue;
-}
-
-// register residency with several chains per pass: one panel per wave (PPW = 1)
-template <typename T, int VEC, int KMAX>
-static hipError_t launch_multi_reg_k(const GibbsArgs& a, hipStream_t s) {
-    const size_t lds = gibbs_lds_bytes(a);
-#define BMC_MR(C)                                                                            \
-    do {                                                                                         \
-        if constexpr (gibbs_bundle_bal_shape(KMAX, sizeof(T) == 4, VEC, C)) {                   \
-            if (a.bundle_slots > 0 && a.bundle_bal)                                              \
-                return launch_or_query(                                                          \
-                    (const void*)gibbs_multi_kernel<T, VEC, MODE_REG, C, KMAX, 2, true, true>,     \
-                    dim3(a.bundle_slots * a.G), dim3(64 * a.waves), lds, s, a, a.query_occupancy); \
-        }                                                                                        \
-        if (a.bundle_bal) return hipErrorInvalidValue;                                           \
-        if constexpr (VEC == 1) {                                                                \
-            if (a.bundle_slots > 0)                                                              \
-                return launch_or_query(                                                          \
-                    (const void*)gibbs_multi_kernel<T, VEC, MODE_REG, C, KMAX, 1, true>,           \
-                    dim3(a.bundle_slots * a.G), dim3(64 * a.waves), lds, s, a, a.query_occupancy); \
-        }                                                                                        \
-        if (a.bundle_slots > 0) return hipErrorInvalidValue;                                     \
-        return launch_or_query((const void*)gibbs_multi_kernel<T, VEC, MODE_REG, C, KMAX, 1>,    \
-                               dim3(a.G), dim3(64 * a.waves), lds, s, a, a.query_occupancy);     \
-    } while (0)
-    // only the combinations that fit the 256-VGPR budget without spilling are built
-    constexpr int CMAX = gibbs_reg_multi_cap(KMAX, sizeof(T) == 4, VEC);
-    switch (a.chains_per_pass) {
-        case 2: if constexpr (CMAX >= 2) BMC_MR(2); break;
-        case 4: if constexpr (CMAX >= 4) BMC_MR(4); break;
-        case 8: if constexpr (CMAX >= 8) BMC_MR(8); break;
-    }
-#undef BMC_MR
-    return hipErrorInvalidValue;
-}
-
-template <typename T>
-static hipError_t launch_multi_reg(const GibbsArgs& a, hipStream_t s) {
-    if (a.reg_ppw != 1) return hipErrorInvalidValue;
-    const int k = a.P.k;
-    if (a.P.vec == 1) {
-        if (k <= 8) return launch_multi_reg_k<T, 1, 8>(a, s);
-        if (k <= 16) return launch_multi_reg_k<T, 1, 16>(a, s);
-        if (k <= 32) return launch_multi_reg_k<T, 1, 32>(a, s);
-        if (k <= 64) return launch_multi_reg_k<T, 1, 64>(a, s);
-    } else if (a.P.vec == 2) {
-        if (k <= 8) return launch_multi_reg_k<T, 2, 8>(a, s);
-        if (k <= 16) return launch_multi_reg_k<T, 2, 16>(a, s);
-        if (k <= 32) return launch_multi_reg_k<T, 2, 32>(a, s);
-        if constexpr (sizeof(T) == 4)
-            if (k <= 64) return launch_multi_reg_k<T, 2, 64>(a, s);
-    }
-    return hipErrorInvalidValue;
-}
-
 // The simplex-constrained sampler in the same one-wave form (simplex_loop_kernel's steps: the
 // proposal, the simplex test of its weights, the residual sum of an inside proposal, the
 // Metropolis test, the sigma2 draw), at most 64 models: lane m keeps column m of Vt_hat.  The
@@ -1347,85 +1133,111 @@ __global__ __launch_bounds__(MANY ? 256 : 64) void simplex_wave_kernel(SimplexAr
     }
 }
 
-template <typename T, int RMAX, int KM>
-static const void* wave_kernel_of(GibbsTag, int waves) {
-    if (waves > 4) {
-        if constexpr (gibbs_wave_fits(RMAX * KM, 8)) return (const void*)gibbs_wave_kernel<T, RMAX, KM, 8>;
-        return nullptr;
-    }
-    return waves > 1 ? (const void*)gibbs_wave_kernel<T, RMAX, KM, 4> : (const void*)gibbs_wave_kernel<T, RMAX, KM, 1>;
+size_t gibbs_lds_bytes(const GibbsArgs& a) {
+    const int cpp = a.chains_per_pass > 1 ? a.chains_per_pass : 1;
+    // (several chains per pass in register residency with one row per lane: lane-wise group sum)
+    const bool lanewise_multi = cpp > 1 && a.mode == MODE_REG && a.P.vec == 1;
+    return lds_plan(a.P.k, a.P.f32 ? 4 : 8, 64 * a.P.vec, a.panels_per_group, a.mode == MODE_LDS, 0,
+                    cpp, lanewise_multi ? cpp : 1).total;
 }
-template <typename T, int RMAX, int KM>
-static const void* wave_kernel_of(SimplexTag, int waves) {
-    if (waves > 4) return nullptr;
-    return waves > 1 ? (const void*)simplex_wave_kernel<T, RMAX, KM, true>
-                     : (const void*)simplex_wave_kernel<T, RMAX, KM, false>;
+size_t simplex_lds_bytes(const SimplexArgs& a) {
+    return lds_plan(a.P.k, a.P.f32 ? 4 : 8, 64 * a.P.vec, a.panels_per_group, a.mode == MODE_LDS,
+                    a.vt_in_lds ? a.P.k * a.Km : 0).total;
 }
 
-template <typename Tag, typename T, int RMAX, typename Args>
-static hipError_t launch_wave_r(const Args& a, int n_blocks, hipStream_t s) {
-    const dim3 grid((unsigned)n_blocks), block(64 * (a.waves > 1 ? a.waves : 1));
-#define BMC_WV(KM)                                                                              \
-    if constexpr (gibbs_wave_capacity(KM, RMAX) > 0) {                                          \
-        const void* fn = wave_kernel_of<T, RMAX, KM>(Tag{}, a.waves);                           \
-        if (!fn) return hipErrorInvalidValue;                                                   \
-        return launch_or_query(fn, grid, block, 0, s, a, a.query_occupancy);                    \
-    }                                                                                           \
-    break
-    switch (wave_kmax(a.P.k)) {
-        case 4: BMC_WV(4);
-        case 8: BMC_WV(8);
-        case 16: BMC_WV(16);
-        case 32: BMC_WV(32);
-    }
-#undef BMC_WV
-    return hipErrorInvalidValue;
+// ---- kernel selection: every instantiation in one table -------------------------------------
+// The keys of bmc_plan.h's loop_kernel_keys(), each instantiated once; a launch's key (from its
+// arguments, as the host plans it) is looked up here.  A key that is not in the table has no
+// kernel: hipErrorInvalidValue.
+constexpr KernelKeys KEYS = loop_kernel_keys();
+
+template <int I>
+static const void* kernel_fn() {
+    constexpr KernelKey k = KEYS.key[I];
+    using T = std::conditional_t<k.f32 != 0, float, double>;
+    if constexpr (k.family == KF_LOOP)
+        return (const void*)gibbs_loop_kernel<T, k.vec, k.mode, k.kmax, k.ppw, k.single, k.pack, k.smallg>;
+    else if constexpr (k.family == KF_MULTI)
+        return (const void*)gibbs_multi_kernel<T, k.vec, k.mode, k.cpp, k.kmax, k.ppw, k.slotted, k.bal>;
+    else if constexpr (k.family == KF_WAVE)
+        return (const void*)gibbs_wave_kernel<T, k.rmax, k.kmax, k.nw>;
+    else if constexpr (k.family == KF_SIMPLEX_LOOP)
+        return (const void*)simplex_loop_kernel<T, k.vec, k.mode, k.kmax, k.ppw, k.single>;
+    else
+        return (const void*)simplex_wave_kernel<T, k.rmax, k.kmax, (k.nw > 1)>;
 }
 
-template <typename Tag, typename T, typename Args>
-static hipError_t launch_wave(const Args& a, int n_blocks, hipStream_t s) {
-    const int nw = a.waves > 1 ? a.waves : 1;
-    const int rpw = (a.P.npanels + nw - 1) / nw;
-    if (a.P.vec != 1 || !gibbs_wave_capacity(a.P.k, rpw) || n_blocks < 1 ||
-        (nw != 1 && nw != 2 && nw != 4 && nw != 8))
-        return hipErrorInvalidValue;
-    switch (wave_rmax(rpw)) {
-        case 2: return launch_wave_r<Tag, T, 2>(a, n_blocks, s);
-        case 4: return launch_wave_r<Tag, T, 4>(a, n_blocks, s);
-        case 8: return launch_wave_r<Tag, T, 8>(a, n_blocks, s);
-        case 12: return launch_wave_r<Tag, T, 12>(a, n_blocks, s);
-        case 16: return launch_wave_r<Tag, T, 16>(a, n_blocks, s);
-    }
-    return hipErrorInvalidValue;
+template <int... I>
+static const void* kernel_of(const KernelKey& key, std::integer_sequence<int, I...>) {
+    static const void* const fns[] = {kernel_fn<I>()...};
+    for (int i = 0; i < KEYS.n; ++i)
+        if (KEYS.key[i] == key) return fns[i];
+    return nullptr;
 }
 
-hipError_t launch_gibbs(const GibbsArgs& a, hipStream_t s) {
-    if (a.one_wave) {
-        if (a.query_regs) return hipErrorInvalidValue;
-        return a.P.f32 ? launch_wave<GibbsTag, float>(a, a.n_chains, s)
-                       : launch_wave<GibbsTag, double>(a, a.n_chains, s);
-    }
-    if (!geometry_ok(a.P.k, a.G, a.waves, a.nslot) ||
-        !gibbs_chains_ok(a.n_chains, a.chains_per_pass, a.waves, a.nslot, a.bundle_slots, a.G, a.mode))
-        return hipErrorInvalidValue;
-    if (a.chains_per_pass > 1) {   // bundles of chains_per_pass chains (one, or one per slot)
-        if (a.query_regs) return hipErrorInvalidValue;
-        if (a.mode == MODE_REG)
-            return a.P.f32 ? launch_multi_reg<float>(a, s) : launch_multi_reg<double>(a, s);
-        return a.P.f32 ? launch_multi_t<float>(a, s) : launch_multi_t<double>(a, s);
-    }
-    return a.P.f32 ? launch_t<GibbsTag, GibbsArgs, float>(a, s)
-                   : launch_t<GibbsTag, GibbsArgs, double>(a, s);
+static Shape shape_of(const Panels& P) { return Shape{P.n, P.k, P.f32, P.vec, P.npanels}; }
+
+// grid: the single-chain loops nslot x G, bundles G (one bundle) or bundle_slots x G, one-wave
+// chains one block each
+static LoopKernel loop_kernel(const KernelKey& key, int slots, int G, int waves, size_t lds) {
+    const bool one_wave = key.family == KF_WAVE || key.family == KF_SIMPLEX_WAVE;
+    LoopKernel r;
+    r.fn = kernel_of(key, std::make_integer_sequence<int, KEYS.n>{});
+    r.grid = dim3(one_wave ? slots : slots * G);
+    r.block = dim3(64 * (waves > 1 ? waves : 1));
+    r.lds = one_wave ? 0 : lds;
+    return r;
 }
 
-hipError_t launch_simplex(const SimplexArgs& a, hipStream_t s) {
-    if (a.one_wave) {
-        if (a.Km < 1 || a.Km > 64) return hipErrorInvalidValue;
-        return a.P.f32 ? launch_wave<SimplexTag, float>(a, 1, s) : launch_wave<SimplexTag, double>(a, 1, s);
-    }
-    if (!geometry_ok(a.P.k, a.G, a.waves, a.nslot) || a.Km < 1) return hipErrorInvalidValue;
-    return a.P.f32 ? launch_t<SimplexTag, SimplexArgs, float>(a, s)
-                   : launch_t<SimplexTag, SimplexArgs, double>(a, s);
+LoopKernel gibbs_kernel(const GibbsArgs& a) {
+    if (!a.one_wave &&
+        (!geometry_ok(a.P.k, a.G, a.waves, a.nslot) ||
+         !gibbs_chains_ok(a.n_chains, a.chains_per_pass, a.waves, a.nslot, a.bundle_slots, a.G, a.mode)))
+        return LoopKernel{};
+    Geometry g{};
+    g.G = a.G;
+    g.mode = a.mode;
+    g.ppw = a.reg_ppw;
+    g.one_wave = a.one_wave;
+    GibbsLaunch l{};
+    l.n_chains = a.n_chains;
+    l.chains_per_pass = a.chains_per_pass;
+    l.waves = a.waves;
+    l.pack = a.pack;
+    l.bundle_slots = a.bundle_slots;
+    l.bundle_bal = a.bundle_bal;
+    const KernelKey key = gibbs_kernel_key(shape_of(a.P), g, l);
+    const int slots = key.family == KF_WAVE ? a.n_chains
+                      : key.family == KF_MULTI ? (key.slotted ? a.bundle_slots : 1)
+                                               : a.nslot;
+    return loop_kernel(key, slots, a.G, a.waves, gibbs_lds_bytes(a));
 }
+
+LoopKernel simplex_kernel(const SimplexArgs& a) {
+    if (a.one_wave ? (a.Km < 1 || a.Km > 64) : (!geometry_ok(a.P.k, a.G, a.waves, a.nslot) || a.Km < 1))
+        return LoopKernel{};
+    Geometry g{};
+    g.G = a.G;
+    g.waves = a.waves;
+    g.mode = a.mode;
+    g.ppw = a.reg_ppw;
+    g.one_wave = a.one_wave;
+    return loop_kernel(simplex_kernel_key(shape_of(a.P), g), a.one_wave ? 1 : a.nslot, a.G, a.waves,
+                       simplex_lds_bytes(a));
+}
+
+template <typename Args>
+static hipError_t launch_loop(const LoopKernel& k, const Args& a, hipStream_t s) {
+    if (!k.fn) return hipErrorInvalidValue;
+    hipError_t e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds);
+    if (e != hipSuccess) return e;
+    Args copy = a;
+    void* params[] = {&copy};
+    e = hipLaunchKernel(k.fn, k.grid, k.block, params, k.lds, s);
+    return e != hipSuccess ? e : hipGetLastError();
+}
+
+hipError_t launch_gibbs(const GibbsArgs& a, hipStream_t s) { return launch_loop(gibbs_kernel(a), a, s); }
+hipError_t launch_simplex(const SimplexArgs& a, hipStream_t s) { return launch_loop(simplex_kernel(a), a, s); }
 
 }  // namespace bmc

@@ -1,13 +1,19 @@
 // CPU check of pybmc_amd/csrc/bmc_plan.h, the launch planner of the Gibbs loop.
-//   (no argument)  one line per named case: the shape, the geometry and every launch of the plan;
-//                  tests/test_launch_plan.py compares them with the plans of the parent commit.
+//   (no argument)  one line per named case: the shape, the geometry and every launch of the plan
+//                  with the kernel it runs; tests/test_launch_plan.py compares them with the plans
+//                  of the parent commit.
 //   sweep          plans over a grid of shapes x chain counts x cu_limit x tunings; every plan
-//                  must cover its chains once and in order, fit its exchange words, and pass the
-//                  argument checks of launch_gibbs.  Prints "sweep <plans> <failures>" last.
+//                  must cover its chains once and in order, fit its exchange words, pass the
+//                  argument checks of launch_gibbs and run compiled kernels only (the simplex
+//                  sampler's geometries too).  Prints the compiled kernels no plan reaches, then
+//                  "sweep <plans> <failures>" last.
+//   names          the demangled names of every compiled loop kernel (kernels_gibbs.hip's table)
 #include "../pybmc_amd/csrc/bmc_plan.h"
 
 #include <cstdio>
 #include <cstring>
+#include <set>
+#include <string>
 
 using namespace bmc;
 
@@ -104,10 +110,10 @@ static void print_case(const Case& c) {
                 "max=%d passes=%lld cpp=%d wpg=%d |",
                 c.name, s.vec, s.npanels, g.G, g.waves, g.ppg, g.mode, g.ppw, g.nslot, g.chains_per_launch,
                 g.one_wave, p.max_per_launch, (long long)p.passes, p.chains_per_pass, p.waves_per_group);
-    // c0+chains cpp/waves/nslot/pack/bundle_slots/bundle_bal/resident
+    // c0+chains cpp/waves/nslot/pack/bundle_slots/bundle_bal/resident=kernel
     for (const GibbsLaunch& l : p.launches)
-        std::printf(" %d+%d:%d/%d/%d/%d/%d/%d/%d", l.c0, l.n_chains, l.chains_per_pass, l.waves, l.nslot, l.pack,
-                    l.bundle_slots, l.bundle_bal, l.resident);
+        std::printf(" %d+%d:%d/%d/%d/%d/%d/%d/%d=%s", l.c0, l.n_chains, l.chains_per_pass, l.waves, l.nslot, l.pack,
+                    l.bundle_slots, l.bundle_bal, l.resident, kernel_name(gibbs_kernel_key(s, g, l)).c_str());
     std::printf("\n");
 }
 
@@ -117,6 +123,14 @@ static void fail(const char* what, const Shape& s, const bmc_tuning& tu, int n_c
         std::printf("FAIL %s: n=%lld k=%d f32=%d chains=%d cu_limit=%d G=%d W=%d res=%d ppw=%d cpp=%d pack=%d\n",
                     what, (long long)s.n, s.k, s.f32, n_chains, tu.cu_limit, tu.groups_per_chain,
                     tu.waves_per_group, tu.residency, tu.panels_per_wave, tu.chains_per_pass, (int)pack);
+}
+
+static std::set<std::string> reached;
+static bool compiled(const KernelKey& k) {
+    if (!kernel_compiled(k)) return false;
+    static KernelKey last;   // (consecutive plans mostly share their kernel)
+    if (!(k == last)) reached.insert(kernel_name(last = k));
+    return true;
 }
 
 static long sweep() {
@@ -142,6 +156,12 @@ static long sweep() {
                         const bmc_tuning tu = tuning(kn[0], kn[1], kn[2], kn[3], kn[4], cl);
                         const Chip chip = chip_of(256, cl);
                         if (tu.groups_per_chain > chip.groups_max) continue;   // run_common: BMC_EINVAL
+                        for (bool one_wave_ok : {false, true}) {   // the simplex sampler (Km > 64, Km <= 64)
+                            const Geometry g = choose_geometry(s, tu, chip, 1, one_wave_ok, 4);
+                            if (!g.one_wave && !geometry_ok(s.k, g.G, g.waves, g.nslot))
+                                fail("launch_simplex argument checks", s, tu, 1, false);
+                            if (!compiled(simplex_kernel_key(s, g))) fail("simplex kernel not compiled", s, tu, 1, false);
+                        }
                         for (int nc : chains) {
                             const Geometry g = choose_geometry(s, tu, chip, nc, true, 8);
                             for (bool flag : {false, true}) {
@@ -156,29 +176,19 @@ static long sweep() {
                                     if (l.n_chains > p.max_per_launch) fail("exceeds max_per_launch", s, tu, nc, pack_ok);
                                     if (l.chains_per_pass > p.chains_per_pass || l.waves > p.waves_per_group)
                                         fail("summary", s, tu, nc, pack_ok);
+                                    if (!compiled(gibbs_kernel_key(s, g, l)))
+                                        fail("kernel not compiled", s, tu, nc, pack_ok);
+                                    if (l.pack && !gibbs_kernel_key(s, g, l).pack)
+                                        fail("packed variant", s, tu, nc, pack_ok);
                                     if (g.one_wave) {
-                                        const int rpw = (s.npanels + l.waves - 1) / l.waves;
-                                        const int f = gibbs_wave_capacity(s.k, rpw);
-                                        if (s.vec != 1 || f == 0 || !gibbs_wave_fits(f, l.waves) || l.chains_per_pass != 1 ||
-                                            (l.waves != 1 && l.waves != 2 && l.waves != 4 && l.waves != 8) ||
-                                            l.n_chains > l.nslot || l.nslot > 2048)
-                                            fail("no one-wave kernel", s, tu, nc, pack_ok);
+                                        if (l.chains_per_pass != 1 || l.n_chains > l.nslot || l.nslot > 2048)
+                                            fail("one-wave launch size", s, tu, nc, pack_ok);
                                         continue;
                                     }
                                     if (!geometry_ok(s.k, g.G, l.waves, l.nslot) ||
                                         !gibbs_chains_ok(l.n_chains, l.chains_per_pass, l.waves, l.nslot,
                                                          l.bundle_slots, g.G, g.mode))
                                         fail("launch_gibbs argument checks", s, tu, nc, pack_ok);
-                                    if (g.mode == 0 && !gibbs_reg_capacity(s.k, s.f32, g.ppw * s.vec))
-                                        fail("register capacity", s, tu, nc, pack_ok);
-                                    if (g.mode == 0 && l.chains_per_pass > gibbs_reg_multi_cap(s.k, s.f32, s.vec) &&
-                                        l.chains_per_pass > 1)
-                                        fail("chains per pass in registers", s, tu, nc, pack_ok);
-                                    if (l.bundle_bal && (!gibbs_bundle_bal_shape(s.k, s.f32, s.vec, l.chains_per_pass) ||
-                                                         l.bundle_slots < 1))
-                                        fail("balanced bundle", s, tu, nc, pack_ok);
-                                    if (l.pack && !gibbs_packable(s.k, s.f32, s.vec, g.ppw))
-                                        fail("packed variant", s, tu, nc, pack_ok);
                                     if ((g.G > 1 || l.chains_per_pass > 1) &&
                                         l.resident > chip.groups_max * (l.pack ? 2 : 1))
                                         fail("co-resident workgroups", s, tu, nc, pack_ok);
@@ -192,10 +202,18 @@ static long sweep() {
 }
 
 int main(int argc, char** argv) {
+    static constexpr KernelKeys keys = loop_kernel_keys();
     if (argc > 1 && std::strcmp(argv[1], "sweep") == 0) {
         const long plans = sweep();
+        int unreached = 0;
+        for (int i = 0; i < keys.n; ++i) unreached += reached.count(kernel_name(keys.key[i])) == 0;
+        std::printf("compiled loop kernels %d, reached by no plan of the sweep %d\n", keys.n, unreached);
         std::printf("sweep %ld %ld\n", plans, failures);
         return failures != 0;
+    }
+    if (argc > 1 && std::strcmp(argv[1], "names") == 0) {
+        for (int i = 0; i < keys.n; ++i) std::printf("%s\n", kernel_name(keys.key[i]).c_str());
+        return 0;
     }
     for (const Case& c : CASES) print_case(c);
     return 0;
