@@ -282,6 +282,34 @@ int bmc_chain_diagnostics_device(bmc_ctx* ctx, const void* d_samples, int32_t n_
                                  double* mean_out, double* sd_out, double* rhat_out,
                                  double* ess_out, double* mcse_out, int64_t* max_lag_out);
 
+/* ---- pointwise log predictive density of a sampled fit (WAIC; not in the reference) ----------
+ * The model the samplers draw from: y_i ~ N(a_i . beta, sigma^2).  A is n_points x k (lda / layout
+ * as in bmc_set_problem: BMC_COL_MAJOR is what U_hat is), y [n_points], theta holds n_draws rows
+ * ldt >= k + 1 doubles apart: k coefficients, then sigma, the layout bmc_gibbs_run* and
+ * bmc_simplex_run write (a larger ldt reads a column subset or every thin-th draw in place).
+ * With  ll[i][s] = -1/2 log(2 pi) - log sigma_s - (y_i - a_i . beta_s)^2 / (2 sigma_s^2),
+ * per point i over the n_draws draws (each output [n_points]; any may be NULL):
+ *   lppd_out     log-mean-exp_s ll[i][s] = logsumexp_s - log n_draws
+ *   pwaic_out    var_s ll[i][s], ddof 1   (p_waic 2 of Gelman, Hwang & Vehtari 2014, eq. 12)
+ *   mean_ll_out  mean_s ll[i][s]
+ * The n_points x n_draws matrix is never stored: the draws are streamed, n_draws is bounded by
+ * the memory of theta alone; device memory used is O(n_points (k + splits) + n_draws).  Results
+ * are deterministic (no atomics).  Non-finite input gives NaN, not an error, by the arithmetic
+ * alone: a NaN or infinity in row i of A or in y_i makes point i's outputs NaN; a NaN in theta or
+ * a sigma_s <= 0 makes every point's outputs NaN.  BMC_EINVAL when n_points < 1, k outside
+ * 1..256, n_draws < 2, lda or ldt too small.  Runs on the context's stream and leaves the
+ * context's problem, prior and predictive draws alone.  bmc_pointwise_loglik stages host arrays
+ * itself; the _device form reads caller-owned DEVICE memory (the caller orders its producer
+ * before the call); outputs are host pointers in both.  The estimators built on these
+ * (elpd_waic, se, ...) are written out in INTEGRATION.md section 8. */
+int bmc_pointwise_loglik(bmc_ctx* ctx, const double* A, int64_t n_points, int32_t k, int64_t lda,
+                         int layout, const double* y, const double* theta, int64_t n_draws,
+                         int64_t ldt, double* lppd_out, double* pwaic_out, double* mean_ll_out);
+int bmc_pointwise_loglik_device(bmc_ctx* ctx, const void* dA, int64_t n_points, int32_t k,
+                                int64_t lda, int layout, const void* dy, const void* dtheta,
+                                int64_t n_draws, int64_t ldt, double* lppd_out,
+                                double* pwaic_out, double* mean_ll_out);
+
 /* ---- on-device variates (exposed so the generator itself can be tested) ----
  * normals_out [count_normal] ~ N(0,1); gammas_out [count_gamma] ~ Gamma(shape,1). */
 int bmc_rng_fill(bmc_ctx* ctx, uint64_t seed, int64_t count_normal, double* normals_out,

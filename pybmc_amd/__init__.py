@@ -8,6 +8,7 @@ from .data import Dataset
 from .diagnostics import chain_diagnostics
 from .inference_utils import gibbs_sampler, gibbs_sampler_simplex, USVt_hat_extraction
 from .sampling_utils import coverage, rndm_m_random_calculator
+from .scoring import pointwise_log_likelihood, waic
 
 __all__ = [
     "Dataset",
@@ -18,4 +19,6 @@ __all__ = [
     "coverage",
     "rndm_m_random_calculator",
     "chain_diagnostics",
+    "pointwise_log_likelihood",
+    "waic",
 ]

@@ -87,6 +87,10 @@ PROTOTYPES = {
     "bmc_chain_diagnostics_device": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int64,
                                                C.c_int64, _D, _D, _D, _D, _D,
                                                C.POINTER(C.c_int64)]),
+    "bmc_pointwise_loglik": (C.c_int, [_P, _D, C.c_int64, C.c_int32, C.c_int64, C.c_int, _D, _D,
+                                       C.c_int64, C.c_int64, _D, _D, _D]),
+    "bmc_pointwise_loglik_device": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int, _P,
+                                              _P, C.c_int64, C.c_int64, _D, _D, _D]),
     "bmc_rng_fill": (C.c_int, [_P, C.c_uint64, C.c_int64, _D, C.c_double, C.c_int64, _D]),
     "bmc_philox_raw": (C.c_int, [_P, C.c_uint64, C.c_uint32, C.c_int64, C.POINTER(C.c_uint32)]),
 }
@@ -475,6 +479,26 @@ class Context:
         stream: the caller orders its producer before the call."""
         return self._diag_call(self._lib.bmc_chain_diagnostics_device, _P(d_ptr), n_chains, iters,
                                n_cols, ld, burn)
+
+    # -- pointwise log predictive density -----------------------------------------------------
+    def _score_call(self, fn, pA, n, k, lda, layout, py, pt, n_draws, ldt):
+        out = {key: np.empty(n) for key in ("lppd", "p_waic", "mean_ll")}
+        self._check(fn(self._h, pA, int(n), int(k), int(lda), int(layout), py, pt, int(n_draws),
+                       int(ldt), _dptr(out["lppd"]), _dptr(out["p_waic"]), _dptr(out["mean_ll"])))
+        return out
+
+    def pointwise_loglik(self, A, n, k, lda, layout, y, theta, n_draws, ldt):
+        """lppd_i, p_waic_i and mean_ll_i of HOST f64 arrays (bmc_pointwise_loglik): A's element
+        (i, j) at i*lda + j (BMC_ROW_MAJOR) or j*lda + i (BMC_COL_MAJOR), draw s at theta + s*ldt.
+        Returns a dict of [n] arrays."""
+        return self._score_call(self._lib.bmc_pointwise_loglik, _dptr(A), n, k, lda, layout,
+                                _dptr(y), _dptr(theta), n_draws, ldt)
+
+    def pointwise_loglik_device(self, dA, n, k, lda, layout, dy, dtheta, n_draws, ldt):
+        """The same on DEVICE memory (bmc_pointwise_loglik_device), read on the context's stream:
+        the caller orders its producers before the call."""
+        return self._score_call(self._lib.bmc_pointwise_loglik_device, _P(dA), n, k, lda, layout,
+                                _P(dy), _P(dtheta), n_draws, ldt)
 
     # -- variates -----------------------------------------------------------------------
     def rng_fill(self, seed, n_normal=0, shape=1.0, n_gamma=0):

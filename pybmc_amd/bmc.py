@@ -184,6 +184,49 @@ class BayesianModelCombination:
         from .diagnostics import KEYS
         return pd.DataFrame({key: np.asarray(d[key]) for key in KEYS}, index=index)
 
+    # ----------------------------------------------------------------- scoring
+    def _chains(self):
+        s = np.asarray(self.samples)
+        return s.reshape(int(self.n_chains or 1), -1, s.shape[-1])
+
+    def waic(self, burn=0):
+        """WAIC of the last ``train()`` on its training data (not in the reference;
+        ``pybmc_amd.scoring``): the likelihood of ``centered_experiment_train`` given ``U_hat`` under
+        every draw, reduced on the GPU.  The pooled ``samples`` are split back into their
+        ``n_chains`` chains and ``burn`` more draws dropped from the start of each.  Returns a dict:
+        ``elpd_waic``, ``p_waic``, ``waic``, ``se``, ``n_high_p``, ``n_points`` and the pointwise
+        ``lppd``, ``p_waic_i``, ``mean_ll``, ``elpd_waic_i``."""
+        if self.samples is None or self.U_hat is None:
+            raise ValueError("Must call `orthogonalize()` and `train()` before computing WAIC.")
+        from .scoring import waic
+        return waic(self.U_hat, np.asarray(self.centered_experiment_train, dtype=np.float64),
+                    self._chains(), burn=burn, device=self.device)
+
+    def log_predictive_density(self, X, burn=0):
+        """Log predictive density of held-out data (a validation or test split): ``X`` is a
+        DataFrame with the model columns and the truth column.  The predictive mean of point p
+        under draw s is ``preds_p . (beta_s Vt_hat + 1/K)`` (reference sampling_utils.py:60-72),
+        so the design row is ``preds_p Vt_hat'`` and the target ``truth_p - mean(preds_p)``.
+        Returns ``elpd`` (the sum of the pointwise ``lppd``; no penalty on held-out data), its
+        ``se``, ``n_points`` and ``lppd``."""
+        if self.samples is None or self.Vt_hat is None:
+            raise ValueError(
+                "Must call `orthogonalize()` and `train()` before computing predictive densities.")
+        if not isinstance(X, pd.DataFrame):
+            raise ValueError(
+                "X must be a pandas DataFrame containing model predictions and the truth column.")
+        if self.truth_column_name not in X.columns:
+            raise ValueError(f"X must contain the truth column '{self.truth_column_name}'.")
+        from .scoring import elpd_summary, pointwise_log_likelihood
+        preds = np.asarray(X[self.models].values, dtype=np.float64)
+        truth = np.asarray(X[self.truth_column_name].values, dtype=np.float64)
+        A = preds @ np.asarray(self.Vt_hat, dtype=np.float64).T
+        pw = pointwise_log_likelihood(A, truth - preds.mean(axis=1), self._chains(), burn=burn,
+                                      device=self.device)
+        out = elpd_summary(pw["lppd"])
+        out["lppd"] = pw["lppd"]
+        return out
+
     # ----------------------------------------------------------------- predict
     def _require_trained(self):
         if self.samples is None or self.Vt_hat is None:

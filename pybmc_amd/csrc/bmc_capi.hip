@@ -70,6 +70,8 @@ struct bmc_ctx {
     DevBuf oFc, oMu, oW, oOut;
     // chain diagnostics (bmc_chain_diagnostics*)
     DevBuf dgIn, dgPart, dgMean, dgM2, dgCols, dgAcovPart, dgAcov;
+    // pointwise log-likelihood (bmc_pointwise_loglik*)
+    DevBuf scA, scY, scTheta, scAp, scYp, scCh, scPart, scOut;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     double predict_ms[4] = {0, 0, 0, 0};   // last bmc_predict: h2d, gemm, order statistics, device
     // pinned staging for results that go back to pageable host memory (copy_to_host)
@@ -789,7 +791,8 @@ void bmc_destroy(bmc_ctx* c) {
                       &c->pPad, &c->pWt, &c->pSig, &c->pR, &c->pRT, &c->pNoise, &c->pAux, &c->pBands, &c->sVt,
                       &c->sStep, &c->sUnif, &c->sOut, &c->sCnt, &c->oFc, &c->oMu, &c->oW, &c->oOut,
                       &c->dgIn, &c->dgPart, &c->dgMean, &c->dgM2, &c->dgCols, &c->dgAcovPart,
-                      &c->dgAcov})
+                      &c->dgAcov, &c->scA, &c->scY, &c->scTheta, &c->scAp, &c->scYp, &c->scCh,
+                      &c->scPart, &c->scOut})
         release(*b);
     for (auto& e : c->ev)
         if (e) (void)hipEventDestroy(e);
@@ -1242,6 +1245,97 @@ int bmc_chain_diagnostics_device(bmc_ctx* c, const void* d_samples, int32_t n_ch
     HIPCHK(c, hipSetDevice(c->device));
     return diag_run(c, (const double*)d_samples, n_chains, iters, n_cols, ld, burn, mean_out, sd_out,
                     rhat_out, ess_out, mcse_out, max_lag_out);
+}
+
+// ---- pointwise log predictive density (kernels_waic.hip) ----------------------
+
+namespace {
+
+int check_score_args(bmc_ctx* c, const void* A, int64_t n, int32_t k, int64_t lda, int layout,
+                     const void* y, const void* theta, int64_t S, int64_t ldt) {
+    if (!c) return BMC_EINVAL;
+    if (!A || !y || !theta) return fail(c, BMC_EINVAL, "A, y and theta must not be NULL");
+    if (n < 1) return fail(c, BMC_EINVAL, "n_points must be >= 1");
+    if (k < 1 || k > SCORE_MAX_K)
+        return fail(c, BMC_EINVAL, "k must be between 1 and " + std::to_string(SCORE_MAX_K));
+    if (layout != BMC_ROW_MAJOR && layout != BMC_COL_MAJOR)
+        return fail(c, BMC_EINVAL, "layout must be BMC_ROW_MAJOR or BMC_COL_MAJOR");
+    if (lda < (layout == BMC_COL_MAJOR ? n : (int64_t)k))
+        return fail(c, BMC_EINVAL, "lda is smaller than the leading dimension of A");
+    if (S < 2) return fail(c, BMC_EINVAL, "n_draws must be >= 2 (the variance has ddof 1)");
+    if (ldt < (int64_t)k + 1) return fail(c, BMC_EINVAL, "ldt must be >= k + 1");
+    return BMC_OK;
+}
+
+// Everything on the context's stream, in buffers of its own: the resident problem, the prior and
+// the predictive draws are not touched.
+int score_run(bmc_ctx* c, const double* dA, int64_t n, int32_t k, int64_t lda, int layout,
+              const double* dy, const double* dtheta, int64_t S, int64_t ldt, double* lppd_out,
+              double* pwaic_out, double* mean_out) {
+    const ScorePlan plan = plan_score(n, S, k, c->n_cu);
+    const ScoreBuffers sb = score_buffers(plan, S);
+    int rc;
+    if ((rc = ensure(c, c->scAp, sb.Ap))) return rc;
+    if ((rc = ensure(c, c->scYp, sb.yp))) return rc;
+    if ((rc = ensure(c, c->scCh, sb.ch))) return rc;
+    if ((rc = ensure(c, c->scPart, sb.part))) return rc;
+    if ((rc = ensure(c, c->scOut, (size_t)n * 3 * 8))) return rc;
+    ScoreArgs a;
+    a.A = dA;
+    a.y = dy;
+    a.theta = dtheta;
+    a.n = n;
+    a.lda = lda;
+    a.S = S;
+    a.ldt = ldt;
+    a.k = k;
+    a.col_major = layout == BMC_COL_MAJOR;
+    a.Ap = (double*)c->scAp.p;
+    a.yp = (double*)c->scYp.p;
+    a.ch = (double*)c->scCh.p;
+    a.part = (double*)c->scPart.p;
+    a.out = (double*)c->scOut.p;
+    HIPCHK(c, launch_score(a, plan, c->stream));
+    double* outs[3] = {lppd_out, pwaic_out, mean_out};
+    for (int f = 0; f < 3; ++f)
+        if (outs[f])
+            HIPCHK(c, hipMemcpyAsync(outs[f], a.out + (size_t)f * n, (size_t)n * 8,
+                                     hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return BMC_OK;
+}
+
+}  // namespace
+
+int bmc_pointwise_loglik(bmc_ctx* c, const double* A, int64_t n_points, int32_t k, int64_t lda,
+                         int layout, const double* y, const double* theta, int64_t n_draws,
+                         int64_t ldt, double* lppd_out, double* pwaic_out, double* mean_ll_out) {
+    int rc = check_score_args(c, A, n_points, k, lda, layout, y, theta, n_draws, ldt);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    // (the last row / column of a strided host array may be shorter than its stride)
+    const size_t abytes = (layout == BMC_COL_MAJOR ? (size_t)lda * (k - 1) + (size_t)n_points
+                                                   : (size_t)lda * (n_points - 1) + (size_t)k) * 8;
+    const size_t tbytes = ((size_t)ldt * (n_draws - 1) + (size_t)k + 1) * 8;
+    if ((rc = ensure(c, c->scA, abytes))) return rc;
+    if ((rc = ensure(c, c->scY, (size_t)n_points * 8))) return rc;
+    if ((rc = ensure(c, c->scTheta, tbytes))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->scA.p, A, abytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->scY.p, y, (size_t)n_points * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->scTheta.p, theta, tbytes, hipMemcpyHostToDevice, c->stream));
+    return score_run(c, (const double*)c->scA.p, n_points, k, lda, layout, (const double*)c->scY.p,
+                     (const double*)c->scTheta.p, n_draws, ldt, lppd_out, pwaic_out, mean_ll_out);
+}
+
+int bmc_pointwise_loglik_device(bmc_ctx* c, const void* dA, int64_t n_points, int32_t k, int64_t lda,
+                                int layout, const void* dy, const void* dtheta, int64_t n_draws,
+                                int64_t ldt, double* lppd_out, double* pwaic_out,
+                                double* mean_ll_out) {
+    int rc = check_score_args(c, dA, n_points, k, lda, layout, dy, dtheta, n_draws, ldt);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    return score_run(c, (const double*)dA, n_points, k, lda, layout, (const double*)dy,
+                     (const double*)dtheta, n_draws, ldt, lppd_out, pwaic_out, mean_ll_out);
 }
 
 int bmc_rng_fill(bmc_ctx* c, uint64_t seed, int64_t count_normal, double* normals_out, double shape,

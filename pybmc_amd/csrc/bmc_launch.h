@@ -247,4 +247,27 @@ hipError_t launch_diag_acov(const DiagShape& d, const double* mean, const int32_
                             int32_t n_active, int64_t t0, int64_t n_lags, double* scratch,
                             double* acov_out, hipStream_t s);
 
+// ---- pointwise log-likelihood (kernels_waic.hip; plan_score in bmc_plan.h) ---------------------
+// ll[i][s] = -1/2 log(2 pi) - log sigma_s - (y_i - a_i . beta_s)^2 / (2 sigma_s^2) for design rows
+// A (n x k, element (i, j) at i*lda + j, or j*lda + i when col_major), targets y [n] and draws
+// theta (row s at theta + s*ldt: k coefficients, then sigma_s).  Per point, over the S draws:
+// out[0][i] = logsumexp_s ll - log S, out[1][i] = var_s ll (ddof 1), out[2][i] = mean_s ll
+// (out is [3][n], device).  The n x S matrix is never stored.  Work buffers (device, sized by
+// score_buffers for the plan): Ap [n_pad][k_pad] and yp [n_pad], the operands padded to whole
+// tiles; ch [2][S], the per-draw constants; part [splits][n_pad][5], the per-split partials.
+struct ScorePlan;
+struct ScoreArgs {
+    const double* A;
+    const double* y;
+    const double* theta;
+    int64_t n, lda, S, ldt;
+    int32_t k, col_major;
+    double *Ap, *yp, *ch, *part, *out;
+};
+struct ScoreBuffers {
+    size_t Ap, yp, ch, part;   // bytes
+};
+ScoreBuffers score_buffers(const ScorePlan& p, int64_t n_draws);
+hipError_t launch_score(const ScoreArgs& a, const ScorePlan& p, hipStream_t s);
+
 }  // namespace bmc

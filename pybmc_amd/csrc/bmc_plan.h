@@ -4,6 +4,8 @@
 // (gibbs_kernel_key / simplex_kernel_key) names one instantiation; kernel_compiled() says whether
 // it is built, and kernels_gibbs.hip instantiates exactly the keys of loop_kernel_keys(), one
 // table entry each.  tests/launch_plan_check.cpp runs the planner and the selection on the CPU.
+// Also here: plan_score, the draw-split plan of the pointwise log-likelihood kernels
+// (kernels_waic.hip; tests/score_plan_check.cpp).
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -607,6 +609,44 @@ inline std::string kernel_name(const KernelKey& k) {
             return "none";
     }
     return buf;
+}
+
+// ---- pointwise log-likelihood (kernels_waic.hip) -------------------------------
+// A workgroup owns SCORE_TILE points and walks draw tiles of SCORE_TILE draws.  Few points and
+// many draws is the common case (377 training rows, 50 000 draws: 6 point tiles for 256 CUs), so
+// the draw tiles are split over `splits` workgroups per point tile; their partials are merged in
+// split order by a second kernel.  The plan depends on the shapes and the CU count only:
+//   * target: SCORE_GROUPS_PER_CU workgroups per CU (two 4-wave groups keep every SIMD supplied
+//     while the other group waits at its slab barrier);
+//   * a split walks at least SCORE_MIN_TILES draw tiles (below that the per-group set-up and the
+//     lane merge at its end outweigh the work), and no split is empty;
+//   * point tiles alone reaching the target means one split.
+constexpr int SCORE_TILE = 64;
+constexpr int SCORE_GROUPS_PER_CU = 2;
+constexpr int SCORE_MIN_TILES = 4;
+constexpr int SCORE_MAX_K = 256;
+
+struct ScorePlan {
+    int64_t point_tiles;      // ceil(n_points / 64)
+    int64_t draw_tiles;       // ceil(n_draws / 64)
+    int64_t tiles_per_split;  // draw tiles of every split but the last
+    int64_t splits;           // split j walks draw tiles [j * tiles_per_split, ...), none empty
+    int32_t k_pad;            // columns rounded up to whole 16-column slabs
+};
+
+inline ScorePlan plan_score(int64_t n_points, int64_t n_draws, int32_t k, int n_cu) {
+    ScorePlan p;
+    p.point_tiles = (n_points + SCORE_TILE - 1) / SCORE_TILE;
+    p.draw_tiles = (n_draws + SCORE_TILE - 1) / SCORE_TILE;
+    p.k_pad = (k + 15) / 16 * 16;
+    const int64_t target = (int64_t)SCORE_GROUPS_PER_CU * (n_cu > 0 ? n_cu : 1);
+    int64_t want = (target + p.point_tiles - 1) / p.point_tiles;   // 1 when the point tiles suffice
+    const int64_t most = p.draw_tiles / SCORE_MIN_TILES;   // (every split at least that long)
+    if (want > most) want = most;
+    if (want < 1) want = 1;
+    p.tiles_per_split = (p.draw_tiles + want - 1) / want;
+    p.splits = (p.draw_tiles + p.tiles_per_split - 1) / p.tiles_per_split;
+    return p;
 }
 
 }  // namespace bmc

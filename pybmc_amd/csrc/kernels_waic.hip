@@ -1,0 +1,347 @@
+// Pointwise log predictive density of a sampled fit: for design
+// rows A (n x k), targets y and draws theta = (beta_s, sigma_s),
+//   ll[i][s] = -1/2 log(2 pi) - log sigma_s - (y_i - a_i . beta_s)^2 / (2 sigma_s^2)
+// and per point i, over the S draws: logsumexp_s ll - log S, var_s ll (ddof 1), mean_s ll.
+//
+//   score_pad      A (either layout, any lda) and y -> whole 64-point tiles and 16-column slabs,
+//                  zero in the padding
+//   score_consts   per draw: c_s = -1/2 log(2 pi) - log sigma_s,  h_s = 1 / (2 sigma_s^2)
+//   score_tile     workgroup = 64 points x the draw tiles of one split.  a_i . beta_s on
+//                  v_mfma_f64_16x16x4_f64 (staging and LDS layout of predict_gemm_kernel; the draws
+//                  are read from theta in place, any ldt); the tile is reduced in the epilogue
+//                  and never stored: per lane and point an online log-sum-exp (running max, one
+//                  rescale per tile) and a mean / centred-M2 pair merged tile by tile (Chan et
+//                  al.); the 16 lanes that share a point merge at the end of the split
+//   score_merge    per point: the splits' partials (max, sumexp, count, mean, M2) merged in split
+//                  order, then lppd = max + log(sumexp) - log S, p_waic = M2 / (S - 1), mean
+//
+// No atomics: every sum has one fixed order (lane, tile, lane tree, split), so two calls return
+// the same bits.  Non-finite inputs propagate by the arithmetic alone: a NaN in a_i or y_i
+// reaches every ll[i][.], a NaN in theta or a sigma_s <= 0 reaches ll[.][s] of every point (the
+// running max ignores a NaN, the sums do not).
+#include "bmc_dev.h"
+#include "bmc_launch.h"
+#include "bmc_plan.h"
+
+namespace bmc {
+
+using f64x4 = __attribute__((ext_vector_type(4))) double;
+
+namespace {
+
+constexpr int SC_KT = 16, SC_LD = 18, SC_TM = SCORE_TILE;
+constexpr double HALF_LOG_2PI = 0.91893853320467274178;
+
+// (max, sum of exp(ll - max), count, mean, centred sum of squares) of a set of draws
+struct LlState {
+    double m, L, cnt, mean, M2;
+};
+
+// The union of two disjoint sets, a's draws before b's.  An empty side (a lane or a split that
+// saw no draw: m = -inf, L = 0) returns the other one untouched.
+__device__ __forceinline__ LlState ll_merge(const LlState& a, const LlState& b) {
+    LlState r;
+    r.m = fmax(a.m, b.m);
+    r.L = a.L * exp(a.m - r.m) + b.L * exp(b.m - r.m);
+    r.cnt = a.cnt + b.cnt;
+    const double d = b.mean - a.mean;
+    r.mean = fma(d, b.cnt / r.cnt, a.mean);
+    r.M2 = (a.M2 + b.M2) + d * d * (a.cnt * b.cnt / r.cnt);
+    if (b.cnt == 0.0) return a;
+    if (a.cnt == 0.0) return b;
+    return r;
+}
+
+__global__ __launch_bounds__(256) void score_pad_kernel(
+    const double* __restrict__ A, const double* __restrict__ y, int64_t n, int32_t k, int64_t lda,
+    int32_t col_major, int64_t n_pad, int32_t k_pad, double* __restrict__ Ap,
+    double* __restrict__ yp) {
+    const int64_t total = n_pad * k_pad;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
+        const int64_t i = e / k_pad;
+        const int32_t j = (int32_t)(e - i * k_pad);
+        double v = 0.0;
+        if (i < n && j < k) v = col_major ? A[(int64_t)j * lda + i] : A[i * lda + j];
+        Ap[e] = v;
+        if (j == 0) yp[i] = i < n ? y[i] : 0.0;
+    }
+}
+
+__global__ __launch_bounds__(256) void score_consts_kernel(const double* __restrict__ theta,
+                                                           int64_t S, int64_t ldt, int32_t k,
+                                                           double* __restrict__ ch) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= S) return;
+    const double sg = theta[s * ldt + k];
+    ch[s] = -HALF_LOG_2PI - log(sg);
+    ch[S + s] = 1.0 / (2.0 * sg * sg);
+}
+
+// The running state of one point in one lane; the count is the lane's (the same for its 4 points).
+struct LlRun {
+    double m, L, mean, M2;
+};
+
+// One 64-draw tile into the lane's running state of ONE point: x[t] = ll of draw cl + 16 t, nb of
+// them exist (ok[t]); w1 = nb / (cnt + nb) and w2 = cnt w1 are Chan's weights for joining nb
+// draws to cnt.  FULL: all four exist.
+template <bool FULL>
+__device__ __forceinline__ void score_fold(LlRun& st, const double (&x)[4], const bool (&ok)[4],
+                                           double nb, double w1, double w2) {
+    double mt = -__builtin_inf(), sum = 0.0;
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+        if (FULL || ok[t]) {
+            mt = fmax(mt, x[t]);
+            sum += x[t];
+        }
+    const double mn = fmax(st.m, mt);
+    double se = 0.0;
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+        if (FULL || ok[t]) se += exp(x[t] - mn);
+    st.L = fma(st.L, exp(st.m - mn), se);   // (first tile: L = 0, exp(-inf) = 0)
+    st.m = mn;
+    const double mb = FULL ? sum * 0.25 : sum / nb;
+    double m2b = 0.0;
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+        if (FULL || ok[t]) {
+            const double e = x[t] - mb;
+            m2b = fma(e, e, m2b);
+        }
+    const double d = mb - st.mean;
+    st.mean = fma(d, w1, st.mean);
+    st.M2 = (st.M2 + m2b) + d * d * w2;
+}
+
+// grid: splits * point_tiles, point tile fastest: the workgroups that run together walk the SAME
+// draws (one split) over different points, so each XCD's L2 fetches a slab of theta once for
+// all of them; the A tiles (64 x k_pad each) stay in L2 for the whole launch.
+__global__ __launch_bounds__(256) void score_tile_kernel(
+    const double* __restrict__ Ap, const double* __restrict__ yp, const double* __restrict__ theta,
+    const double* __restrict__ ch, int64_t S, int64_t ldt, int32_t k, int32_t k_pad,
+    uint32_t point_tiles, int64_t tiles_per_split, int64_t draw_tiles, int64_t n_pad,
+    double* __restrict__ part) {
+    __shared__ double As[2 * SC_TM * SC_LD];
+    __shared__ double Bs[2 * SC_TM * SC_LD];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const uint32_t pt = blockIdx.x % point_tiles;
+    const int64_t split = blockIdx.x / point_tiles;
+    const int64_t p0 = (int64_t)pt * SC_TM;
+    const int64_t dt0 = split * tiles_per_split;
+    const int64_t dt1 = dt0 + tiles_per_split < draw_tiles ? dt0 + tiles_per_split : draw_tiles;
+    const int cl = lane & 15, kq = lane >> 4;
+
+    // staging: element tid + 256 q of a 64 x 16 slab -> row sr + 16 q, column sc
+    const int sr = tid >> 4, sc = tid & 15;
+    const double* arow = Ap + (p0 + sr) * k_pad + sc;   // rows 16 k_pad apart, no bounds: padded
+    const double* brow[4];
+    double ra[4], rb[4];
+    // theta is read in place: a draw past S reads draw S - 1 (its ll is dropped in the epilogue),
+    // a column past k reads column k (in bounds) and stages 0
+    auto point_rows = [&](int64_t s0) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int64_t sd = s0 + sr + 16 * q;
+            brow[q] = theta + (sd < S ? sd : S - 1) * ldt;
+        }
+    };
+    auto fetch = [&](int m0) {
+        const int j = m0 + sc;
+        const int jc = j < k ? j : k;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            ra[q] = arow[(int64_t)(16 * q) * k_pad + m0];
+            const double v = brow[q][jc];
+            rb[q] = j < k ? v : 0.0;
+        }
+    };
+    double* as_w = As + sr * SC_LD + sc;
+    double* bs_w = Bs + sr * SC_LD + sc;
+    auto stash = [&](int buf) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            as_w[(buf * SC_TM + 16 * q) * SC_LD] = ra[q];
+            bs_w[(buf * SC_TM + 16 * q) * SC_LD] = rb[q];
+        }
+    };
+    const double* a_r = As + (16 * wave + cl) * SC_LD + kq;
+    const double* b_r = Bs + cl * SC_LD + kq;
+    const int nslab = k_pad / SC_KT;
+    const int last_nk = (k - SC_KT * (nslab - 1) + 3) / 4;   // k-steps of the last slab, 1 .. 4
+
+    // this lane's four points: rows 16 wave + kq + 4 r of the tile (MFMA D: row = kq + 4 reg)
+    double yv[4];
+    LlRun st[4];
+    double cnt = 0.0;   // draws this lane has folded
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        yv[r] = yp[p0 + 16 * wave + kq + 4 * r];
+        st[r] = LlRun{-__builtin_inf(), 0.0, 0.0, 0.0};
+    }
+
+    point_rows(dt0 * SC_TM);
+    fetch(0);
+    for (int64_t dt = dt0; dt < dt1; ++dt) {
+        const int64_t s0 = dt * SC_TM;
+        f64x4 acc[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) acc[t] = f64x4{0.0, 0.0, 0.0, 0.0};
+        stash(0);
+        __syncthreads();
+        for (int sl = 0; sl + 1 < nslab; ++sl) {
+            const int buf = sl & 1;
+            fetch((sl + 1) * SC_KT);
+            const double* Ab = a_r + buf * SC_TM * SC_LD;
+            const double* Bb = b_r + buf * SC_TM * SC_LD;
+#pragma unroll
+            for (int kk = 0; kk < SC_KT / 4; ++kk) {
+                const double a = Ab[4 * kk];
+#pragma unroll
+                for (int t = 0; t < 4; ++t)
+                    acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Bb[16 * t * SC_LD + 4 * kk],
+                                                                  acc[t], 0, 0, 0);
+            }
+            stash(buf ^ 1);
+            __syncthreads();
+        }
+        {
+            const int buf = (nslab - 1) & 1;
+            const double* Ab = a_r + buf * SC_TM * SC_LD;
+            const double* Bb = b_r + buf * SC_TM * SC_LD;
+            for (int kk = 0; kk < last_nk; ++kk) {
+                const double a = Ab[4 * kk];
+#pragma unroll
+                for (int t = 0; t < 4; ++t)
+                    acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Bb[16 * t * SC_LD + 4 * kk],
+                                                                  acc[t], 0, 0, 0);
+            }
+        }
+        // every wave is done with the LDS slabs before the next tile's first slab lands there;
+        // its global reads are issued now and wait behind the epilogue
+        __syncthreads();
+        if (dt + 1 < dt1) {
+            point_rows(s0 + SC_TM);
+            fetch(0);
+        }
+
+        // epilogue: ll = c_s - h_s r^2 for the lane's 4 points x 4 draws, folded into the running
+        // state of each point
+        double cs[4], hs[4];
+        bool ok[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const int64_t sd = s0 + cl + 16 * t;
+            ok[t] = sd < S;
+            const int64_t sdc = ok[t] ? sd : S - 1;
+            cs[t] = ch[sdc];
+            hs[t] = ch[S + sdc];
+        }
+        const bool full = s0 + SC_TM <= S;   // wave-uniform
+        const double nb = (double)((int)ok[0] + (int)ok[1] + (int)ok[2] + (int)ok[3]);
+        if (nb > 0.0) {   // (not a lane whose draws of the last tile are all past S)
+            const double w1 = nb / (cnt + nb), w2 = cnt * w1;
+            cnt += nb;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                double x[4];
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    const double res = yv[r] - acc[t][r];
+                    x[t] = fma(-(hs[t] * res), res, cs[t]);
+                }
+                if (full) score_fold<true>(st[r], x, ok, nb, w1, w2);
+                else score_fold<false>(st[r], x, ok, nb, w1, w2);
+            }
+        }
+    }
+
+    // the 16 lanes (cl) that hold draws of the same four points: a tree over cl, the lower lane's
+    // draws first, so every lane ends with the same bits; lane cl = 0 writes them
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        LlState me{st[r].m, st[r].L, cnt, st[r].mean, st[r].M2};
+#pragma unroll
+        for (int bit = 1; bit < 16; bit <<= 1) {
+            LlState o;
+            o.m = __shfl_xor(me.m, bit);
+            o.L = __shfl_xor(me.L, bit);
+            o.cnt = __shfl_xor(me.cnt, bit);
+            o.mean = __shfl_xor(me.mean, bit);
+            o.M2 = __shfl_xor(me.M2, bit);
+            me = (cl & bit) ? ll_merge(o, me) : ll_merge(me, o);
+        }
+        if (cl == 0) {
+            double* o = part + ((int64_t)split * n_pad + p0 + 16 * wave + kq + 4 * r) * 5;
+            o[0] = me.m;
+            o[1] = me.L;
+            o[2] = me.cnt;
+            o[3] = me.mean;
+            o[4] = me.M2;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void score_merge_kernel(const double* __restrict__ part,
+                                                          int64_t n, int64_t n_pad, int64_t splits,
+                                                          int64_t S, double* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    auto load = [&](int64_t sp) {
+        const double* p = part + (sp * n_pad + i) * 5;
+        return LlState{p[0], p[1], p[2], p[3], p[4]};
+    };
+    LlState st = load(0);
+    for (int64_t sp = 1; sp < splits; ++sp) st = ll_merge(st, load(sp));
+    out[i] = st.m + (log(st.L) - log((double)S));
+    out[n + i] = st.M2 / (double)(S - 1);
+    out[2 * n + i] = st.mean;
+}
+
+}  // namespace
+
+ScoreBuffers score_buffers(const ScorePlan& p, int64_t n_draws) {
+    const size_t n_pad = (size_t)p.point_tiles * SC_TM;
+    ScoreBuffers b;
+    b.Ap = n_pad * (size_t)p.k_pad * 8;
+    b.yp = n_pad * 8;
+    b.ch = (size_t)n_draws * 2 * 8;
+    b.part = (size_t)p.splits * n_pad * 5 * 8;
+    return b;
+}
+
+hipError_t launch_score(const ScoreArgs& a, const ScorePlan& p, hipStream_t s) {
+    if (a.n < 1 || a.S < 2 || a.k < 1 || a.k > SCORE_MAX_K || a.ldt < a.k + 1 ||
+        a.lda < (a.col_major ? a.n : (int64_t)a.k) || p.k_pad < a.k || p.k_pad % SC_KT != 0 ||
+        p.point_tiles != (a.n + SC_TM - 1) / SC_TM || p.draw_tiles != (a.S + SC_TM - 1) / SC_TM ||
+        p.splits < 1 || p.tiles_per_split < 1 || p.splits * p.tiles_per_split < p.draw_tiles ||
+        (p.splits - 1) * p.tiles_per_split >= p.draw_tiles)
+        return hipErrorInvalidValue;
+    const uint64_t groups = (uint64_t)p.splits * (uint64_t)p.point_tiles;
+    if (groups > 0x7fffffffull || p.point_tiles > 0x7fffffffll) return hipErrorInvalidValue;
+    const int64_t n_pad = p.point_tiles * SC_TM;
+    {
+        int64_t blocks = (n_pad * p.k_pad + 255) / 256;
+        if (blocks > 8192) blocks = 8192;
+        hipLaunchKernelGGL(score_pad_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a.A, a.y, a.n,
+                           a.k, a.lda, a.col_major, n_pad, p.k_pad, a.Ap, a.yp);
+    }
+    {
+        const int64_t blocks = (a.S + 255) / 256;
+        if (blocks > 0x7fffffffll) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(score_consts_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a.theta, a.S,
+                           a.ldt, a.k, a.ch);
+    }
+    hipLaunchKernelGGL(score_tile_kernel, dim3((unsigned)groups), dim3(256), 0, s,
+                       (const double*)a.Ap, (const double*)a.yp, a.theta, (const double*)a.ch, a.S,
+                       a.ldt, a.k, p.k_pad, (uint32_t)p.point_tiles, p.tiles_per_split,
+                       p.draw_tiles, n_pad, a.part);
+    hipLaunchKernelGGL(score_merge_kernel, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, s,
+                       (const double*)a.part, a.n, n_pad, p.splits, a.S, a.out);
+    return hipGetLastError();
+}
+
+}  // namespace bmc
