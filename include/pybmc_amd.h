@@ -152,6 +152,17 @@ int bmc_get_gram(bmc_ctx* ctx, double* gram_out);
 int bmc_get_basis(bmc_ctx* ctx, double* W_out, double* lam_out, double* sigma2_init);
 int bmc_conditional_moments(bmc_ctx* ctx, double sigma2, double* mean_out,
                             double* cov_out);
+/* The persistent loop kernels launched by the LAST bmc_gibbs_run* or bmc_simplex_run on this
+ * context: their demangled names (e.g. "gibbs_loop_kernel<double, 1, 0, 32, 1, false, false,
+ * true>"), one per launch, in launch order, each followed by '\n', the whole NUL-terminated.
+ * *n_out = launches, *needed_out = bytes including the NUL (either may be NULL); names_out may be
+ * NULL to ask for the size only, BMC_EINVAL when capacity < *needed_out.  A run without a loop
+ * kernel (rss_mode 1, zero iterations) or no run yet gives an empty list; the list is emptied
+ * when a run is entered, so a rejected run leaves it empty and a run that fails part-way leaves
+ * the launches made before the failure.  The names are built on the host from the key the
+ * launcher looked its kernel up with; nothing is read from the device. */
+int bmc_last_kernels(bmc_ctx* ctx, char* names_out, int64_t capacity, int32_t* n_out,
+                     int64_t* needed_out);
 
 /* ---- residual reduction: rss[b] = sum_i (y_i - sum_j X_ij beta[b][j])^2 -------
  * Replaces inference_utils.py:48-51 as a stand-alone streaming kernel over the

@@ -62,6 +62,8 @@ PROTOTYPES = {
     "bmc_get_gram": (C.c_int, [_P, _D]),
     "bmc_get_basis": (C.c_int, [_P, _D, _D, _D]),
     "bmc_conditional_moments": (C.c_int, [_P, C.c_double, _D, _D]),
+    "bmc_last_kernels": (C.c_int, [_P, C.c_char_p, C.c_int64, C.POINTER(C.c_int32),
+                                   C.POINTER(C.c_int64)]),
     "bmc_residual_rss": (C.c_int, [_P, _D, C.c_int32, _D]),
     "bmc_residual_rss_bench": (C.c_int, [_P, C.c_int32, C.c_int32, _D]),
     "bmc_gram_bench": (C.c_int, [_P, C.c_int32, _D]),
@@ -298,6 +300,15 @@ class Context:
         self._check(self._lib.bmc_conditional_moments(self._h, float(sigma2), _dptr(mean),
                                                       _dptr(cov)))
         return mean, cov
+
+    def last_kernels(self):
+        """Demangled names of the persistent loop kernels the last gibbs_run* / simplex_run on
+        this context launched, one per launch, in launch order ([] for rss_mode 1)."""
+        need = C.c_int64()
+        self._check(self._lib.bmc_last_kernels(self._h, None, 0, None, C.byref(need)))
+        buf = C.create_string_buffer(need.value)
+        self._check(self._lib.bmc_last_kernels(self._h, buf, need.value, None, None))
+        return buf.value.decode().splitlines()
 
     def residual_rss(self, beta):
         beta = np.ascontiguousarray(np.atleast_2d(beta), dtype=np.float64)

@@ -62,6 +62,9 @@ struct bmc_ctx {
     DevBuf gramScratch, gramOut, rssPartial, rssOut, coef, stage, ticket;
     // run buffers
     DevBuf xi, gam, uout, samples, gran, status, seeds, dbg, placement;
+    // the persistent loop kernels of the last bmc_gibbs_run* / bmc_simplex_run, one name per
+    // launch in launch order (bmc_last_kernels)
+    std::vector<std::string> last_kernels;
     // predictive buffers
     DevBuf pPreds, pPad, pTheta, pVt, pWt, pSig, pR, pRT, pNoise, pAux, pBands;
     int64_t pM = 0;                        // last bmc_predict: points, draws, padded draws
@@ -386,6 +389,7 @@ int run_common(bmc_ctx* c, int32_t n_chains, int64_t iters, const uint64_t* seed
                const double* xi, const double* g, double* samples_host, void* samples_dev,
                bmc_stats* stats) {
     if (!c) return BMC_EINVAL;
+    c->last_kernels.clear();
     if (!c->have_problem || !c->have_prior)
         return fail(c, BMC_ESTATE, "bmc_set_problem and bmc_set_prior must be called first");
     if (n_chains < 1 || iters < 0) return fail(c, BMC_EINVAL, "need n_chains >= 1, iters >= 0");
@@ -523,7 +527,9 @@ int run_common(bmc_ctx* c, int32_t n_chains, int64_t iters, const uint64_t* seed
         if (a.G > 1 || l.chains_per_pass > 1)   // (a single-workgroup chain waits for nobody)
             if ((rc = check_residency(c, gibbs_kernel(a), l.resident, "persistent Gibbs kernel")))
                 return rc;
-        HIPCHK(c, launch_gibbs(a, c->stream));
+        KernelKey launched;
+        HIPCHK(c, launch_gibbs(a, c->stream, &launched));
+        c->last_kernels.push_back(kernel_name(launched));
         ++launches;
     }
     HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
@@ -1120,6 +1126,19 @@ int bmc_get_basis(bmc_ctx* c, double* W_out, double* lam_out, double* sigma2_ini
     return BMC_OK;
 }
 
+int bmc_last_kernels(bmc_ctx* c, char* names_out, int64_t capacity, int32_t* n_out, int64_t* needed_out) {
+    if (!c) return BMC_EINVAL;
+    std::string all;
+    for (const std::string& name : c->last_kernels) all += name + "\n";
+    if (n_out) *n_out = (int32_t)c->last_kernels.size();
+    if (needed_out) *needed_out = (int64_t)all.size() + 1;
+    if (names_out) {
+        if (capacity < (int64_t)all.size() + 1) return fail(c, BMC_EINVAL, "bmc_last_kernels: buffer too small");
+        std::memcpy(names_out, all.c_str(), all.size() + 1);
+    }
+    return BMC_OK;
+}
+
 int bmc_conditional_moments(bmc_ctx* c, double sigma2, double* mean_out, double* cov_out) {
     if (!c) return BMC_EINVAL;
     if (!c->have_prior) return fail(c, BMC_ESTATE, "no prior set");
@@ -1368,6 +1387,7 @@ int bmc_simplex_run(bmc_ctx* c, const double* Vt_hat, int32_t Km, const double* 
                     int64_t n_unif, const double* g, double* samples_out, int64_t* accepted_out,
                     int64_t* unif_used_out, bmc_stats* stats) {
     if (!c) return BMC_EINVAL;
+    c->last_kernels.clear();
     if (!c->have_problem) return fail(c, BMC_ESTATE, "bmc_set_problem must be called first");
     if (!Vt_hat || !S_hat || Km < 1) return fail(c, BMC_EINVAL, "Vt_hat/S_hat/n_models invalid");
     if (burn < 0) return fail(c, BMC_EINVAL, "Burn-in iterations must be non-negative.");
@@ -1463,7 +1483,9 @@ int bmc_simplex_run(bmc_ctx* c, const double* Vt_hat, int32_t Km, const double* 
         if (a.G > 1 &&
             (rc = check_residency(c, simplex_kernel(a), a.G, "persistent simplex kernel")))
             return rc;
-        HIPCHK(c, launch_simplex(a, c->stream));
+        KernelKey launched;
+        HIPCHK(c, launch_simplex(a, c->stream, &launched));
+        c->last_kernels.push_back(kernel_name(launched));
     }
     HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
     int32_t st = 0, place = 0;

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bmc_plan.h"
+
 namespace bmc {
 
 // Storage description of the panelised problem (see bmc_dev.h "panel layout").
@@ -203,12 +205,14 @@ struct SimplexArgs {
     int32_t one_wave = 0;   // host-only. 1: simplex_wave_kernel (gibbs_wave_capacity() > 0, Km <= 64)
 };
 size_t simplex_lds_bytes(const SimplexArgs& a);
-hipError_t launch_simplex(const SimplexArgs& a, hipStream_t s);
+// (launched: as for launch_gibbs)
+hipError_t launch_simplex(const SimplexArgs& a, hipStream_t s, KernelKey* launched = nullptr);
 // uniforms in (0,1]: out[i] = u53(philox(counter = (i, STREAM_UNIFORM), key = seed))
 hipError_t launch_uniform_fill(uint64_t seed, int64_t n, double* out, hipStream_t s);
 
 size_t gibbs_lds_bytes(const GibbsArgs& a);
-hipError_t launch_gibbs(const GibbsArgs& a, hipStream_t s);
+// launched (optional): the key of the instantiation the launcher looked up and launched
+hipError_t launch_gibbs(const GibbsArgs& a, hipStream_t s, KernelKey* launched = nullptr);
 
 // The kernel that launch_gibbs / launch_simplex would launch for these arguments: the
 // instantiation of bmc_plan.h's gibbs_kernel_key / simplex_kernel_key, its grid, block and dynamic
@@ -219,6 +223,7 @@ struct LoopKernel {
     const void* fn;
     dim3 grid, block;
     size_t lds;
+    KernelKey key;   // the instantiation fn is (family KF_NONE with fn = nullptr)
 };
 LoopKernel gibbs_kernel(const GibbsArgs& a);
 LoopKernel simplex_kernel(const SimplexArgs& a);

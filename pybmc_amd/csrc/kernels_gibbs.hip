@@ -1183,6 +1183,7 @@ static LoopKernel loop_kernel(const KernelKey& key, int slots, int G, int waves,
     const bool one_wave = key.family == KF_WAVE || key.family == KF_SIMPLEX_WAVE;
     LoopKernel r;
     r.fn = kernel_of(key, std::make_integer_sequence<int, KEYS.n>{});
+    r.key = r.fn ? key : KernelKey{};
     r.grid = dim3(one_wave ? slots : slots * G);
     r.block = dim3(64 * (waves > 1 ? waves : 1));
     r.lds = one_wave ? 0 : lds;
@@ -1227,8 +1228,9 @@ LoopKernel simplex_kernel(const SimplexArgs& a) {
 }
 
 template <typename Args>
-static hipError_t launch_loop(const LoopKernel& k, const Args& a, hipStream_t s) {
+static hipError_t launch_loop(const LoopKernel& k, const Args& a, hipStream_t s, KernelKey* launched) {
     if (!k.fn) return hipErrorInvalidValue;
+    if (launched) *launched = k.key;
     hipError_t e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds);
     if (e != hipSuccess) return e;
     Args copy = a;
@@ -1237,7 +1239,11 @@ static hipError_t launch_loop(const LoopKernel& k, const Args& a, hipStream_t s)
     return e != hipSuccess ? e : hipGetLastError();
 }
 
-hipError_t launch_gibbs(const GibbsArgs& a, hipStream_t s) { return launch_loop(gibbs_kernel(a), a, s); }
-hipError_t launch_simplex(const SimplexArgs& a, hipStream_t s) { return launch_loop(simplex_kernel(a), a, s); }
+hipError_t launch_gibbs(const GibbsArgs& a, hipStream_t s, KernelKey* launched) {
+    return launch_loop(gibbs_kernel(a), a, s, launched);
+}
+hipError_t launch_simplex(const SimplexArgs& a, hipStream_t s, KernelKey* launched) {
+    return launch_loop(simplex_kernel(a), a, s, launched);
+}
 
 }  // namespace bmc

@@ -8,12 +8,26 @@
 //                  sampler's geometries too).  Prints the compiled kernels no plan reaches, then
 //                  "sweep <plans> <failures>" last.
 //   names          the demangled names of every compiled loop kernel (kernels_gibbs.hip's table)
+//   census         for every compiled loop kernel the cheapest recipe (smallest n * k * chains) of a
+//                  grid of shapes x chain counts x cu_limit x tunings whose plan launches it, as
+//                  "name | recipe", or "name | unreached"; tests/kernel_census.txt pins the output
+//                  (regenerate: g++ -std=c++17 -O2 -o /tmp/lpc tests/launch_plan_check.cpp &&
+//                  /tmp/lpc census > tests/kernel_census.txt)
+//   replan FILE    re-plans every recipe of such a table: "name | the launches in order, joined by
+//                  ;, each kernel@first chain+chains:chains per pass | the same had the device
+//                  given the other pack answer"
 #include "../pybmc_amd/csrc/bmc_plan.h"
 
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
+#include <fstream>
 #include <set>
+#include <array>
+#include <iterator>
 #include <string>
+#include <unordered_map>
+#include <vector>
 
 using namespace bmc;
 
@@ -201,8 +215,173 @@ static long sweep() {
     return plans;
 }
 
+// ---- census: the cheapest recipe that launches each compiled kernel ---------------------------
+// A recipe is a problem the samplers accept and the parity tests can perturb: k >= 2 (one column
+// cannot show a column mix-up, nor lose a column), n >= 2 k + 2 (X'X stays regular with the last
+// row dropped); the simplex sampler needs k < n_models, and its
+// one-wave kernels n_models <= 64 (ow = 1), so k <= 62 there.  Recipes assume a 256-CU device.
+struct Recipe {
+    int sampler = 0;   // 0 Gibbs, 1 simplex
+    int64_t n = 0;
+    int k = 0, f32 = 0, chains = 0, cu = 0, G = 0, W = 0, res = 0, ppw = 0, cpp = 0, pack = 0, ow = 0;
+    double cost() const { return (double)n * k * chains; }
+};
+
+static std::vector<std::string> plan_recipe(const Recipe& r, bool pack_answer) {
+    const Shape s = shape_of(r.n, r.k, r.f32);
+    const bmc_tuning tu = tuning(r.G, r.W, r.res, r.ppw, r.cpp, r.cu);
+    const Chip chip = chip_of(256, r.cu);
+    std::vector<std::string> out;
+    if (r.sampler == 1) {
+        const Geometry g = choose_geometry(s, tu, chip, 1, r.ow != 0, 4);
+        out.push_back(kernel_name(simplex_kernel_key(s, g)) + "@0+1:1");
+        return out;
+    }
+    const Geometry g = choose_geometry(s, tu, chip, r.chains, true, 8);
+    const bool pack_ok = pack_answer && gibbs_packable(s.k, s.f32, s.vec, g.ppw);
+    for (const GibbsLaunch& l : plan_gibbs(g, s, tu, chip, r.chains, pack_ok).launches)
+        out.push_back(kernel_name(gibbs_kernel_key(s, g, l)) + "@" + std::to_string(l.c0) + "+" +
+                      std::to_string(l.n_chains) + ":" + std::to_string(l.chains_per_pass));
+    return out;
+}
+
+static void print_recipe(const Recipe& r) {
+    std::printf("%s n=%lld k=%d f32=%d chains=%d cu=%d G=%d W=%d res=%d ppw=%d cpp=%d pack=%d ow=%d",
+                r.sampler ? "simplex" : "gibbs", (long long)r.n, r.k, r.f32, r.chains, r.cu, r.G, r.W, r.res,
+                r.ppw, r.cpp, r.pack, r.ow);
+}
+
+static void census(const KernelKeys& keys) {
+    // the sweep's grid, the multiples of 64 also one row short (a ragged last panel costs less and
+    // wins), small n for the one-wave shapes (2 / 4 / 8 panels per wave in 1, 2, 4 or 8 waves), the
+    // rows-per-lane boundaries of choose_vec, k in every kmax bracket
+    const int64_t ns[] = {1, 3, 63, 64, 100, 127, 200, 255, 300, 400, 511, 629, 767, 1000, 1023, 1500, 2047,
+                          2500, 3000, 3999, 4000, 5000, 6000, 7999, 8000, 10000, 12000, 15999, 16000, 20000,
+                          30000, 40000, 65000, 100000, 131071, 131137, 140000, 199999, 200000, 262143, 262209,
+                          300000, 399999, 400000, 600000, 999999, 1000000};
+    const int ks[] = {1, 2, 3, 4, 5, 8, 9, 12, 16, 17, 24, 32, 33, 48, 64, 65, 128, 256};
+    const int cu_limits[] = {0, 128, 64, 32, 16};
+    const int chains[] = {1, 2, 3, 4, 5, 7, 8, 9, 12, 15, 16, 17, 19, 24, 31, 32, 33, 37, 40, 45, 48,
+                          63, 64, 65, 100, 130, 256, 300, 2048, 3000};
+    std::vector<std::array<int, 5>> knobs = {
+        {0, 0, 0, 0, 0}, {0, 1, 0, 0, 0}, {0, 2, 0, 0, 0}, {0, 4, 0, 0, 0}, {0, 8, 0, 0, 0}, {1, 0, 0, 0, 0},
+        {10, 0, 0, 0, 0}, {32, 0, 0, 0, 0}, {10, 1, 0, 0, 0}, {1, 4, 0, 0, 0}, {3, 2, 2, 0, 0}, {0, 0, 1, 0, 0},
+        {0, 0, 2, 0, 0}, {0, 0, 3, 0, 0}, {0, 0, 3, 0, 1}, {0, 0, 1, 0, 1}, {0, 0, 0, 0, 1}, {0, 0, 0, 0, 2},
+        {0, 0, 0, 0, 4}, {0, 0, 0, 0, 8}, {0, 0, 0, 1, 0}, {0, 0, 0, 2, 0}, {0, 0, 0, 4, 0}};
+    // and what the sweep's 23 tunings leave out: groups x waves x residency x panels per wave x
+    // chains per pass in combination
+    for (int G : {0, 1, 3, 40, 200})
+        for (int W : {0, 2, 8})
+            for (int res : {0, 1, 2, 3})
+                for (int ppw : {0, 1, 2, 4})
+                    for (int cpp : {0, 2, 4}) knobs.push_back({G, W, res, ppw, cpp});
+    const size_t n_sweep_knobs = 23;   // (the tunings added above run with the chain counts below only)
+    const int few_chains[] = {1, 2, 4, 8, 9};
+    std::vector<Recipe> best(keys.n);
+    std::unordered_map<uint64_t, int> index;
+    auto packed = [](const KernelKey& k) {
+        return (uint64_t)k.family | (uint64_t)k.f32 << 3 | (uint64_t)k.vec << 4 | (uint64_t)k.mode << 7 |
+               (uint64_t)k.kmax << 9 | (uint64_t)k.ppw << 17 | (uint64_t)k.cpp << 20 | (uint64_t)k.rmax << 24 |
+               (uint64_t)k.nw << 29 | (uint64_t)k.single << 33 | (uint64_t)k.pack << 34 | (uint64_t)k.smallg << 35 |
+               (uint64_t)k.slotted << 36 | (uint64_t)k.bal << 37;
+    };
+    for (int i = 0; i < keys.n; ++i) index[packed(keys.key[i])] = i;
+    auto offer = [&](const KernelKey& key, const Recipe& r) {
+        const auto it = index.find(packed(key));
+        if (it == index.end()) return;
+        Recipe& b = best[it->second];
+        if (b.chains == 0 || r.cost() < b.cost()) b = r;
+    };
+    for (int64_t n : ns)
+        for (int k : ks) {
+            if (k < 2 || n < 2 * k + 2) continue;
+            for (int f32 : {0, 1}) {
+                const Shape s = shape_of(n, k, f32);
+                for (size_t ki = 0; ki < knobs.size(); ++ki)
+                    for (int cl : cu_limits) {
+                        const auto& kn = knobs[ki];
+                        const bmc_tuning tu = tuning(kn[0], kn[1], kn[2], kn[3], kn[4], cl);
+                        const Chip chip = chip_of(256, cl);
+                        if (tu.groups_per_chain > chip.groups_max) continue;   // run_common: BMC_EINVAL
+                        Recipe r;
+                        r.n = n; r.k = k; r.f32 = f32; r.cu = cl;
+                        r.G = kn[0]; r.W = kn[1]; r.res = kn[2]; r.ppw = kn[3]; r.cpp = kn[4];
+                        if (kn[4] == 0)   // (the simplex sampler has no chains per pass)
+                            for (int ow : {1, 0}) {
+                                if (ow && k > 62) continue;
+                                const Geometry g = choose_geometry(s, tu, chip, 1, ow != 0, 4);
+                                if (!g.one_wave && !geometry_ok(s.k, g.G, g.waves, g.nslot)) continue;
+                                r.sampler = 1; r.chains = 1; r.ow = ow; r.pack = 0;
+                                offer(simplex_kernel_key(s, g), r);
+                            }
+                        r.sampler = 0; r.ow = 0;
+                        const int* nc_begin = ki < n_sweep_knobs ? std::begin(chains) : std::begin(few_chains);
+                        const int* nc_end = ki < n_sweep_knobs ? std::end(chains) : std::end(few_chains);
+                        for (const int* pnc = nc_begin; pnc != nc_end; ++pnc) {
+                            const int nc = *pnc;
+                            const Geometry g = choose_geometry(s, tu, chip, nc, true, 8);
+                            for (int flag : {0, 1}) {
+                                const bool pack_ok = flag && gibbs_packable(s.k, s.f32, s.vec, g.ppw);
+                                if (flag && !pack_ok) continue;   // (the same plan as without)
+                                // where the packed variant exists and the plan asks the device, a
+                                // recipe counts on its yes (128 VGPRs, two groups per CU)
+                                if (!flag && gibbs_packable(s.k, s.f32, s.vec, g.ppw) &&
+                                    gibbs_pack_candidate(g, chip, tu, nc))
+                                    continue;
+                                r.chains = nc; r.pack = flag;
+                                for (const GibbsLaunch& l : plan_gibbs(g, s, tu, chip, nc, pack_ok).launches)
+                                    offer(gibbs_kernel_key(s, g, l), r);
+                            }
+                        }
+                    }
+            }
+        }
+    for (int i = 0; i < keys.n; ++i) {
+        std::printf("%s | ", kernel_name(keys.key[i]).c_str());
+        if (best[i].chains == 0) std::printf("unreached");
+        else print_recipe(best[i]);
+        std::printf("\n");
+    }
+}
+
+static int replan(const char* file) {
+    std::ifstream in(file);
+    if (!in) return 2;
+    std::string line;
+    while (std::getline(in, line)) {
+        const size_t bar = line.find(" | ");
+        if (bar == std::string::npos) continue;
+        const std::string name = line.substr(0, bar), rec = line.substr(bar + 3);
+        if (rec == "unreached") {
+            std::printf("%s | unreached\n", name.c_str());
+            continue;
+        }
+        Recipe r;
+        char sampler[16];
+        long long n;
+        if (std::sscanf(rec.c_str(), "%15s n=%lld k=%d f32=%d chains=%d cu=%d G=%d W=%d res=%d ppw=%d cpp=%d pack=%d ow=%d",
+                        sampler, &n, &r.k, &r.f32, &r.chains, &r.cu, &r.G, &r.W, &r.res, &r.ppw, &r.cpp, &r.pack,
+                        &r.ow) != 13)
+            return 3;
+        r.n = n;
+        r.sampler = std::strcmp(sampler, "simplex") == 0;
+        std::printf("%s |", name.c_str());
+        for (int other : {0, 1}) {
+            const std::vector<std::string> ks = plan_recipe(r, other ? !r.pack : r.pack != 0);
+            for (size_t i = 0; i < ks.size(); ++i) std::printf("%s%s", i ? ";" : " ", ks[i].c_str());
+            std::printf(other ? "\n" : " |");
+        }
+    }
+    return 0;
+}
+
 int main(int argc, char** argv) {
     static constexpr KernelKeys keys = loop_kernel_keys();
+    if (argc > 1 && std::strcmp(argv[1], "census") == 0) {
+        census(keys);
+        return 0;
+    }
+    if (argc > 2 && std::strcmp(argv[1], "replan") == 0) return replan(argv[2]);
     if (argc > 1 && std::strcmp(argv[1], "sweep") == 0) {
         const long plans = sweep();
         int unreached = 0;

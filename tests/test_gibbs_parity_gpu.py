@@ -11,6 +11,7 @@ Tiers:
 import numpy as np
 import pytest
 
+import census_common as cc
 from gpu_common import golden_case, gpu_ctx, replay_inputs
 from oracle import bmc_oracle as O
 from pybmc_amd.chains import posterior_summary
@@ -528,6 +529,52 @@ def test_t2_long_chain_at_c2_size():
         assert rel(a[key], b[key]) < REL_BAR, key
 
 
+@pytest.fixture(scope="module")
+def planner(tmp_path_factory):
+    return cc.build_planner(tmp_path_factory.mktemp("planner"))
+
+
+def replay_distinct_streams(ctx, planner, tmp_path, y, X, prior, dt, nch, T, **tune):
+    """nch chains of the problem set on ctx in replay mode, the first, one middle and the last slot
+    of every launch and of every bundle on DIFFERENT streams (census_common.colour_slots, from the
+    launches the CPU planner predicts; Context.last_kernels() must agree with one of its two pack
+    answers), every slot compared with its OWN oracle chain: a kernel that reads another slot's
+    variates, or a bundle that swaps two chains, fails.  f64 storage: the replay bar 1e-9; f32:
+    test_t2_float32_storage's bar on posterior_summary, the oracle run on the f32-rounded data.
+    Returns (stats, launches)."""
+    f32 = np.dtype(dt) == np.float32
+    Xd, yd = np.asarray(X, dt).astype(np.float64), np.asarray(y, dt).astype(np.float64)
+    plans = cc.plan_launches(planner, tmp_path, Xd.shape[0], Xd.shape[1], f32, nch,
+                             res=tune.get("residency", 0), cpp=tune.get("chains_per_pass", 0))
+    n_streams = cc.N_STREAMS if nch > 2 else nch
+    colour = cc.colour_slots(plans[0], n_streams, plans[1])
+    streams = cc.gibbs_streams(yd, Xd, prior, n_streams, T)
+    chains = [cc.gibbs_chain(yd, Xd, prior, Z, G) for Z, G in streams]
+    W, lam, _ = ctx.basis()
+    st_o = O.chain_setup(yd, Xd, prior)
+    xis = [O.innovations_in_basis(st_o, yd, Xd, ref, W, lam, trace) for ref, trace in chains]
+    ctx.set_tuning(**tune)
+    try:
+        out, st = ctx.gibbs_run(nch, T, xi=np.stack([xis[colour[c]] for c in range(nch)]),
+                                g=np.stack([streams[colour[c]][1] for c in range(nch)]))
+        got = ctx.last_kernels()
+    finally:
+        ctx.set_tuning()
+    took = [p for p in plans if [l[0] for l in p] == got]
+    assert took, (got, plans)
+    cc.assert_separated(colour, took[0])
+    assert len({colour[c] for c in range(nch)}) == min(nch, n_streams)
+    for c in range(nch):
+        ref = chains[colour[c]][0]
+        if f32:
+            a, b = posterior_summary(out[c]), posterior_summary(ref)
+            for key in b:
+                assert rel(a[key], b[key]) < 1e-5, (c, key)
+        else:
+            assert np.abs(out[c] - ref).max() < 1e-9 * max(1.0, np.abs(ref).max()), c
+    return st, took[0]
+
+
 @pytest.mark.parametrize("n,k,res,nch", [(3000, 8, 3, 8), (3000, 8, 2, 5), (700, 130, 3, 3),
                                          (5000, 33, 3, 8)])
 def test_several_chains_per_pass(n, k, res, nch):
@@ -565,6 +612,24 @@ def test_several_chains_per_pass(n, k, res, nch):
     assert st["chains_per_pass"] in (2, 4)
     for c in range(4):
         assert np.abs(out[c] - ref).max() < 1e-9 * max(1.0, np.abs(ref).max())
+
+
+@pytest.mark.parametrize("n,k,res,nch", [(3000, 8, 3, 8), (3000, 8, 2, 5), (700, 130, 3, 3),
+                                         (5000, 33, 3, 8)])
+def test_several_chains_per_pass_distinct_streams(n, k, res, nch, planner, tmp_path):
+    """test_several_chains_per_pass's shapes and chain counts with a different stream per slot:
+    each chain of a shared pass against its own oracle chain."""
+    ctx = gpu_ctx()
+    rng = np.random.default_rng(n + k)
+    X = rng.standard_normal((n, k)) / np.sqrt(n)
+    y = X @ rng.standard_normal(k) + 0.1 * rng.standard_normal(n)
+    prior = (np.zeros(k), np.eye(k) * 10.0, 1.0, 0.02)
+    ctx.set_problem(y, X)
+    ctx.set_prior(*prior)
+    st, launches = replay_distinct_streams(ctx, planner, tmp_path, y, X, prior, np.float64, nch, 100,
+                                           residency=res)
+    assert st["residency"] == res and st["chains_per_pass"] in (2, 4, 8)
+    assert any(l[0].startswith("gibbs_multi_kernel<") for l in launches)
 
 
 def c2_like_problem(ctx, n=10000, k=32, seed=7):
@@ -701,6 +766,22 @@ def test_bundles_replay_the_reference_chain():
         assert rel(a[key], b[key]) < REL_BAR, key
 
 
+@pytest.mark.parametrize("nch,cpp", [(32, 4), (64, 8), (19, 2)])
+def test_bundles_replay_distinct_streams(nch, cpp, planner, tmp_path):
+    """The C2 fixture's problem in a launch of bundles (4 chains per XCD as above, the balanced
+    bundles of 8, and bundles of 2 with a remainder launch), a different stream in the first, a
+    middle and the last slot of every bundle and launch, each slot against its own oracle chain."""
+    ctx = gpu_ctx()
+    g, y, X, prior = golden_case("gibbs_c2_10000x32")
+    ctx.set_problem(y, X)
+    ctx.set_prior(*prior)
+    tune = dict(chains_per_pass=2) if cpp == 2 else {}
+    st, launches = replay_distinct_streams(ctx, planner, tmp_path, y, np.asarray(X, float), prior, np.float64,
+                                           nch, 130, **tune)
+    assert st["chains_per_pass"] == cpp and st["residency"] == 1
+    assert launches[0][3] == cpp and "true" in launches[0][0]   # (slotted bundles)
+
+
 @pytest.mark.parametrize("n,k,dt,nch", [(100000, 32, np.float64, 8), (120000, 7, np.float64, 5),
                                         (200000, 64, np.float32, 8), (150000, 20, np.float32, 4)])
 def test_several_chains_per_pass_register_residency(n, k, dt, nch):
@@ -740,6 +821,24 @@ def test_several_chains_per_pass_register_residency(n, k, dt, nch):
         assert st["chains_per_pass"] in (2, 4) and st["residency"] == 1
         for c in range(4):
             assert np.abs(out[c] - ref).max() < 1e-9 * max(1.0, np.abs(ref).max())
+
+
+@pytest.mark.parametrize("n,k,dt,nch", [(100000, 32, np.float64, 8), (120000, 7, np.float64, 5),
+                                        (200000, 64, np.float32, 8), (150000, 20, np.float32, 4)])
+def test_several_chains_per_pass_register_residency_distinct_streams(n, k, dt, nch, planner, tmp_path):
+    """test_several_chains_per_pass_register_residency's shapes, storage types and chain counts
+    with a different stream per slot, each chain against its own oracle chain (f32 storage: the
+    oracle on the f32-rounded data, summary bar 1e-5)."""
+    ctx = gpu_ctx()
+    rng = np.random.default_rng(n + k)
+    X = (rng.standard_normal((n, k)) / np.sqrt(n)).astype(dt)
+    y = (X.astype(np.float64) @ rng.standard_normal(k) + 0.1 * rng.standard_normal(n)).astype(dt)
+    prior = (np.zeros(k), np.eye(k) * 10.0, 1.0, 0.02)
+    ctx.set_problem(y, np.asfortranarray(X), dtype=dt)
+    ctx.set_prior(*prior)
+    st, launches = replay_distinct_streams(ctx, planner, tmp_path, y, X, prior, dt, nch, 60)
+    assert st["residency"] == 1 and st["chains_per_pass"] in (2, 4, 8)
+    assert any(l[0].startswith("gibbs_multi_kernel<") for l in launches)
 
 
 @pytest.mark.parametrize("n,k,dt,res", [(200000, 64, np.float32, 1), (50000, 256, np.float64, 3),
