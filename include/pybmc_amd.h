@@ -321,6 +321,33 @@ int bmc_pointwise_loglik_device(bmc_ctx* ctx, const void* dA, int64_t n_points, 
                                 int64_t n_draws, int64_t ldt, double* lppd_out,
                                 double* pwaic_out, double* mean_ll_out);
 
+/* ---- PSIS-LOO: Pareto-smoothed importance-sampling leave-one-out (not in the reference) ------
+ * Same model, arguments and ll[i][s] as bmc_pointwise_loglik.  Per point i, over the n_draws
+ * draws, with lw_s = -ll[i][s] shifted so that its largest is 0 and r_eff taken as 1 (as
+ * loo::psis does when none is given): the M = min(floor(n_draws / 5), ceil(3 sqrt(n_draws)))
+ * largest lw are replaced, in rank order, by quantiles of a generalised Pareto distribution fitted
+ * to them above the next largest (Zhang & Stephens 2009 with the weak prior of loo::gpdfit), all
+ * lw truncated at 0 (each output [n_points]; any may be NULL):
+ *   elpd_loo_out  logsumexp_s(ll + lw) - logsumexp_s(lw)
+ *   pareto_k_out  the fitted shape k-hat; +inf where nothing was smoothed (n_draws < 25, a tail of
+ *                 equal values, a non-finite fit): elpd_loo is then the raw importance-sampling one
+ *   lppd_out      as bmc_pointwise_loglik (p_loo_i = lppd_i - elpd_loo_i)
+ * Ties are by value: the result does not depend on the order of the draws.  The matrix is never
+ * stored: it is recomputed for a bounded number of passes (an exact radix select of the tail,
+ * at most 11 passes for any input); device memory used is O(n_points (M + splits) + n_draws).
+ * Results are deterministic.  Non-finite input as bmc_pointwise_loglik: NaN in every output of the
+ * point (a NaN or infinity in row i of A or y_i) or of all points (a NaN in theta, a sigma_s <= 0).
+ * BMC_EINVAL as bmc_pointwise_loglik, and when n_draws exceeds about 7.4 million (M > 8191: the
+ * per-point sort is done in on-chip memory).  The summaries (elpd_loo, p_loo, looic, se,
+ * n_high_k) are written out in INTEGRATION.md section 9. */
+int bmc_psis_loo(bmc_ctx* ctx, const double* A, int64_t n_points, int32_t k, int64_t lda,
+                 int layout, const double* y, const double* theta, int64_t n_draws, int64_t ldt,
+                 double* elpd_loo_out, double* pareto_k_out, double* lppd_out);
+int bmc_psis_loo_device(bmc_ctx* ctx, const void* dA, int64_t n_points, int32_t k, int64_t lda,
+                        int layout, const void* dy, const void* dtheta, int64_t n_draws,
+                        int64_t ldt, double* elpd_loo_out, double* pareto_k_out,
+                        double* lppd_out);
+
 /* ---- on-device variates (exposed so the generator itself can be tested) ----
  * normals_out [count_normal] ~ N(0,1); gammas_out [count_gamma] ~ Gamma(shape,1). */
 int bmc_rng_fill(bmc_ctx* ctx, uint64_t seed, int64_t count_normal, double* normals_out,

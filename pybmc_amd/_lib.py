@@ -93,6 +93,10 @@ PROTOTYPES = {
                                        C.c_int64, C.c_int64, _D, _D, _D]),
     "bmc_pointwise_loglik_device": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int, _P,
                                               _P, C.c_int64, C.c_int64, _D, _D, _D]),
+    "bmc_psis_loo": (C.c_int, [_P, _D, C.c_int64, C.c_int32, C.c_int64, C.c_int, _D, _D, C.c_int64,
+                               C.c_int64, _D, _D, _D]),
+    "bmc_psis_loo_device": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int, _P, _P,
+                                      C.c_int64, C.c_int64, _D, _D, _D]),
     "bmc_rng_fill": (C.c_int, [_P, C.c_uint64, C.c_int64, _D, C.c_double, C.c_int64, _D]),
     "bmc_philox_raw": (C.c_int, [_P, C.c_uint64, C.c_uint32, C.c_int64, C.POINTER(C.c_uint32)]),
 }
@@ -510,6 +514,25 @@ class Context:
         the caller orders its producers before the call."""
         return self._score_call(self._lib.bmc_pointwise_loglik_device, _P(dA), n, k, lda, layout,
                                 _P(dy), _P(dtheta), n_draws, ldt)
+
+    # -- PSIS-LOO ---------------------------------------------------------------------------
+    def _loo_call(self, fn, pA, n, k, lda, layout, py, pt, n_draws, ldt):
+        out = {key: np.empty(n) for key in ("elpd_loo", "pareto_k", "lppd")}
+        self._check(fn(self._h, pA, int(n), int(k), int(lda), int(layout), py, pt, int(n_draws),
+                       int(ldt), _dptr(out["elpd_loo"]), _dptr(out["pareto_k"]), _dptr(out["lppd"])))
+        return out
+
+    def psis_loo(self, A, n, k, lda, layout, y, theta, n_draws, ldt):
+        """elpd_loo_i, pareto_k_i and lppd_i of HOST f64 arrays (bmc_psis_loo); arguments as
+        pointwise_loglik.  Returns a dict of [n] arrays."""
+        return self._loo_call(self._lib.bmc_psis_loo, _dptr(A), n, k, lda, layout, _dptr(y),
+                              _dptr(theta), n_draws, ldt)
+
+    def psis_loo_device(self, dA, n, k, lda, layout, dy, dtheta, n_draws, ldt):
+        """The same on DEVICE memory (bmc_psis_loo_device), read on the context's stream: the
+        caller orders its producers before the call."""
+        return self._loo_call(self._lib.bmc_psis_loo_device, _P(dA), n, k, lda, layout, _P(dy),
+                              _P(dtheta), n_draws, ldt)
 
     # -- variates -----------------------------------------------------------------------
     def rng_fill(self, seed, n_normal=0, shape=1.0, n_gamma=0):

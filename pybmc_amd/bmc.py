@@ -202,6 +202,19 @@ class BayesianModelCombination:
         return waic(self.U_hat, np.asarray(self.centered_experiment_train, dtype=np.float64),
                     self._chains(), burn=burn, device=self.device)
 
+    def loo(self, burn=0):
+        """PSIS-LOO cross-validation of the last ``train()`` on its training data (not in the
+        reference; ``pybmc_amd.scoring.psis_loo``), on the same data as ``waic()``: ``U_hat``,
+        ``centered_experiment_train`` and the chains, ``burn`` more draws dropped from the start of
+        each.  Returns a dict: ``elpd_loo``, ``p_loo``, ``looic``, ``se``, ``n_high_k``,
+        ``k_threshold``, ``n_above_threshold``, ``n_points``, ``n_draws`` and the pointwise
+        ``elpd_loo_i``, ``p_loo_i``, ``pareto_k``, ``lppd``."""
+        if self.samples is None or self.U_hat is None:
+            raise ValueError("Must call `orthogonalize()` and `train()` before computing LOO.")
+        from .scoring import psis_loo
+        return psis_loo(self.U_hat, np.asarray(self.centered_experiment_train, dtype=np.float64),
+                        self._chains(), burn=burn, device=self.device)
+
     def log_predictive_density(self, X, burn=0):
         """Log predictive density of held-out data (a validation or test split): ``X`` is a
         DataFrame with the model columns and the truth column.  The predictive mean of point p

@@ -75,6 +75,8 @@ struct bmc_ctx {
     DevBuf dgIn, dgPart, dgMean, dgM2, dgCols, dgAcovPart, dgAcov;
     // pointwise log-likelihood (bmc_pointwise_loglik*)
     DevBuf scA, scY, scTheta, scAp, scYp, scCh, scPart, scOut;
+    // PSIS-LOO (bmc_psis_loo*): the select state and candidate slots, besides the score buffers
+    DevBuf looWork;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     double predict_ms[4] = {0, 0, 0, 0};   // last bmc_predict: h2d, gemm, order statistics, device
     // pinned staging for results that go back to pageable host memory (copy_to_host)
@@ -798,7 +800,7 @@ void bmc_destroy(bmc_ctx* c) {
                       &c->sStep, &c->sUnif, &c->sOut, &c->sCnt, &c->oFc, &c->oMu, &c->oW, &c->oOut,
                       &c->dgIn, &c->dgPart, &c->dgMean, &c->dgM2, &c->dgCols, &c->dgAcovPart,
                       &c->dgAcov, &c->scA, &c->scY, &c->scTheta, &c->scAp, &c->scYp, &c->scCh,
-                      &c->scPart, &c->scOut})
+                      &c->scPart, &c->scOut, &c->looWork})
         release(*b);
     for (auto& e : c->ev)
         if (e) (void)hipEventDestroy(e);
@@ -1286,12 +1288,10 @@ int check_score_args(bmc_ctx* c, const void* A, int64_t n, int32_t k, int64_t ld
     return BMC_OK;
 }
 
-// Everything on the context's stream, in buffers of its own: the resident problem, the prior and
-// the predictive draws are not touched.
-int score_run(bmc_ctx* c, const double* dA, int64_t n, int32_t k, int64_t lda, int layout,
-              const double* dy, const double* dtheta, int64_t S, int64_t ldt, double* lppd_out,
-              double* pwaic_out, double* mean_out) {
-    const ScorePlan plan = plan_score(n, S, k, c->n_cu);
+// The score kernels' arguments in the context's buffers
+int score_args(bmc_ctx* c, const ScorePlan& plan, const double* dA, int64_t n, int32_t k, int64_t lda,
+               int layout, const double* dy, const double* dtheta, int64_t S, int64_t ldt,
+               ScoreArgs& a) {
     const ScoreBuffers sb = score_buffers(plan, S);
     int rc;
     if ((rc = ensure(c, c->scAp, sb.Ap))) return rc;
@@ -1299,7 +1299,6 @@ int score_run(bmc_ctx* c, const double* dA, int64_t n, int32_t k, int64_t lda, i
     if ((rc = ensure(c, c->scCh, sb.ch))) return rc;
     if ((rc = ensure(c, c->scPart, sb.part))) return rc;
     if ((rc = ensure(c, c->scOut, (size_t)n * 3 * 8))) return rc;
-    ScoreArgs a;
     a.A = dA;
     a.y = dy;
     a.theta = dtheta;
@@ -1314,6 +1313,18 @@ int score_run(bmc_ctx* c, const double* dA, int64_t n, int32_t k, int64_t lda, i
     a.ch = (double*)c->scCh.p;
     a.part = (double*)c->scPart.p;
     a.out = (double*)c->scOut.p;
+    return BMC_OK;
+}
+
+// Everything on the context's stream, in buffers of its own: the resident problem, the prior and
+// the predictive draws are not touched.
+int score_run(bmc_ctx* c, const double* dA, int64_t n, int32_t k, int64_t lda, int layout,
+              const double* dy, const double* dtheta, int64_t S, int64_t ldt, double* lppd_out,
+              double* pwaic_out, double* mean_out) {
+    const ScorePlan plan = plan_score(n, S, k, c->n_cu);
+    ScoreArgs a;
+    int rc = score_args(c, plan, dA, n, k, lda, layout, dy, dtheta, S, ldt, a);
+    if (rc) return rc;
     HIPCHK(c, launch_score(a, plan, c->stream));
     double* outs[3] = {lppd_out, pwaic_out, mean_out};
     for (int f = 0; f < 3; ++f)
@@ -1321,6 +1332,47 @@ int score_run(bmc_ctx* c, const double* dA, int64_t n, int32_t k, int64_t lda, i
             HIPCHK(c, hipMemcpyAsync(outs[f], a.out + (size_t)f * n, (size_t)n * 8,
                                      hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return BMC_OK;
+}
+
+int loo_run(bmc_ctx* c, const double* dA, int64_t n, int32_t k, int64_t lda, int layout,
+            const double* dy, const double* dtheta, int64_t S, int64_t ldt, double* elpd_out,
+            double* k_out, double* lppd_out) {
+    const LooPlan plan = plan_loo(n, S, k, c->n_cu);
+    if (!plan.ok)
+        return fail(c, BMC_EINVAL, "n_draws is too large for the per-point sort (tail of " +
+                                       std::to_string(plan.tail) + " draws)");
+    LooArgs a;
+    int rc = score_args(c, plan.score, dA, n, k, lda, layout, dy, dtheta, S, ldt, a.score);
+    if (rc) return rc;
+    if ((rc = ensure(c, c->looWork, loo_buffers(plan, n).total()))) return rc;
+    a.work = c->looWork.p;
+    HIPCHK(c, launch_loo(a, plan, c->stream));
+    const double* lo = loo_out(a, plan);
+    const double* src[3] = {lo, lo + n, a.score.out};
+    double* outs[3] = {elpd_out, k_out, lppd_out};
+    for (int f = 0; f < 3; ++f)
+        if (outs[f])
+            HIPCHK(c, hipMemcpyAsync(outs[f], src[f], (size_t)n * 8, hipMemcpyDeviceToHost,
+                                     c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return BMC_OK;
+}
+
+// Host A, y and theta into the context's staging buffers (on its stream)
+int score_stage(bmc_ctx* c, const double* A, int64_t n_points, int32_t k, int64_t lda, int layout,
+                const double* y, const double* theta, int64_t n_draws, int64_t ldt) {
+    int rc;
+    // (the last row / column of a strided host array may be shorter than its stride)
+    const size_t abytes = (layout == BMC_COL_MAJOR ? (size_t)lda * (k - 1) + (size_t)n_points
+                                                   : (size_t)lda * (n_points - 1) + (size_t)k) * 8;
+    const size_t tbytes = ((size_t)ldt * (n_draws - 1) + (size_t)k + 1) * 8;
+    if ((rc = ensure(c, c->scA, abytes))) return rc;
+    if ((rc = ensure(c, c->scY, (size_t)n_points * 8))) return rc;
+    if ((rc = ensure(c, c->scTheta, tbytes))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->scA.p, A, abytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->scY.p, y, (size_t)n_points * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->scTheta.p, theta, tbytes, hipMemcpyHostToDevice, c->stream));
     return BMC_OK;
 }
 
@@ -1332,16 +1384,7 @@ int bmc_pointwise_loglik(bmc_ctx* c, const double* A, int64_t n_points, int32_t 
     int rc = check_score_args(c, A, n_points, k, lda, layout, y, theta, n_draws, ldt);
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    // (the last row / column of a strided host array may be shorter than its stride)
-    const size_t abytes = (layout == BMC_COL_MAJOR ? (size_t)lda * (k - 1) + (size_t)n_points
-                                                   : (size_t)lda * (n_points - 1) + (size_t)k) * 8;
-    const size_t tbytes = ((size_t)ldt * (n_draws - 1) + (size_t)k + 1) * 8;
-    if ((rc = ensure(c, c->scA, abytes))) return rc;
-    if ((rc = ensure(c, c->scY, (size_t)n_points * 8))) return rc;
-    if ((rc = ensure(c, c->scTheta, tbytes))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->scA.p, A, abytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->scY.p, y, (size_t)n_points * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->scTheta.p, theta, tbytes, hipMemcpyHostToDevice, c->stream));
+    if ((rc = score_stage(c, A, n_points, k, lda, layout, y, theta, n_draws, ldt))) return rc;
     return score_run(c, (const double*)c->scA.p, n_points, k, lda, layout, (const double*)c->scY.p,
                      (const double*)c->scTheta.p, n_draws, ldt, lppd_out, pwaic_out, mean_ll_out);
 }
@@ -1355,6 +1398,29 @@ int bmc_pointwise_loglik_device(bmc_ctx* c, const void* dA, int64_t n_points, in
     HIPCHK(c, hipSetDevice(c->device));
     return score_run(c, (const double*)dA, n_points, k, lda, layout, (const double*)dy,
                      (const double*)dtheta, n_draws, ldt, lppd_out, pwaic_out, mean_ll_out);
+}
+
+// ---- PSIS-LOO (kernels_loo.hip) -----------------------------------------------
+
+int bmc_psis_loo(bmc_ctx* c, const double* A, int64_t n_points, int32_t k, int64_t lda, int layout,
+                 const double* y, const double* theta, int64_t n_draws, int64_t ldt,
+                 double* elpd_loo_out, double* pareto_k_out, double* lppd_out) {
+    int rc = check_score_args(c, A, n_points, k, lda, layout, y, theta, n_draws, ldt);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = score_stage(c, A, n_points, k, lda, layout, y, theta, n_draws, ldt))) return rc;
+    return loo_run(c, (const double*)c->scA.p, n_points, k, lda, layout, (const double*)c->scY.p,
+                   (const double*)c->scTheta.p, n_draws, ldt, elpd_loo_out, pareto_k_out, lppd_out);
+}
+
+int bmc_psis_loo_device(bmc_ctx* c, const void* dA, int64_t n_points, int32_t k, int64_t lda,
+                        int layout, const void* dy, const void* dtheta, int64_t n_draws, int64_t ldt,
+                        double* elpd_loo_out, double* pareto_k_out, double* lppd_out) {
+    int rc = check_score_args(c, dA, n_points, k, lda, layout, dy, dtheta, n_draws, ldt);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    return loo_run(c, (const double*)dA, n_points, k, lda, layout, (const double*)dy,
+                   (const double*)dtheta, n_draws, ldt, elpd_loo_out, pareto_k_out, lppd_out);
 }
 
 int bmc_rng_fill(bmc_ctx* c, uint64_t seed, int64_t count_normal, double* normals_out, double shape,

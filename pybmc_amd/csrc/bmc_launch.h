@@ -275,4 +275,16 @@ struct ScoreBuffers {
 ScoreBuffers score_buffers(const ScorePlan& p, int64_t n_draws);
 hipError_t launch_score(const ScoreArgs& a, const ScorePlan& p, hipStream_t s);
 
+// ---- PSIS-LOO (kernels_loo.hip; plan_loo in bmc_plan.h) -----------------------------------------
+// Pareto-smoothed importance-sampling leave-one-out of the same model and arguments as
+// launch_score (whose kernels run first, into `score`'s buffers: score.out[0][i] = lppd_i).  work:
+// loo_buffers(plan, n).total() bytes (device, 256-byte aligned); its `out` part, at loo_out(),
+// receives elpd_loo_i [n] then pareto_k [n].
+struct LooArgs {
+    ScoreArgs score;
+    void* work;
+};
+double* loo_out(const LooArgs& a, const LooPlan& p);
+hipError_t launch_loo(const LooArgs& a, const LooPlan& p, hipStream_t s);
+
 }  // namespace bmc

@@ -5,7 +5,8 @@
 // it is built, and kernels_gibbs.hip instantiates exactly the keys of loop_kernel_keys(), one
 // table entry each.  tests/launch_plan_check.cpp runs the planner and the selection on the CPU.
 // Also here: plan_score, the draw-split plan of the pointwise log-likelihood kernels
-// (kernels_waic.hip; tests/score_plan_check.cpp).
+// (kernels_waic.hip; tests/score_plan_check.cpp), and plan_loo, the pass and candidate plan of
+// the PSIS-LOO kernels (kernels_loo.hip; tests/loo_plan_check.cpp).
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -647,6 +648,89 @@ inline ScorePlan plan_score(int64_t n_points, int64_t n_draws, int32_t k, int n_
     p.tiles_per_split = (p.draw_tiles + want - 1) / want;
     p.splits = (p.draw_tiles + p.tiles_per_split - 1) / p.tiles_per_split;
     return p;
+}
+
+// ---- PSIS-LOO (kernels_loo.hip) ------------------------------------------------
+// Per point the M smallest ll[i][.] (the M largest importance ratios) and the next one, of a
+// matrix that is never stored.  Every pass over the matrix is the tile loop of the score kernels
+// with the same draw splits (plan_score).  The passes:
+//   1        the score kernels themselves (lppd_i; they also pad A, y and make the draw constants)
+//   1        range: smallest and largest order-preserving 64-bit key of ll per point
+//   0 .. 8   radix select on the key bits below the point's common prefix, LOO_DIGIT_BITS per
+//            pass, digits counted in LDS per 64-point tile; a point is settled once the bucket
+//            that holds rank M + 1, plus everything below it, fits `cap` candidates, or once all
+//            64 bits are fixed (then the bucket is ONE value, repeated).  A workgroup whose 64
+//            points are settled returns at once, so the launches past the second or third are
+//            empty for ordinary input; 64 / LOO_DIGIT_BITS bounds them for any input.
+//   1        append: keys below the bucket (at most M, by the definition of the bucket) and, if
+//            it fits, the bucket itself go to the point's candidate slots; exp(lw) of everything
+//            above is summed in a fixed order.  At most `cap` slots are ever written.
+// then one workgroup per point sorts its candidates and does the fit.  No select pass is needed
+// when S <= cap (everything is a candidate) or when S < 25 (no tail).
+constexpr int LOO_DIGIT_BITS = 8;
+constexpr int LOO_MAX_SELECT_PASSES = 64 / LOO_DIGIT_BITS;
+constexpr int64_t LOO_MIN_CAP = 64;
+constexpr int64_t LOO_MAX_CAP = 16384;   // the per-point sort is done in LDS: 128 KiB of doubles
+constexpr int LOO_MIN_TAIL = 5;
+
+// M = min(floor(S / 5), ceil(3 sqrt(S))), in integers; 0 when that is below LOO_MIN_TAIL
+inline int64_t loo_tail(int64_t n_draws) {
+    int64_t t = 0;   // smallest t with t^2 >= 9 S
+    for (int64_t bit = (int64_t)1 << 31; bit > 0; bit >>= 1)
+        if ((t + bit - 1) * (t + bit - 1) < 9 * n_draws) t += bit;
+    int64_t M = n_draws / 5 < t ? n_draws / 5 : t;
+    return M < LOO_MIN_TAIL ? 0 : M;
+}
+
+struct LooPlan {
+    ScorePlan score;         // tiles and draw splits of every pass over the matrix
+    int64_t tail;            // M; 0: no smoothing (S < 25)
+    int64_t cap;             // candidate slots per point: a power of two >= 2 (M + 1)
+    int32_t select_passes;   // launches of the select kernel (0 or LOO_MAX_SELECT_PASSES)
+    int32_t matrix_passes;   // all launches that walk the matrix: score, range, select, append
+    bool ok;                 // cap <= LOO_MAX_CAP (about 7.4 million draws)
+};
+
+inline LooPlan plan_loo(int64_t n_points, int64_t n_draws, int32_t k, int n_cu) {
+    LooPlan p;
+    p.score = plan_score(n_points, n_draws, k, n_cu);
+    p.tail = loo_tail(n_draws);
+    p.cap = LOO_MIN_CAP;
+    while (p.cap < 2 * (p.tail + 1)) p.cap <<= 1;
+    p.ok = p.cap <= LOO_MAX_CAP;
+    p.select_passes = (p.tail > 0 && n_draws > p.cap) ? LOO_MAX_SELECT_PASSES : 0;
+    p.matrix_passes = 3 + p.select_passes;
+    return p;
+}
+
+// Device work space of launch_loo besides the score kernels' own (score_buffers), in bytes:
+// O(n_points (M + 256 + splits)).
+struct LooBuffers {
+    size_t range;    // [splits][n_pad][3] u64: smallest key, largest key, non-finite seen
+    size_t prefix;   // [n_pad] u64: the fixed high bits of the threshold key
+    size_t kmin;     // [n_pad] u64: the smallest key (c_i = -ll of it)
+    size_t meta;     // [n_pad][4] u32: bits fixed, keys below the bucket, keys in it, flags
+    size_t hist;     // [n_pad][256] u32: digit counts of the current select pass
+    size_t count;    // [n_pad] u32: candidates appended
+    size_t cand;     // [n_pad][cap] f64
+    size_t body;     // [splits][n_pad] f64: sum of exp(lw) above the bucket
+    size_t out;      // [2][n_points] f64: elpd_loo_i, pareto_k
+    size_t total() const { return range + prefix + kmin + meta + hist + count + cand + body + out; }
+};
+inline LooBuffers loo_buffers(const LooPlan& p, int64_t n_points) {
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t n_pad = (size_t)p.score.point_tiles * SCORE_TILE, sp = (size_t)p.score.splits;
+    LooBuffers b;
+    b.range = up(sp * n_pad * 3 * 8);
+    b.prefix = up(n_pad * 8);
+    b.kmin = up(n_pad * 8);
+    b.meta = up(n_pad * 16);
+    b.hist = up(n_pad * ((size_t)1 << LOO_DIGIT_BITS) * 4);
+    b.count = up(n_pad * 4);
+    b.cand = up(n_pad * (size_t)p.cap * 8);
+    b.body = up(sp * n_pad * 8);
+    b.out = up((size_t)n_points * 2 * 8);
+    return b;
 }
 
 }  // namespace bmc

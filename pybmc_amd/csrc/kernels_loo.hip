@@ -1,0 +1,597 @@
+// PSIS-LOO: Pareto-smoothed importance-sampling leave-one-out cross-validation of a sampled fit
+// (Vehtari, Gelman & Gabry 2017; Vehtari et al. 2024; the
+// generalised Pareto fit of Zhang & Stephens 2009).  With ll[i][s] as in kernels_waic.hip and
+// lw = -ll, each point needs the M largest lw (the M smallest ll) and the next one, of a matrix
+// that is never stored.  The passes (plan_loo in bmc_plan.h says what bounds each):
+//
+//   launch_score   lppd_i, and the padded A, y and per-draw constants every later pass reads
+//   loo_range      per point the smallest and largest KEY of ll: the IEEE bits mapped to an
+//                  unsigned integer of the same order; and whether any ll is not finite
+//   loo_init       the point's select state: the bits kmin and kmax share are fixed
+//   loo_select     one radix digit: keys that match the fixed bits are counted by their next
+//                  LOO_DIGIT_BITS bits, in LDS per 64-point tile, then added to the point's
+//                  global counts (integer atomics: any order, the same result)
+//   loo_scan       per point: the digit whose bucket holds rank M + 1 joins the fixed bits;
+//                  settled when bucket + everything below fits the candidate slots, or when all
+//                  64 bits are fixed (the bucket is then one value, repeated)
+//   loo_append     keys below the bucket, and the bucket if it fits, to the point's slots (in
+//                  any order: they are sorted next); exp(lw) of every key above it summed per
+//                  lane, tile, lane tree and split, one fixed order
+//   loo_fit        one workgroup per point: bitonic sort of the candidates in LDS, tail and
+//                  cutoff, the Pareto fit, the smoothed tail, elpd_loo_i
+//
+// Two calls return the same bits: the only atomics are integer counts and slot numbers of values
+// that are sorted before use.  A point with a non-finite ll (a NaN or infinity in a_i, y_i or any
+// draw, a sigma_s <= 0) is flagged by loo_range and gets NaN; its keys are never used as an index
+// (digits are masked, slots are bounded by the cap).
+#include "bmc_dev.h"
+#include "bmc_launch.h"
+#include "bmc_plan.h"
+#include "bmc_score_tile.h"
+
+namespace bmc {
+
+namespace {
+
+constexpr uint32_t LF_DONE = 1, LF_APPEND_EQ = 2, LF_NOTAIL = 4, LF_BAD = 8;
+constexpr int LOO_BINS = 1 << LOO_DIGIT_BITS;
+constexpr uint64_t SIGN = 0x8000000000000000ull;
+constexpr size_t LOO_SELECT_LDS = 2 * SC_LDS_DOUBLES * 8 + (size_t)SC_TM * LOO_BINS * 4;
+
+// a < b as doubles  <=>  ord_key(a) < ord_key(b) as unsigned (for all non-NaN a, b; -0 < +0)
+__device__ __forceinline__ uint64_t ord_key(double x) {
+    const uint64_t u = (uint64_t)__double_as_longlong(x);
+    return (u & SIGN) ? ~u : (u | SIGN);
+}
+__device__ __forceinline__ double key_value(uint64_t key) {
+    return __longlong_as_double((long long)((key & SIGN) ? (key ^ SIGN) : ~key));
+}
+// the r highest bits of a key
+__device__ __forceinline__ uint64_t key_top(uint64_t key, uint32_t r) {
+    return r == 0 ? 0ull : key >> (64 - r);
+}
+__device__ __forceinline__ bool not_finite(double x) { return !(fabs(x) < __builtin_inf()); }
+
+// The split and point tile of a workgroup (grid of score_tile_kernel: point tile fastest)
+struct TilePos {
+    int64_t p0, split, dt0, dt1;
+    __device__ __forceinline__ TilePos(uint32_t point_tiles, int64_t tiles_per_split,
+                                       int64_t draw_tiles) {
+        const uint32_t pt = blockIdx.x % point_tiles;
+        split = blockIdx.x / point_tiles;
+        p0 = (int64_t)pt * SC_TM;
+        dt0 = split * tiles_per_split;
+        dt1 = dt0 + tiles_per_split < draw_tiles ? dt0 + tiles_per_split : draw_tiles;
+    }
+};
+
+// Arguments every pass over the matrix shares
+struct PassArgs {
+    const double *Ap, *yp, *theta, *ch;
+    int64_t S, ldt, tiles_per_split, draw_tiles, n_pad;
+    int32_t k, k_pad;
+    uint32_t point_tiles;
+};
+
+__global__ __launch_bounds__(256) void loo_range_kernel(PassArgs a, uint64_t* __restrict__ range) {
+    __shared__ double As[SC_LDS_DOUBLES];
+    __shared__ double Bs[SC_LDS_DOUBLES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, cl = lane & 15, kq = lane >> 4;
+    const TilePos pos(a.point_tiles, a.tiles_per_split, a.draw_tiles);
+    double yv[4];
+    uint64_t kmin[4], kmax[4], bad[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        yv[r] = a.yp[pos.p0 + 16 * wave + kq + 4 * r];
+        kmin[r] = ~0ull;
+        kmax[r] = 0ull;
+        bad[r] = 0ull;
+    }
+    score_tile_loop(a.Ap, a.theta, a.S, a.ldt, a.k, a.k_pad, pos.p0, pos.dt0, pos.dt1, As, Bs,
+                    [&](int64_t s0, const f64x4(&acc)[4]) {
+        const TileDraws d(a.ch, a.S, s0, cl);
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+                if (d.ok[t]) {
+                    const double x = d.ll(yv[r], acc[t][r], t);
+                    const uint64_t key = ord_key(x);
+                    kmin[r] = key < kmin[r] ? key : kmin[r];
+                    kmax[r] = key > kmax[r] ? key : kmax[r];
+                    bad[r] |= not_finite(x) ? 1ull : 0ull;
+                }
+    });
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+#pragma unroll
+        for (int bit = 1; bit < 16; bit <<= 1) {
+            const uint64_t lo = __shfl_xor((unsigned long long)kmin[r], bit);
+            const uint64_t hi = __shfl_xor((unsigned long long)kmax[r], bit);
+            const uint64_t b = __shfl_xor((unsigned long long)bad[r], bit);
+            kmin[r] = lo < kmin[r] ? lo : kmin[r];
+            kmax[r] = hi > kmax[r] ? hi : kmax[r];
+            bad[r] |= b;
+        }
+        if (cl == 0) {
+            uint64_t* o = range + ((int64_t)pos.split * a.n_pad + pos.p0 + 16 * wave + kq + 4 * r) * 3;
+            o[0] = kmin[r];
+            o[1] = kmax[r];
+            o[2] = bad[r];
+        }
+    }
+}
+
+// meta: x = bits fixed, y = keys below the bucket, z = keys in the bucket, w = flags
+__global__ __launch_bounds__(256) void loo_init_kernel(const uint64_t* __restrict__ range,
+                                                       int64_t n_pad, int64_t splits, int64_t S,
+                                                       int32_t M, int32_t cap,
+                                                       uint64_t* __restrict__ prefix,
+                                                       uint64_t* __restrict__ kmin_out,
+                                                       uint4* __restrict__ meta) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_pad) return;
+    uint64_t lo = ~0ull, hi = 0ull, bad = 0ull;
+    for (int64_t sp = 0; sp < splits; ++sp) {
+        const uint64_t* p = range + (sp * n_pad + i) * 3;
+        lo = p[0] < lo ? p[0] : lo;
+        hi = p[1] > hi ? p[1] : hi;
+        bad |= p[2];
+    }
+    uint4 m{0u, 0u, (uint32_t)S, 0u};
+    uint64_t pre = 0ull;
+    if (bad) {
+        m.w = LF_BAD | LF_DONE;
+    } else if (M == 0) {
+        m.w = LF_NOTAIL | LF_DONE;
+    } else if (S <= (int64_t)cap) {
+        m.w = LF_DONE | LF_APPEND_EQ;   // no bit fixed: every key is in the bucket
+    } else if (lo == hi) {
+        m.x = 64u;
+        pre = lo;
+        m.w = LF_DONE;
+    } else {
+        m.x = (uint32_t)__builtin_clzll(lo ^ hi);
+        pre = key_top(lo, m.x);
+    }
+    prefix[i] = pre;
+    kmin_out[i] = lo;
+    meta[i] = m;
+}
+
+__global__ __launch_bounds__(256) void loo_select_kernel(PassArgs a,
+                                                         const uint64_t* __restrict__ prefix,
+                                                         const uint4* __restrict__ meta,
+                                                         uint32_t* __restrict__ hist) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    double* As = (double*)smem_raw;
+    double* Bs = As + SC_LDS_DOUBLES;
+    uint32_t* h = (uint32_t*)(Bs + SC_LDS_DOUBLES);   // [64][LOO_BINS]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, cl = lane & 15, kq = lane >> 4;
+    const TilePos pos(a.point_tiles, a.tiles_per_split, a.draw_tiles);
+    double yv[4];
+    uint64_t pre[4];
+    uint32_t fixed[4], low[4], mask[4];
+    bool live[4];
+    int any = 0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int64_t pi = pos.p0 + 16 * wave + kq + 4 * r;
+        const uint4 m = meta[pi];
+        yv[r] = a.yp[pi];
+        pre[r] = prefix[pi];
+        live[r] = !(m.w & LF_DONE);
+        fixed[r] = live[r] ? m.x : 0u;   // (a settled point may have all 64 bits fixed)
+        const uint32_t nb = 64u - fixed[r] < (uint32_t)LOO_DIGIT_BITS ? 64u - fixed[r]
+                                                                       : (uint32_t)LOO_DIGIT_BITS;
+        low[r] = 64u - fixed[r] - nb;
+        mask[r] = (1u << nb) - 1u;
+        any |= live[r];
+    }
+    if (!__syncthreads_or(any)) return;   // all 64 points settled
+    for (int e = tid; e < SC_TM * LOO_BINS; e += 256) h[e] = 0u;
+    __syncthreads();
+    score_tile_loop(a.Ap, a.theta, a.S, a.ldt, a.k, a.k_pad, pos.p0, pos.dt0, pos.dt1, As, Bs,
+                    [&](int64_t s0, const f64x4(&acc)[4]) {
+        const TileDraws d(a.ch, a.S, s0, cl);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            if (!live[r]) continue;
+            uint32_t* hr = h + (16 * wave + kq + 4 * r) * LOO_BINS;
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+                if (d.ok[t]) {
+                    const uint64_t key = ord_key(d.ll(yv[r], acc[t][r], t));
+                    if (key_top(key, fixed[r]) == pre[r])
+                        atomicAdd(hr + ((uint32_t)(key >> low[r]) & mask[r]), 1u);
+                }
+        }
+    });
+    __syncthreads();
+    for (int e = tid; e < SC_TM * LOO_BINS; e += 256) {
+        const uint32_t v = h[e];
+        if (v) atomicAdd(hist + pos.p0 * LOO_BINS + e, v);
+    }
+}
+
+__global__ __launch_bounds__(256) void loo_scan_kernel(int64_t n_pad, int32_t M, int32_t cap,
+                                                       uint64_t* __restrict__ prefix,
+                                                       uint4* __restrict__ meta,
+                                                       uint32_t* __restrict__ hist) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_pad) return;
+    uint4 m = meta[i];
+    if (m.w & LF_DONE) return;
+    const uint32_t nb = 64u - m.x < (uint32_t)LOO_DIGIT_BITS ? 64u - m.x : (uint32_t)LOO_DIGIT_BITS;
+    const uint32_t want = (uint32_t)M + 1u - m.y;   // rank of the threshold inside the bucket, >= 1
+    uint4* hp = (uint4*)(hist + i * LOO_BINS);
+    uint32_t cum = 0, below = 0, in = 0;
+    int digit = -1;
+    for (int q = 0; q < LOO_BINS / 4; ++q) {
+        const uint4 c4 = hp[q];
+        const uint32_t c[4] = {c4.x, c4.y, c4.z, c4.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (digit < 0 && cum + c[e] >= want) {
+                digit = 4 * q + e;
+                below = cum;
+                in = c[e];
+            }
+            cum += c[e];
+        }
+        hp[q] = uint4{0u, 0u, 0u, 0u};
+    }
+    if (digit < 0 || cum != m.z) {   // the counts do not add up: cannot happen; a value, not a hang
+        m.w = LF_BAD | LF_DONE;
+        meta[i] = m;
+        return;
+    }
+    prefix[i] = (prefix[i] << nb) | (uint64_t)digit;
+    m.x += nb;
+    m.y += below;
+    m.z = in;
+    if ((uint64_t)m.y + m.z <= (uint64_t)cap) m.w = LF_DONE | LF_APPEND_EQ;
+    else if (m.x == 64u) m.w = LF_DONE;
+    meta[i] = m;
+}
+
+__global__ __launch_bounds__(256) void loo_append_kernel(PassArgs a,
+                                                         const uint64_t* __restrict__ prefix,
+                                                         const uint64_t* __restrict__ kmin,
+                                                         const uint4* __restrict__ meta,
+                                                         uint32_t cap, uint32_t* __restrict__ count,
+                                                         double* __restrict__ cand,
+                                                         double* __restrict__ body) {
+    __shared__ double As[SC_LDS_DOUBLES];
+    __shared__ double Bs[SC_LDS_DOUBLES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, cl = lane & 15, kq = lane >> 4;
+    const TilePos pos(a.point_tiles, a.tiles_per_split, a.draw_tiles);
+    double yv[4], llmin[4], sum[4];
+    uint64_t pre[4];
+    uint32_t fixed[4], flags[4];
+    int64_t pi[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        pi[r] = pos.p0 + 16 * wave + kq + 4 * r;
+        const uint4 m = meta[pi[r]];
+        yv[r] = a.yp[pi[r]];
+        pre[r] = prefix[pi[r]];
+        llmin[r] = key_value(kmin[pi[r]]);
+        fixed[r] = m.x;
+        flags[r] = m.w;
+        sum[r] = 0.0;
+    }
+    score_tile_loop(a.Ap, a.theta, a.S, a.ldt, a.k, a.k_pad, pos.p0, pos.dt0, pos.dt1, As, Bs,
+                    [&](int64_t s0, const f64x4(&acc)[4]) {
+        const TileDraws d(a.ch, a.S, s0, cl);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            if (flags[r] & LF_BAD) continue;
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+                if (d.ok[t]) {
+                    const double x = d.ll(yv[r], acc[t][r], t);
+                    const uint64_t top = key_top(ord_key(x), fixed[r]);
+                    if ((flags[r] & LF_NOTAIL) || top > pre[r]) {
+                        sum[r] += exp(llmin[r] - x);
+                    } else if (top < pre[r] || (flags[r] & LF_APPEND_EQ)) {
+                        const uint32_t slot = atomicAdd(count + pi[r], 1u);
+                        if (slot < cap) cand[pi[r] * (int64_t)cap + slot] = x;
+                    }
+                }
+        }
+    });
+    // the 16 lanes that hold draws of the same point: a tree over cl, every lane the same bits
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        double v = sum[r];
+#pragma unroll
+        for (int bit = 1; bit < 16; bit <<= 1) {
+            const double o = __shfl_xor(v, bit);
+            v = (cl & bit) ? o + v : v + o;
+        }
+        if (cl == 0) body[(int64_t)pos.split * a.n_pad + pi[r]] = v;
+    }
+}
+
+// sums and maxima over the workgroup in one fixed order: thread-strided partials, then a tree
+__device__ __forceinline__ double block_sum(double v, double* red) {
+    const int tid = threadIdx.x;
+    red[tid] = v;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) red[tid] += red[tid + s];
+        __syncthreads();
+    }
+    const double r = red[0];
+    __syncthreads();
+    return r;
+}
+__device__ __forceinline__ double block_max(double v, double* red) {
+    const int tid = threadIdx.x;
+    red[tid] = v;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) red[tid] = fmax(red[tid], red[tid + s]);
+        __syncthreads();
+    }
+    const double r = red[0];
+    __syncthreads();
+    return r;
+}
+
+// One workgroup per point.  buf: `cap` doubles of LDS, cap >= 2 (M + 1): the sorted candidates in
+// buf[0 .. M] and, behind them, M doubles for the tail's x_j and then its smoothed lw.
+__global__ __launch_bounds__(256) void loo_fit_kernel(const uint64_t* __restrict__ prefix,
+                                                      const uint64_t* __restrict__ kmin,
+                                                      const uint4* __restrict__ meta,
+                                                      const uint32_t* __restrict__ count,
+                                                      const double* __restrict__ cand,
+                                                      const double* __restrict__ body, int64_t n,
+                                                      int64_t n_pad, int64_t splits, int64_t S,
+                                                      int32_t M, int32_t cap,
+                                                      double* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    double* buf = (double*)smem_raw;
+    __shared__ double red[256];
+    __shared__ double g_theta[128], g_l[128], g_w[128];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t i = blockIdx.x;
+    const uint4 m = meta[i];
+    const double inf = __builtin_inf();
+    if (m.w & LF_BAD) {
+        if (tid == 0) {
+            out[i] = __builtin_nan("");
+            out[n + i] = __builtin_nan("");
+        }
+        return;
+    }
+    const double llmin = key_value(kmin[i]);   // -c_i
+    double B = 0.0;
+    for (int64_t sp = 0; sp < splits; ++sp) B += body[sp * n_pad + i];
+    if (m.w & LF_NOTAIL) {
+        // raw importance sampling: every ll + lw is -c
+        if (tid == 0) {
+            out[i] = (log((double)S) + llmin) - log(B);
+            out[n + i] = inf;
+        }
+        return;
+    }
+
+    // ---- sort ------------------------------------------------------------------------------
+    const uint32_t cnt_raw = count[i];
+    const int c_n = (int)(cnt_raw < (uint32_t)cap ? cnt_raw : (uint32_t)cap);
+    if ((m.w & LF_APPEND_EQ) ? c_n <= M : c_n != (int)m.y) {
+        // the slots do not hold what the select counted: cannot happen; a value, not a wild read
+        if (tid == 0) {
+            out[i] = __builtin_nan("");
+            out[n + i] = __builtin_nan("");
+        }
+        return;
+    }
+    int P2 = 2;
+    while (P2 < c_n) P2 <<= 1;
+    for (int j = tid; j < P2; j += 256) buf[j] = j < c_n ? cand[i * (int64_t)cap + j] : inf;
+    __syncthreads();
+    for (int ks = 2; ks <= P2; ks <<= 1)
+        for (int j = ks >> 1; j > 0; j >>= 1) {
+            for (int e = tid; e < P2; e += 256) {
+                const int o = e ^ j;
+                if (o > e) {
+                    const double x = buf[e], y = buf[o];
+                    if ((e & ks) == 0 ? x > y : x < y) {
+                        buf[e] = y;
+                        buf[o] = x;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+
+    // ---- the body's share of the bucket -------------------------------------------------------
+    double extra;
+    if (m.w & LF_APPEND_EQ) {
+        // candidates M .. c_n - 1 (the cutoff and what else of the bucket is not in the tail)
+        double part = 0.0;
+        for (int j = M + tid; j < c_n; j += 256) part += exp(llmin - buf[j]);
+        extra = block_sum(part, red);
+    } else {
+        // the bucket is one value v, repeated m.z times; the slots hold the m.y keys below it
+        const double v = key_value(prefix[i]);
+        __syncthreads();
+        for (int j = c_n + tid; j <= M; j += 256) buf[j] = v;
+        __syncthreads();
+        extra = (double)((int64_t)m.y + (int64_t)m.z - (int64_t)M) * exp(llmin - v);
+    }
+    const double Btot = B + extra;
+    const double cut = llmin - buf[M];   // cutoff, as lw
+    const double ecut = exp(cut);
+    bool smooth = buf[0] != buf[M - 1];
+    double khat = inf, sigma = 0.0;
+    double* xs = buf + M + 1;
+    __syncthreads();   // (buf[M + 1 ..] has been read above)
+
+    // ---- generalised Pareto fit (Zhang & Stephens 2009, as loo::gpdfit) -----------------------
+    if (smooth) {
+        const double dM = (double)M;
+        for (int j = tid; j < M; j += 256) xs[j] = exp(llmin - buf[M - 1 - j]) - ecut;
+        __syncthreads();
+        int rt = (int)sqrt(dM);
+        while ((int64_t)rt * rt > M) --rt;
+        while ((int64_t)(rt + 1) * (rt + 1) <= M) ++rt;
+        const int mg = 30 + rt;   // <= 128 for cap <= LOO_MAX_CAP
+        const double xM = xs[M - 1], xq = xs[(M + 2) / 4 - 1];
+        // a wave per grid point: lane-strided sums, then a butterfly (every lane the same bits)
+        for (int j = wave; j < mg; j += 4) {
+            const double th = 1.0 / xM + (1.0 - sqrt((double)mg / ((double)j + 0.5))) / (3.0 * xq);
+            double s = 0.0;
+            for (int e = lane; e < M; e += 64) s += log1p(-th * xs[e]);
+#pragma unroll
+            for (int bit = 1; bit < 64; bit <<= 1) {
+                const double o = __shfl_xor(s, bit);
+                s = (lane & bit) ? o + s : s + o;
+            }
+            const double kj = s / dM;
+            if (lane == 0) {
+                g_theta[j] = th;
+                g_l[j] = dM * (log(-th / kj) - kj - 1.0);
+            }
+        }
+        __syncthreads();
+        if (tid < mg) {
+            double s = 0.0;
+            for (int e = 0; e < mg; ++e) s += exp(g_l[e] - g_l[tid]);   // (+inf: weight 0)
+            g_w[tid] = 1.0 / s;
+        }
+        __syncthreads();
+        double theta = 0.0;
+        for (int e = 0; e < mg; ++e) theta += g_w[e] * g_theta[e];
+        double part = 0.0;
+        for (int e = tid; e < M; e += 256) part += log1p(-theta * xs[e]);
+        const double kraw = block_sum(part, red) / dM;
+        sigma = -kraw / theta;
+        khat = (dM * kraw + 5.0) / (dM + 10.0);
+        if (not_finite(khat)) {
+            khat = inf;
+            smooth = false;
+        }
+    }
+
+    // ---- the tail's weights, smoothed or raw, truncated at 0; then elpd_loo_i -----------------
+    double dpart = 0.0, mpart = -inf;
+    for (int j = tid; j < M; j += 256) {
+        const double llj = buf[M - 1 - j];
+        double lw;
+        if (smooth) {
+            const double l1p = log1p(-((double)j + 0.5) / (double)M);
+            const double q = fabs(khat) < 1e-30 ? -sigma * l1p : sigma * expm1(-khat * l1p) / khat;
+            lw = log(ecut + q);
+        } else {
+            lw = llmin - llj;
+        }
+        lw = lw > 0.0 ? 0.0 : lw;
+        xs[j] = lw;
+        dpart += exp(lw);
+        mpart = fmax(mpart, llj + lw);
+    }
+    const double den = log(Btot + block_sum(dpart, red));
+    const double mx = fmax(block_max(mpart, red), llmin);
+    double npart = 0.0;
+    for (int j = tid; j < M; j += 256) npart += exp((buf[M - 1 - j] + xs[j]) - mx);
+    const double num = mx + log((double)(S - M) * exp(llmin - mx) + block_sum(npart, red));
+    if (tid == 0) {
+        out[i] = num - den;
+        out[n + i] = khat;
+    }
+}
+
+struct Work {
+    uint64_t *range, *prefix, *kmin;
+    uint4* meta;
+    uint32_t *hist, *count;
+    double *cand, *body, *out;
+    Work(void* base, const LooBuffers& b) {
+        char* p = (char*)base;
+        auto take = [&](size_t bytes) {
+            char* q = p;
+            p += bytes;
+            return q;
+        };
+        range = (uint64_t*)take(b.range);
+        prefix = (uint64_t*)take(b.prefix);
+        kmin = (uint64_t*)take(b.kmin);
+        meta = (uint4*)take(b.meta);
+        hist = (uint32_t*)take(b.hist);
+        count = (uint32_t*)take(b.count);
+        cand = (double*)take(b.cand);
+        body = (double*)take(b.body);
+        out = (double*)take(b.out);
+    }
+};
+
+}  // namespace
+
+double* loo_out(const LooArgs& a, const LooPlan& p) {
+    return Work(a.work, loo_buffers(p, a.score.n)).out;
+}
+
+hipError_t launch_loo(const LooArgs& a, const LooPlan& p, hipStream_t s) {
+    const ScoreArgs& sa = a.score;
+    const ScorePlan& sp = p.score;
+    if (!p.ok || !a.work || sa.S - p.tail < 1 || p.cap < 2 * (p.tail + 1) || p.cap > LOO_MAX_CAP ||
+        (p.cap & (p.cap - 1)) != 0 || p.tail != loo_tail(sa.S))
+        return hipErrorInvalidValue;
+    hipError_t e = launch_score(sa, sp, s);   // (checks the shapes and the split plan)
+    if (e != hipSuccess) return e;
+    const LooBuffers lb = loo_buffers(p, sa.n);
+    const Work w(a.work, lb);
+    const int64_t n_pad = sp.point_tiles * SC_TM;
+    const unsigned groups = (unsigned)((uint64_t)sp.splits * (uint64_t)sp.point_tiles);
+    const unsigned pblocks = (unsigned)((n_pad + 255) / 256);
+    const int32_t M = (int32_t)p.tail, cap = (int32_t)p.cap;
+    PassArgs pa;
+    pa.Ap = sa.Ap;
+    pa.yp = sa.yp;
+    pa.theta = sa.theta;
+    pa.ch = sa.ch;
+    pa.S = sa.S;
+    pa.ldt = sa.ldt;
+    pa.tiles_per_split = sp.tiles_per_split;
+    pa.draw_tiles = sp.draw_tiles;
+    pa.n_pad = n_pad;
+    pa.k = sa.k;
+    pa.k_pad = sp.k_pad;
+    pa.point_tiles = (uint32_t)sp.point_tiles;
+
+    if ((e = hipMemsetAsync(w.hist, 0, lb.hist, s)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(w.count, 0, lb.count, s)) != hipSuccess) return e;
+    hipLaunchKernelGGL(loo_range_kernel, dim3(groups), dim3(256), 0, s, pa, w.range);
+    hipLaunchKernelGGL(loo_init_kernel, dim3(pblocks), dim3(256), 0, s, (const uint64_t*)w.range,
+                       n_pad, sp.splits, sa.S, M, cap, w.prefix, w.kmin, w.meta);
+    if (p.select_passes > 0) {
+        e = hipFuncSetAttribute((const void*)loo_select_kernel,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)LOO_SELECT_LDS);
+        if (e != hipSuccess) return e;
+        for (int pass = 0; pass < p.select_passes; ++pass) {
+            hipLaunchKernelGGL(loo_select_kernel, dim3(groups), dim3(256), LOO_SELECT_LDS, s, pa,
+                               (const uint64_t*)w.prefix, (const uint4*)w.meta, w.hist);
+            hipLaunchKernelGGL(loo_scan_kernel, dim3(pblocks), dim3(256), 0, s, n_pad, M, cap,
+                               w.prefix, w.meta, w.hist);
+        }
+    }
+    hipLaunchKernelGGL(loo_append_kernel, dim3(groups), dim3(256), 0, s, pa,
+                       (const uint64_t*)w.prefix, (const uint64_t*)w.kmin, (const uint4*)w.meta,
+                       (uint32_t)cap, w.count, w.cand, w.body);
+    const size_t fit_lds = (size_t)cap * 8;
+    e = hipFuncSetAttribute((const void*)loo_fit_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)fit_lds);
+    if (e != hipSuccess) return e;
+    if (sa.n > 0x7fffffffll) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(loo_fit_kernel, dim3((unsigned)sa.n), dim3(256), fit_lds, s,
+                       (const uint64_t*)w.prefix, (const uint64_t*)w.kmin, (const uint4*)w.meta,
+                       (const uint32_t*)w.count, (const double*)w.cand, (const double*)w.body, sa.n,
+                       n_pad, sp.splits, sa.S, M, cap, w.out);
+    return hipGetLastError();
+}
+
+}  // namespace bmc

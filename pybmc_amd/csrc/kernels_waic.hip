@@ -7,8 +7,8 @@
 //                  zero in the padding
 //   score_consts   per draw: c_s = -1/2 log(2 pi) - log sigma_s,  h_s = 1 / (2 sigma_s^2)
 //   score_tile     workgroup = 64 points x the draw tiles of one split.  a_i . beta_s on
-//                  v_mfma_f64_16x16x4_f64 (staging and LDS layout of predict_gemm_kernel; the draws
-//                  are read from theta in place, any ldt); the tile is reduced in the epilogue
+//                  v_mfma_f64_16x16x4_f64 (the tile loop of bmc_score_tile.h, shared with
+//                  kernels_loo.hip); the tile is reduced in the epilogue
 //                  and never stored: per lane and point an online log-sum-exp (running max, one
 //                  rescale per tile) and a mean / centred-M2 pair merged tile by tile (Chan et
 //                  al.); the 16 lanes that share a point merge at the end of the split
@@ -22,15 +22,11 @@
 #include "bmc_dev.h"
 #include "bmc_launch.h"
 #include "bmc_plan.h"
+#include "bmc_score_tile.h"
 
 namespace bmc {
 
-using f64x4 = __attribute__((ext_vector_type(4))) double;
-
 namespace {
-
-constexpr int SC_KT = 16, SC_LD = 18, SC_TM = SCORE_TILE;
-constexpr double HALF_LOG_2PI = 0.91893853320467274178;
 
 // (max, sum of exp(ll - max), count, mean, centred sum of squares) of a set of draws
 struct LlState {
@@ -124,8 +120,8 @@ __global__ __launch_bounds__(256) void score_tile_kernel(
     const double* __restrict__ ch, int64_t S, int64_t ldt, int32_t k, int32_t k_pad,
     uint32_t point_tiles, int64_t tiles_per_split, int64_t draw_tiles, int64_t n_pad,
     double* __restrict__ part) {
-    __shared__ double As[2 * SC_TM * SC_LD];
-    __shared__ double Bs[2 * SC_TM * SC_LD];
+    __shared__ double As[SC_LDS_DOUBLES];
+    __shared__ double Bs[SC_LDS_DOUBLES];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t pt = blockIdx.x % point_tiles;
@@ -134,44 +130,6 @@ __global__ __launch_bounds__(256) void score_tile_kernel(
     const int64_t dt0 = split * tiles_per_split;
     const int64_t dt1 = dt0 + tiles_per_split < draw_tiles ? dt0 + tiles_per_split : draw_tiles;
     const int cl = lane & 15, kq = lane >> 4;
-
-    // staging: element tid + 256 q of a 64 x 16 slab -> row sr + 16 q, column sc
-    const int sr = tid >> 4, sc = tid & 15;
-    const double* arow = Ap + (p0 + sr) * k_pad + sc;   // rows 16 k_pad apart, no bounds: padded
-    const double* brow[4];
-    double ra[4], rb[4];
-    // theta is read in place: a draw past S reads draw S - 1 (its ll is dropped in the epilogue),
-    // a column past k reads column k (in bounds) and stages 0
-    auto point_rows = [&](int64_t s0) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int64_t sd = s0 + sr + 16 * q;
-            brow[q] = theta + (sd < S ? sd : S - 1) * ldt;
-        }
-    };
-    auto fetch = [&](int m0) {
-        const int j = m0 + sc;
-        const int jc = j < k ? j : k;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            ra[q] = arow[(int64_t)(16 * q) * k_pad + m0];
-            const double v = brow[q][jc];
-            rb[q] = j < k ? v : 0.0;
-        }
-    };
-    double* as_w = As + sr * SC_LD + sc;
-    double* bs_w = Bs + sr * SC_LD + sc;
-    auto stash = [&](int buf) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            as_w[(buf * SC_TM + 16 * q) * SC_LD] = ra[q];
-            bs_w[(buf * SC_TM + 16 * q) * SC_LD] = rb[q];
-        }
-    };
-    const double* a_r = As + (16 * wave + cl) * SC_LD + kq;
-    const double* b_r = Bs + cl * SC_LD + kq;
-    const int nslab = k_pad / SC_KT;
-    const int last_nk = (k - SC_KT * (nslab - 1) + 3) / 4;   // k-steps of the last slab, 1 .. 4
 
     // this lane's four points: rows 16 wave + kq + 4 r of the tile (MFMA D: row = kq + 4 reg)
     double yv[4];
@@ -183,65 +141,13 @@ __global__ __launch_bounds__(256) void score_tile_kernel(
         st[r] = LlRun{-__builtin_inf(), 0.0, 0.0, 0.0};
     }
 
-    point_rows(dt0 * SC_TM);
-    fetch(0);
-    for (int64_t dt = dt0; dt < dt1; ++dt) {
-        const int64_t s0 = dt * SC_TM;
-        f64x4 acc[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) acc[t] = f64x4{0.0, 0.0, 0.0, 0.0};
-        stash(0);
-        __syncthreads();
-        for (int sl = 0; sl + 1 < nslab; ++sl) {
-            const int buf = sl & 1;
-            fetch((sl + 1) * SC_KT);
-            const double* Ab = a_r + buf * SC_TM * SC_LD;
-            const double* Bb = b_r + buf * SC_TM * SC_LD;
-#pragma unroll
-            for (int kk = 0; kk < SC_KT / 4; ++kk) {
-                const double a = Ab[4 * kk];
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-                    acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Bb[16 * t * SC_LD + 4 * kk],
-                                                                  acc[t], 0, 0, 0);
-            }
-            stash(buf ^ 1);
-            __syncthreads();
-        }
-        {
-            const int buf = (nslab - 1) & 1;
-            const double* Ab = a_r + buf * SC_TM * SC_LD;
-            const double* Bb = b_r + buf * SC_TM * SC_LD;
-            for (int kk = 0; kk < last_nk; ++kk) {
-                const double a = Ab[4 * kk];
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-                    acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Bb[16 * t * SC_LD + 4 * kk],
-                                                                  acc[t], 0, 0, 0);
-            }
-        }
-        // every wave is done with the LDS slabs before the next tile's first slab lands there;
-        // its global reads are issued now and wait behind the epilogue
-        __syncthreads();
-        if (dt + 1 < dt1) {
-            point_rows(s0 + SC_TM);
-            fetch(0);
-        }
-
-        // epilogue: ll = c_s - h_s r^2 for the lane's 4 points x 4 draws, folded into the running
-        // state of each point
-        double cs[4], hs[4];
-        bool ok[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int64_t sd = s0 + cl + 16 * t;
-            ok[t] = sd < S;
-            const int64_t sdc = ok[t] ? sd : S - 1;
-            cs[t] = ch[sdc];
-            hs[t] = ch[S + sdc];
-        }
+    // epilogue: ll = c_s - h_s r^2 for the lane's 4 points x 4 draws, folded into the running
+    // state of each point
+    score_tile_loop(Ap, theta, S, ldt, k, k_pad, p0, dt0, dt1, As, Bs,
+                    [&](int64_t s0, const f64x4(&acc)[4]) {
+        const TileDraws d(ch, S, s0, cl);
         const bool full = s0 + SC_TM <= S;   // wave-uniform
-        const double nb = (double)((int)ok[0] + (int)ok[1] + (int)ok[2] + (int)ok[3]);
+        const double nb = (double)((int)d.ok[0] + (int)d.ok[1] + (int)d.ok[2] + (int)d.ok[3]);
         if (nb > 0.0) {   // (not a lane whose draws of the last tile are all past S)
             const double w1 = nb / (cnt + nb), w2 = cnt * w1;
             cnt += nb;
@@ -249,15 +155,12 @@ __global__ __launch_bounds__(256) void score_tile_kernel(
             for (int r = 0; r < 4; ++r) {
                 double x[4];
 #pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    const double res = yv[r] - acc[t][r];
-                    x[t] = fma(-(hs[t] * res), res, cs[t]);
-                }
-                if (full) score_fold<true>(st[r], x, ok, nb, w1, w2);
-                else score_fold<false>(st[r], x, ok, nb, w1, w2);
+                for (int t = 0; t < 4; ++t) x[t] = d.ll(yv[r], acc[t][r], t);
+                if (full) score_fold<true>(st[r], x, d.ok, nb, w1, w2);
+                else score_fold<false>(st[r], x, d.ok, nb, w1, w2);
             }
         }
-    }
+    });
 
     // the 16 lanes (cl) that hold draws of the same four points: a tree over cl, the lower lane's
     // draws first, so every lane ends with the same bits; lane cl = 0 writes them

@@ -1,4 +1,4 @@
-"""Scoring a sampled fit on the GPU: pointwise log predictive density and WAIC.
+"""Scoring a sampled fit on the GPU: pointwise log predictive density, WAIC and PSIS-LOO.
 
 The reference package has no numeric score of a fit; this is a capability of this build.  The
 model is the one the samplers draw from, ``y_i ~ N(a_i . beta, sigma^2)``.  For design rows ``A``
@@ -21,8 +21,30 @@ S. Watanabe, "Asymptotic equivalence of Bayes cross validation and widely applic
 criterion in singular learning theory", JMLR 11, 2010; A. Gelman, J. Hwang, A. Vehtari,
 "Understanding predictive information criteria for Bayesian models", Stat. Comput. 24, 2014.
 
-On the device (``kernels_waic.hip``) the n x S matrix is never stored: an f64 MFMA GEMM whose
-tiles are reduced in the epilogue.  Non-finite input gives NaN outputs, not an error.
+PSIS-LOO (``psis_loo``; A. Vehtari, A. Gelman, J. Gabry, "Practical Bayesian model evaluation using
+leave-one-out cross-validation and WAIC", Stat. Comput. 27, 2017; A. Vehtari, D. Simpson,
+A. Gelman, Y. Yao, J. Gabry, "Pareto smoothed importance sampling", JMLR 25, 2024).  Per point i,
+over the S pooled kept draws, with r_eff = 1:
+
+1. ``lw_s = -ll[i, s]``, shifted so that the largest is 0 (``c`` the shift);
+2. ``M = min(floor(S / 5), ceil(3 sqrt(S)))``; ``M < 5``: nothing is smoothed, ``pareto_k = +inf``;
+3. the tail is the M largest ``lw`` (ties by value), ``cutoff`` the largest below it; a tail of equal
+   values: nothing is smoothed, ``pareto_k = +inf``;
+4. a generalised Pareto distribution is fitted to ``exp(lw_(j)) - exp(cutoff)`` (J. Zhang,
+   M. A. Stephens, "A new and efficient estimation method for the generalized Pareto
+   distribution", Technometrics 51, 2009, as ``loo::gpdfit``: 30 + floor(sqrt(M)) grid points,
+   prior 3, then ``k = (M k + 5) / (M + 10)``); ``pareto_k = k``; a non-finite k: no smoothing;
+5. the tail is replaced in rank order by ``log(exp(cutoff) + sigma expm1(-k log1p(-p_j)) / k)``,
+   ``p_j = (j - 1/2) / M``, and every ``lw`` truncated at 0;
+6. ``elpd_loo_i = logsumexp_s(ll + lw) - logsumexp_s(lw)``, ``p_loo_i = lppd_i - elpd_loo_i``;
+
+and on the host ``elpd_loo = sum_i``, ``p_loo = sum_i``, ``looic = -2 elpd_loo``,
+``se = sqrt(n var_i(elpd_loo_i, ddof=1))``, ``n_high_k = #{i : pareto_k_i > 0.7}``,
+``k_threshold = min(1 - 1 / log10(S), 0.7)`` and ``n_above_threshold``.
+
+On the device (``kernels_waic.hip``, ``kernels_loo.hip``) the n x S matrix is never stored: an f64 MFMA GEMM whose
+tiles are reduced in the epilogue; PSIS-LOO recomputes it for an exact radix select of each
+point's tail.  Non-finite input gives NaN outputs, not an error.
 """
 from __future__ import annotations
 
@@ -30,6 +52,7 @@ import numpy as np
 
 POINTWISE_KEYS = ("lppd", "p_waic", "mean_ll")
 HIGH_P_WAIC = 0.4
+HIGH_PARETO_K = 0.7
 MAX_K = 256
 
 
@@ -90,15 +113,10 @@ def _host_matrix(A):
     return A, k, BMC_ROW_MAJOR
 
 
-def pointwise_log_likelihood(A, y, samples, burn=0, thin=1, device=0):
-    """``lppd_i``, ``p_waic_i`` and ``mean_ll_i`` of every row of ``A`` (module docstring).
-
-    ``A`` is ``(n_points, k)`` float64 (either memory order: ``U_hat`` is Fortran-ordered), ``y``
-    ``(n_points,)``.  ``samples`` is ``(T, k+1)`` or ``(C, T, k+1)`` float64, the samplers' layout
-    (last column sigma): a numpy array, or a CUDA torch tensor whose last dimension is contiguous
-    (read in place; ``device`` is then the tensor's).  The first ``burn`` draws of every chain are
-    dropped, every ``thin``-th of the rest kept, and the chains pooled.  Returns a dict of
-    ``[n_points]`` arrays ``lppd``, ``p_waic``, ``mean_ll``."""
+def _pointwise_call(host_call, device_call, A, y, samples, burn, thin, device):
+    """The argument handling ``pointwise_log_likelihood`` and ``psis_loo`` share: checks, burn /
+    thin / pooling in place where the strides allow it, then the context method named
+    ``host_call`` (numpy draws) or ``device_call`` (CUDA tensor draws)."""
     from . import _lib
 
     if _is_torch(samples) and not samples.is_cuda:
@@ -128,8 +146,8 @@ def pointwise_log_likelihood(A, y, samples, burn=0, thin=1, device=0):
         # producer of `samples`) must be done first (cf. diagnostics.chain_diagnostics)
         torch.cuda.current_stream(dev).synchronize()
         with ctx.lock:
-            return ctx.pointwise_loglik_device(Ad.data_ptr(), n, k, k, _lib.BMC_ROW_MAJOR,
-                                               yd.data_ptr(), t.data_ptr(), C * kept, ld)
+            return getattr(ctx, device_call)(Ad.data_ptr(), n, k, k, _lib.BMC_ROW_MAJOR,
+                                             yd.data_ptr(), t.data_ptr(), C * kept, ld)
 
     s = np.asarray(samples)
     if s.dtype != np.float64:
@@ -146,7 +164,20 @@ def pointwise_log_likelihood(A, y, samples, burn=0, thin=1, device=0):
     y = np.ascontiguousarray(y)
     ctx = _lib.default_context(device)
     with ctx.lock:
-        return ctx.pointwise_loglik(A, n, k, lda, layout, y, s, C * kept, ld)
+        return getattr(ctx, host_call)(A, n, k, lda, layout, y, s, C * kept, ld)
+
+
+def pointwise_log_likelihood(A, y, samples, burn=0, thin=1, device=0):
+    """``lppd_i``, ``p_waic_i`` and ``mean_ll_i`` of every row of ``A`` (module docstring).
+
+    ``A`` is ``(n_points, k)`` float64 (either memory order: ``U_hat`` is Fortran-ordered), ``y``
+    ``(n_points,)``.  ``samples`` is ``(T, k+1)`` or ``(C, T, k+1)`` float64, the samplers' layout
+    (last column sigma): a numpy array, or a CUDA torch tensor whose last dimension is contiguous
+    (read in place; ``device`` is then the tensor's).  The first ``burn`` draws of every chain are
+    dropped, every ``thin``-th of the rest kept, and the chains pooled.  Returns a dict of
+    ``[n_points]`` arrays ``lppd``, ``p_waic``, ``mean_ll``."""
+    return _pointwise_call("pointwise_loglik", "pointwise_loglik_device", A, y, samples, burn,
+                           thin, device)
 
 
 def _se(v):
@@ -179,4 +210,34 @@ def waic(A, y, samples, burn=0, thin=1, device=0):
     out = waic_summary(pw["lppd"], pw["p_waic"])
     out.update(lppd=pw["lppd"], p_waic_i=pw["p_waic"], mean_ll=pw["mean_ll"],
                elpd_waic_i=pw["lppd"] - pw["p_waic"])
+    return out
+
+
+def loo_summary(elpd_loo_i, lppd, pareto_k, n_draws):
+    """The PSIS-LOO summary of the module docstring from the pointwise vectors (host, float64);
+    ``n_draws`` is the number of pooled kept draws S (for ``k_threshold``)."""
+    e = np.asarray(elpd_loo_i, dtype=np.float64)
+    lppd = np.asarray(lppd, dtype=np.float64)
+    kh = np.asarray(pareto_k, dtype=np.float64)
+    elpd = float(np.sum(e))
+    thr = min(1.0 - 1.0 / np.log10(n_draws), HIGH_PARETO_K)
+    return {"elpd_loo": elpd, "p_loo": float(np.sum(lppd - e)), "looic": -2.0 * elpd, "se": _se(e),
+            "n_high_k": int(np.sum(kh > HIGH_PARETO_K)), "k_threshold": float(thr),
+            "n_above_threshold": int(np.sum(kh > thr)), "n_points": int(e.shape[0]),
+            "n_draws": int(n_draws)}
+
+
+def psis_loo(A, y, samples, burn=0, thin=1, device=0):
+    """PSIS-LOO of a fit on its training data (module docstring): ``elpd_loo``, ``p_loo``,
+    ``looic``, ``se``, ``n_high_k``, ``k_threshold``, ``n_above_threshold``, ``n_points``,
+    ``n_draws`` and the pointwise ``elpd_loo_i``, ``p_loo_i``, ``pareto_k``, ``lppd``.  Arguments
+    as ``pointwise_log_likelihood``.  The relative efficiency r_eff of the draws is taken as 1, as
+    ``loo::psis`` does when none is given.  ``pareto_k`` is ``+inf`` where nothing was smoothed
+    (fewer than 25 draws, a tail of equal values, a non-finite fit)."""
+    pw = _pointwise_call("psis_loo", "psis_loo_device", A, y, samples, burn, thin, device)
+    sh = tuple(samples.shape)
+    C, T = (1, sh[0]) if len(sh) == 2 else sh[:2]
+    out = loo_summary(pw["elpd_loo"], pw["lppd"], pw["pareto_k"], C * kept_draws(T, burn, thin))
+    out.update(elpd_loo_i=pw["elpd_loo"], p_loo_i=pw["lppd"] - pw["elpd_loo"],
+               pareto_k=pw["pareto_k"], lppd=pw["lppd"])
     return out
