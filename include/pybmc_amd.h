@@ -152,7 +152,7 @@ int bmc_get_gram(bmc_ctx* ctx, double* gram_out);
 int bmc_get_basis(bmc_ctx* ctx, double* W_out, double* lam_out, double* sigma2_init);
 int bmc_conditional_moments(bmc_ctx* ctx, double sigma2, double* mean_out,
                             double* cov_out);
-/* The persistent loop kernels launched by the LAST bmc_gibbs_run* or bmc_simplex_run on this
+/* The persistent loop kernels launched by the LAST bmc_gibbs_run* or bmc_simplex_run* on this
  * context: their demangled names (e.g. "gibbs_loop_kernel<double, 1, 0, 32, 1, false, false,
  * true>"), one per launch, in launch order, each followed by '\n', the whole NUL-terminated.
  * *n_out = launches, *needed_out = bytes including the NUL (either may be NULL); names_out may be
@@ -211,6 +211,34 @@ int bmc_simplex_run(bmc_ctx* ctx, const double* Vt_hat, int32_t n_models, const 
                     int rng_mode, uint64_t seed, const double* xi, const double* unif,
                     int64_t n_unif, const double* g, double* samples_out,
                     int64_t* accepted_out, int64_t* unif_used_out, bmc_stats* stats);
+
+/* Several simplex chains in one call: chain c < n_chains is an independent run of bmc_simplex_run
+ * on the same problem, Vt_hat, S_hat, step size and prior.  Every per-chain array gains a leading
+ * chain axis: seeds [n_chains] (device mode), xi [n_chains][burn+iters][k], unif
+ * [n_chains][unif_ld] of which chain c may consume the first n_unif[c] <= unif_ld, g
+ * [n_chains][burn+iters]; samples_out [n_chains][iters][k+1], accepted_out [n_chains],
+ * unif_used_out [n_chains] (either may be NULL).  The chains run side by side on the device: all
+ * of them in one launch of the one-wave kernels, as many per launch as the device keeps resident
+ * in the workgroup form, the rest in following launches (stats->launches; bmc_last_kernels lists
+ * one name per launch).  stats->n_chains, launches and xcd_local_chains are filled, stats->passes
+ * is the number of uniforms consumed by all chains, the rest is as for bmc_simplex_run.
+ * CONTRACT: chain c of a device-mode call is bit for bit bmc_simplex_run(seed = seeds[c]) --
+ * samples, acceptance count and uniforms used -- whatever its index, its launch or its
+ * neighbours; a replay-mode chain is bit for bit the solo replay of its three streams.
+ * Every chain starts at beta = 0 as the reference does (:82), and burn-in is PER CHAIN: each
+ * chain runs burn + iters steps and keeps the last iters.
+ * Argument checks and status codes are those of bmc_simplex_run, plus BMC_EINVAL for
+ * n_chains < 1 or an n_unif[c] outside 0..unif_ld; BMC_ENOMEM when the variate and output
+ * buffers, which grow with n_chains, cannot be allocated.  BMC_ETIMEOUT and "fewer uniforms
+ * supplied than proposals" name the first failing chain in bmc_last_error ("(chain c)"); the
+ * other chains' results are still written. */
+int bmc_simplex_run_chains(bmc_ctx* ctx, const double* Vt_hat, int32_t n_models,
+                           const double* S_hat, int32_t n_chains, int64_t iters, int64_t burn,
+                           double stepsize, double nu0, double sigma20, int rng_mode,
+                           const uint64_t* seeds, const double* xi, const double* unif,
+                           int64_t unif_ld, const int64_t* n_unif, const double* g,
+                           double* samples_out, int64_t* accepted_out, int64_t* unif_used_out,
+                           bmc_stats* stats);
 
 /* ---- posterior predictive -----------------------------------------------------
  * Replaces rndm_m_random_calculator, pybmc/sampling_utils.py:40-84 (callers

@@ -80,6 +80,11 @@ PROTOTYPES = {
     "bmc_simplex_run": (C.c_int, [_P, _D, C.c_int32, _D, C.c_int64, C.c_int64, C.c_double, C.c_double,
                                   C.c_double, C.c_int, C.c_uint64, _D, _D, C.c_int64, _D, _D,
                                   C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(Stats)]),
+    "bmc_simplex_run_chains": (C.c_int, [_P, _D, C.c_int32, _D, C.c_int32, C.c_int64, C.c_int64,
+                                         C.c_double, C.c_double, C.c_double, C.c_int,
+                                         C.POINTER(C.c_uint64), _D, _D, C.c_int64,
+                                         C.POINTER(C.c_int64), _D, _D, C.POINTER(C.c_int64),
+                                         C.POINTER(C.c_int64), C.POINTER(Stats)]),
     "bmc_predict": (C.c_int, [_P, _D, C.c_int64, C.c_int32, _D, C.c_int32, C.c_int32, _D, C.c_int,
                               C.c_uint64, _D, C.POINTER(C.c_int32), _D, C.c_int32, _D,
                               C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, _D, _D,
@@ -415,6 +420,51 @@ class Context:
         if return_stats:
             return out, acc.value, used.value, st.as_dict()
         return out, acc.value
+
+    def simplex_run_chains(self, Vt_hat, S_hat, n_chains, iters, nu0, sigma20, burn, stepsize,
+                           seeds=None, xi=None, unif=None, n_unif=None, g=None, return_stats=False):
+        """``n_chains`` independent simplex chains side by side on the device.  Device mode:
+        ``seeds`` (n_chains,); chain c is bit for bit ``simplex_run(seed=seeds[c])``.  Replay mode:
+        ``xi`` (n_chains, burn+iters, k), ``g`` (n_chains, burn+iters), ``unif`` (n_chains, ld) of
+        which chain c may consume the first ``n_unif[c]`` (default: all ld).  Every chain starts
+        at beta = 0 and burn-in is per chain.  Returns (samples (n_chains, iters, k+1), accepted
+        (n_chains,), uniforms used (n_chains,)) [+ stats]."""
+        Vt_hat = np.ascontiguousarray(Vt_hat, dtype=np.float64)
+        S_hat = np.ascontiguousarray(S_hat, dtype=np.float64).reshape(-1)
+        if Vt_hat.ndim != 2 or Vt_hat.shape[0] != self.k or S_hat.shape[0] != self.k:
+            raise ValueError("Vt_hat must be (k, n_models) and S_hat (k,)")
+        n_chains = int(n_chains)
+        if n_chains < 1:
+            raise ValueError("n_chains must be >= 1")
+        out = np.empty((n_chains, iters, self.k + 1))
+        acc = np.zeros(n_chains, dtype=np.int64)
+        used = np.zeros(n_chains, dtype=np.int64)
+        st = Stats()
+        i64 = C.POINTER(C.c_int64)
+        if xi is not None:
+            tt = burn + iters
+            xi = np.ascontiguousarray(xi, dtype=np.float64).reshape(n_chains, tt, self.k)
+            g = np.ascontiguousarray(g, dtype=np.float64).reshape(n_chains, tt)
+            unif = np.ascontiguousarray(unif, dtype=np.float64).reshape(n_chains, -1)
+            ld = unif.shape[1]
+            nu = (np.full(n_chains, ld, dtype=np.int64) if n_unif is None
+                  else np.ascontiguousarray(n_unif, dtype=np.int64).reshape(n_chains))
+            rc = self._lib.bmc_simplex_run_chains(
+                self._h, _dptr(Vt_hat), Vt_hat.shape[1], _dptr(S_hat), n_chains, iters, burn,
+                stepsize, nu0, sigma20, BMC_RNG_REPLAY, None, _dptr(xi), _dptr(unif), ld,
+                nu.ctypes.data_as(i64), _dptr(g), _dptr(out), acc.ctypes.data_as(i64),
+                used.ctypes.data_as(i64), C.byref(st))
+        else:
+            sd = np.ascontiguousarray(seeds, dtype=np.uint64).reshape(n_chains)
+            rc = self._lib.bmc_simplex_run_chains(
+                self._h, _dptr(Vt_hat), Vt_hat.shape[1], _dptr(S_hat), n_chains, iters, burn,
+                stepsize, nu0, sigma20, BMC_RNG_DEVICE, sd.ctypes.data_as(C.POINTER(C.c_uint64)),
+                None, None, 0, None, None, _dptr(out), acc.ctypes.data_as(i64),
+                used.ctypes.data_as(i64), C.byref(st))
+        self._check(rc)
+        if return_stats:
+            return out, acc, used, st.as_dict()
+        return out, acc, used
 
     # -- posterior predictive --------------------------------------------------------------
     def predict_draws(self, order="C"):

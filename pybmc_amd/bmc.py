@@ -109,7 +109,10 @@ class BayesianModelCombination:
         ``n_chains`` (pooled along the sample axis), ``seeds``, ``dtype`` (``"float32"`` stores
         U_hat and y in float32 on the device, sums stay float64 -- BASELINE configs[3]),
         ``devices`` (list of GPU ids: the chains are split over them, one host thread and one
-        context per device, and pooled in chain order)."""
+        context per device, and pooled in chain order; Gibbs sampler only -- with the simplex
+        sampler it raises ``ValueError``).  The simplex sampler honours ``n_chains`` and ``seeds``
+        the same way: its chains run side by side on this GPU, each from beta = 0 with its own
+        ``burn`` steps dropped, and are pooled in chain order."""
         if self.U_hat is None:
             raise ValueError("Must call `orthogonalize()` before training.")
         opts = training_options if training_options is not None else {}
@@ -130,11 +133,20 @@ class BayesianModelCombination:
         sigma20 = get_option("sigma20_chosen", 0.02)
 
         if sampler == "simplex":
+            devices = opts.get("devices")
+            if devices is not None and list(devices) != [self.device]:
+                raise ValueError('"devices" is for the Gibbs sampler: simplex chains run on one '
+                                 'GPU (use n_chains for several chains on this device)')
+            n_chains = int(opts.get("n_chains", 1))
             self._device_problem = None   # the simplex path sets its own problem
-            self.samples = gibbs_sampler_simplex(
+            res, stats = gibbs_sampler_simplex(
                 self.centered_experiment_train, self.U_hat, self.Vt_hat, self.S_hat,
-                iterations, [nu0, sigma20], burn=burn, stepsize=stepsize, device=self.device)
-            self.n_chains = 1
+                iterations, [nu0, sigma20], burn=burn, stepsize=stepsize, device=self.device,
+                n_chains=n_chains, seeds=opts.get("seeds"), return_stats=True)
+            self.last_stats = stats
+            # several chains are pooled along the sample axis, in chain order
+            self.samples = res if res.ndim == 2 else res.reshape(-1, res.shape[-1])
+            self.n_chains = n_chains
         else:
             dtype = opts.get("dtype")
             if dtype is not None and np.dtype(dtype) not in (np.dtype(np.float32),

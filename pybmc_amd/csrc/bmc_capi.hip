@@ -62,14 +62,14 @@ struct bmc_ctx {
     DevBuf gramScratch, gramOut, rssPartial, rssOut, coef, stage, ticket;
     // run buffers
     DevBuf xi, gam, uout, samples, gran, status, seeds, dbg, placement;
-    // the persistent loop kernels of the last bmc_gibbs_run* / bmc_simplex_run, one name per
+    // the persistent loop kernels of the last bmc_gibbs_run* / bmc_simplex_run*, one name per
     // launch in launch order (bmc_last_kernels)
     std::vector<std::string> last_kernels;
     // predictive buffers
     DevBuf pPreds, pPad, pTheta, pVt, pWt, pSig, pR, pRT, pNoise, pAux, pBands;
     int64_t pM = 0;                        // last bmc_predict: points, draws, padded draws
     int32_t pS = 0, pS_pad = 0;
-    DevBuf sVt, sStep, sUnif, sOut, sCnt;
+    DevBuf sVt, sStep, sUnif, sOut, sCnt, sNUnif;
     DevBuf oFc, oMu, oW, oOut;
     // chain diagnostics (bmc_chain_diagnostics*)
     DevBuf dgIn, dgPart, dgMean, dgM2, dgCols, dgAcovPart, dgAcov;
@@ -797,7 +797,7 @@ void bmc_destroy(bmc_ctx* c) {
                       &c->stage, &c->xi, &c->gam, &c->uout, &c->samples, &c->gran, &c->status,
                       &c->seeds, &c->dbg, &c->placement, &c->pPreds, &c->pTheta, &c->pVt,
                       &c->pPad, &c->pWt, &c->pSig, &c->pR, &c->pRT, &c->pNoise, &c->pAux, &c->pBands, &c->sVt,
-                      &c->sStep, &c->sUnif, &c->sOut, &c->sCnt, &c->oFc, &c->oMu, &c->oW, &c->oOut,
+                      &c->sStep, &c->sUnif, &c->sOut, &c->sCnt, &c->sNUnif, &c->oFc, &c->oMu, &c->oW, &c->oOut,
                       &c->dgIn, &c->dgPart, &c->dgMean, &c->dgM2, &c->dgCols, &c->dgAcovPart,
                       &c->dgAcov, &c->scA, &c->scY, &c->scTheta, &c->scAp, &c->scYp, &c->scCh,
                       &c->scPart, &c->scOut, &c->looWork})
@@ -1447,24 +1447,35 @@ int bmc_rng_fill(bmc_ctx* c, uint64_t seed, int64_t count_normal, double* normal
     return BMC_OK;
 }
 
-int bmc_simplex_run(bmc_ctx* c, const double* Vt_hat, int32_t Km, const double* S_hat,
-                    int64_t iters, int64_t burn, double stepsize, double nu0, double sigma20,
-                    int rng_mode, uint64_t seed, const double* xi, const double* unif,
-                    int64_t n_unif, const double* g, double* samples_out, int64_t* accepted_out,
-                    int64_t* unif_used_out, bmc_stats* stats) {
+int bmc_simplex_run_chains(bmc_ctx* c, const double* Vt_hat, int32_t Km, const double* S_hat,
+                           int32_t n_chains, int64_t iters, int64_t burn, double stepsize, double nu0,
+                           double sigma20, int rng_mode, const uint64_t* seeds, const double* xi,
+                           const double* unif, int64_t unif_ld, const int64_t* n_unif, const double* g,
+                           double* samples_out, int64_t* accepted_out, int64_t* unif_used_out,
+                           bmc_stats* stats) {
     if (!c) return BMC_EINVAL;
     c->last_kernels.clear();
     if (!c->have_problem) return fail(c, BMC_ESTATE, "bmc_set_problem must be called first");
     if (!Vt_hat || !S_hat || Km < 1) return fail(c, BMC_EINVAL, "Vt_hat/S_hat/n_models invalid");
+    if (n_chains < 1) return fail(c, BMC_EINVAL, "need n_chains >= 1");
     if (burn < 0) return fail(c, BMC_EINVAL, "Burn-in iterations must be non-negative.");
     if (!(stepsize > 0)) return fail(c, BMC_EINVAL, "Stepsize must be positive.");
     if (iters < 0 || burn + iters >= 0xffffffffll) return fail(c, BMC_EINVAL, "bad iteration count");
     if (iters > 0 && !samples_out) return fail(c, BMC_EINVAL, "samples_out must not be NULL");
+    const size_t C = (size_t)n_chains;
+    std::vector<int64_t> nu(C, 0);   // uniforms chain c may consume
     if (rng_mode == BMC_RNG_REPLAY) {
-        if (!xi || !g || (n_unif > 0 && !unif) || n_unif < 0)
-            return fail(c, BMC_EINVAL, "xi, g and unif required in replay mode");
+        bool bad = !xi || !g || !n_unif || unif_ld < 0;
+        int64_t most = 0;
+        for (size_t i = 0; !bad && i < C; ++i) {
+            nu[i] = n_unif[i];
+            bad = nu[i] < 0 || nu[i] > unif_ld;
+            if (nu[i] > most) most = nu[i];
+        }
+        if (bad || (most > 0 && !unif)) return fail(c, BMC_EINVAL, "xi, g and unif required in replay mode");
     } else if (rng_mode == BMC_RNG_DEVICE) {
         if (xi || g || unif) return fail(c, BMC_EINVAL, "xi/g/unif must be NULL in device RNG mode");
+        if (!seeds) return fail(c, BMC_EINVAL, "seeds required in device RNG mode");
     } else {
         return fail(c, BMC_EINVAL, "rng_mode must be 0 or 1");
     }
@@ -1472,45 +1483,54 @@ int bmc_simplex_run(bmc_ctx* c, const double* Vt_hat, int32_t Km, const double* 
     const int K = c->k;
     const size_t Tt = (size_t)(burn + iters);
     int rc;
-    // -log_likelihood at beta = 0 (inference_utils.py:83-85) through the residual kernel
+    // -log_likelihood at beta = 0 (inference_utils.py:83-85) through the residual kernel: every
+    // chain starts there (:82)
     std::vector<double> zero(K, 0.0);
     double rss0 = 0.0;
     if ((rc = rss_on_raw(c, zero.data(), 1, &rss0))) return rc;
-    if ((rc = ensure(c, c->xi, Tt * K * 8)) || (rc = ensure(c, c->gam, Tt * 8)) ||
+    if (rng_mode == BMC_RNG_DEVICE) {
+        unif_ld = (int64_t)Tt;
+        for (size_t i = 0; i < C; ++i) nu[i] = (int64_t)Tt;
+    }
+    const size_t uld = (size_t)unif_ld;
+    if ((rc = ensure(c, c->xi, C * Tt * K * 8)) || (rc = ensure(c, c->gam, C * Tt * 8)) ||
         (rc = ensure(c, c->sVt, (size_t)K * Km * 8)) || (rc = ensure(c, c->sStep, (size_t)K * 8)) ||
-        (rc = ensure(c, c->sOut, (size_t)iters * (K + 1) * 8)) || (rc = ensure(c, c->sCnt, 64)) ||
-        (rc = ensure(c, c->status, 16)) || (rc = ensure(c, c->placement, 16)) ||
-        (rc = ensure(c, c->seeds, 16)))
+        (rc = ensure(c, c->sOut, C * (size_t)iters * (K + 1) * 8)) || (rc = ensure(c, c->sCnt, C * 16 + 48)) ||
+        (rc = ensure(c, c->sNUnif, C * 8)) || (rc = ensure(c, c->status, C * 4 + 12)) ||
+        (rc = ensure(c, c->placement, C * 4 + 12)) || (rc = ensure(c, c->seeds, C * 8 + 8)) ||
+        (rc = ensure(c, c->sUnif, (C * uld > 0 ? C * uld : 1) * 8)))
         return rc;
-    if (rng_mode == BMC_RNG_DEVICE) n_unif = (int64_t)Tt;
-    if ((rc = ensure(c, c->sUnif, (size_t)(n_unif > 0 ? n_unif : 1) * 8))) return rc;
     std::vector<double> step(K);
     for (int j = 0; j < K; ++j) step[j] = std::sqrt(S_hat[j] * S_hat[j] * stepsize * stepsize);  // :80
     if ((rc = check_tuning_fits(c))) return rc;
-    const Geometry geo = choose_geometry(shape_of(c), c->tune, chip_of(c), 1, Km <= 64, 4);   // (a model per lane)
+    // the geometry of ONE chain (a model per lane in the one-wave form) and the chains' launches
+    const SimplexPlan plan = plan_simplex_launches(shape_of(c), c->tune, chip_of(c), Km, n_chains);
+    const Geometry& geo = plan.geo;
     const int gran_stride = bmc::gran_slot_words(geo.G);
-    if ((rc = ensure(c, c->gran, (size_t)3 * gran_stride * 8))) return rc;
-    HIPCHK(c, hipMemsetAsync(c->gran.p, 0, (size_t)3 * gran_stride * 8, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->status.p, 0, 16, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->placement.p, 0, 16, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->sCnt.p, 0, 64, c->stream));
+    const size_t gran_chain = (size_t)3 * gran_stride * 8;   // bytes of one chain's exchange words
+    if ((rc = ensure(c, c->gran, (size_t)plan.max_per_launch * gran_chain))) return rc;
+    HIPCHK(c, hipMemsetAsync(c->status.p, 0, C * 4 + 12, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->placement.p, 0, C * 4 + 12, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->sCnt.p, 0, C * 16 + 48, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->sVt.p, Vt_hat, (size_t)K * Km * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->sStep.p, step.data(), (size_t)K * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->sNUnif.p, nu.data(), C * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
     if (Tt > 0) {
         if (rng_mode == BMC_RNG_DEVICE) {
-            HIPCHK(c, hipMemcpyAsync(c->seeds.p, &seed, 8, hipMemcpyHostToDevice, c->stream));
+            // chain c: the three streams of DESIGN.md 6 under its own seed, whatever its index
+            HIPCHK(c, hipMemcpyAsync(c->seeds.p, seeds, C * 8, hipMemcpyHostToDevice, c->stream));
             const double shape = (nu0 + (double)c->n) / 2.0;                       // :115
-            HIPCHK(c, launch_rng_fill((const uint64_t*)c->seeds.p, 1, (int64_t)Tt * K,
+            HIPCHK(c, launch_rng_fill((const uint64_t*)c->seeds.p, n_chains, (int64_t)Tt * K,
                                       (double*)c->xi.p, shape, (int64_t)Tt, (double*)c->gam.p,
                                       c->stream));
-            HIPCHK(c, launch_uniform_fill(seed, n_unif, (double*)c->sUnif.p, c->stream));
+            HIPCHK(c, launch_uniform_fill_chains((const uint64_t*)c->seeds.p, n_chains, unif_ld, unif_ld,
+                                                 (double*)c->sUnif.p, c->stream));
         } else {
-            HIPCHK(c, hipMemcpyAsync(c->xi.p, xi, Tt * K * 8, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(c->gam.p, g, Tt * 8, hipMemcpyHostToDevice, c->stream));
-            if (n_unif > 0)
-                HIPCHK(c, hipMemcpyAsync(c->sUnif.p, unif, (size_t)n_unif * 8, hipMemcpyHostToDevice,
-                                         c->stream));
+            HIPCHK(c, hipMemcpyAsync(c->xi.p, xi, C * Tt * K * 8, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(c->gam.p, g, C * Tt * 8, hipMemcpyHostToDevice, c->stream));
+            if (C * uld > 0)
+                HIPCHK(c, hipMemcpyAsync(c->sUnif.p, unif, C * uld * 8, hipMemcpyHostToDevice, c->stream));
         }
     }
     HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
@@ -1522,18 +1542,12 @@ int bmc_simplex_run(bmc_ctx* c, const double* Vt_hat, int32_t Km, const double* 
     a.step = (const double*)c->sStep.p;
     a.nu0_s20 = nu0 * sigma20;
     a.rss_init = rss0;
-    a.xi = (const double*)c->xi.p;
-    a.unif = (const double*)c->sUnif.p;
-    a.n_unif = n_unif;
-    a.gam = (const double*)c->gam.p;
-    a.out = (double*)c->sOut.p;
+    a.unif_ld = unif_ld;
     a.gran = (unsigned long long*)c->gran.p;
     a.gran_stride = gran_stride;
-    a.status = (int32_t*)c->status.p;
-    a.placement = (int32_t*)c->placement.p;
-    a.counters = (long long*)c->sCnt.p;
     a.iters = iters;
     a.burn = burn;
+    a.n_chains = 1;
     a.G = geo.G;
     a.waves = geo.waves;
     a.mode = geo.mode;
@@ -1542,29 +1556,48 @@ int bmc_simplex_run(bmc_ctx* c, const double* Vt_hat, int32_t Km, const double* 
     a.force_agent_scope = c->tune.force_agent_scope;
     a.panels_per_group = geo.ppg;
     a.one_wave = geo.one_wave;
-    a.epoch0 = launch_nonce(c, (uint64_t)Tt);
     if (a.vt_in_lds && simplex_lds_bytes(a) > LDS_LIMIT) a.vt_in_lds = 0;
     if (simplex_lds_bytes(a) > LDS_LIMIT) return fail(c, BMC_EINVAL, "LDS plan exceeds 160 KiB");
-    if (Tt > 0) {
-        if (a.G > 1 &&
-            (rc = check_residency(c, simplex_kernel(a), a.G, "persistent simplex kernel")))
+    int launches = 0;
+    for (size_t i = 0; Tt > 0 && i < plan.launches.size(); ++i) {
+        const SimplexLaunch& l = plan.launches[i];
+        const size_t c0 = (size_t)l.c0;
+        a.n_chains = l.n_chains;
+        a.nslot = l.nslot;
+        a.xi = (const double*)c->xi.p + c0 * Tt * K;
+        a.gam = (const double*)c->gam.p + c0 * Tt;
+        a.unif = (const double*)c->sUnif.p + c0 * uld;
+        a.n_unif = (const int64_t*)c->sNUnif.p + c0;
+        a.out = (double*)c->sOut.p + c0 * (size_t)iters * (K + 1);
+        a.status = (int32_t*)c->status.p + c0;
+        a.placement = (int32_t*)c->placement.p + c0;
+        a.counters = (long long*)c->sCnt.p + 2 * c0;
+        a.epoch0 = launch_nonce(c, (uint64_t)Tt);
+        HIPCHK(c, hipMemsetAsync(c->gran.p, 0, (size_t)l.n_chains * gran_chain, c->stream));
+        if (a.G > 1 &&   // (a single-workgroup chain waits for nobody)
+            (rc = check_residency(c, simplex_kernel(a), l.resident, "persistent simplex kernel")))
             return rc;
         KernelKey launched;
         HIPCHK(c, launch_simplex(a, c->stream, &launched));
         c->last_kernels.push_back(kernel_name(launched));
+        ++launches;
     }
     HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
-    int32_t st = 0, place = 0;
-    long long cnt[2] = {0, 0};
-    HIPCHK(c, hipMemcpyAsync(&st, c->status.p, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(&place, c->placement.p, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(cnt, c->sCnt.p, 16, hipMemcpyDeviceToHost, c->stream));
+    std::vector<int32_t> st(C, 0), place(C, 0);
+    std::vector<long long> cnt(2 * C, 0);
+    HIPCHK(c, hipMemcpyAsync(st.data(), c->status.p, C * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(place.data(), c->placement.p, C * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(cnt.data(), c->sCnt.p, C * 16, hipMemcpyDeviceToHost, c->stream));
     if (iters > 0)
-        HIPCHK(c, hipMemcpyAsync(samples_out, c->sOut.p, (size_t)iters * (K + 1) * 8,
+        HIPCHK(c, hipMemcpyAsync(samples_out, c->sOut.p, C * (size_t)iters * (K + 1) * 8,
                                  hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (accepted_out) *accepted_out = cnt[0];
-    if (unif_used_out) *unif_used_out = cnt[1];
+    int64_t used_all = 0;
+    for (size_t i = 0; i < C; ++i) {
+        if (accepted_out) accepted_out[i] = cnt[2 * i];
+        if (unif_used_out) unif_used_out[i] = cnt[2 * i + 1];
+        used_all += cnt[2 * i + 1];
+    }
     if (stats) {
         float ms = 0;
         std::memset(stats, 0, sizeof(*stats));
@@ -1572,19 +1605,36 @@ int bmc_simplex_run(bmc_ctx* c, const double* Vt_hat, int32_t Km, const double* 
         HIPCHK(c, hipEventElapsedTime(&ms, c->ev[1], c->ev[2])); stats->loop_ms = ms;
         HIPCHK(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[2])); stats->total_ms = ms;
         stats->iterations = burn + iters;
-        stats->n_chains = 1;
-        stats->launches = Tt > 0 ? 1 : 0;
+        stats->n_chains = n_chains;
+        stats->launches = launches;
         stats->groups_per_chain = geo.G;
         stats->waves_per_group = geo.waves;
         stats->chains_per_pass = 1;
         stats->residency = geo.mode + 1;
-        stats->xcd_local_chains = place ? 1 : 0;
+        stats->xcd_local_chains = 0;
+        for (size_t i = 0; i < C; ++i) stats->xcd_local_chains += place[i] ? 1 : 0;
         stats->bytes_per_pass = ((int64_t)c->n * K + c->n) * (c->f32 ? 4 : 8);
-        stats->passes = cnt[1];
+        stats->passes = used_all;
     }
-    if (st == 1) return fail(c, BMC_ETIMEOUT, "persistent simplex kernel: bounded spin expired");
-    if (st == 2) return fail(c, BMC_EINVAL, "replay: fewer uniforms supplied than proposals inside the simplex");
+    // the first failing chain is named when the call has more than one
+    for (size_t i = 0; i < C; ++i) {
+        const std::string which = n_chains > 1 ? " (chain " + std::to_string(i) + ")" : "";
+        if (st[i] == 1) return fail(c, BMC_ETIMEOUT, "persistent simplex kernel: bounded spin expired" + which);
+        if (st[i] == 2)
+            return fail(c, BMC_EINVAL, "replay: fewer uniforms supplied than proposals inside the simplex" + which);
+    }
     return BMC_OK;
+}
+
+// one chain: the C = 1 case of bmc_simplex_run_chains
+int bmc_simplex_run(bmc_ctx* c, const double* Vt_hat, int32_t Km, const double* S_hat,
+                    int64_t iters, int64_t burn, double stepsize, double nu0, double sigma20,
+                    int rng_mode, uint64_t seed, const double* xi, const double* unif,
+                    int64_t n_unif, const double* g, double* samples_out, int64_t* accepted_out,
+                    int64_t* unif_used_out, bmc_stats* stats) {
+    return bmc_simplex_run_chains(c, Vt_hat, Km, S_hat, 1, iters, burn, stepsize, nu0, sigma20, rng_mode,
+                                  &seed, xi, unif, n_unif, &n_unif, g, samples_out, accepted_out,
+                                  unif_used_out, stats);
 }
 
 int bmc_predict(bmc_ctx* c, const double* preds, int64_t M, int32_t Km, const double* theta,

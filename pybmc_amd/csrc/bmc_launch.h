@@ -181,6 +181,9 @@ struct GramArgs {
 };
 hipError_t launch_gibbs_gram(const GramArgs& a, hipStream_t s);
 
+// Per-chain arrays are indexed by the chain of the launch (wave form: chain = blockIdx.x;
+// workgroup form: chain = blockIdx.x % nslot, group = blockIdx.x / nslot, slots >= n_chains leave at
+// once).  Chains share the panels, Vt_hat and the step and nothing else: they never synchronise.
 struct SimplexArgs {
     Panels P;               // UN-rotated panels (the simplex sampler proposes beta itself)
     const double* Vt;       // [k][Km]  Vt_hat
@@ -188,18 +191,20 @@ struct SimplexArgs {
     int32_t vt_in_lds;      // Vt_hat kept in LDS (k*Km <= 4096 doubles)
     const double* step;     // [k]  S_hat * stepsize
     double nu0_s20;
-    double rss_init;        // sum y^2 (beta = 0)
-    const double* xi;       // [burn+iters][k]
-    const double* unif;     // [n_unif]
-    int64_t n_unif;
-    const double* gam;      // [burn+iters]
-    double* out;            // [iters][k+1]
-    unsigned long long* gran;
+    double rss_init;        // sum y^2 (beta = 0: every chain starts there)
+    const double* xi;       // [C][burn+iters][k]
+    const double* unif;     // [C][unif_ld]
+    int64_t unif_ld;        // doubles between the uniform streams of consecutive chains
+    const int64_t* n_unif;  // [C] (device) uniforms chain c may consume
+    const double* gam;      // [C][burn+iters]
+    double* out;            // [C][iters][k+1]
+    unsigned long long* gran;  // [C][3][gran_stride], zeroed (as in GibbsArgs)
     int32_t gran_stride;
-    int32_t* status;        // 0 ok, 1 timeout, 2 uniforms exhausted
-    int32_t* placement;
-    long long* counters;    // [2] accepted (sampling phase), uniforms consumed
+    int32_t* status;        // [C] 0 ok, 1 timeout, 2 uniforms exhausted
+    int32_t* placement;     // [C]
+    long long* counters;    // [C][2] accepted (sampling phase), uniforms consumed
     int64_t iters, burn;
+    int32_t n_chains;       // chains in THIS launch
     int32_t G, waves, mode, reg_ppw, nslot, force_agent_scope, panels_per_group;
     uint32_t epoch0 = 0;    // as in GibbsArgs
     int32_t one_wave = 0;   // host-only. 1: simplex_wave_kernel (gibbs_wave_capacity() > 0, Km <= 64)
@@ -209,6 +214,10 @@ size_t simplex_lds_bytes(const SimplexArgs& a);
 hipError_t launch_simplex(const SimplexArgs& a, hipStream_t s, KernelKey* launched = nullptr);
 // uniforms in (0,1]: out[i] = u53(philox(counter = (i, STREAM_UNIFORM), key = seed))
 hipError_t launch_uniform_fill(uint64_t seed, int64_t n, double* out, hipStream_t s);
+// the same for n_chains seeds (device): out[c * ld + i], i < n, is what launch_uniform_fill(seeds[c],
+// n, out + c * ld) writes -- the counter is the index within the chain, the key the chain's seed
+hipError_t launch_uniform_fill_chains(const uint64_t* seeds_dev, int32_t n_chains, int64_t n, int64_t ld,
+                                      double* out, hipStream_t s);
 
 size_t gibbs_lds_bytes(const GibbsArgs& a);
 // launched (optional): the key of the instantiation the launcher looked up and launched

@@ -582,6 +582,53 @@ inline KernelKey simplex_kernel_key(const Shape& s, const Geometry& g) {
     return loop_kernel_key(KF_SIMPLEX_LOOP, s, g);
 }
 
+// ---- simplex chains over launches -----------------------------------------------------------
+// One launch of the simplex loop: chains c0 .. c0 + n_chains - 1 of the call.
+struct SimplexLaunch {
+    int c0, n_chains;
+    int nslot;      // workgroup form: grid = nslot x G, chain = block % nslot (wave form: unused)
+    int resident;   // workgroups that wait for one another inside the loop: n_chains x G
+};
+struct SimplexPlan {
+    Geometry geo;   // of ONE chain: every chain of every launch runs simplex_kernel_key(shape, geo)
+    std::vector<SimplexLaunch> launches;
+    int max_per_launch = 0;   // the most chains one launch holds (sizes the exchange words)
+};
+
+// Split n_chains simplex chains over launches.  The geometry is the one a single chain gets
+// (choose_geometry for one chain; the one-wave form needs a model per lane), so a chain runs the
+// same kernel on the same grid shape whatever its neighbours: that is what makes chain c of a call
+// bit for bit its solo run.
+//   one-wave form   one block per chain, all chains in one launch up to the 2048 blocks the Gibbs
+//                   one-wave launches use as well
+//   workgroup form  a chain needs G co-resident workgroups, and the device holds groups_max (one
+//                   per CU, cu_limit): groups_max / G chain slots per launch.  Where one chain
+//                   gets the XCD labelling (geo.nslot = the XCD count: its groups are the blocks
+//                   b = slot mod 8, which share an XCD) every chain keeps it: one chain per XCD,
+//                   slot c for chain c, as plan_gibbs batches its single-chain loops.
+inline SimplexPlan plan_simplex_launches(const Shape& s, const bmc_tuning& tu, const Chip& chip, int n_models,
+                                         int n_chains) {
+    SimplexPlan p;
+    p.geo = choose_geometry(s, tu, chip, 1, n_models <= 64, 4);
+    const bool xcd_slots = !p.geo.one_wave && chip.xcds > 1 && p.geo.nslot == chip.xcds;
+    int cap = 2048;
+    if (!p.geo.one_wave) {
+        cap = xcd_slots ? chip.xcds : chip.groups_max / p.geo.G;
+        if (cap < 1) cap = 1;
+    }
+    for (int c0 = 0; c0 < n_chains;) {
+        SimplexLaunch l{};
+        l.c0 = c0;
+        l.n_chains = n_chains - c0 < cap ? n_chains - c0 : cap;
+        l.nslot = xcd_slots ? chip.xcds : l.n_chains;
+        l.resident = l.n_chains * p.geo.G;
+        if (l.n_chains > p.max_per_launch) p.max_per_launch = l.n_chains;
+        p.launches.push_back(l);
+        c0 += l.n_chains;
+    }
+    return p;
+}
+
 // The key as the demangled kernel name, e.g. gibbs_loop_kernel<double, 1, 0, 32, 1, false, false, true>
 inline std::string kernel_name(const KernelKey& k) {
     const char* T = k.f32 ? "float" : "double";

@@ -841,6 +841,10 @@ hipError_t launch_gibbs_gram(const GramArgs& a, hipStream_t s) {
 // proposal outside the simplex skips the residual pass AND consumes no uniform (:102,
 // :124): every group evaluates the simplex test on identical bits, so all skip together;
 // the exchange epoch counts exchanges, not iterations.
+// Any number of chains per launch (SimplexArgs.n_chains): a chain is one block of the wave form and
+// one slot (G blocks) of the workgroup form, with its own variate streams, exchange words, status
+// word and counters.  Chains never wait for one another, and the loop of a chain is the same
+// operations whatever shares the launch: chain c is bit for bit its solo run.
 // ======================================================================================
 // SINGLE: the chain lives in ONE workgroup (G == 1, register residency: the reference's own
 // sizes): nothing to exchange -- as a run-time test it cost the multi-group shapes 2 %.
@@ -849,13 +853,22 @@ __global__ __launch_bounds__(512) void simplex_loop_kernel(SimplexArgs a) {
     constexpr int RP = 64 * VEC;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int K = a.P.k, Km = a.Km, G = a.G;
+    // chain = slot of the grid (nslot x G, as in gibbs_loop_kernel); chains never synchronise
+    // with one another: each has its own granules, status word, counters and variate streams
     const int chain = blockIdx.x % a.nslot;
     const int g = blockIdx.x / a.nslot;
-    if (chain >= 1) return;
+    if (chain >= a.n_chains) return;       // unused slot: the whole workgroup leaves
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nw = blockDim.x >> 6;
     const int64_t T_tot = a.burn + a.iters;
+    // this chain's streams and outputs (wave-uniform: the offsets are scalar, taken once)
+    const double* xi = a.xi + (int64_t)chain * T_tot * K;
+    const double* gam = a.gam + (int64_t)chain * T_tot;
+    const double* unif = a.unif + (int64_t)chain * a.unif_ld;
+    const int64_t n_unif = a.n_unif[chain];
+    double* out = a.out + (int64_t)chain * a.iters * (K + 1);
+    int32_t* status = a.status + chain;
 
     const int aux_n = a.vt_in_lds ? K * Km : 0;
     const LdsPlan L = lds_plan(K, (int)sizeof(T), RP, a.panels_per_group, MODE == MODE_LDS, aux_n);
@@ -875,19 +888,19 @@ __global__ __launch_bounds__(512) void simplex_loop_kernel(SimplexArgs a) {
     PanelStore<T, VEC, MODE, KMAX, PPW> store;
     store.init(a.P, G, g, reinterpret_cast<T*>(smem + L.x), reinterpret_cast<T*>(smem + L.y));
 
-    gu64* gr = a.gran;
+    gu64* gr = a.gran + (size_t)chain * 3 * a.gran_stride;
     if constexpr (!SINGLE) {
         if (wave == 0) {
             const int place = detect_placement(gr + 2 * a.gran_stride, G, g, lane, a.epoch0);
             if (lane == 0) {
-                if (place < 0) { ctl[1] = 1.0; a.status[0] = 1; }
+                if (place < 0) { ctl[1] = 1.0; *status = 1; }
                 ctl[2] = (place == 1 && !a.force_agent_scope) ? 1.0 : 0.0;
             }
         }
     }
     __syncthreads();
     const bool local = ctl[2] != 0.0;
-    if (g == 0 && tid == 0) a.placement[0] = (local || SINGLE) ? 1 : 0;
+    if (g == 0 && tid == 0) a.placement[chain] = (local || SINGLE) ? 1 : 0;
 
     // lane-chunks of 64 columns: one, known at compile time, in register mode (K <= 64)
     constexpr int KCH = (MODE == MODE_REG) ? 1 : MAX_KCH;
@@ -906,10 +919,10 @@ __global__ __launch_bounds__(512) void simplex_loop_kernel(SimplexArgs a) {
             b_cur[ch] = 0.0;                            // :82
             b_prop[ch] = 0.0;
             step_r[ch] = j < K ? a.step[j] : 0.0;
-            xi_next[ch] = (j < K && T_tot > 0) ? a.xi[j] : 0.0;
+            xi_next[ch] = (j < K && T_tot > 0) ? xi[j] : 0.0;
         }
-        if (T_tot > 0) gam_next = a.gam[0];
-        if (a.n_unif > 0) unif_next = a.unif[0];
+        if (T_tot > 0) gam_next = gam[0];
+        if (n_unif > 0) unif_next = unif[0];
     }
 
 #if BMC_LEADER_PRIO > 0
@@ -955,9 +968,9 @@ __global__ __launch_bounds__(512) void simplex_loop_kernel(SimplexArgs a) {
 #pragma unroll
             for (int ch = 0; ch < KCH; ++ch) {
                 const int j = ch * 64 + lane;
-                if (ch * 64 < K && j < K) xi_next[ch] = a.xi[(t + 1) * K + j];
+                if (ch * 64 < K && j < K) xi_next[ch] = xi[(t + 1) * K + j];
             }
-            gam_next = a.gam[t + 1];
+            gam_next = gam[t + 1];
         }
 
         if (inside) {
@@ -974,15 +987,15 @@ __global__ __launch_bounds__(512) void simplex_loop_kernel(SimplexArgs a) {
                 nex + 1 + a.epoch0, local, got STAMP_ARGS);
             ++nex;
             if (wave == 0) {
-                if (!got || iu >= a.n_unif) {
-                    if (lane == 0) { ctl[1] = 1.0; a.status[0] = got ? 2 : 1; }
+                if (!got || iu >= n_unif) {
+                    if (lane == 0) { ctl[1] = 1.0; *status = got ? 2 : 1; }
                 } else {
                     // min(1, exp((ll_prop - ll_cur) / sigma2)), ll = -rss     (:106-109)
                     const double ratio = exp((rss_cur - rss_prop) / s2);
                     const double p_acc = ratio < 1.0 ? ratio : 1.0;
                     const double uu = unif_next;
                     ++iu;
-                    if (iu < a.n_unif) unif_next = a.unif[iu];
+                    if (iu < n_unif) unif_next = unif[iu];
                     if (uu < p_acc) {                                          // :110-112
 #pragma unroll
                         for (int ch = 0; ch < KCH; ++ch) b_cur[ch] = b_prop[ch];
@@ -997,7 +1010,7 @@ __global__ __launch_bounds__(512) void simplex_loop_kernel(SimplexArgs a) {
             const double scale_post = (a.nu0_s20 + rss_cur) * 0.5;
             s2 = scale_post / gam_t;
             if (g == 0 && t >= a.burn) {
-                double* row = a.out + (t - a.burn) * (K + 1);
+                double* row = out + (t - a.burn) * (K + 1);
 #pragma unroll
                 for (int ch = 0; ch < KCH; ++ch) {
                     const int j = ch * 64 + lane;
@@ -1008,8 +1021,8 @@ __global__ __launch_bounds__(512) void simplex_loop_kernel(SimplexArgs a) {
         }
     }
     if (g == 0 && tid == 0) {
-        a.counters[0] = accepted;
-        a.counters[1] = iu;
+        a.counters[2 * chain] = accepted;
+        a.counters[2 * chain + 1] = iu;
     }
 }
 
@@ -1027,8 +1040,17 @@ __global__ __launch_bounds__(MANY ? 256 : 64) void simplex_wave_kernel(SimplexAr
     const int rpw = (NP + nw - 1) / nw, p0 = wave * rpw;
     const bool rec = wave == 0;
     unsigned nex = 0;   // residual sums exchanged so far (parity of the LDS slots)
-    if (blockIdx.x != 0) return;
+    // one block per chain, any number of chains per launch (as in gibbs_wave_kernel); a chain
+    // that runs out of replay uniforms ends alone and marks its own status word
+    const int chain = blockIdx.x;
+    if (chain >= a.n_chains) return;
     const int64_t T_tot = a.burn + a.iters;
+    // this chain's streams and outputs (wave-uniform: the offsets are scalar, taken once)
+    const double* xi = a.xi + (int64_t)chain * T_tot * K;
+    const double* gam = a.gam + (int64_t)chain * T_tot;
+    const double* unif = a.unif + (int64_t)chain * a.unif_ld;
+    const int64_t n_unif = a.n_unif[chain];
+    double* out = a.out + (int64_t)chain * a.iters * (K + 1);
     const T* Xp = reinterpret_cast<const T*>(a.P.X);
     const T* yp = reinterpret_cast<const T*>(a.P.y);
     double x[RMAX][KMAX], y[RMAX], vtr[KMAX];
@@ -1048,14 +1070,14 @@ __global__ __launch_bounds__(MANY ? 256 : 64) void simplex_wave_kernel(SimplexAr
 #pragma unroll
     for (int j = 0; j < KMAX; ++j) vtr[j] = (j < K && model) ? a.Vt[(size_t)j * Km + lane] : 0.0;
     const double step = act ? a.step[lane] : 0.0;
-    if (threadIdx.x == 0) a.placement[0] = 1;
+    if (threadIdx.x == 0) a.placement[chain] = 1;
     double b_cur = 0.0;                                 // :82
     double rss_cur = a.rss_init;                        // -log_likelihood_current (:85)
     double s2 = a.rss_init / (double)a.P.n;             // :86
     double s2_cap = 1.0;                                // lane i: sigma2 behind staged row i
-    double xi_next = (act && T_tot > 0) ? a.xi[lane] : 0.0;
-    double gam_next = T_tot > 0 ? a.gam[0] : 1.0;
-    double unif_next = a.n_unif > 0 ? a.unif[0] : 0.5;
+    double xi_next = (act && T_tot > 0) ? xi[lane] : 0.0;
+    double gam_next = T_tot > 0 ? gam[0] : 1.0;
+    double unif_next = n_unif > 0 ? unif[0] : 0.5;
     int64_t iu = 0, accepted = 0;
     const double w0 = 1.0 / (double)Km;
     const int K1 = K + 1;
@@ -1066,8 +1088,8 @@ __global__ __launch_bounds__(MANY ? 256 : 64) void simplex_wave_kernel(SimplexAr
         const double gam_t = gam_next;
         {
             const int64_t tn = t + 1 < T_tot ? t + 1 : t;
-            xi_next = act ? a.xi[tn * K + lane] : 0.0;
-            gam_next = a.gam[tn];
+            xi_next = act ? xi[tn * K + lane] : 0.0;
+            gam_next = gam[tn];
         }
         double uj[KMAX];
 #pragma unroll
@@ -1095,8 +1117,8 @@ __global__ __launch_bounds__(MANY ? 256 : 64) void simplex_wave_kernel(SimplexAr
                 rss_prop = (ws[0] + ws[1]) + (ws[2] + ws[3]);
                 ++nex;
             }
-            if (iu >= a.n_unif) {
-                if (threadIdx.x == 0) a.status[0] = 2;
+            if (iu >= n_unif) {
+                if (threadIdx.x == 0) a.status[chain] = 2;
                 break;
             }
             // min(1, exp((ll_prop - ll_cur) / sigma2)), ll = -rss     (:106-109)
@@ -1104,7 +1126,7 @@ __global__ __launch_bounds__(MANY ? 256 : 64) void simplex_wave_kernel(SimplexAr
             const double p_acc = ratio < 1.0 ? ratio : 1.0;
             const double uu = unif_next;
             ++iu;
-            if (iu < a.n_unif) unif_next = a.unif[iu];
+            if (iu < n_unif) unif_next = unif[iu];
             if (uu < p_acc) {                                          // :110-112
                 b_cur = b_prop;
                 rss_cur = rss_prop;
@@ -1122,14 +1144,14 @@ __global__ __launch_bounds__(MANY ? 256 : 64) void simplex_wave_kernel(SimplexAr
                 const int nrows = slot + 1;
                 const double sig = sqrt(s2_cap);
                 if (lane < nrows) rows[lane * K1 + K] = sig;
-                double* dst = a.out + (kept - slot) * K1;
+                double* dst = out + (kept - slot) * K1;
                 for (int idx = lane; idx < nrows * K1; idx += 64) dst[idx] = rows[idx];
             }
         }
     }
     if (threadIdx.x == 0) {
-        a.counters[0] = accepted;
-        a.counters[1] = iu;
+        a.counters[2 * chain] = accepted;
+        a.counters[2 * chain + 1] = iu;
     }
 }
 
@@ -1215,7 +1237,9 @@ LoopKernel gibbs_kernel(const GibbsArgs& a) {
 }
 
 LoopKernel simplex_kernel(const SimplexArgs& a) {
-    if (a.one_wave ? (a.Km < 1 || a.Km > 64) : (!geometry_ok(a.P.k, a.G, a.waves, a.nslot) || a.Km < 1))
+    if (a.n_chains < 1 || (a.one_wave ? (a.Km < 1 || a.Km > 64 || a.n_chains > 2048)
+                                      : (!geometry_ok(a.P.k, a.G, a.waves, a.nslot) || a.Km < 1 ||
+                                         a.n_chains > a.nslot)))
         return LoopKernel{};
     Geometry g{};
     g.G = a.G;
@@ -1223,7 +1247,7 @@ LoopKernel simplex_kernel(const SimplexArgs& a) {
     g.mode = a.mode;
     g.ppw = a.reg_ppw;
     g.one_wave = a.one_wave;
-    return loop_kernel(simplex_kernel_key(shape_of(a.P), g), a.one_wave ? 1 : a.nslot, a.G, a.waves,
+    return loop_kernel(simplex_kernel_key(shape_of(a.P), g), a.one_wave ? a.n_chains : a.nslot, a.G, a.waves,
                        simplex_lds_bytes(a));
 }
 

@@ -863,6 +863,33 @@ hipError_t launch_uniform_fill(uint64_t seed, int64_t n, double* out, hipStream_
     return hipGetLastError();
 }
 
+// chain blockIdx.y: the stream of uniform_fill_kernel under that chain's own seed
+__global__ __launch_bounds__(256) void uniform_fill_chains_kernel(const uint64_t* __restrict__ seeds,
+                                                                  int64_t n, int64_t ld,
+                                                                  double* __restrict__ out_all) {
+    const uint64_t seed = seeds[blockIdx.y];
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    double* out = out_all + (int64_t)blockIdx.y * ld;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; 2 * i < n; i += stride) {
+        const u32x4 r = philox4x32_10(u32x4{(uint32_t)i, (uint32_t)((uint64_t)i >> 32),
+                                            STREAM_UNIFORM, 0u}, k0, k1);
+        out[2 * i] = u53_open0(r.x, r.y);
+        if (2 * i + 1 < n) out[2 * i + 1] = u53_open0(r.z, r.w);
+    }
+}
+
+hipError_t launch_uniform_fill_chains(const uint64_t* seeds_dev, int32_t n_chains, int64_t n, int64_t ld,
+                                      double* out, hipStream_t s) {
+    if (n <= 0 || n_chains <= 0) return hipSuccess;
+    if (ld < n || n_chains > 65535) return hipErrorInvalidValue;
+    int64_t blocks = ((n + 1) / 2 + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(uniform_fill_chains_kernel, dim3((unsigned)blocks, (unsigned)n_chains), dim3(256), 0,
+                       s, seeds_dev, n, ld, out);
+    return hipGetLastError();
+}
+
 __global__ __launch_bounds__(256) void philox_raw_kernel(uint32_t k0, uint32_t k1,
                                                          uint32_t stream, int64_t n4,
                                                          uint32_t* __restrict__ out) {

@@ -74,21 +74,56 @@ def USVt_hat_extraction(U, S, Vt, components_kept):
 
 
 def gibbs_sampler_simplex(y, X, Vt_hat, S_hat, iterations, prior_info, burn=10000,
-                          stepsize=0.001, *, seed=None, device=0):
+                          stepsize=0.001, *, seed=None, seeds=None, n_chains=1, device=0,
+                          return_stats=False):
     """Random-walk Metropolis on the weight simplex with a Gibbs sigma2 step
     (reference inference_utils.py:59-144).  Same arguments, result, ``ValueError``s
-    (:91-94) and acceptance-rate print (:143) as the reference."""
+    (:91-94) and acceptance-rate print (:143) as the reference.
+
+    Extensions (keyword-only, defaults preserve the reference behaviour): ``n_chains`` > 1 runs
+    that many independent chains side by side on the device and returns ``(n_chains, iterations,
+    k+1)``; ``seeds`` (length ``n_chains``) fixes the per-chain Philox keys (``seed`` is the
+    one-chain form; giving both is an error), by default they come from numpy's global stream.
+    Chain c is bit for bit the one-chain run with ``seed=seeds[c]``.  Every chain starts at
+    beta = 0 as the reference does (:82) and ``burn`` is per chain: each chain runs ``burn +
+    iterations`` steps and keeps the last ``iterations``.  With several chains the reference's
+    line gives the mean acceptance rate and a second line the smallest and largest of the chains.
+    """
     if burn < 0:
         raise ValueError("Burn-in iterations must be non-negative.")
     if stepsize <= 0:
         raise ValueError("Stepsize must be positive.")
+    n_chains = int(n_chains)
+    if n_chains < 1:
+        raise ValueError("n_chains must be >= 1")
+    if seed is not None and seeds is not None:
+        raise ValueError("give seed (one chain) or seeds (one per chain), not both")
+    if seeds is not None:
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint64).reshape(-1)
+        if seeds.shape[0] != n_chains:
+            raise ValueError(f"seeds has {seeds.shape[0]} entries for n_chains = {n_chains}")
+    elif seed is not None:
+        if n_chains != 1:
+            raise ValueError("seed names one chain; give seeds (one per chain) with n_chains > 1")
+        seeds = np.array([int(seed) & (2 ** 64 - 1)], dtype=np.uint64)
     nu0, s20 = prior_info
     ctx = _lib.default_context(device)
     with ctx.lock:
         ctx.set_problem(y, X)
-        if seed is None:
-            seed = int(_draw_seeds(1)[0])
-        samples, accepted = ctx.simplex_run(Vt_hat, S_hat, int(iterations), float(nu0), float(s20),
-                                            int(burn), float(stepsize), seed=seed)
-    print(f"Acceptance rate: {accepted / iterations * 100:.2f}%")
-    return samples
+        if seeds is None:
+            seeds = _draw_seeds(n_chains)
+        if n_chains == 1:
+            samples, accepted, _, stats = ctx.simplex_run(
+                Vt_hat, S_hat, int(iterations), float(nu0), float(s20), int(burn), float(stepsize),
+                seed=int(seeds[0]), return_stats=True)
+        else:
+            samples, acc, _, stats = ctx.simplex_run_chains(
+                Vt_hat, S_hat, n_chains, int(iterations), float(nu0), float(s20), int(burn),
+                float(stepsize), seeds=seeds, return_stats=True)
+    if n_chains == 1:
+        print(f"Acceptance rate: {accepted / iterations * 100:.2f}%")
+    else:
+        rates = acc / iterations * 100
+        print(f"Acceptance rate: {rates.mean():.2f}%")
+        print(f"Acceptance rate per chain: min {rates.min():.2f}%, max {rates.max():.2f}%")
+    return (samples, stats) if return_stats else samples

@@ -66,6 +66,8 @@ CASES = {   # name: (problem factory, dtype, chains, iterations)
     # chains = -3: the simplex-constrained sampler (reference inference_utils.py:59-144), us per step
     "simplex_c2": (lambda: synth(10000, 32), np.float64, -3, 20000),
     "simplex_small": (lambda: synth(629, 3), np.float64, -3, 50000),
+    # (one chain of the simplex sampler per build on its three bench shapes, the workgroup form with
+    # more than 64 models included: scripts/simplex_bench.py --ab)
 }
 
 
