@@ -376,6 +376,29 @@ int bmc_psis_loo_device(bmc_ctx* ctx, const void* dA, int64_t n_points, int32_t 
                         int64_t ldt, double* elpd_loo_out, double* pareto_k_out,
                         double* lppd_out);
 
+/* ---- PSIS-LOO predictive moments: what the fit would have predicted for y_i without it -------
+ * Arguments, weights, elpd_loo_out, pareto_k_out and lppd_out as bmc_psis_loo.  With W_s the
+ * truncated (smoothed or raw) weight of draw s for point i, every draw of a run of equal ll[i][s]
+ * given the mean W of the ranks the run occupies (ties are by value), w_s = W_s / sum_t W_t and
+ * r_s = y_i - a_i . beta_s (each output [n_points]; any may be NULL):
+ *   loo_mean_out  y_i - sum_s w_s r_s                  (the leave-one-out predictive mean)
+ *   loo_sd_out    sqrt(sum_s w_s (sigma_s^2 + r_s^2) - (sum_s w_s r_s)^2)
+ *   loo_pit_out   sum_s w_s Phi(r_s / sigma_s)         (Phi the standard normal distribution function)
+ *   ess_out       1 / sum_s w_s^2                      (between 1 and n_draws)
+ * One more pass over the matrix than bmc_psis_loo at most; deterministic; NaN as bmc_psis_loo.
+ * BMC_EINVAL as bmc_pointwise_loglik, and when n_draws exceeds 1 863 225 (M > 4095: the per-point
+ * sort keeps the draw index of every candidate in on-chip memory).  INTEGRATION.md section 10. */
+int bmc_psis_loo_predict(bmc_ctx* ctx, const double* A, int64_t n_points, int32_t k, int64_t lda,
+                         int layout, const double* y, const double* theta, int64_t n_draws,
+                         int64_t ldt, double* elpd_loo_out, double* pareto_k_out, double* lppd_out,
+                         double* loo_mean_out, double* loo_sd_out, double* loo_pit_out,
+                         double* ess_out);
+int bmc_psis_loo_predict_device(bmc_ctx* ctx, const void* dA, int64_t n_points, int32_t k,
+                                int64_t lda, int layout, const void* dy, const void* dtheta,
+                                int64_t n_draws, int64_t ldt, double* elpd_loo_out,
+                                double* pareto_k_out, double* lppd_out, double* loo_mean_out,
+                                double* loo_sd_out, double* loo_pit_out, double* ess_out);
+
 /* ---- on-device variates (exposed so the generator itself can be tested) ----
  * normals_out [count_normal] ~ N(0,1); gammas_out [count_gamma] ~ Gamma(shape,1). */
 int bmc_rng_fill(bmc_ctx* ctx, uint64_t seed, int64_t count_normal, double* normals_out,

@@ -8,7 +8,7 @@ from .data import Dataset
 from .diagnostics import chain_diagnostics
 from .inference_utils import gibbs_sampler, gibbs_sampler_simplex, USVt_hat_extraction
 from .sampling_utils import coverage, rndm_m_random_calculator
-from .scoring import pointwise_log_likelihood, psis_loo, waic
+from .scoring import pointwise_log_likelihood, psis_loo, psis_loo_predict, waic
 
 __all__ = [
     "Dataset",
@@ -22,4 +22,5 @@ __all__ = [
     "pointwise_log_likelihood",
     "waic",
     "psis_loo",
+    "psis_loo_predict",
 ]

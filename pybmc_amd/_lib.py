@@ -102,6 +102,10 @@ PROTOTYPES = {
                                C.c_int64, _D, _D, _D]),
     "bmc_psis_loo_device": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int, _P, _P,
                                       C.c_int64, C.c_int64, _D, _D, _D]),
+    "bmc_psis_loo_predict": (C.c_int, [_P, _D, C.c_int64, C.c_int32, C.c_int64, C.c_int, _D, _D,
+                                       C.c_int64, C.c_int64, _D, _D, _D, _D, _D, _D, _D]),
+    "bmc_psis_loo_predict_device": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int, _P,
+                                              _P, C.c_int64, C.c_int64, _D, _D, _D, _D, _D, _D, _D]),
     "bmc_rng_fill": (C.c_int, [_P, C.c_uint64, C.c_int64, _D, C.c_double, C.c_int64, _D]),
     "bmc_philox_raw": (C.c_int, [_P, C.c_uint64, C.c_uint32, C.c_int64, C.POINTER(C.c_uint32)]),
 }
@@ -583,6 +587,28 @@ class Context:
         caller orders its producers before the call."""
         return self._loo_call(self._lib.bmc_psis_loo_device, _P(dA), n, k, lda, layout, _P(dy),
                               _P(dtheta), n_draws, ldt)
+
+    # -- PSIS-LOO predictive moments ----------------------------------------------------------
+    LOO_PREDICT_KEYS = ("elpd_loo", "pareto_k", "lppd", "loo_mean", "loo_sd", "loo_pit", "ess")
+
+    def _loo_predict_call(self, fn, pA, n, k, lda, layout, py, pt, n_draws, ldt):
+        out = {key: np.empty(n) for key in self.LOO_PREDICT_KEYS}
+        self._check(fn(self._h, pA, int(n), int(k), int(lda), int(layout), py, pt, int(n_draws),
+                       int(ldt), *(_dptr(out[key]) for key in self.LOO_PREDICT_KEYS)))
+        return out
+
+    def psis_loo_predict(self, A, n, k, lda, layout, y, theta, n_draws, ldt):
+        """What psis_loo returns and the leave-one-out predictive loo_mean_i, loo_sd_i, loo_pit_i
+        and the PSIS effective sample size ess_i of HOST f64 arrays (bmc_psis_loo_predict);
+        arguments as pointwise_loglik.  Returns a dict of [n] arrays."""
+        return self._loo_predict_call(self._lib.bmc_psis_loo_predict, _dptr(A), n, k, lda, layout,
+                                      _dptr(y), _dptr(theta), n_draws, ldt)
+
+    def psis_loo_predict_device(self, dA, n, k, lda, layout, dy, dtheta, n_draws, ldt):
+        """The same on DEVICE memory (bmc_psis_loo_predict_device), read on the context's stream:
+        the caller orders its producers before the call."""
+        return self._loo_predict_call(self._lib.bmc_psis_loo_predict_device, _P(dA), n, k, lda,
+                                      layout, _P(dy), _P(dtheta), n_draws, ldt)
 
     # -- variates -----------------------------------------------------------------------
     def rng_fill(self, seed, n_normal=0, shape=1.0, n_gamma=0):

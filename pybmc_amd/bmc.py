@@ -227,6 +227,23 @@ class BayesianModelCombination:
         return psis_loo(self.U_hat, np.asarray(self.centered_experiment_train, dtype=np.float64),
                         self._chains(), burn=burn, device=self.device)
 
+    def loo_predict(self, burn=0):
+        """What the combination would have predicted for every training point had that point not
+        been in the fit (not in the reference; ``pybmc_amd.scoring.psis_loo_predict``), from the
+        data of ``loo()``.  Returns that function's dict (``loo_mean`` is the prediction of the
+        centred target) and, in the truth's units, ``predicted = loo_mean +`` the row mean of the
+        model predictions, ``truth`` and ``residual = truth - predicted``."""
+        if self.samples is None or self.U_hat is None:
+            raise ValueError("Must call `orthogonalize()` and `train()` before computing LOO.")
+        from .scoring import psis_loo_predict
+        y = np.asarray(self.centered_experiment_train, dtype=np.float64)
+        out = psis_loo_predict(self.U_hat, y, self._chains(), burn=burn, device=self.device)
+        mu = np.asarray(self._predictions_mean_train, dtype=np.float64)
+        out["predicted"] = out["loo_mean"] + mu
+        out["truth"] = y + mu
+        out["residual"] = y - out["loo_mean"]
+        return out
+
     def log_predictive_density(self, X, burn=0):
         """Log predictive density of held-out data (a validation or test split): ``X`` is a
         DataFrame with the model columns and the truth column.  The predictive mean of point p

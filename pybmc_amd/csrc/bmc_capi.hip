@@ -75,7 +75,8 @@ struct bmc_ctx {
     DevBuf dgIn, dgPart, dgMean, dgM2, dgCols, dgAcovPart, dgAcov;
     // pointwise log-likelihood (bmc_pointwise_loglik*)
     DevBuf scA, scY, scTheta, scAp, scYp, scCh, scPart, scOut;
-    // PSIS-LOO (bmc_psis_loo*): the select state and candidate slots, besides the score buffers
+    // PSIS-LOO (bmc_psis_loo*, bmc_psis_loo_predict*): the select state and candidate slots,
+    // besides the score buffers
     DevBuf looWork;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     double predict_ms[4] = {0, 0, 0, 0};   // last bmc_predict: h2d, gemm, order statistics, device
@@ -1359,6 +1360,31 @@ int loo_run(bmc_ctx* c, const double* dA, int64_t n, int32_t k, int64_t lda, int
     return BMC_OK;
 }
 
+// out[0 .. 6]: elpd_loo, pareto_k, lppd, loo_mean, loo_sd, loo_pit, ess (host, any may be NULL)
+int loo_predict_run(bmc_ctx* c, const double* dA, int64_t n, int32_t k, int64_t lda, int layout,
+                    const double* dy, const double* dtheta, int64_t S, int64_t ldt,
+                    double* const (&outs)[7]) {
+    const LooPredictPlan plan = plan_loo_predict(n, S, k, c->n_cu);
+    if (!plan.ok)
+        return fail(c, BMC_EINVAL, "n_draws is too large for the per-point sort of the predictive "
+                                   "moments (at most " + std::to_string(LOO_PREDICT_MAX_DRAWS) +
+                                       " draws; tail of " + std::to_string(plan.loo.tail) + ")");
+    LooArgs a;
+    int rc = score_args(c, plan.loo.score, dA, n, k, lda, layout, dy, dtheta, S, ldt, a.score);
+    if (rc) return rc;
+    if ((rc = ensure(c, c->looWork, loo_predict_buffers(plan, n).total()))) return rc;
+    a.work = c->looWork.p;
+    HIPCHK(c, launch_loo_predict(a, plan, c->stream));
+    const double* lo = loo_predict_out(a, plan);
+    const double* src[7] = {lo, lo + n, a.score.out, lo + 2 * n, lo + 3 * n, lo + 4 * n, lo + 5 * n};
+    for (int f = 0; f < 7; ++f)
+        if (outs[f])
+            HIPCHK(c, hipMemcpyAsync(outs[f], src[f], (size_t)n * 8, hipMemcpyDeviceToHost,
+                                     c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return BMC_OK;
+}
+
 // Host A, y and theta into the context's staging buffers (on its stream)
 int score_stage(bmc_ctx* c, const double* A, int64_t n_points, int32_t k, int64_t lda, int layout,
                 const double* y, const double* theta, int64_t n_draws, int64_t ldt) {
@@ -1421,6 +1447,35 @@ int bmc_psis_loo_device(bmc_ctx* c, const void* dA, int64_t n_points, int32_t k,
     HIPCHK(c, hipSetDevice(c->device));
     return loo_run(c, (const double*)dA, n_points, k, lda, layout, (const double*)dy,
                    (const double*)dtheta, n_draws, ldt, elpd_loo_out, pareto_k_out, lppd_out);
+}
+
+int bmc_psis_loo_predict(bmc_ctx* c, const double* A, int64_t n_points, int32_t k, int64_t lda,
+                         int layout, const double* y, const double* theta, int64_t n_draws,
+                         int64_t ldt, double* elpd_loo_out, double* pareto_k_out, double* lppd_out,
+                         double* loo_mean_out, double* loo_sd_out, double* loo_pit_out,
+                         double* ess_out) {
+    int rc = check_score_args(c, A, n_points, k, lda, layout, y, theta, n_draws, ldt);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = score_stage(c, A, n_points, k, lda, layout, y, theta, n_draws, ldt))) return rc;
+    double* const outs[7] = {elpd_loo_out, pareto_k_out, lppd_out, loo_mean_out,
+                             loo_sd_out,   loo_pit_out,  ess_out};
+    return loo_predict_run(c, (const double*)c->scA.p, n_points, k, lda, layout,
+                           (const double*)c->scY.p, (const double*)c->scTheta.p, n_draws, ldt, outs);
+}
+
+int bmc_psis_loo_predict_device(bmc_ctx* c, const void* dA, int64_t n_points, int32_t k, int64_t lda,
+                                int layout, const void* dy, const void* dtheta, int64_t n_draws,
+                                int64_t ldt, double* elpd_loo_out, double* pareto_k_out,
+                                double* lppd_out, double* loo_mean_out, double* loo_sd_out,
+                                double* loo_pit_out, double* ess_out) {
+    int rc = check_score_args(c, dA, n_points, k, lda, layout, dy, dtheta, n_draws, ldt);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    double* const outs[7] = {elpd_loo_out, pareto_k_out, lppd_out, loo_mean_out,
+                             loo_sd_out,   loo_pit_out,  ess_out};
+    return loo_predict_run(c, (const double*)dA, n_points, k, lda, layout, (const double*)dy,
+                           (const double*)dtheta, n_draws, ldt, outs);
 }
 
 int bmc_rng_fill(bmc_ctx* c, uint64_t seed, int64_t count_normal, double* normals_out, double shape,

@@ -296,4 +296,10 @@ struct LooArgs {
 double* loo_out(const LooArgs& a, const LooPlan& p);
 hipError_t launch_loo(const LooArgs& a, const LooPlan& p, hipStream_t s);
 
+// The leave-one-out predictive moments of every point with the same weights.
+// work: loo_predict_buffers(plan, n).total() bytes; at loo_predict_out(): elpd_loo_i, pareto_k,
+// loo_mean, loo_sd, loo_pit, ess, [n] each.
+double* loo_predict_out(const LooArgs& a, const LooPredictPlan& p);
+hipError_t launch_loo_predict(const LooArgs& a, const LooPredictPlan& p, hipStream_t s);
+
 }  // namespace bmc

@@ -6,7 +6,8 @@
 // table entry each.  tests/launch_plan_check.cpp runs the planner and the selection on the CPU.
 // Also here: plan_score, the draw-split plan of the pointwise log-likelihood kernels
 // (kernels_waic.hip; tests/score_plan_check.cpp), and plan_loo, the pass and candidate plan of
-// the PSIS-LOO kernels (kernels_loo.hip; tests/loo_plan_check.cpp).
+// the PSIS-LOO kernels (kernels_loo.hip; tests/loo_plan_check.cpp), with plan_loo_predict for the
+// leave-one-out predictive moments (tests/loo_predict_plan_check.cpp).
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -777,6 +778,64 @@ inline LooBuffers loo_buffers(const LooPlan& p, int64_t n_points) {
     b.cand = up(n_pad * (size_t)p.cap * 8);
     b.body = up(sp * n_pad * 8);
     b.out = up((size_t)n_points * 2 * 8);
+    return b;
+}
+
+// ---- PSIS-LOO predictive moments (kernels_loo.hip) ------------------------------
+// The passes of plan_loo with the PREDICT variants of append and fit, and between them one more
+// pass over the matrix for the points whose bucket is one repeated value (only when the select
+// runs; a workgroup without such a point returns at once).  The fit sorts (value, draw) pairs and
+// keeps every sorted candidate next to the tail's weights: LOO_PREDICT_SLOT_LDS bytes of LDS per
+// candidate slot (8 value, 4 tail, 4 draw index) where plan_loo needs 8, so of gfx950's 160 KiB
+// (less the fit's LOO_FIT_STATIC_LDS of reduction and grid arrays) the largest cap is 8192:
+// M = ceil(3 sqrt(S)) <= 4095, S <= 4095^2 / 9 = LOO_PREDICT_MAX_DRAWS.
+constexpr int64_t LOO_PREDICT_SLOT_LDS = 16;
+constexpr int64_t LOO_PREDICT_MAX_CAP = 8192;
+constexpr int64_t LOO_PREDICT_MAX_DRAWS = 1863225;
+constexpr int64_t LOO_FIT_STATIC_LDS = 6144;       // (an upper bound: 5 KiB of arrays and a few scalars)
+constexpr int64_t LOO_LDS_BYTES = 160 * 1024;
+constexpr int LOO_PREDICT_OUTS = 6;     // elpd_loo_i, pareto_k, loo_mean, loo_sd, loo_pit, ess
+constexpr int LOO_PREDICT_SUMS = 4;     // per point besides sum w: w r, w (sigma^2 + r^2), w Phi, w^2
+constexpr int LOO_BUCKET_SUMS = 3;      // of a one-value bucket: r, sigma^2 + r^2, Phi
+
+struct LooPredictPlan {
+    LooPlan loo;             // the passes both calls share
+    int64_t record_bytes;    // global memory per candidate: the value and its draw index
+    int64_t fit_lds;         // dynamic LDS of the fit: cap * LOO_PREDICT_SLOT_LDS
+    int32_t bucket_pass;     // 1: the one-value-bucket pass is launched
+    int32_t matrix_passes;   // all launches that walk the matrix
+    bool ok;                 // loo.cap <= LOO_PREDICT_MAX_CAP (LOO_PREDICT_MAX_DRAWS draws)
+};
+
+inline LooPredictPlan plan_loo_predict(int64_t n_points, int64_t n_draws, int32_t k, int n_cu) {
+    LooPredictPlan p;
+    p.loo = plan_loo(n_points, n_draws, k, n_cu);
+    p.record_bytes = 8 + 4;
+    p.fit_lds = p.loo.cap * LOO_PREDICT_SLOT_LDS;
+    p.bucket_pass = p.loo.select_passes > 0 ? 1 : 0;
+    p.matrix_passes = p.loo.matrix_passes + p.bucket_pass;
+    p.ok = p.loo.cap <= LOO_PREDICT_MAX_CAP;
+    return p;
+}
+
+// Device work space of launch_loo_predict: loo_buffers, then
+struct LooPredictBuffers {
+    LooBuffers loo;
+    size_t candidx;   // [n_pad][cap] u32: the draw of every candidate
+    size_t pay;       // [splits][n_pad][4] f64: the payload sums above the bucket
+    size_t bucket;    // [splits][n_pad][3] f64: the payload sums of a one-value bucket
+    size_t out;       // [6][n_points] f64
+    size_t total() const { return loo.total() + candidx + pay + bucket + out; }
+};
+inline LooPredictBuffers loo_predict_buffers(const LooPredictPlan& p, int64_t n_points) {
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t n_pad = (size_t)p.loo.score.point_tiles * SCORE_TILE, sp = (size_t)p.loo.score.splits;
+    LooPredictBuffers b;
+    b.loo = loo_buffers(p.loo, n_points);
+    b.candidx = up(n_pad * (size_t)p.loo.cap * 4);
+    b.pay = up(sp * n_pad * LOO_PREDICT_SUMS * 8);
+    b.bucket = up(sp * n_pad * LOO_BUCKET_SUMS * 8);
+    b.out = up((size_t)n_points * LOO_PREDICT_OUTS * 8);
     return b;
 }
 

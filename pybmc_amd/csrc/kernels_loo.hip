@@ -20,6 +20,12 @@
 //   loo_fit        one workgroup per point: bitonic sort of the candidates in LDS, tail and
 //                  cutoff, the Pareto fit, the smoothed tail, elpd_loo_i
 //
+// The leave-one-out predictive moments (launch_loo_predict) run the same passes with
+// the PREDICT variants of the last two: the append also records each candidate's draw index and
+// sums w r, w (sigma^2 + r^2), w Phi(r / sigma) and w^2 of everything above the bucket, one more
+// pass (loo_bucket) sums the payload of a bucket that is one repeated value, and the fit sorts
+// (value, draw) pairs, shares the weights of equal values and adds the payload up.
+//
 // Two calls return the same bits: the only atomics are integer counts and slot numbers of values
 // that are sorted before use.  A point with a non-finite ll (a NaN or infinity in a_i, y_i or any
 // draw, a sigma_s <= 0) is flagged by loo_range and gets NaN; its keys are never used as an index
@@ -255,18 +261,30 @@ __global__ __launch_bounds__(256) void loo_scan_kernel(int64_t n_pad, int32_t M,
     meta[i] = m;
 }
 
+// sigma_s^2 and Phi(r / sigma_s) of a draw with h_s = 1 / (2 sigma_s^2): r / (sigma sqrt 2) = r sqrt(h)
+__device__ __forceinline__ double draw_phi(double res, double sqrt_h) {
+    return 0.5 * erfc(-(res * sqrt_h));
+}
+
+// PREDICT: besides sum w (body), pay[split][point][4] = sum w r, sum w (sigma^2 + r^2),
+// sum w Phi(r / sigma), sum w^2 over the keys above the bucket, each in the order of `body`; and
+// the draw index of every candidate next to its value.
+template <bool PREDICT>
 __global__ __launch_bounds__(256) void loo_append_kernel(PassArgs a,
                                                          const uint64_t* __restrict__ prefix,
                                                          const uint64_t* __restrict__ kmin,
                                                          const uint4* __restrict__ meta,
                                                          uint32_t cap, uint32_t* __restrict__ count,
                                                          double* __restrict__ cand,
-                                                         double* __restrict__ body) {
+                                                         double* __restrict__ body,
+                                                         uint32_t* __restrict__ candidx,
+                                                         double* __restrict__ pay) {
     __shared__ double As[SC_LDS_DOUBLES];
     __shared__ double Bs[SC_LDS_DOUBLES];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, cl = lane & 15, kq = lane >> 4;
     const TilePos pos(a.point_tiles, a.tiles_per_split, a.draw_tiles);
     double yv[4], llmin[4], sum[4];
+    double psum[PREDICT ? 4 : 1][4];
     uint64_t pre[4];
     uint32_t fixed[4], flags[4];
     int64_t pi[4];
@@ -280,10 +298,20 @@ __global__ __launch_bounds__(256) void loo_append_kernel(PassArgs a,
         fixed[r] = m.x;
         flags[r] = m.w;
         sum[r] = 0.0;
+        if constexpr (PREDICT)
+#pragma unroll
+            for (int f = 0; f < 4; ++f) psum[f][r] = 0.0;
     }
     score_tile_loop(a.Ap, a.theta, a.S, a.ldt, a.k, a.k_pad, pos.p0, pos.dt0, pos.dt1, As, Bs,
                     [&](int64_t s0, const f64x4(&acc)[4]) {
         const TileDraws d(a.ch, a.S, s0, cl);
+        double s2[4], sq[4];
+        if constexpr (PREDICT)
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                s2[t] = 1.0 / (2.0 * d.hs[t]);
+                sq[t] = sqrt(d.hs[t]);
+            }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             if (flags[r] & LF_BAD) continue;
@@ -293,10 +321,22 @@ __global__ __launch_bounds__(256) void loo_append_kernel(PassArgs a,
                     const double x = d.ll(yv[r], acc[t][r], t);
                     const uint64_t top = key_top(ord_key(x), fixed[r]);
                     if ((flags[r] & LF_NOTAIL) || top > pre[r]) {
-                        sum[r] += exp(llmin[r] - x);
+                        const double w = exp(llmin[r] - x);
+                        sum[r] += w;
+                        if constexpr (PREDICT) {
+                            const double res = yv[r] - acc[t][r];
+                            psum[0][r] += w * res;
+                            psum[1][r] += w * (s2[t] + res * res);
+                            psum[2][r] += w * draw_phi(res, sq[t]);
+                            psum[3][r] += w * w;
+                        }
                     } else if (top < pre[r] || (flags[r] & LF_APPEND_EQ)) {
                         const uint32_t slot = atomicAdd(count + pi[r], 1u);
-                        if (slot < cap) cand[pi[r] * (int64_t)cap + slot] = x;
+                        if (slot < cap) {
+                            cand[pi[r] * (int64_t)cap + slot] = x;
+                            if constexpr (PREDICT)
+                                candidx[pi[r] * (int64_t)cap + slot] = (uint32_t)(s0 + cl + 16 * t);
+                        }
                     }
                 }
         }
@@ -311,7 +351,76 @@ __global__ __launch_bounds__(256) void loo_append_kernel(PassArgs a,
             v = (cl & bit) ? o + v : v + o;
         }
         if (cl == 0) body[(int64_t)pos.split * a.n_pad + pi[r]] = v;
+        if constexpr (PREDICT)
+#pragma unroll
+            for (int f = 0; f < 4; ++f) {
+                double u = psum[f][r];
+#pragma unroll
+                for (int bit = 1; bit < 16; bit <<= 1) {
+                    const double o = __shfl_xor(u, bit);
+                    u = (cl & bit) ? o + u : u + o;
+                }
+                if (cl == 0) pay[((int64_t)pos.split * a.n_pad + pi[r]) * 4 + f] = u;
+            }
     }
+}
+
+// A point whose bucket is ONE value, repeated (settled with all 64 bits fixed): its draws are not
+// candidates, and they share one weight.  bucket[split][point][3] = sum r, sum (sigma^2 + r^2),
+// sum Phi(r / sigma) over them, in the order of `body`.  A workgroup without such a point (every
+// one, for ordinary input) returns at once.
+__global__ __launch_bounds__(256) void loo_bucket_kernel(PassArgs a,
+                                                         const uint64_t* __restrict__ prefix,
+                                                         const uint4* __restrict__ meta,
+                                                         double* __restrict__ bucket) {
+    __shared__ double As[SC_LDS_DOUBLES];
+    __shared__ double Bs[SC_LDS_DOUBLES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, cl = lane & 15, kq = lane >> 4;
+    const TilePos pos(a.point_tiles, a.tiles_per_split, a.draw_tiles);
+    double yv[4], sum[3][4];
+    uint64_t pre[4];
+    bool live[4];
+    int64_t pi[4];
+    int any = 0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        pi[r] = pos.p0 + 16 * wave + kq + 4 * r;
+        yv[r] = a.yp[pi[r]];
+        pre[r] = prefix[pi[r]];
+        live[r] = (meta[pi[r]].w & (LF_DONE | LF_APPEND_EQ | LF_NOTAIL | LF_BAD)) == LF_DONE;
+        any |= live[r];
+#pragma unroll
+        for (int f = 0; f < 3; ++f) sum[f][r] = 0.0;
+    }
+    if (!__syncthreads_or(any)) return;
+    score_tile_loop(a.Ap, a.theta, a.S, a.ldt, a.k, a.k_pad, pos.p0, pos.dt0, pos.dt1, As, Bs,
+                    [&](int64_t s0, const f64x4(&acc)[4]) {
+        const TileDraws d(a.ch, a.S, s0, cl);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            if (!live[r]) continue;
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+                if (d.ok[t] && ord_key(d.ll(yv[r], acc[t][r], t)) == pre[r]) {
+                    const double res = yv[r] - acc[t][r];
+                    sum[0][r] += res;
+                    sum[1][r] += 1.0 / (2.0 * d.hs[t]) + res * res;
+                    sum[2][r] += draw_phi(res, sqrt(d.hs[t]));
+                }
+        }
+    });
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int f = 0; f < 3; ++f) {
+            double u = sum[f][r];
+#pragma unroll
+            for (int bit = 1; bit < 16; bit <<= 1) {
+                const double o = __shfl_xor(u, bit);
+                u = (cl & bit) ? o + u : u + o;
+            }
+            if (cl == 0 && live[r]) bucket[((int64_t)pos.split * a.n_pad + pi[r]) * 3 + f] = u;
+        }
 }
 
 // sums and maxima over the workgroup in one fixed order: thread-strided partials, then a tree
@@ -340,8 +449,33 @@ __device__ __forceinline__ double block_max(double v, double* red) {
     return r;
 }
 
+// What the PREDICT fit reads besides the select state: the padded operands and per-draw constants
+// of the score kernels (a candidate's r and sigma are recomputed from its draw index), the
+// candidates' draw indices and the payload sums of loo_append_kernel<true> and loo_bucket_kernel.
+struct FitPayload {
+    const double *Ap, *yp, *theta, *ch, *pay, *bucket;
+    const uint32_t* candidx;
+    int64_t ldt;
+    int32_t k, k_pad;
+};
+
+// out[2 .. 5][i] from the point's sums over all draws: W = sum w, then sum w r, sum w (sigma^2 + r^2),
+// sum w Phi, sum w^2
+__device__ __forceinline__ void predict_store(double* __restrict__ out, int64_t n, int64_t i,
+                                              double y, double W, const double (&t)[4]) {
+    const double mr = t[0] / W;
+    out[2 * n + i] = y - mr;
+    out[3 * n + i] = sqrt(t[1] / W - mr * mr);
+    out[4 * n + i] = t[2] / W;
+    out[5 * n + i] = W * (W / t[3]);
+}
+
 // One workgroup per point.  buf: `cap` doubles of LDS, cap >= 2 (M + 1): the sorted candidates in
 // buf[0 .. M] and, behind them, M doubles for the tail's x_j and then its smoothed lw.
+// PREDICT: 16 bytes of LDS per slot: every sorted candidate stays in buf[0 .. cap), the tail's M
+// doubles are buf[cap .. cap + cap / 2), then the candidates' draw indices, sorted along as the
+// second key; out is [6][n]: elpd_loo_i, pareto_k, loo_mean, loo_sd, loo_pit, ess.
+template <bool PREDICT>
 __global__ __launch_bounds__(256) void loo_fit_kernel(const uint64_t* __restrict__ prefix,
                                                       const uint64_t* __restrict__ kmin,
                                                       const uint4* __restrict__ meta,
@@ -350,7 +484,7 @@ __global__ __launch_bounds__(256) void loo_fit_kernel(const uint64_t* __restrict
                                                       const double* __restrict__ body, int64_t n,
                                                       int64_t n_pad, int64_t splits, int64_t S,
                                                       int32_t M, int32_t cap,
-                                                      double* __restrict__ out) {
+                                                      double* __restrict__ out, FitPayload pa) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     double* buf = (double*)smem_raw;
     __shared__ double red[256];
@@ -359,21 +493,25 @@ __global__ __launch_bounds__(256) void loo_fit_kernel(const uint64_t* __restrict
     const int64_t i = blockIdx.x;
     const uint4 m = meta[i];
     const double inf = __builtin_inf();
+    constexpr int N_OUT = PREDICT ? 6 : 2;
     if (m.w & LF_BAD) {
-        if (tid == 0) {
-            out[i] = __builtin_nan("");
-            out[n + i] = __builtin_nan("");
-        }
+        if (tid == 0)
+            for (int f = 0; f < N_OUT; ++f) out[f * n + i] = __builtin_nan("");
         return;
     }
     const double llmin = key_value(kmin[i]);   // -c_i
     double B = 0.0;
     for (int64_t sp = 0; sp < splits; ++sp) B += body[sp * n_pad + i];
+    double tot[4] = {0.0, 0.0, 0.0, 0.0};   // PREDICT: the payload sums over all draws
+    if constexpr (PREDICT)
+        for (int64_t sp = 0; sp < splits; ++sp)
+            for (int f = 0; f < 4; ++f) tot[f] += pa.pay[(sp * n_pad + i) * 4 + f];
     if (m.w & LF_NOTAIL) {
         // raw importance sampling: every ll + lw is -c
         if (tid == 0) {
             out[i] = (log((double)S) + llmin) - log(B);
             out[n + i] = inf;
+            if constexpr (PREDICT) predict_store(out, n, i, pa.yp[i], B, tot);
         }
         return;
     }
@@ -383,15 +521,17 @@ __global__ __launch_bounds__(256) void loo_fit_kernel(const uint64_t* __restrict
     const int c_n = (int)(cnt_raw < (uint32_t)cap ? cnt_raw : (uint32_t)cap);
     if ((m.w & LF_APPEND_EQ) ? c_n <= M : c_n != (int)m.y) {
         // the slots do not hold what the select counted: cannot happen; a value, not a wild read
-        if (tid == 0) {
-            out[i] = __builtin_nan("");
-            out[n + i] = __builtin_nan("");
-        }
+        if (tid == 0)
+            for (int f = 0; f < N_OUT; ++f) out[f * n + i] = __builtin_nan("");
         return;
     }
     int P2 = 2;
     while (P2 < c_n) P2 <<= 1;
-    for (int j = tid; j < P2; j += 256) buf[j] = j < c_n ? cand[i * (int64_t)cap + j] : inf;
+    uint32_t* ids = (uint32_t*)(buf + cap + cap / 2);   // (PREDICT)
+    for (int j = tid; j < P2; j += 256) {
+        buf[j] = j < c_n ? cand[i * (int64_t)cap + j] : inf;
+        if constexpr (PREDICT) ids[j] = j < c_n ? pa.candidx[i * (int64_t)cap + j] : ~0u;
+    }
     __syncthreads();
     for (int ks = 2; ks <= P2; ks <<= 1)
         for (int j = ks >> 1; j > 0; j >>= 1) {
@@ -399,7 +539,17 @@ __global__ __launch_bounds__(256) void loo_fit_kernel(const uint64_t* __restrict
                 const int o = e ^ j;
                 if (o > e) {
                     const double x = buf[e], y = buf[o];
-                    if ((e & ks) == 0 ? x > y : x < y) {
+                    if constexpr (PREDICT) {
+                        // by value, then by draw: one layout whatever the slot order was
+                        const uint32_t ix = ids[e], iy = ids[o];
+                        const bool gt = x > y || (x == y && ix > iy), lt = x < y || (x == y && ix < iy);
+                        if ((e & ks) == 0 ? gt : lt) {
+                            buf[e] = y;
+                            buf[o] = x;
+                            ids[e] = iy;
+                            ids[o] = ix;
+                        }
+                    } else if ((e & ks) == 0 ? x > y : x < y) {
                         buf[e] = y;
                         buf[o] = x;
                     }
@@ -428,7 +578,7 @@ __global__ __launch_bounds__(256) void loo_fit_kernel(const uint64_t* __restrict
     const double ecut = exp(cut);
     bool smooth = buf[0] != buf[M - 1];
     double khat = inf, sigma = 0.0;
-    double* xs = buf + M + 1;
+    double* xs = PREDICT ? buf + cap : buf + M + 1;
     __syncthreads();   // (buf[M + 1 ..] has been read above)
 
     // ---- generalised Pareto fit (Zhang & Stephens 2009, as loo::gpdfit) -----------------------
@@ -494,7 +644,8 @@ __global__ __launch_bounds__(256) void loo_fit_kernel(const uint64_t* __restrict
         dpart += exp(lw);
         mpart = fmax(mpart, llj + lw);
     }
-    const double den = log(Btot + block_sum(dpart, red));
+    const double wsum = Btot + block_sum(dpart, red);
+    const double den = log(wsum);
     const double mx = fmax(block_max(mpart, red), llmin);
     double npart = 0.0;
     for (int j = tid; j < M; j += 256) npart += exp((buf[M - 1 - j] + xs[j]) - mx);
@@ -503,6 +654,81 @@ __global__ __launch_bounds__(256) void loo_fit_kernel(const uint64_t* __restrict
         out[i] = num - den;
         out[n + i] = khat;
     }
+
+    if constexpr (PREDICT) {
+        // ---- ties share: every draw of a run of equal ll gets the mean W of the run's ranks ------
+        // xs[j] becomes W of rank M - 1 - j; the one run that may cross rank M (its other ranks
+        // carry the raw weight) is remembered: ranks M .. cross_end - 1 have weight cross_w.  A
+        // one-value bucket is such a run, of ranks m.y .. m.y + m.z - 1 (buf[m.y .. M] stand for it).
+        // A run is found with == on doubles while the select works on keys, for which -0 < +0: a
+        // point whose ll take BOTH zeros (ll exactly 0 under two draws, one of each sign) could have
+        // that run cut at the bucket's edge and its two parts not share.  The fma of TileDraws::ll
+        // gives -0 only for c_s = -0 and a zero residual, so this is not reachable in practice.
+        // One thread sums and rewrites its run in rank order (at most M ranks of it are in the
+        // tail): the time of this step grows with the longest run of ties in a point's tail.
+        __shared__ long long cross_end;
+        __shared__ double cross_w;
+        const bool eq = (m.w & LF_APPEND_EQ) != 0;
+        const int n_valid = eq ? c_n : M + 1;
+        const long long n_ranks = eq ? (long long)c_n : (long long)m.y + (long long)m.z;
+        if (tid == 0) {
+            cross_end = M;
+            cross_w = 0.0;
+        }
+        for (int j = tid; j < M; j += 256) xs[j] = exp(xs[j]);
+        __syncthreads();
+        for (int q = tid; q < M; q += 256) {
+            const double v = buf[q];
+            if (q > 0 && buf[q - 1] == v) continue;   // (the run's first rank does the work)
+            int lo = q + 1, hi = n_valid;
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (buf[mid] == v) lo = mid + 1;
+                else hi = mid;
+            }
+            const long long end = (!eq && lo == n_valid) ? n_ranks : (long long)lo;
+            if (end - q < 2) continue;
+            const int t_end = end < (long long)M ? (int)end : M;
+            double sw = 0.0;
+            for (int p = q; p < t_end; ++p) sw += xs[M - 1 - p];
+            if (end > (long long)M) sw += (double)(end - M) * exp(llmin - v);
+            const double wbar = sw / (double)(end - q);
+            for (int p = q; p < t_end; ++p) xs[M - 1 - p] = wbar;
+            if (end > (long long)M) {
+                cross_end = end;
+                cross_w = wbar;
+            }
+        }
+        __syncthreads();
+
+        // ---- the candidates' payload, then the bucket's and the body's ------------------------------
+        const double* arow = pa.Ap + i * (int64_t)pa.k_pad;
+        const double yi = pa.yp[i];
+        double part[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int q = tid; q < c_n; q += 256) {
+            const double w = q < M ? xs[M - 1 - q]
+                                   : ((long long)q < cross_end ? cross_w : exp(llmin - buf[q]));
+            const int64_t sd = (int64_t)ids[q] < S ? (int64_t)ids[q] : S - 1;
+            const double* th = pa.theta + sd * pa.ldt;
+            double dot = 0.0;
+            for (int j = 0; j < pa.k; ++j) dot = fma(arow[j], th[j], dot);
+            const double res = yi - dot, h = pa.ch[S + sd];
+            part[0] += w * res;
+            part[1] += w * (1.0 / (2.0 * h) + res * res);
+            part[2] += w * draw_phi(res, sqrt(h));
+            part[3] += w * w;
+        }
+        for (int f = 0; f < 4; ++f) tot[f] += block_sum(part[f], red);
+        if (!eq) {
+            const double wb = (int)m.y < M ? cross_w : exp(llmin - key_value(prefix[i]));
+            double bs[3] = {0.0, 0.0, 0.0};
+            for (int64_t sp = 0; sp < splits; ++sp)
+                for (int f = 0; f < 3; ++f) bs[f] += pa.bucket[(sp * n_pad + i) * 3 + f];
+            for (int f = 0; f < 3; ++f) tot[f] += wb * bs[f];
+            tot[3] += (double)m.z * (wb * wb);
+        }
+        if (tid == 0) predict_store(out, n, i, yi, wsum, tot);
+    }
 }
 
 struct Work {
@@ -510,6 +736,7 @@ struct Work {
     uint4* meta;
     uint32_t *hist, *count;
     double *cand, *body, *out;
+    char* end;
     Work(void* base, const LooBuffers& b) {
         char* p = (char*)base;
         auto take = [&](size_t bytes) {
@@ -526,6 +753,20 @@ struct Work {
         cand = (double*)take(b.cand);
         body = (double*)take(b.body);
         out = (double*)take(b.out);
+        end = p;
+    }
+};
+
+// The PREDICT passes' own buffers, behind the ones every call has
+struct PredictWork {
+    uint32_t* candidx;
+    double *pay, *bucket, *out;
+    PredictWork(const Work& w, const LooPredictBuffers& b) {
+        char* p = w.end;
+        candidx = (uint32_t*)p;
+        pay = (double*)(p += b.candidx);
+        bucket = (double*)(p += b.pay);
+        out = (double*)(p += b.bucket);
     }
 };
 
@@ -535,12 +776,22 @@ double* loo_out(const LooArgs& a, const LooPlan& p) {
     return Work(a.work, loo_buffers(p, a.score.n)).out;
 }
 
-hipError_t launch_loo(const LooArgs& a, const LooPlan& p, hipStream_t s) {
+double* loo_predict_out(const LooArgs& a, const LooPredictPlan& p) {
+    const LooPredictBuffers b = loo_predict_buffers(p, a.score.n);
+    return PredictWork(Work(a.work, b.loo), b).out;
+}
+
+namespace {
+
+// Both calls: the score kernels, then range, init, select and scan; then append and fit, or their
+// PREDICT variants with the bucket pass between them (pp != nullptr).
+hipError_t launch_loo_passes(const LooArgs& a, const LooPlan& p, const LooPredictPlan* pp,
+                             hipStream_t s) {
     const ScoreArgs& sa = a.score;
     const ScorePlan& sp = p.score;
     if (!p.ok || !a.work || sa.S - p.tail < 1 || p.cap < 2 * (p.tail + 1) || p.cap > LOO_MAX_CAP ||
-        (p.cap & (p.cap - 1)) != 0 || p.tail != loo_tail(sa.S))
-        return hipErrorInvalidValue;
+        (p.cap & (p.cap - 1)) != 0 || p.tail != loo_tail(sa.S) || sa.n > 0x7fffffffll)
+        return hipErrorInvalidValue;   // (the fit's grid is one workgroup per point)
     hipError_t e = launch_score(sa, sp, s);   // (checks the shapes and the split plan)
     if (e != hipSuccess) return e;
     const LooBuffers lb = loo_buffers(p, sa.n);
@@ -579,19 +830,60 @@ hipError_t launch_loo(const LooArgs& a, const LooPlan& p, hipStream_t s) {
                                w.prefix, w.meta, w.hist);
         }
     }
-    hipLaunchKernelGGL(loo_append_kernel, dim3(groups), dim3(256), 0, s, pa,
+    if (pp) {
+        const PredictWork pw(w, loo_predict_buffers(*pp, sa.n));
+        hipLaunchKernelGGL(loo_append_kernel<true>, dim3(groups), dim3(256), 0, s, pa,
+                           (const uint64_t*)w.prefix, (const uint64_t*)w.kmin,
+                           (const uint4*)w.meta, (uint32_t)cap, w.count, w.cand, w.body, pw.candidx,
+                           pw.pay);
+        if (pp->bucket_pass)
+            hipLaunchKernelGGL(loo_bucket_kernel, dim3(groups), dim3(256), 0, s, pa,
+                               (const uint64_t*)w.prefix, (const uint4*)w.meta, pw.bucket);
+        FitPayload fp;
+        fp.Ap = sa.Ap;
+        fp.yp = sa.yp;
+        fp.theta = sa.theta;
+        fp.ch = sa.ch;
+        fp.pay = pw.pay;
+        fp.bucket = pw.bucket;
+        fp.candidx = pw.candidx;
+        fp.ldt = sa.ldt;
+        fp.k = sa.k;
+        fp.k_pad = sp.k_pad;
+        e = hipFuncSetAttribute((const void*)loo_fit_kernel<true>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)pp->fit_lds);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(loo_fit_kernel<true>, dim3((unsigned)sa.n), dim3(256),
+                           (size_t)pp->fit_lds, s, (const uint64_t*)w.prefix,
+                           (const uint64_t*)w.kmin, (const uint4*)w.meta, (const uint32_t*)w.count,
+                           (const double*)w.cand, (const double*)w.body, sa.n, n_pad, sp.splits, sa.S,
+                           M, cap, pw.out, fp);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL(loo_append_kernel<false>, dim3(groups), dim3(256), 0, s, pa,
                        (const uint64_t*)w.prefix, (const uint64_t*)w.kmin, (const uint4*)w.meta,
-                       (uint32_t)cap, w.count, w.cand, w.body);
+                       (uint32_t)cap, w.count, w.cand, w.body, (uint32_t*)nullptr, (double*)nullptr);
     const size_t fit_lds = (size_t)cap * 8;
-    e = hipFuncSetAttribute((const void*)loo_fit_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)fit_lds);
+    e = hipFuncSetAttribute((const void*)loo_fit_kernel<false>,
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)fit_lds);
     if (e != hipSuccess) return e;
-    if (sa.n > 0x7fffffffll) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(loo_fit_kernel, dim3((unsigned)sa.n), dim3(256), fit_lds, s,
+    hipLaunchKernelGGL(loo_fit_kernel<false>, dim3((unsigned)sa.n), dim3(256), fit_lds, s,
                        (const uint64_t*)w.prefix, (const uint64_t*)w.kmin, (const uint4*)w.meta,
                        (const uint32_t*)w.count, (const double*)w.cand, (const double*)w.body, sa.n,
-                       n_pad, sp.splits, sa.S, M, cap, w.out);
+                       n_pad, sp.splits, sa.S, M, cap, w.out, FitPayload{});
     return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_loo(const LooArgs& a, const LooPlan& p, hipStream_t s) {
+    return launch_loo_passes(a, p, nullptr, s);
+}
+
+hipError_t launch_loo_predict(const LooArgs& a, const LooPredictPlan& p, hipStream_t s) {
+    if (!p.ok || p.loo.cap > LOO_PREDICT_MAX_CAP || p.fit_lds != p.loo.cap * LOO_PREDICT_SLOT_LDS)
+        return hipErrorInvalidValue;
+    return launch_loo_passes(a, p.loo, &p, s);
 }
 
 }  // namespace bmc

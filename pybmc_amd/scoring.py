@@ -1,4 +1,5 @@
-"""Scoring a sampled fit on the GPU: pointwise log predictive density, WAIC and PSIS-LOO.
+"""Scoring a sampled fit on the GPU: pointwise log predictive density, WAIC, PSIS-LOO and the
+leave-one-out predictive mean, sd and PIT of every training point.
 
 The reference package has no numeric score of a fit; this is a capability of this build.  The
 model is the one the samplers draw from, ``y_i ~ N(a_i . beta, sigma^2)``.  For design rows ``A``
@@ -41,6 +42,25 @@ over the S pooled kept draws, with r_eff = 1:
 and on the host ``elpd_loo = sum_i``, ``p_loo = sum_i``, ``looic = -2 elpd_loo``,
 ``se = sqrt(n var_i(elpd_loo_i, ddof=1))``, ``n_high_k = #{i : pareto_k_i > 0.7}``,
 ``k_threshold = min(1 - 1 / log10(S), 0.7)`` and ``n_above_threshold``.
+
+The leave-one-out predictive distribution (``psis_loo_predict``).  Steps 1-5 give every draw an
+unnormalised weight ``W_s = exp(lw_s)`` (smoothed for the M tail ranks, raw elsewhere, truncated at
+0; raw throughout where nothing is smoothed).  Ties share: draws of point i with equal ``ll[i, s]``
+each get the arithmetic mean of the ``W`` of the ranks their run occupies (a run may straddle the
+cutoff), so ``sum W`` and ``sum W exp(ll)`` -- ``elpd_loo_i``, ``pareto_k`` -- are unchanged and
+every output is a function of the draws' values alone.  With ``w_s = W_s / sum_t W_t``,
+``mu_s = a_i . beta_s`` and ``r_s = y_i - mu_s``:
+
+* ``loo_mean_i = y_i - sum_s w_s r_s`` (in the space of ``A`` and ``y``);
+* ``loo_sd_i   = sqrt(sum_s w_s (sigma_s^2 + r_s^2) - (sum_s w_s r_s)^2)``;
+* ``loo_pit_i  = sum_s w_s Phi(r_s / sigma_s)``, ``Phi(z) = erfc(-z / sqrt 2) / 2``: the
+  leave-one-out predictive probability of a value at or below the observed one;
+* ``ess_i      = 1 / sum_s w_s^2``, the PSIS effective sample size with r_eff = 1 (1 .. S);
+
+a point with a non-finite ``ll`` gets NaN in each.  On the host ``loo_rmse =
+sqrt(mean_i (y_i - loo_mean_i)^2)``, ``pit_coverage[j]`` = the percentage of points with
+``|2 loo_pit_i - 1| <= p_j / 100`` for ``p = 0, 5, .., 100`` (the levels and units of
+``BayesianModelCombination.evaluate``) and ``min_ess``.  At most 1 863 225 pooled draws.
 
 On the device (``kernels_waic.hip``, ``kernels_loo.hip``) the n x S matrix is never stored: an f64 MFMA GEMM whose
 tiles are reduced in the epilogue; PSIS-LOO recomputes it for an exact radix select of each
@@ -240,4 +260,36 @@ def psis_loo(A, y, samples, burn=0, thin=1, device=0):
     out = loo_summary(pw["elpd_loo"], pw["lppd"], pw["pareto_k"], C * kept_draws(T, burn, thin))
     out.update(elpd_loo_i=pw["elpd_loo"], p_loo_i=pw["lppd"] - pw["elpd_loo"],
                pareto_k=pw["pareto_k"], lppd=pw["lppd"])
+    return out
+
+
+PIT_LEVELS = tuple(range(0, 101, 5))
+
+
+def loo_predict_summary(y, loo_mean, loo_pit, ess):
+    """``loo_rmse``, ``pit_coverage`` (21 percentages, levels ``PIT_LEVELS``) and ``min_ess`` of
+    the module docstring from the pointwise vectors (host, float64)."""
+    y = np.asarray(y, dtype=np.float64)
+    m = np.asarray(loo_mean, dtype=np.float64)
+    dev = np.abs(2.0 * np.asarray(loo_pit, dtype=np.float64) - 1.0)
+    n = y.shape[0]
+    cov = [float(np.count_nonzero(dev <= p / 100.0)) / n * 100.0 for p in PIT_LEVELS]
+    return {"loo_rmse": float(np.sqrt(np.mean((y - m) ** 2))), "pit_coverage": cov,
+            "min_ess": float(np.min(np.asarray(ess, dtype=np.float64)))}
+
+
+def psis_loo_predict(A, y, samples, burn=0, thin=1, device=0):
+    """PSIS-LOO with the leave-one-out predictive distribution of every training point (module
+    docstring): everything ``psis_loo`` returns, the pointwise ``loo_mean``, ``loo_sd``,
+    ``loo_pit``, ``ess`` and ``loo_rmse``, ``pit_coverage``, ``min_ess``.  Arguments as
+    ``pointwise_log_likelihood``; ``loo_mean`` is in the space of ``A`` and ``y``."""
+    pw = _pointwise_call("psis_loo_predict", "psis_loo_predict_device", A, y, samples, burn, thin,
+                         device)
+    sh = tuple(samples.shape)
+    C, T = (1, sh[0]) if len(sh) == 2 else sh[:2]
+    out = loo_summary(pw["elpd_loo"], pw["lppd"], pw["pareto_k"], C * kept_draws(T, burn, thin))
+    out.update(elpd_loo_i=pw["elpd_loo"], p_loo_i=pw["lppd"] - pw["elpd_loo"],
+               pareto_k=pw["pareto_k"], lppd=pw["lppd"], loo_mean=pw["loo_mean"],
+               loo_sd=pw["loo_sd"], loo_pit=pw["loo_pit"], ess=pw["ess"])
+    out.update(loo_predict_summary(np.asarray(y), pw["loo_mean"], pw["loo_pit"], pw["ess"]))
     return out
