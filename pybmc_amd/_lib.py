@@ -549,66 +549,56 @@ class Context:
         return self._diag_call(self._lib.bmc_chain_diagnostics_device, _P(d_ptr), n_chains, iters,
                                n_cols, ld, burn)
 
-    # -- pointwise log predictive density -----------------------------------------------------
-    def _score_call(self, fn, pA, n, k, lda, layout, py, pt, n_draws, ldt):
-        out = {key: np.empty(n) for key in ("lppd", "p_waic", "mean_ll")}
-        self._check(fn(self._h, pA, int(n), int(k), int(lda), int(layout), py, pt, int(n_draws),
-                       int(ldt), _dptr(out["lppd"]), _dptr(out["p_waic"]), _dptr(out["mean_ll"])))
+    # -- scoring: pointwise log predictive density, PSIS-LOO and its predictive moments -----------
+    SCORE_KEYS = ("lppd", "p_waic", "mean_ll")
+    LOO_KEYS = ("elpd_loo", "pareto_k", "lppd")
+    LOO_PREDICT_KEYS = LOO_KEYS + ("loo_mean", "loo_sd", "loo_pit", "ess")
+
+    def _score_call(self, fn, keys, ptr, A, n, k, lda, layout, y, theta, n_draws, ldt):
+        """One scoring entry point: `ptr` turns A, y and theta into what it takes (_dptr: host
+        arrays, _P: device addresses), one [n] output vector per key."""
+        out = {key: np.empty(n) for key in keys}
+        self._check(fn(self._h, ptr(A), int(n), int(k), int(lda), int(layout), ptr(y), ptr(theta),
+                       int(n_draws), int(ldt), *(_dptr(out[key]) for key in keys)))
         return out
 
     def pointwise_loglik(self, A, n, k, lda, layout, y, theta, n_draws, ldt):
         """lppd_i, p_waic_i and mean_ll_i of HOST f64 arrays (bmc_pointwise_loglik): A's element
         (i, j) at i*lda + j (BMC_ROW_MAJOR) or j*lda + i (BMC_COL_MAJOR), draw s at theta + s*ldt.
         Returns a dict of [n] arrays."""
-        return self._score_call(self._lib.bmc_pointwise_loglik, _dptr(A), n, k, lda, layout,
-                                _dptr(y), _dptr(theta), n_draws, ldt)
+        return self._score_call(self._lib.bmc_pointwise_loglik, self.SCORE_KEYS, _dptr,
+                                A, n, k, lda, layout, y, theta, n_draws, ldt)
 
     def pointwise_loglik_device(self, dA, n, k, lda, layout, dy, dtheta, n_draws, ldt):
         """The same on DEVICE memory (bmc_pointwise_loglik_device), read on the context's stream:
         the caller orders its producers before the call."""
-        return self._score_call(self._lib.bmc_pointwise_loglik_device, _P(dA), n, k, lda, layout,
-                                _P(dy), _P(dtheta), n_draws, ldt)
-
-    # -- PSIS-LOO ---------------------------------------------------------------------------
-    def _loo_call(self, fn, pA, n, k, lda, layout, py, pt, n_draws, ldt):
-        out = {key: np.empty(n) for key in ("elpd_loo", "pareto_k", "lppd")}
-        self._check(fn(self._h, pA, int(n), int(k), int(lda), int(layout), py, pt, int(n_draws),
-                       int(ldt), _dptr(out["elpd_loo"]), _dptr(out["pareto_k"]), _dptr(out["lppd"])))
-        return out
+        return self._score_call(self._lib.bmc_pointwise_loglik_device, self.SCORE_KEYS, _P,
+                                dA, n, k, lda, layout, dy, dtheta, n_draws, ldt)
 
     def psis_loo(self, A, n, k, lda, layout, y, theta, n_draws, ldt):
         """elpd_loo_i, pareto_k_i and lppd_i of HOST f64 arrays (bmc_psis_loo); arguments as
         pointwise_loglik.  Returns a dict of [n] arrays."""
-        return self._loo_call(self._lib.bmc_psis_loo, _dptr(A), n, k, lda, layout, _dptr(y),
-                              _dptr(theta), n_draws, ldt)
+        return self._score_call(self._lib.bmc_psis_loo, self.LOO_KEYS, _dptr,
+                                A, n, k, lda, layout, y, theta, n_draws, ldt)
 
     def psis_loo_device(self, dA, n, k, lda, layout, dy, dtheta, n_draws, ldt):
         """The same on DEVICE memory (bmc_psis_loo_device), read on the context's stream: the
         caller orders its producers before the call."""
-        return self._loo_call(self._lib.bmc_psis_loo_device, _P(dA), n, k, lda, layout, _P(dy),
-                              _P(dtheta), n_draws, ldt)
-
-    # -- PSIS-LOO predictive moments ----------------------------------------------------------
-    LOO_PREDICT_KEYS = ("elpd_loo", "pareto_k", "lppd", "loo_mean", "loo_sd", "loo_pit", "ess")
-
-    def _loo_predict_call(self, fn, pA, n, k, lda, layout, py, pt, n_draws, ldt):
-        out = {key: np.empty(n) for key in self.LOO_PREDICT_KEYS}
-        self._check(fn(self._h, pA, int(n), int(k), int(lda), int(layout), py, pt, int(n_draws),
-                       int(ldt), *(_dptr(out[key]) for key in self.LOO_PREDICT_KEYS)))
-        return out
+        return self._score_call(self._lib.bmc_psis_loo_device, self.LOO_KEYS, _P,
+                                dA, n, k, lda, layout, dy, dtheta, n_draws, ldt)
 
     def psis_loo_predict(self, A, n, k, lda, layout, y, theta, n_draws, ldt):
         """What psis_loo returns and the leave-one-out predictive loo_mean_i, loo_sd_i, loo_pit_i
         and the PSIS effective sample size ess_i of HOST f64 arrays (bmc_psis_loo_predict);
         arguments as pointwise_loglik.  Returns a dict of [n] arrays."""
-        return self._loo_predict_call(self._lib.bmc_psis_loo_predict, _dptr(A), n, k, lda, layout,
-                                      _dptr(y), _dptr(theta), n_draws, ldt)
+        return self._score_call(self._lib.bmc_psis_loo_predict, self.LOO_PREDICT_KEYS, _dptr,
+                                A, n, k, lda, layout, y, theta, n_draws, ldt)
 
     def psis_loo_predict_device(self, dA, n, k, lda, layout, dy, dtheta, n_draws, ldt):
         """The same on DEVICE memory (bmc_psis_loo_predict_device), read on the context's stream:
         the caller orders its producers before the call."""
-        return self._loo_predict_call(self._lib.bmc_psis_loo_predict_device, _P(dA), n, k, lda,
-                                      layout, _P(dy), _P(dtheta), n_draws, ldt)
+        return self._score_call(self._lib.bmc_psis_loo_predict_device, self.LOO_PREDICT_KEYS, _P,
+                                dA, n, k, lda, layout, dy, dtheta, n_draws, ldt)
 
     # -- variates -----------------------------------------------------------------------
     def rng_fill(self, seed, n_normal=0, shape=1.0, n_gamma=0):

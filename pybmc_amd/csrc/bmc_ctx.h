@@ -1,0 +1,147 @@
+// The context behind the C ABI (include/pybmc_amd.h) and what its host files share.  Internal:
+// not installed.  capi_*.hip hold the entry points, one feature family each; every function
+// declared here is defined in capi_core.hip.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <rccl/rccl.h>   // types only: the library itself is loaded on first use (bmc_comm_*)
+
+#include <initializer_list>
+#include <string>
+#include <vector>
+
+#include "../../include/pybmc_amd.h"
+#include "bmc_launch.h"
+#include "bmc_plan.h"
+
+using namespace bmc;
+
+#pragma GCC visibility push(hidden)
+
+// A device block that grows on demand (ensure) and frees itself.
+struct DevBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() {
+        if (p) (void)hipFree(p);
+    }
+};
+
+// The stream, the events and the pinned staging.  A base of bmc_ctx, so that they are destroyed
+// after its members: device memory goes first, as bmc_destroy has always done it.
+struct CtxHandles {
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    // pinned staging for results that go back to pageable host memory (copy_to_host)
+    void* hstage[2] = {nullptr, nullptr};
+    hipEvent_t hev[2] = {nullptr, nullptr};
+    ~CtxHandles() {
+        for (auto& e : ev)
+            if (e) (void)hipEventDestroy(e);
+        for (int i = 0; i < 2; ++i) {
+            if (hev[i]) (void)hipEventDestroy(hev[i]);
+            if (hstage[i]) (void)hipHostFree(hstage[i]);
+        }
+        if (own_stream && stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+struct bmc_ctx : CtxHandles {
+    int device = 0;
+    std::string err;
+    bmc_tuning tune{};
+    int n_cu = 256;
+    int env_cu_limit = 0;   // PYBMC_AMD_CU_LIMIT at bmc_create: the default of bmc_tuning.cu_limit
+    uint64_t nonce_state = 0x9E3779B97F4A7C15ull;   // per-launch exchange nonces (launch_nonce)
+
+    // problem
+    bool have_problem = false, have_prior = false;
+    int64_t n = 0;
+    int32_t k = 0, vec = 1, npanels = 0, f32 = 0;
+    DevBuf Xraw, Yp, Xrot;
+    std::vector<double> gram;
+
+    // prior / basis (host copies)
+    std::vector<double> W, lam, c1, c2, b0;
+    double nu0 = 0, s20 = 0, sigma2_init = 0;
+    DevBuf dW, dWT, dLam, dC1, dC2;
+    // sufficient statistics in the rotated basis (rss_mode 1; host part made by bmc_set_prior
+    // when k <= 64, device part on first use)
+    std::vector<double> Gt, u0, g0;
+    bool have_gram_dev = false;
+    double rss0 = 0;
+    DevBuf dGt, dU0, dG0;
+
+    // scratch
+    DevBuf gramScratch, gramOut, rssPartial, rssOut, coef, stage, ticket;
+    // run buffers
+    DevBuf xi, gam, uout, samples, gran, status, seeds, dbg, placement;
+    // the persistent loop kernels of the last bmc_gibbs_run* / bmc_simplex_run*, one name per
+    // launch in launch order (bmc_last_kernels)
+    std::vector<std::string> last_kernels;
+    // predictive buffers
+    DevBuf pPreds, pPad, pTheta, pVt, pWt, pSig, pR, pRT, pNoise, pAux, pBands;
+    int64_t pM = 0;                        // last bmc_predict: points, draws, padded draws
+    int32_t pS = 0, pS_pad = 0;
+    DevBuf sVt, sStep, sUnif, sOut, sCnt, sNUnif;
+    DevBuf oFc, oMu, oW, oOut;
+    // chain diagnostics (bmc_chain_diagnostics*)
+    DevBuf dgIn, dgPart, dgMean, dgM2, dgCols, dgAcovPart, dgAcov;
+    // pointwise log-likelihood (bmc_pointwise_loglik*)
+    DevBuf scA, scY, scTheta, scAp, scYp, scCh, scPart, scOut;
+    // PSIS-LOO (bmc_psis_loo*, bmc_psis_loo_predict*): the select state and candidate slots,
+    // besides the score buffers
+    DevBuf looWork;
+    double predict_ms[4] = {0, 0, 0, 0};   // last bmc_predict: h2d, gemm, order statistics, device
+    // pooling over GPUs (bmc_comm_*): RCCL communicator bound to this context's device
+    ncclComm_t comm = nullptr;
+    int32_t comm_world = 0, comm_rank = 0;
+};
+
+int fail(bmc_ctx* c, int code, const std::string& msg);
+
+#define HIPCHK(ctx, expr)                                                              \
+    do {                                                                               \
+        hipError_t e__ = (expr);                                                       \
+        if (e__ != hipSuccess)                                                         \
+            return fail(ctx, e__ == hipErrorOutOfMemory ? BMC_ENOMEM : BMC_EHIP,       \
+                        std::string(#expr) + ": " + hipGetErrorString(e__));           \
+    } while (0)
+
+// At least `bytes` in b (0 bytes means 16).  Grows only; the stream is synchronised before the
+// old block is freed.
+int ensure(bmc_ctx* c, DevBuf& b, size_t bytes);
+// ensure() for each {buffer, bytes} in turn; the first error
+struct Want {
+    DevBuf& b;
+    size_t bytes;
+};
+int ensure_all(bmc_ctx* c, std::initializer_list<Want> wants);
+// what launch_residual_rss needs for n_out results: the partials, the results, the zeroed tickets
+int ensure_rss(bmc_ctx* c, const Panels& P, size_t n_out);
+
+// rows of `row_bytes` taken every `src_pitch` bytes on the device, written densely to `dst`
+// (src_pitch == row_bytes: one contiguous block of row_bytes * rows).  Blocks until the data is
+// in `dst`.
+int copy_to_host(bmc_ctx* c, void* dst, const void* src_dev, size_t row_bytes, size_t src_pitch,
+                 size_t rows);
+
+Panels panels_of(const bmc_ctx* c, const void* X);
+Shape shape_of(const bmc_ctx* c);
+Chip chip_of(const bmc_ctx* c);
+uint32_t launch_nonce(bmc_ctx* c, uint64_t n_tags);
+
+// milliseconds from c->ev[from] to c->ev[to]
+int event_ms(bmc_ctx* c, int from, int to, double* ms);
+
+// bytes of an n x k host matrix of `es`-byte elements with leading dimension ld: the last row
+// (column, when col-major) may be shorter than ld
+size_t strided_bytes(int64_t n, int32_t k, int64_t ld, int layout, size_t es);
+
+// rss of nb host coefficient vectors on the un-rotated panels -> out_host
+int rss_on_raw(bmc_ctx* c, const double* coef_host, int32_t nb, double* out_host);
+
+#pragma GCC visibility pop

@@ -1,0 +1,192 @@
+// C ABI, scoring a fit: the pointwise log predictive density (kernels_waic.hip),
+// PSIS-LOO and its predictive moments (kernels_loo.hip).  The three families
+// differ in their plan, their launcher and where their results lie; score_entry is the rest.
+#include "bmc_ctx.h"
+
+namespace {
+
+// What every scoring entry point is given: the design rows, the targets and the draws
+struct ScoreIn {
+    const void *A, *y, *theta;   // host or device
+    int64_t n, lda, S, ldt;
+    int32_t k, layout;
+};
+
+int check_score_args(bmc_ctx* c, const void* A, int64_t n, int32_t k, int64_t lda, int layout,
+                     const void* y, const void* theta, int64_t S, int64_t ldt) {
+    if (!c) return BMC_EINVAL;
+    if (!A || !y || !theta) return fail(c, BMC_EINVAL, "A, y and theta must not be NULL");
+    if (n < 1) return fail(c, BMC_EINVAL, "n_points must be >= 1");
+    if (k < 1 || k > SCORE_MAX_K)
+        return fail(c, BMC_EINVAL, "k must be between 1 and " + std::to_string(SCORE_MAX_K));
+    if (layout != BMC_ROW_MAJOR && layout != BMC_COL_MAJOR)
+        return fail(c, BMC_EINVAL, "layout must be BMC_ROW_MAJOR or BMC_COL_MAJOR");
+    if (lda < (layout == BMC_COL_MAJOR ? n : (int64_t)k))
+        return fail(c, BMC_EINVAL, "lda is smaller than the leading dimension of A");
+    if (S < 2) return fail(c, BMC_EINVAL, "n_draws must be >= 2 (the variance has ddof 1)");
+    if (ldt < (int64_t)k + 1) return fail(c, BMC_EINVAL, "ldt must be >= k + 1");
+    return BMC_OK;
+}
+
+// The score kernels' arguments in the context's buffers
+int score_args(bmc_ctx* c, const ScorePlan& plan, const ScoreIn& in, ScoreArgs& a) {
+    const ScoreBuffers sb = score_buffers(plan, in.S);
+    if (int rc = ensure_all(c, {{c->scAp, sb.Ap}, {c->scYp, sb.yp}, {c->scCh, sb.ch}, {c->scPart, sb.part},
+                                {c->scOut, (size_t)in.n * 3 * 8}}))
+        return rc;
+    a.A = (const double*)in.A;
+    a.y = (const double*)in.y;
+    a.theta = (const double*)in.theta;
+    a.n = in.n;
+    a.lda = in.lda;
+    a.S = in.S;
+    a.ldt = in.ldt;
+    a.k = in.k;
+    a.col_major = in.layout == BMC_COL_MAJOR;
+    a.Ap = (double*)c->scAp.p;
+    a.yp = (double*)c->scYp.p;
+    a.ch = (double*)c->scCh.p;
+    a.part = (double*)c->scPart.p;
+    a.out = (double*)c->scOut.p;
+    return BMC_OK;
+}
+
+// Host A, y and theta into the context's staging buffers (on its stream); `in` then names those
+int score_stage(bmc_ctx* c, ScoreIn& in) {
+    const size_t abytes = strided_bytes(in.n, in.k, in.lda, in.layout, 8);
+    const size_t tbytes = strided_bytes(in.S, in.k + 1, in.ldt, BMC_ROW_MAJOR, 8);
+    if (int rc = ensure_all(c, {{c->scA, abytes}, {c->scY, (size_t)in.n * 8}, {c->scTheta, tbytes}}))
+        return rc;
+    HIPCHK(c, hipMemcpyAsync(c->scA.p, in.A, abytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->scY.p, in.y, (size_t)in.n * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->scTheta.p, in.theta, tbytes, hipMemcpyHostToDevice, c->stream));
+    in.A = c->scA.p, in.y = c->scY.p, in.theta = c->scTheta.p;
+    return BMC_OK;
+}
+
+// A family plans and launches on device operands and says where result f lies: src[f], [n] each
+using ScoreFamily = int (*)(bmc_ctx* c, const ScoreIn& in, const double** src);
+
+// lppd, p_waic, mean_ll
+int pointwise_family(bmc_ctx* c, const ScoreIn& in, const double** src) {
+    const ScorePlan plan = plan_score(in.n, in.S, in.k, c->n_cu);
+    ScoreArgs a;
+    if (int rc = score_args(c, plan, in, a)) return rc;
+    HIPCHK(c, launch_score(a, plan, c->stream));
+    for (int f = 0; f < 3; ++f) src[f] = a.out + (size_t)f * in.n;
+    return BMC_OK;
+}
+
+// elpd_loo, pareto_k, lppd
+int loo_family(bmc_ctx* c, const ScoreIn& in, const double** src) {
+    const LooPlan plan = plan_loo(in.n, in.S, in.k, c->n_cu);
+    if (!plan.ok)
+        return fail(c, BMC_EINVAL, "n_draws is too large for the per-point sort (tail of " +
+                                       std::to_string(plan.tail) + " draws)");
+    LooArgs a;
+    int rc;
+    if ((rc = score_args(c, plan.score, in, a.score)) ||
+        (rc = ensure(c, c->looWork, loo_buffers(plan, in.n).total())))
+        return rc;
+    a.work = c->looWork.p;
+    HIPCHK(c, launch_loo(a, plan, c->stream));
+    const double* lo = loo_out(a, plan);
+    src[0] = lo, src[1] = lo + in.n, src[2] = a.score.out;
+    return BMC_OK;
+}
+
+// elpd_loo, pareto_k, lppd, loo_mean, loo_sd, loo_pit, ess
+int loo_predict_family(bmc_ctx* c, const ScoreIn& in, const double** src) {
+    const LooPredictPlan plan = plan_loo_predict(in.n, in.S, in.k, c->n_cu);
+    if (!plan.ok)
+        return fail(c, BMC_EINVAL, "n_draws is too large for the per-point sort of the predictive "
+                                   "moments (at most " + std::to_string(LOO_PREDICT_MAX_DRAWS) +
+                                       " draws; tail of " + std::to_string(plan.loo.tail) + ")");
+    LooArgs a;
+    int rc;
+    if ((rc = score_args(c, plan.loo.score, in, a.score)) ||
+        (rc = ensure(c, c->looWork, loo_predict_buffers(plan, in.n).total())))
+        return rc;
+    a.work = c->looWork.p;
+    HIPCHK(c, launch_loo_predict(a, plan, c->stream));
+    const double* lo = loo_predict_out(a, plan);
+    src[0] = lo, src[1] = lo + in.n, src[2] = a.score.out;
+    for (int f = 3; f < 7; ++f) src[f] = lo + (size_t)(f - 1) * in.n;
+    return BMC_OK;
+}
+
+// One scoring call: host operands are staged first, the family runs, result f goes to dst[f]
+// (host, any may be NULL), then one sync.  Everything on the context's stream, in buffers of its
+// own: the resident problem, the prior and the predictive draws are not touched.
+int score_entry(bmc_ctx* c, ScoreIn in, bool on_host, ScoreFamily family,
+                std::initializer_list<double*> dst) {
+    int rc = check_score_args(c, in.A, in.n, in.k, in.lda, in.layout, in.y, in.theta, in.S, in.ldt);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (on_host && (rc = score_stage(c, in))) return rc;
+    const double* src[7] = {};
+    if ((rc = family(c, in, src))) return rc;
+    int f = 0;
+    for (double* out : dst) {
+        if (out)
+            HIPCHK(c, hipMemcpyAsync(out, src[f], (size_t)in.n * 8, hipMemcpyDeviceToHost, c->stream));
+        ++f;
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return BMC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bmc_pointwise_loglik(bmc_ctx* c, const double* A, int64_t n_points, int32_t k, int64_t lda,
+                         int layout, const double* y, const double* theta, int64_t n_draws,
+                         int64_t ldt, double* lppd_out, double* pwaic_out, double* mean_ll_out) {
+    return score_entry(c, {A, y, theta, n_points, lda, n_draws, ldt, k, layout}, true, pointwise_family,
+                       {lppd_out, pwaic_out, mean_ll_out});
+}
+
+int bmc_pointwise_loglik_device(bmc_ctx* c, const void* dA, int64_t n_points, int32_t k, int64_t lda,
+                                int layout, const void* dy, const void* dtheta, int64_t n_draws,
+                                int64_t ldt, double* lppd_out, double* pwaic_out,
+                                double* mean_ll_out) {
+    return score_entry(c, {dA, dy, dtheta, n_points, lda, n_draws, ldt, k, layout}, false,
+                       pointwise_family, {lppd_out, pwaic_out, mean_ll_out});
+}
+
+int bmc_psis_loo(bmc_ctx* c, const double* A, int64_t n_points, int32_t k, int64_t lda, int layout,
+                 const double* y, const double* theta, int64_t n_draws, int64_t ldt,
+                 double* elpd_loo_out, double* pareto_k_out, double* lppd_out) {
+    return score_entry(c, {A, y, theta, n_points, lda, n_draws, ldt, k, layout}, true, loo_family,
+                       {elpd_loo_out, pareto_k_out, lppd_out});
+}
+
+int bmc_psis_loo_device(bmc_ctx* c, const void* dA, int64_t n_points, int32_t k, int64_t lda,
+                        int layout, const void* dy, const void* dtheta, int64_t n_draws, int64_t ldt,
+                        double* elpd_loo_out, double* pareto_k_out, double* lppd_out) {
+    return score_entry(c, {dA, dy, dtheta, n_points, lda, n_draws, ldt, k, layout}, false, loo_family,
+                       {elpd_loo_out, pareto_k_out, lppd_out});
+}
+
+int bmc_psis_loo_predict(bmc_ctx* c, const double* A, int64_t n_points, int32_t k, int64_t lda,
+                         int layout, const double* y, const double* theta, int64_t n_draws,
+                         int64_t ldt, double* elpd_loo_out, double* pareto_k_out, double* lppd_out,
+                         double* loo_mean_out, double* loo_sd_out, double* loo_pit_out,
+                         double* ess_out) {
+    return score_entry(c, {A, y, theta, n_points, lda, n_draws, ldt, k, layout}, true, loo_predict_family,
+                       {elpd_loo_out, pareto_k_out, lppd_out, loo_mean_out, loo_sd_out, loo_pit_out,
+                        ess_out});
+}
+
+int bmc_psis_loo_predict_device(bmc_ctx* c, const void* dA, int64_t n_points, int32_t k, int64_t lda,
+                                int layout, const void* dy, const void* dtheta, int64_t n_draws,
+                                int64_t ldt, double* elpd_loo_out, double* pareto_k_out,
+                                double* lppd_out, double* loo_mean_out, double* loo_sd_out,
+                                double* loo_pit_out, double* ess_out) {
+    return score_entry(c, {dA, dy, dtheta, n_points, lda, n_draws, ldt, k, layout}, false,
+                       loo_predict_family, {elpd_loo_out, pareto_k_out, lppd_out, loo_mean_out,
+                                            loo_sd_out, loo_pit_out, ess_out});
+}
+
+}  // extern "C"
