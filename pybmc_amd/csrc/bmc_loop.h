@@ -398,7 +398,6 @@ struct PanelStore {
                                                           int c_lo = 0, int c_hi = CPP) const {
         static_assert(MODE == MODE_REG, "register residency only");
         typedef const __attribute__((address_space(3))) double lds_cd;
-#ifndef BMC_REGMULTI_LDS
         // From 16 columns on: u through DPP row broadcasts, as in partial_rss -- per chain one
         // ds_read_b64 per 16 columns (lane l <- u[c][16 r + (l & 15)]) instead of one LDS broadcast
         // read per (chain, column).  With 4 chains x 64 columns (C4) that was 256 reads per wave
@@ -439,7 +438,6 @@ struct PanelStore {
                     // (tried in round 3: u_j of the first 4 / 8 columns of every block of 16 from an LDS
                     // broadcast read + plain v_fma_f64 instead of the DPP form, the LDS pipe being idle
                     // in this pass -- 64 chains at C2 2.34 -> 2.53 / 2.77 us per iteration: rejected)
-#ifndef BMC_NO_BLOCK_ASM
                     if constexpr (PPW * VEC == 1 && KMAX % 16 == 0 && sizeof(T) == 8) {
                         static_for<NU>([&](auto rc) {      // (one statement per block of 16 columns)
                             constexpr int r = decltype(rc)::value;
@@ -449,7 +447,6 @@ struct PanelStore {
                             fmac16_rowbcast_neg(acc[0][0], urow[c][r], xb);
                         });
                     } else
-#endif
                     static_for<KMAX>([&](auto jc) {
                         constexpr int j = decltype(jc)::value;
 #pragma unroll
@@ -483,7 +480,7 @@ struct PanelStore {
             });
             return;
         }
-#endif
+        // fewer than 16 columns: u from LDS broadcast reads (the few reads are not the bound), in
         // blocks of UB values of u, DEPTH blocks in flight (fewer where the panel already
         // fills 128 VGPRs)
         // (Stamps: the pass is LDS-latency bound, one block of u at a time -- the volatile asm
@@ -640,7 +637,6 @@ struct PanelStore {
                 double urow[NU];
 #pragma unroll
                 for (int r = 0; r < NU; ++r) urow[r] = u_lds[r * 16 + (lane & 15)];
-#ifndef BMC_NO_BLOCK_ASM
                 if constexpr (JD == 0 && PPW * VEC == 1 && KMAX % 16 == 0 && sizeof(T) == 8) {
                     static_for<NU>([&](auto rc) {
                         constexpr int r = decltype(rc)::value;
@@ -650,7 +646,6 @@ struct PanelStore {
                         fmac16_rowbcast_neg(acc[0][0], urow[r], xb);
                     });
                 } else
-#endif
                 static_for<KMAX - JD>([&](auto jc) {
                     constexpr int j = decltype(jc)::value + JD;
 #pragma unroll
@@ -700,6 +695,17 @@ struct PanelStore {
 // per chain; the slots of waves that do not exist stay 0 (zeroed by the caller before the
 // loop).  Lane w < 8 reads slot w and three DPP steps add them in a fixed tree,
 // ((r0+r1)+(r2+r3)) + ((r7+r6)+(r5+r4)): no trip count, one LDS read, 4 VGPRs.
+// sum_wave_rows (the lane-wise forms): `rows` holds 8 rows of 64 lane partials, one per wave (or
+// panel); the rows of absent waves stay 0.  The rows are added lane by lane in the fixed tree
+// ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), then ONE wave-level sum.  Every lane-wise reduction
+// is this function, which is what makes a chain's bits the same in every kernel that uses one.
+__device__ __forceinline__ double sum_wave_rows(const double* rows, int lane) {
+    const double* r = rows + lane;
+    const double r0 = r[0], r1 = r[64], r2 = r[128], r3 = r[192];
+    const double r4 = r[256], r5 = r[320], r6 = r[384], r7 = r[448];
+    return wave_sum(((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)));
+}
+
 __device__ __forceinline__ double sum_wave_slots(const double* red, int lane) {
     double v = lane < 8 ? red[lane] : 0.0;
     v += dpp_mov_f64<0xB1>(v);          // quad_perm [1,0,3,2]
@@ -742,7 +748,7 @@ struct NoIdleWork {
 // most 32 groups and runs one of two copies of its loop, chosen once after the placement check:
 // with both run-time tests and the dead two-level code out of the loop an iteration at C2 is
 // 3 % shorter (1.090 -> 1.059 us, same-box A/B).
-template <bool RELAY = false, typename F = NoIdleWork, int TEAMS = -1, int LOCAL = -1>
+template <bool RELAY = false, int TEAMS = -1, int LOCAL = -1, typename F = NoIdleWork>
 __device__ __forceinline__ double exchange_sum(double s, gu64* gp, int G, int g, int lane,
                                                unsigned epoch, bool local, bool& ok STAMP_PARAMS,
                                                F idle = F()) {
@@ -767,15 +773,11 @@ __device__ __forceinline__ double exchange_sum(double s, gu64* gp, int G, int g,
     ok = granule_gather1(gp1, 2 * members, epoch, lane, x STAMP_ARGS);
     GSTAMP(5);
     // (the expired spin leaves at once: as `ok ? sum : 0` the flag travelled through the whole
-    // serial path as set / test / branch pairs)
-#ifndef BMC_NO_EXPECT
+    // serial path as set / test / branch pairs -- tried, rejected: part of the three changes
+    // that took C2 from 0.9425 to 0.9411 us per iteration)
     if (__builtin_expect(!ok, 0)) return 0.0;
     double tot = granule_sum1(x, lane);
     if (teams) {
-#else
-    double tot = ok ? granule_sum1(x, lane) : 0.0;
-    if (teams && ok) {
-#endif
         // second level: 8 team-total pairs, then 8 relay pairs, GRAN_L2_STRIDE words (512 bytes)
         // apart: each pair is written by one XCD and polled by all (bmc_launch.h)
         gu64* gp2 = gp + (size_t)256 * GRAN_PAIR_STRIDE;
@@ -802,8 +804,8 @@ __device__ __forceinline__ double exchange_sum(double s, gu64* gp, int G, int g,
 // LANEWISE (register residency with one row per lane: C2, notebook-sized chains, N = 100 000 x
 // 32): the waves of a group do NOT reduce their lanes first.  Every wave leaves its 64 lane
 // partials in its row of `red` ([8 waves][64 lanes], rows of absent waves stay 0: zeroed by the
-// caller before the loop), and after the barrier wave 0 adds the 8 rows lane by lane in a fixed
-// tree, ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), and runs ONE wave-level sum -- instead of a
+// caller before the loop), and after the barrier wave 0 adds the 8 rows lane by lane and runs
+// ONE wave-level sum (sum_wave_rows) -- instead of a
 // wave_sum per wave in front of the barrier (two of them interleaved on the SIMD that two of a
 // CU's five waves share) and a second, 8-slot one behind it.  Same-box A/B (14 rounds): C2
 // 1.112 -> 1.085 us, N = 629 0.599 -> 0.570, N = 100 000 x 32 2.25 -> 2.02; but C4 (two rows
@@ -817,26 +819,21 @@ template <bool SINGLE = false, bool LANEWISE = false, int TEAMS = -1, int LOCAL 
 __device__ __forceinline__ double group_allreduce(double s, double* red, gu64* gp, int G, int g,
                                                   int wave, int nw, int lane, unsigned epoch,
                                                   bool local, bool& ok STAMP_PARAMS, F idle = F()) {
-    if constexpr (LANEWISE) {
-        if constexpr (!PREWRITTEN) red[wave * 64 + lane] = s;
-    } else if constexpr (!PREWRITTEN) {
+    static_assert(LANEWISE || !PREWRITTEN, "only the lane-wise form is written ahead");
+    if constexpr (!LANEWISE) {
         s = wave_sum(s);
         if (lane == 0) red[wave] = s;
+    } else if constexpr (!PREWRITTEN) {
+        red[wave * 64 + lane] = s;
     }
     GSTAMP(3);
     __syncthreads();
     ok = true;
     if (ROLE < 0 ? wave != 0 : ROLE != 0) return 0.0;   // (ROLE: the caller knows its wave's role)
-    if constexpr (LANEWISE) {
-        const double r0 = red[lane], r1 = red[64 + lane], r2 = red[128 + lane], r3 = red[192 + lane];
-        const double r4 = red[256 + lane], r5 = red[320 + lane], r6 = red[384 + lane], r7 = red[448 + lane];
-        s = wave_sum(((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)));
-    } else {
-        s = sum_wave_slots(red, lane);
-    }
+    s = LANEWISE ? sum_wave_rows(red, lane) : sum_wave_slots(red, lane);
     GSTAMP(4);
     if constexpr (SINGLE) return s;
-    return exchange_sum<false, F, TEAMS, LOCAL>(s, gp, G, g, lane, epoch, local, ok STAMP_ARGS, idle);
+    return exchange_sum<false, TEAMS, LOCAL>(s, gp, G, g, lane, epoch, local, ok STAMP_ARGS, idle);
 }
 
 // ---- several chains per pass (streaming / LDS residency) ---------------------------------
@@ -931,12 +928,12 @@ __device__ __forceinline__ void panel_rss_multi(const T* __restrict__ xp, const 
 
 // All-reduce of CPP lane partials: wave c < CPP leads chain c (sums the waves' partials of
 // its chain, publishes and gathers on that chain's granules).  Every wave calls it.
-template <int CPP, typename F = NoIdleWork>
+template <int CPP, typename F>
 __device__ __forceinline__ double group_allreduce_multi(const double (&s)[CPP], double* red,
                                                         gu64* gp_chain0, size_t chain_stride,
                                                         int G, int g, int wave, int nw, int lane,
                                                         unsigned epoch, bool local, bool& ok STAMP_PARAMS,
-                                                        F idle = F()) {
+                                                        F idle) {
 #pragma unroll
     for (int c = 0; c < CPP; ++c) {
         const double t = wave_sum(s[c]);
@@ -952,44 +949,41 @@ __device__ __forceinline__ double group_allreduce_multi(const double (&s)[CPP], 
                                     local, ok STAMP_ARGS, idle);
 }
 
-// Balanced bundles (partial_rss_reg_bal): rows are written by the caller; this is the leader's
-// half of group_allreduce_multi_lanewise.
-template <int CPP, int TEAMS = -1, typename F = NoIdleWork>
+// The lane-wise form of group_allreduce<LANEWISE, .., PREWRITTEN> for several chains: every wave
+// has left its 64 lane partials of every chain in LDS ([chain][wave or panel][lane], rows of
+// absent waves stay 0) and leader c reduces the 8 rows of its chain with sum_wave_rows -- the
+// reduction of the single-chain kernel, so a chain's bits do not depend on whether it shares its
+// pass -- instead of CPP wave sums in every wave in front of the barrier.  Here the caller wrote
+// the rows (the balanced bundles of partial_rss_reg_bal).
+template <int CPP, int TEAMS, typename F>
 __device__ __forceinline__ double group_allreduce_multi_prewritten(double* red, gu64* gp_chain0,
                                                                    size_t chain_stride, int G, int g,
                                                                    int wave, int lane, unsigned epoch,
                                                                    bool local, bool& ok STAMP_PARAMS,
-                                                                   F idle = F()) {
+                                                                   F idle) {
     GSTAMP(3);
     __syncthreads();
     ok = true;
     if (wave >= CPP) return 0.0;
-    const double* r = red + (size_t)wave * 512 + lane;
-    const double r0 = r[0], r1 = r[64], r2 = r[128], r3 = r[192];
-    const double r4 = r[256], r5 = r[320], r6 = r[384], r7 = r[448];
-    const double t = wave_sum(((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)));
+    const double t = sum_wave_rows(red + (size_t)wave * 512, lane);
     GSTAMP(4);
-    return exchange_sum<(CPP >= 4), F, TEAMS>(t, gp_chain0 + (size_t)wave * chain_stride, G, g, lane,
-                                             epoch, local, ok STAMP_ARGS, idle);
+    return exchange_sum<(CPP >= 4), TEAMS>(t, gp_chain0 + (size_t)wave * chain_stride, G, g, lane,
+                                          epoch, local, ok STAMP_ARGS, idle);
 }
 
-// The same for register residency with one row per lane, in the lane-wise form of
-// group_allreduce<LANEWISE>: every wave leaves its 64 lane partials of every chain in LDS
-// ([chain][wave][lane], rows of absent waves stay 0), and leader c adds the 8 rows of its chain
-// lane by lane in the fixed tree ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) and runs ONE wave-level sum
-// -- instead of CPP wave sums in every wave in front of the barrier.  Operation for operation
-// the reduction of the single-chain kernel, so a chain's bits do not depend on whether it
-// shares its pass.
+// The same with the rows written here (one panel per wave).  (Tried: this function as "write the
+// rows, then call the form above" -- the nested inlining changed the register allocation of the
+// bundle kernels, so the leader's half stays written out in both.)
 // `row` = the local panel the wave computed (its own index, or the shared last panel's), and
 // [c_lo, c_hi) the chains it computed it for: rows are indexed by PANEL, as in the single-chain
 // kernel, whichever wave did the work.
-template <int CPP, int TEAMS = -1, typename F = NoIdleWork>
+template <int CPP, int TEAMS, typename F>
 __device__ __forceinline__ double group_allreduce_multi_lanewise(const double (&s)[CPP], double* red,
                                                                  int row, int c_lo, int c_hi,
                                                                  gu64* gp_chain0, size_t chain_stride,
                                                                  int G, int g, int wave, int lane,
                                                                  unsigned epoch, bool local,
-                                                                 bool& ok STAMP_PARAMS, F idle = F()) {
+                                                                 bool& ok STAMP_PARAMS, F idle) {
 #pragma unroll
     for (int c = 0; c < CPP; ++c)
         if (c >= c_lo && c < c_hi) red[(c * 8 + row) * 64 + lane] = s[c];
@@ -997,13 +991,10 @@ __device__ __forceinline__ double group_allreduce_multi_lanewise(const double (&
     __syncthreads();
     ok = true;
     if (wave >= CPP) return 0.0;
-    const double* r = red + (size_t)wave * 512 + lane;
-    const double r0 = r[0], r1 = r[64], r2 = r[128], r3 = r[192];
-    const double r4 = r[256], r5 = r[320], r6 = r[384], r7 = r[448];
-    const double t = wave_sum(((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)));
+    const double t = sum_wave_rows(red + (size_t)wave * 512, lane);
     GSTAMP(4);
-    return exchange_sum<(CPP >= 4), F, TEAMS>(t, gp_chain0 + (size_t)wave * chain_stride, G, g, lane,
-                                             epoch, local, ok STAMP_ARGS, idle);
+    return exchange_sum<(CPP >= 4), TEAMS>(t, gp_chain0 + (size_t)wave * chain_stride, G, g, lane,
+                                          epoch, local, ok STAMP_ARGS, idle);
 }
 
 }  // namespace bmc

@@ -98,16 +98,12 @@ BMC_HD void sincos_2pi(double u, double& sn, double& cs) {
 }
 
 // two independent N(0,1) variates from two uniforms, u1 in (0, 1] and u2 in [0, 1]  (Box-Muller)
+// (the library's log() and sincospi() in this place were the baseline these routines replaced:
+// slower, and the normals then depend on the device library's version -- see the header)
 BMC_HD void box_muller_pair(double u1, double u2, double& z0, double& z1) {
-#if defined(BMC_LIBM_NORMALS) && defined(__HIPCC__)   // A/B builds: the general-purpose library calls
-    const double rad = sqrt(-2.0 * log(u1));
-    double sn, cs;
-    sincospi(2.0 * u2, &sn, &cs);
-#else
     const double rad = sqrt(-2.0 * log_normal_arg(u1));
     double sn, cs;
     sincos_2pi(u2, sn, cs);
-#endif
     z0 = rad * cs;
     z1 = rad * sn;
 }

@@ -397,11 +397,9 @@ inline GibbsPlan plan_gibbs(const Geometry& geo, const Shape& s, const bmc_tunin
             // bundles of 8 on 8 waves, at most 5 panels per group, two panels of K columns in a
             // wave's registers: the balanced layout (4 chains of panel w % 4 + 1 chain of the
             // fifth panel per wave instead of 8 chains of one panel on waves 0 .. 3)
-#ifndef BMC_NO_BAL
             // (panels_per_wave = 1 asked for explicitly keeps the one-panel layout: the A/B knob)
             l.bundle_bal = gibbs_bundle_bal_shape(K, s.f32, s.vec, cpp) && l.waves == 8 && geo.ppg <= 5 &&
                            tu.panels_per_wave != 1;
-#endif
             l.resident = bundles * geo.G;
             p.passes += bundles;
         } else if (cpp_max > 1 && left >= 2) {

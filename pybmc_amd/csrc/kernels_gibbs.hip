@@ -54,39 +54,38 @@ namespace bmc {
 // v_rsq_f64 + one Newton step each, which the in-order pipeline overlaps, instead of a full
 // sqrt (rsq + two Newton steps + range scaling, ~14 dependent f64 operations) at the end of the
 // previous iteration's sigma2 step, all of it on the serial path.
+// (tried: sqrt(sp) from the sigma2 step, handed to the draw -- C2 1.165 us per iteration against
+// 1.120 with the two rsqrt side by side: rejected)
 // 1/sqrt(x) for finite x > 0: v_rsq_f64 and one Newton step, the arithmetic of the library
 // rsqrt() without its tests for 0 / inf / nan arguments (D and sp are sums of positive terms).
+// (tried: the library rsqrt() itself -- C2 1.120 against 1.113 without the tests: rejected)
 __device__ __forceinline__ double rsqrt_pos(double x) {
-#ifdef BMC_LIB_RSQRT
-    return rsqrt(x);
-#else
     const double y0 = __builtin_amdgcn_rsq(x);
     const double e = fma(-x * y0, y0, 1.0);           // 1 - x y0^2
     return fma(y0 * e, fma(e, 0.375, 0.5), y0);       // y0 (1 + e/2 + 3 e^2 / 8)
-#endif
 }
 
 __device__ __forceinline__ double draw_u(double lam, double c1, double c2, double xi, double sp,
-                                         double g, double sq_sp_unused) {
-#ifndef BMC_SQRT_SEPARATE
-    (void)sq_sp_unused;
+                                         double g) {
     const double D = fma(lam, g, sp);
     const double r = rsqrt_pos(D);
     const double rs = rsqrt_pos(sp);
     const double m = fma(c2, g, c1 * sp);
     return fma(r * r, m, ((sp * rs) * r) * xi);
-#else
-    const double D = fma(lam, g, sp);
-    const double r = rsqrt(D);
-    const double m = fma(c2, g, c1 * sp);
-    return fma(r * r, m, (sq_sp_unused * r) * xi);
-#endif
 }
-#ifndef BMC_SQRT_SEPARATE
-#define BMC_SQRT_OF(x) 0.0     /* not used: draw_u takes sqrt(sp) as sp * rsqrt(sp) */
-#else
-#define BMC_SQRT_OF(x) sqrt(x)
-#endif
+
+// sigma2 | beta = scale_post / g_t, floored at 1e-6 (inference_utils.py:50-52), as the pair
+// (sp, g): scale_post = (nu0 s20 + rss) / 2; the floor is the pair (1e-6, 1).  Every Gibbs kernel
+// takes this step through here and its draw through draw_u: that is what keeps a chain's bits
+// the same whichever kernel runs it.
+struct Sigma2 {
+    double sp, g;   // sigma2 = sp / g
+};
+__device__ __forceinline__ Sigma2 sigma2_step(double nu0_s20, double rss, double gam_t) {
+    const double scale_post = (nu0_s20 + rss) * 0.5;
+    const bool floor_hit = scale_post < 1e-6 * gam_t;
+    return Sigma2{floor_hit ? 1e-6 : scale_post, floor_hit ? 1.0 : gam_t};
+}
 
 // PACK: the same kernel held to 128 VGPRs (4 waves per SIMD), so that two 5-wave groups of
 // different chains fit a CU side by side whatever SIMDs their waves land on -- used when more
@@ -113,7 +112,6 @@ void gibbs_loop_kernel(GibbsArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nw = blockDim.x >> 6;
     const int64_t T_it = a.iters;
-#ifndef BMC_NO_XCD_REMAP
     // One chain over the whole chip (G > 32, a multiple of 8): team j = the groups with g mod 8 = j
     // is meant to be the groups of XCD j.  The hardware deals the workgroups of a launch round
     // robin, but starts at an XCD that depends on the queue: renumber the groups so that group
@@ -131,7 +129,6 @@ void gibbs_loop_kernel(GibbsArgs a) {
             if (rot_c >= 0) g = (g & ~7) | ((g + rot_c) & 7);
         }
     }
-#endif
 
     const LdsPlan L = lds_plan(K, (int)sizeof(T), RP, a.panels_per_group, MODE == MODE_LDS);
     double* u_lds = reinterpret_cast<double*>(smem + L.u);
@@ -167,18 +164,14 @@ void gibbs_loop_kernel(GibbsArgs a) {
     // the wave that records the draws (group 0): wave 1 -- on a SIMD of its own -- rather than the
     // last one, which at five waves on four SIMDs shares the leader's SIMD and would issue its
     // ~35 f64 operations of sqrt(sp / g) per iteration beside the serial chain
-#ifdef BMC_REC_LAST
-    const bool recorder = (g == 0) && (wave == nw - 1);
-#else
     const bool recorder = (g == 0) && (wave == (nw > 1 ? 1 : 0));
-#endif
 
     // Every load issued so far (the panels into registers) is complete from here on, and hipcc
     // knows it: otherwise it guards the first FMA of every iteration with s_waitcnt vmcnt(0),
     // which makes the recording wave wait for ITS stores of the previous iteration.
     __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0), other counters untouched
     // sigma2 = sp_eff / g_eff; starts at the OLS value (inference_utils.py:37)
-    double sp_eff = a.sigma2_init, g_eff = 1.0, sq_sp = BMC_SQRT_OF(a.sigma2_init);
+    double sp_eff = a.sigma2_init, g_eff = 1.0;
     double xi_next[KCH], lam_r[KCH], c1_r[KCH], c2_r[KCH];
     double gam_next = 0.0;
     if (wave == 0) {
@@ -227,14 +220,13 @@ void gibbs_loop_kernel(GibbsArgs a) {
                 // the serial path; columns K..63 have lam = c1 = c2 = xi = 0 and draw u = 0 into
                 // the zero padding of u_lds
                 if (MODE == MODE_REG || (ch * 64 < K && j < K))
-                    u_lds[j] = draw_u(lam_r[ch], c1_r[ch], c2_r[ch], xi_next[ch], sp_eff, g_eff, sq_sp);
+                    u_lds[j] = draw_u(lam_r[ch], c1_r[ch], c2_r[ch], xi_next[ch], sp_eff, g_eff);
             }
-#ifndef BMC_CTL_EARLY
             // the (sp, g) pair of the sigma2 just drawn, for the recording wave: written here,
             // behind u, rather than between the sigma2 step and the draw it feeds (both are in
-            // front of barrier B1, after which the recorder reads them)
+            // front of barrier B1, after which the recorder reads them; tried there: slower,
+            // part of the three changes that took C2 from 0.9425 to 0.9411 us)
             if (lane == 0) { ctl[0] = sp_eff; ctl[3] = g_eff; }
-#endif
         }
         STAMP(0);
         __syncthreads();  // B1: u (and the previous sp, g / abort word) visible to all waves
@@ -272,27 +264,16 @@ void gibbs_loop_kernel(GibbsArgs a) {
         // ---- partial rss over this group's panels, then over the chain's groups ---------
         const double part = store.partial_rss(u_lds);
         constexpr bool LANEWISE = (MODE == MODE_REG && VEC == 1);
-#ifndef BMC_TAIL
-#define BMC_TAIL 1
-#endif
-        // (round 3) BMC_TAIL 1: the lane partials go to LDS at once, ahead of the abort test and
-        // the leader's prefetch (stamps had 216 cycles between the end of the pass and the LDS
-        // write -- on the leader's way to the group barrier, i.e. on every wave's).  2: the
-        // prefetch moved behind the publication of the group total as well -- slower (C2 0.945 ->
-        // 0.984 us): vmcnt counts in order, so the polls then wait for the prefetch's L2 misses.
-        // (BMC_TAIL 3: the same for the wave-sum form of the group sum -- two rows per lane,
-        // LDS-pinned and streamed panels: the wave's total goes to its slot before the abort test.
-        // Same-box A/B: C4 3.067 -> 3.057, C5 15.76 -> 15.80, 410 MB 62.0 -> 64.2 us: not the default)
-        constexpr bool EARLY = ((BMC_TAIL >= 1) && LANEWISE && !SINGLE) || ((BMC_TAIL == 3) && !SINGLE);
-        constexpr bool IDLE_PREFETCH = (BMC_TAIL == 2) && EARLY;
-        if constexpr (EARLY) {
-            if constexpr (LANEWISE) {
-                red[wave * 64 + lane] = part;
-            } else {
-                const double ws = wave_sum(part);
-                if (lane == 0) red[wave] = ws;
-            }
-        }
+        // The lane partials go to LDS at once, ahead of the abort test and the leader's prefetch
+        // (stamps had 216 cycles between the end of the pass and the LDS write -- on the leader's
+        // way to the group barrier, i.e. on every wave's).
+        // (tried: the prefetch moved behind the publication of the group total as well -- C2 0.945
+        // -> 0.984 us: vmcnt counts in order, so the polls then wait for the prefetch's L2 misses.
+        // Tried: the same early write for the wave-sum form of the group sum, the wave's total to
+        // its slot before the abort test -- C4 3.067 -> 3.057, C5 15.76 -> 15.80, 410 MB 62.0 ->
+        // 64.2 us: rejected)
+        constexpr bool EARLY = LANEWISE && !SINGLE;
+        if constexpr (EARLY) red[wave * 64 + lane] = part;
         {   // (the empty asm ties the test to `part`, or hipcc moves it back up)
             double abort_late = abort_w;
             asm volatile("" : "+v"(abort_late) : "v"(part));
@@ -302,12 +283,15 @@ void gibbs_loop_kernel(GibbsArgs a) {
         // behind the residual pass: issued in front of it, hipcc made wave 0's first FMA wait
         // for these loads (vmcnt is in-order and the panel registers were loaded "before" them
         // as far as the loop header can tell); the exchange hides them here
-        if constexpr (!SINGLE && !IDLE_PREFETCH) prefetch();
+        if constexpr (!SINGLE) prefetch();
         bool got;
-        auto idle_prefetch = [&]() { if constexpr (IDLE_PREFETCH) prefetch(); };
+        // (no idle work.  The empty closure is still passed: it gives this kernel an instantiation
+        // of the reduction of its own.  Sharing one with simplex_loop_kernel changes the order in
+        // which hipcc inlines the exchange into that kernel, and with it the register allocation
+        // of its LDS-pinned, streamed and two-rows-per-lane forms.)
         const double rss = group_allreduce<SINGLE, LANEWISE, (SMALLG ? 0 : -1), LOCALK, ROLE, EARLY>(
             part, red, gr + (size_t)(t & 1) * a.gran_stride, G, g, wave, nw, lane, epoch, local,
-            got STAMP_ARGS, idle_prefetch);
+            got STAMP_ARGS, [] {});
         STAMP(8);
         if (is_rec) {
             // row t = [u_t, .]; sigma of the PREVIOUS row (its sp, g were final at B1)
@@ -322,23 +306,15 @@ void gibbs_loop_kernel(GibbsArgs a) {
             if (__builtin_expect(!got, 0)) {
                 if (lane == 0) { ctl[1] = 1.0; a.status[chain] = 1; }
             } else {
-                // sigma2 | beta = scale_post / g_t, floored at 1e-6            (:50-52)
-                const double scale_post = (a.nu0_s20 + rss) * 0.5;
-                const bool floor_hit = scale_post < 1e-6 * gam_t;
-                sp_eff = floor_hit ? 1e-6 : scale_post;
-                g_eff = floor_hit ? 1.0 : gam_t;
-                sq_sp = BMC_SQRT_OF(sp_eff);
-#ifdef BMC_CTL_EARLY
-                if (lane == 0) { ctl[0] = sp_eff; ctl[3] = g_eff; }
-#endif
+                const Sigma2 s2 = sigma2_step(a.nu0_s20, rss, gam_t);
+                sp_eff = s2.sp;
+                g_eff = s2.g;
             }
             STAMP(6);
         }
     }
-#ifndef BMC_CTL_EARLY
     // (the last sigma2, for the row recorded behind the loop)
     if (is_leader && lane == 0 && ctl[1] == 0.0) { ctl[0] = sp_eff; ctl[3] = g_eff; }
-#endif
     };   // run_loop
     using I0 = std::integral_constant<int, 0>;
     using I1 = std::integral_constant<int, 1>;
@@ -371,7 +347,8 @@ void gibbs_loop_kernel(GibbsArgs a) {
 // Several chains per pass.  When the panels are streamed (or LDS-pinned), one read of X
 // serves CPP chains: wave c < CPP is the leader of chain c (its u, its granules, its sigma2
 // state, and -- in group 0 -- its recorded draws); all waves accumulate CPP partial sums per
-// panel column.  Arithmetic per chain is that of gibbs_loop_kernel, operation for operation.
+// panel column.  Arithmetic per chain is that of gibbs_loop_kernel: the same draw_u and
+// sigma2_step, the lane-wise group sum through the same sum_wave_rows (bmc_loop.h).
 // ======================================================================================
 // SLOTTED: one bundle per XCD slot (bundle_slots > 0), which implies G <= 32: the one-level
 // exchange is known at compile time and the two-level code leaves the loop.
@@ -402,7 +379,6 @@ __global__ __launch_bounds__(512) void gibbs_multi_kernel(GibbsArgs a) {
     const int nw = blockDim.x >> 6;
     const int64_t T_it = a.iters;
     gu64* gran0 = a.gran + (size_t)chain0 * 3 * a.gran_stride;   // this bundle's first chain
-#ifndef BMC_NO_XCD_REMAP
     // team j on XCD j whichever XCD the launch starts on (see gibbs_loop_kernel)
     if (!SLOTTED && G > 32 && (G & 7) == 0) {
         __shared__ int rot_c;
@@ -413,7 +389,6 @@ __global__ __launch_bounds__(512) void gibbs_multi_kernel(GibbsArgs a) {
         __syncthreads();
         if (rot_c >= 0) g = (g & ~7) | ((g + rot_c) & 7);
     }
-#endif
 
     const LdsPlan L = lds_plan(K, (int)sizeof(T), RP, a.panels_per_group, MODE == MODE_LDS, 0, CPP,
                                LANEWISE ? CPP : 1);
@@ -468,7 +443,7 @@ __global__ __launch_bounds__(512) void gibbs_multi_kernel(GibbsArgs a) {
     double* u_mine = u_lds + (size_t)chain_l * kpad;
 
     __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): see gibbs_loop_kernel
-    double sp_eff = a.sigma2_init, g_eff = 1.0, sq_sp = BMC_SQRT_OF(a.sigma2_init);
+    double sp_eff = a.sigma2_init, g_eff = 1.0;
     double xi_next[KCH], lam_r[KCH], c1_r[KCH], c2_r[KCH];
     double gam_next = 0.0;
     if (leader) {
@@ -499,7 +474,7 @@ __global__ __launch_bounds__(512) void gibbs_multi_kernel(GibbsArgs a) {
                 const int j = ch * 64 + lane;
                 u_rec[ch] = 0.0;
                 if (ch * 64 < K && j < K) {
-                    u_rec[ch] = draw_u(lam_r[ch], c1_r[ch], c2_r[ch], xi_next[ch], sp_eff, g_eff, sq_sp);
+                    u_rec[ch] = draw_u(lam_r[ch], c1_r[ch], c2_r[ch], xi_next[ch], sp_eff, g_eff);
                     u_mine[j] = u_rec[ch];
                 }
             }
@@ -597,11 +572,9 @@ __global__ __launch_bounds__(512) void gibbs_multi_kernel(GibbsArgs a) {
             if (__builtin_expect(!got, 0)) {
                 if (lane == 0) { ctl[1] = 1.0; a.status[chain] = 1; }
             } else {
-                const double scale_post = (a.nu0_s20 + rss) * 0.5;
-                const bool floor_hit = scale_post < 1e-6 * gam_t;
-                sp_eff = floor_hit ? 1e-6 : scale_post;
-                g_eff = floor_hit ? 1.0 : gam_t;
-                sq_sp = BMC_SQRT_OF(sp_eff);
+                const Sigma2 s2 = sigma2_step(a.nu0_s20, rss, gam_t);
+                sp_eff = s2.sp;
+                g_eff = s2.g;
             }
         }
         GSTAMP(6);
@@ -623,9 +596,9 @@ __global__ __launch_bounds__(512) void gibbs_multi_kernel(GibbsArgs a) {
 // an iteration costs K^2 FMAs and touches no data.  u0 is the least-squares point, where
 // rss(u0) is smallest and both other terms vanish to first order, so nothing cancels: every
 // term is >= 0 or tiny.  One wave per chain (lane j = component j, row j of G in registers),
-// no barriers, no exchange; any number of chains per launch.  The draw u is computed with the
-// operations of gibbs_loop_kernel, so a chain differs from the data-pass chain only through
-// the rounding of rss.
+// no barriers, no exchange; any number of chains per launch.  The draw and the sigma2 step are
+// draw_u and sigma2_step, as in gibbs_loop_kernel, so a chain differs from the data-pass chain
+// only through the rounding of rss.
 // ======================================================================================
 template <int KMAX>
 __global__ __launch_bounds__(64) void gibbs_gram_kernel(GramArgs a) {
@@ -648,7 +621,7 @@ __global__ __launch_bounds__(64) void gibbs_gram_kernel(GramArgs a) {
     const double c2 = act ? a.c2[lane] : 0.0, u0 = act ? a.u0[lane] : 0.0;
     const double g0x2 = act ? 2.0 * a.g0[lane] : 0.0;
     d_lds[lane] = 0.0;
-    double sp_eff = a.sigma2_init, g_eff = 1.0, sq_sp = BMC_SQRT_OF(a.sigma2_init);
+    double sp_eff = a.sigma2_init, g_eff = 1.0;
     double sp_cap = 1.0, g_cap = 1.0;   // lane i: the (sp, g) pair behind staged row i
     double xi_next = (act && T_it > 0) ? xi[lane] : 0.0;
     double gam_next = T_it > 0 ? gam[0] : 1.0;
@@ -656,8 +629,8 @@ __global__ __launch_bounds__(64) void gibbs_gram_kernel(GramArgs a) {
     __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): see gibbs_wave_kernel
     for (int64_t t = 0; t < T_it; ++t) {
         const int slot = (int)(t & 63);
-        // u | sigma2, the operations of gibbs_loop_kernel (lanes K .. 63: all inputs 0, u = 0)
-        const double u = draw_u(lam, c1, c2, xi_next, sp_eff, g_eff, sq_sp);
+        // u | sigma2 (lanes K .. 63: all inputs 0, u = 0)
+        const double u = draw_u(lam, c1, c2, xi_next, sp_eff, g_eff);
         const double gam_t = gam_next;
         {
             const int64_t tn = t + 1 < T_it ? t + 1 : t;
@@ -680,12 +653,9 @@ __global__ __launch_bounds__(64) void gibbs_gram_kernel(GramArgs a) {
         const double q = wave_sum(d * (gd - g0x2));
         double rss = a.rss0 + q;
         rss = rss > 0.0 ? rss : 0.0;
-        // sigma2 | beta = scale_post / g_t, floored at 1e-6            (:50-52)
-        const double scale_post = (a.nu0_s20 + rss) * 0.5;
-        const bool floor_hit = scale_post < 1e-6 * gam_t;
-        sp_eff = floor_hit ? 1e-6 : scale_post;
-        g_eff = floor_hit ? 1.0 : gam_t;
-        sq_sp = BMC_SQRT_OF(sp_eff);
+        const Sigma2 s2 = sigma2_step(a.nu0_s20, rss, gam_t);
+        sp_eff = s2.sp;
+        g_eff = s2.g;
         const bool mine = lane == slot;
         sp_cap = mine ? sp_eff : sp_cap;
         g_cap = mine ? g_eff : g_cap;
@@ -708,8 +678,9 @@ __global__ __launch_bounds__(64) void gibbs_gram_kernel(GramArgs a) {
 // the same chain (gibbs_loop_kernel<.., SINGLE>: 5 waves, two barriers, u and the lane
 // partials through LDS) spends ~1340 cycles per iteration at N = 629, K = 3, nearly all of it
 // hand-over latency.  Any number of chains per launch, one wave each.
-// The draw and the sigma2 step are those of gibbs_loop_kernel; per row the residual is the
-// chain acc = y, acc = fma(-x_j, u_j, acc), j ascending, rows summed into two accumulators.
+// The draw and the sigma2 step are draw_u and sigma2_step, as in every Gibbs kernel; per row the
+// residual is the chain acc = y, acc = fma(-x_j, u_j, acc), j ascending, rows summed into two
+// accumulators.
 // ======================================================================================
 template <typename T, int RMAX, int KMAX, int NWMAX = 1>
 __global__ __launch_bounds__(64 * NWMAX) void gibbs_wave_kernel(GibbsArgs a) {
@@ -765,7 +736,7 @@ __global__ __launch_bounds__(64 * NWMAX) void gibbs_wave_kernel(GibbsArgs a) {
     __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
     for (int64_t t = 0; t < T_it; ++t) {
         const int slot = (int)(t & 63);
-        const double u = draw_u(lam, c1, c2, xi_next, sp_eff, g_eff, 0.0);
+        const double u = draw_u(lam, c1, c2, xi_next, sp_eff, g_eff);
         const double gam_t = gam_next;
         {   // next iteration's variates (clamped index: no branch around the loads)
             const int64_t tn = t + 1 < T_it ? t + 1 : t;
@@ -800,11 +771,9 @@ __global__ __launch_bounds__(64 * NWMAX) void gibbs_wave_kernel(GibbsArgs a) {
             rss = (ws[0] + ws[1]) + (ws[2] + ws[3]);
             if constexpr (NWMAX > 4) rss += (ws[4] + ws[5]) + (ws[6] + ws[7]);
         }
-        // sigma2 | beta = scale_post / g_t, floored at 1e-6            (:50-52)
-        const double scale_post = (a.nu0_s20 + rss) * 0.5;
-        const bool floor_hit = scale_post < 1e-6 * gam_t;
-        sp_eff = floor_hit ? 1e-6 : scale_post;
-        g_eff = floor_hit ? 1.0 : gam_t;
+        const Sigma2 s2 = sigma2_step(a.nu0_s20, rss, gam_t);
+        sp_eff = s2.sp;
+        g_eff = s2.g;
         // The recorded sigma_t = sqrt(sp / g) is a correctly rounded division and square root,
         // ~35 dependent f64 operations that nothing in this wave can hide.  Lane (t mod 64)
         // keeps the pair instead, and every 64 iterations all lanes take their roots at once
