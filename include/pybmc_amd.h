@@ -399,6 +399,32 @@ int bmc_psis_loo_predict_device(bmc_ctx* ctx, const void* dA, int64_t n_points, 
                                 double* pareto_k_out, double* lppd_out, double* loo_mean_out,
                                 double* loo_sd_out, double* loo_pit_out, double* ess_out);
 
+/* ---- exact K-fold / leave-group-out cross-validation, all folds in one call -------------------
+ * A (n x k host f64, k <= 64, element (i, j) as in bmc_pointwise_loglik), y [n], fold [n] labels in
+ * 0 .. n_folds-1 (2 <= n_folds <= 1024; no fold empty; every training set, the rows of the OTHER
+ * folds, of at least k rows), the prior of bmc_set_prior.  For every fold f the posterior given
+ * its training rows is sampled by n_chains chains of `iters` iterations: chain (f, c) consumes the
+ * streams of seeds[f * n_chains + c] and is, up to the rounding of its residual sums, the chain
+ * bmc_gibbs_run draws on those rows under that seed (same conditionals, initial sigma2, gamma
+ * shape (nu0 + n_train) / 2, ridge and floors).  The first `burn` draws of a chain are dropped,
+ * every `thin`-th of the rest kept (kept = ceil((iters - burn) / thin); n_chains * kept >= 2) and
+ * the chains of a fold pooled: S = n_chains * kept draws.  For every row i, with f its own fold:
+ *   elpd_out[i]   logsumexp_s ll[i][s] - log S over the draws of fold f   (ll: bmc_pointwise_loglik)
+ *   mean_out[i]   a_i . mean_s beta_s
+ *   draws_out     [n_folds][n_chains][kept][k+1], rows [beta, sigma]; may be NULL
+ * The training statistics of all folds come from one pass over the rows (per-fold Gram on the
+ * matrix cores, total minus own), all n_folds * n_chains chains run one wave each in launches of
+ * at most 2048, in as many batches of folds as the free device memory asks for.  The resident
+ * problem and prior of the context are not touched.  Deterministic.
+ * BMC_EINVAL for bad arguments (the message names the offending fold), BMC_ESINGULAR when C0 or
+ * the training Gram of a fold is numerically singular (the message names the fold), BMC_ENOMEM
+ * when not even one fold's chains fit the device.  INTEGRATION.md section 11. */
+int bmc_kfold_cv(bmc_ctx* ctx, const double* A, int64_t n, int32_t k, int64_t lda, int layout,
+                 const double* y, const int64_t* fold, int32_t n_folds, const double* b0,
+                 const double* C0, double nu0, double sigma20, int32_t n_chains, int64_t iters,
+                 int64_t burn, int64_t thin, const uint64_t* seeds, double* elpd_out,
+                 double* mean_out, double* draws_out);
+
 /* ---- on-device variates (exposed so the generator itself can be tested) ----
  * normals_out [count_normal] ~ N(0,1); gammas_out [count_gamma] ~ Gamma(shape,1). */
 int bmc_rng_fill(bmc_ctx* ctx, uint64_t seed, int64_t count_normal, double* normals_out,

@@ -4,6 +4,7 @@ Public names follow the reference package (pybmc/__init__.py:11-24); the
 nonexistent ``Model`` of its ``__all__`` is dropped.
 """
 from .bmc import BayesianModelCombination
+from .cv import fold_labels, kfold_cv
 from .data import Dataset
 from .diagnostics import chain_diagnostics
 from .inference_utils import gibbs_sampler, gibbs_sampler_simplex, USVt_hat_extraction
@@ -23,4 +24,6 @@ __all__ = [
     "waic",
     "psis_loo",
     "psis_loo_predict",
+    "kfold_cv",
+    "fold_labels",
 ]

@@ -106,6 +106,10 @@ PROTOTYPES = {
                                        C.c_int64, C.c_int64, _D, _D, _D, _D, _D, _D, _D]),
     "bmc_psis_loo_predict_device": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int, _P,
                                               _P, C.c_int64, C.c_int64, _D, _D, _D, _D, _D, _D, _D]),
+    "bmc_kfold_cv": (C.c_int, [_P, _D, C.c_int64, C.c_int32, C.c_int64, C.c_int, _D,
+                               C.POINTER(C.c_int64), C.c_int32, _D, _D, C.c_double, C.c_double,
+                               C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_uint64), _D,
+                               _D, _D]),
     "bmc_rng_fill": (C.c_int, [_P, C.c_uint64, C.c_int64, _D, C.c_double, C.c_int64, _D]),
     "bmc_philox_raw": (C.c_int, [_P, C.c_uint64, C.c_uint32, C.c_int64, C.POINTER(C.c_uint32)]),
 }
@@ -172,6 +176,11 @@ def _dptr(a):
 
 class BmcError(RuntimeError):
     pass
+
+
+class SingularFoldError(BmcError, np.linalg.LinAlgError):
+    """A fold of ``kfold_cv`` whose training Gram is numerically singular (BMC_ESINGULAR): the
+    library's error, and the ``LinAlgError`` a refit of that fold would raise."""
 
 
 class Context:
@@ -599,6 +608,30 @@ class Context:
         the caller orders its producers before the call."""
         return self._score_call(self._lib.bmc_psis_loo_predict_device, self.LOO_PREDICT_KEYS, _P,
                                 dA, n, k, lda, layout, dy, dtheta, n_draws, ldt)
+
+    # -- exact K-fold / leave-group-out cross-validation --------------------------------------------
+    def kfold_cv(self, A, n, k, lda, layout, y, fold, n_folds, b0, C0, nu0, sigma20, n_chains, iters,
+                 burn, thin, seeds, return_draws=False):
+        """bmc_kfold_cv of HOST arrays: A's element (i, j) as in pointwise_loglik, y [n] f64, fold
+        [n] int64 labels, seeds [n_folds * n_chains] uint64.  Returns (elpd_cv_i [n], cv_mean_i [n],
+        draws (n_folds, n_chains, kept, k+1) or None).  A singular fold raises SingularFoldError."""
+        kept = max(0, -(-(int(iters) - int(burn)) // int(thin)))
+        elpd, mean = np.empty(n), np.empty(n)
+        draws = np.empty((n_folds, n_chains, kept, k + 1)) if return_draws else None
+        b0 = np.ascontiguousarray(b0, dtype=np.float64)
+        C0 = np.ascontiguousarray(C0, dtype=np.float64)
+        fold = np.ascontiguousarray(fold, dtype=np.int64)
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+        rc = self._lib.bmc_kfold_cv(
+            self._h, _dptr(A), int(n), int(k), int(lda), int(layout), _dptr(y),
+            fold.ctypes.data_as(C.POINTER(C.c_int64)), int(n_folds), _dptr(b0), _dptr(C0),
+            float(nu0), float(sigma20), int(n_chains), int(iters), int(burn), int(thin),
+            seeds.ctypes.data_as(C.POINTER(C.c_uint64)), _dptr(elpd), _dptr(mean), _dptr(draws))
+        if rc == BMC_ESINGULAR:
+            raise SingularFoldError(
+                (self._lib.bmc_last_error(self._h) or b"").decode("utf-8", "replace"))
+        self._check(rc)
+        return elpd, mean, draws
 
     # -- variates -----------------------------------------------------------------------
     def rng_fill(self, seed, n_normal=0, shape=1.0, n_gamma=0):

@@ -45,6 +45,7 @@ class BayesianModelCombination:
         self.centered_experiment_train = None
         self.U_hat = self.S_hat = self.Vt_hat = self.Vt_hat_normalized = None
         self._predictions_mean_train = None
+        self._train_df = None
         self.last_stats = None
         self._device_problem = None
 
@@ -100,6 +101,7 @@ class BayesianModelCombination:
         self.U_hat, self.S_hat = U_hat, S_hat
         self.Vt_hat, self.Vt_hat_normalized = Vt_hat, Vt_norm
         self._predictions_mean_train = mu
+        self._train_df = train_df
 
     # ------------------------------------------------------------------- train
     def train(self, training_options=None):
@@ -242,6 +244,66 @@ class BayesianModelCombination:
         out["predicted"] = out["loo_mean"] + mu
         out["truth"] = y + mu
         out["residual"] = y - out["loo_mean"]
+        return out
+
+    def cross_validate(self, n_folds=10, groups=None, training_options=None, seed=None):
+        """Exact K-fold or leave-group-out cross-validation of the combination (not in the
+        reference; ``pybmc_amd.cv.kfold_cv``): for every fold the Gibbs sampler is run on
+        ``U_hat`` and ``centered_experiment_train`` WITHOUT that fold's rows and the held-out rows
+        are scored against it -- all folds in one call on the GPU, no ``train()`` needed.
+
+        ``n_folds`` balanced random folds (``cv.fold_labels(n, n_folds, seed)``), or, with
+        ``groups``, one fold per distinct value: ``groups`` is a column name of the training frame
+        given to ``orthogonalize()`` or an array with one entry per training row (leave-group-out:
+        "what if this isotopic chain had not been measured?").  ``training_options`` are those of
+        ``train()`` with the same defaults (``iterations``, ``burn``, ``b_mean_prior``,
+        ``b_mean_cov``, ``nu0_chosen``, ``sigma20_chosen``, ``n_chains``) plus ``thin``; ``seed``
+        fixes the fold labels and the chains' seeds.  Gibbs sampler only: ``sampler == "simplex"``
+        raises ``ValueError``.
+
+        The SVD basis is held fixed: ``U_hat`` is the basis ``orthogonalize()`` made from ALL
+        training rows and is not recomputed per fold.  That basis depends on the model predictions
+        only, never on the truth, so no held-out truth reaches a fold's fit; it is the same
+        conditioning as ``loo()``, whose ``elpd_loo`` is therefore comparable with ``elpd_cv``.
+
+        Returns the dict of ``kfold_cv`` (``elpd_cv``, ``se``, ``cv_rmse``, ``elpd_fold``,
+        ``n_fold``, ``n_points``, ``n_folds``, ``n_draws``, ``elpd_cv_i``, ``cv_mean_i``, ``seeds``),
+        ``folds`` (the labels), ``groups`` (the distinct values, with ``groups``) and, in the
+        truth's units as ``loo_predict()``, ``predicted = cv_mean_i +`` the row mean of the model
+        predictions, ``truth`` and ``residual = truth - predicted``."""
+        if self.U_hat is None:
+            raise ValueError("Must call `orthogonalize()` before cross-validating.")
+        opts = training_options if training_options is not None else {}
+        if opts.get("sampler", "gibbs_sampling") == "simplex":
+            raise ValueError('cross_validate supports the Gibbs sampler only (sampler == "simplex")')
+        from .cv import fold_labels, group_labels, kfold_cv
+        y = np.asarray(self.centered_experiment_train, dtype=np.float64)
+        n, kc = self.U_hat.shape
+        values = None
+        if groups is not None:
+            if isinstance(groups, str):
+                if self._train_df is None or groups not in self._train_df.columns:
+                    raise ValueError(f"groups: the training frame has no column '{groups}'")
+                groups = self._train_df[groups].values
+            groups = np.asarray(groups)
+            if groups.shape != (n,):
+                raise ValueError(f"groups must have one entry per training row ({n},); got {groups.shape}")
+            folds, values = group_labels(groups)
+        else:
+            folds = fold_labels(n, n_folds, seed)
+        prior = [opts.get("b_mean_prior", np.zeros(kc)), opts.get("b_mean_cov", np.diag(self.S_hat ** 2)),
+                 opts.get("nu0_chosen", 1.0), opts.get("sigma20_chosen", 0.02)]
+        out = kfold_cv(np.asarray(self.U_hat, dtype=np.float64), y, prior, folds,
+                       opts.get("iterations", 50000), burn=opts.get("burn", 10000),
+                       thin=opts.get("thin", 1), n_chains=int(opts.get("n_chains", 1)), seed=seed,
+                       device=self.device)
+        mu = np.asarray(self._predictions_mean_train, dtype=np.float64)
+        out["folds"] = folds
+        if values is not None:
+            out["groups"] = values
+        out["predicted"] = out["cv_mean_i"] + mu
+        out["truth"] = y + mu
+        out["residual"] = y - out["cv_mean_i"]
         return out
 
     def log_predictive_density(self, X, burn=0):

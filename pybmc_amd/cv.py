@@ -1,0 +1,153 @@
+"""Exact K-fold and leave-group-out cross-validation on the GPU, every fold in one call.
+
+PSIS-LOO (``pybmc_amd.scoring.psis_loo``) estimates what leaving ONE point out would do, from one
+fit, and says where it cannot be trusted (``pareto_k > 0.7``).  The remedy there, and the only way
+to ask "what if this whole group had not been measured?", is to refit without the rows in question.
+``kfold_cv`` does those refits exactly, all at once.  Rows carry integer labels ``folds[i]`` in
+``0 .. F-1``; for every fold f
+
+* the **training rows** are those with ``folds != f``;
+* the **posterior** is that of ``gibbs_sampler(y[train], A[train], iterations, prior_info)``: the
+  same conditionals, initial sigma^2, gamma shape ``(nu0 + n_train) / 2``, ridge and floors, and
+  chain (f, c) consumes the variate streams of ``seeds[f, c]`` -- it is the chain
+  ``gibbs_sampler(..., seeds=[seeds[f, c]])`` draws on those rows up to the rounding of its
+  residual sums of squares, which come from sufficient statistics (``rss="gram"``);
+* the **held-out rows** ``folds == f`` are scored against the S pooled kept draws of fold f (the
+  first ``burn`` draws of a chain dropped, every ``thin``-th of the rest kept):
+  ``elpd_cv_i = logsumexp_s ll[i, s] - log S`` with ``ll`` of ``pybmc_amd.scoring``, and
+  ``cv_mean_i = a_i . mean_s beta_s``.
+
+On the host, in float64: ``elpd_cv = sum_i elpd_cv_i``, ``se = sqrt(n var_i(elpd_cv_i, ddof=1))``,
+``cv_rmse = sqrt(mean_i (y_i - cv_mean_i)^2)``, ``elpd_fold[f]`` and ``n_fold[f]``.
+
+On the device (``kernels_cv.hip``): the rows are gathered into fold order once, one pass on the
+matrix cores gives the Gram of every fold's own rows, and the training statistics of fold f are the
+total minus its own.  The F x C chains then run from those statistics alone, one wave each, in
+launches of at most 2048 chains.  At most 64 columns and 1024 folds.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from .scoring import _check_int, _check_shapes, _host_matrix, _se, kept_draws
+
+MAX_K = 64
+MIN_FOLDS, MAX_FOLDS = 2, 1024
+
+
+def fold_labels(n, n_folds, seed=None):
+    """Balanced random fold labels: a random permutation of ``i % n_folds``, so fold sizes differ by
+    at most one.  ``seed`` makes them reproducible (``numpy.random.default_rng(seed)``)."""
+    n = _check_int("n", n, 1)
+    n_folds = _check_int("n_folds", n_folds, MIN_FOLDS)
+    if n_folds > n:
+        raise ValueError(f"n_folds = {n_folds} exceeds the number of rows ({n}): a fold would be empty")
+    return np.random.default_rng(seed).permutation(np.arange(n, dtype=np.int64) % n_folds)
+
+
+def group_labels(values):
+    """One fold per distinct value (leave-group-out): ``(labels, groups)`` with
+    ``groups[labels[i]] == values[i]``, the groups in sorted order."""
+    groups, labels = np.unique(np.asarray(values), return_inverse=True)
+    return labels.astype(np.int64).reshape(-1), groups
+
+
+def _check_folds(folds, n, k):
+    """int64 labels and F of valid fold labels; ValueError otherwise (no GPU needed)."""
+    f = np.asarray(folds)
+    if f.shape != (n,):
+        raise ValueError(f"folds must be ({n},); got {f.shape}")
+    if f.dtype == np.bool_ or not np.issubdtype(f.dtype, np.integer):
+        raise ValueError(f"folds must be integer labels; got dtype {f.dtype}")
+    f = f.astype(np.int64)
+    if f.min() < 0:
+        raise ValueError("fold labels must be integers in 0 .. n_folds - 1; got a negative label")
+    F = int(f.max()) + 1
+    if F < MIN_FOLDS or F > MAX_FOLDS:
+        raise ValueError(f"need between {MIN_FOLDS} and {MAX_FOLDS} folds; the labels name {F}")
+    count = np.bincount(f, minlength=F)
+    if (count == 0).any():
+        raise ValueError(f"fold {int(np.argmin(count > 0))} is empty (labels must be 0 .. n_folds - 1, "
+                         "every one used)")
+    short = np.nonzero(n - count < k)[0]
+    if short.size:
+        raise ValueError(f"fold {int(short[0])}: its training set has {int(n - count[short[0]])} rows, "
+                         f"fewer than k = {k}")
+    return f, F, count
+
+
+def _check_seeds(seed, seeds, F, C):
+    from .chains import chain_seeds
+    if seeds is not None and seed is not None:
+        raise ValueError("give seed or seeds, not both")
+    if seeds is None:
+        if seed is None:
+            from .inference_utils import _draw_seeds
+            seed = int(_draw_seeds(1)[0])
+        return chain_seeds(int(seed), np.arange(F * C)).reshape(F, C)
+    s = np.asarray(seeds)
+    if s.shape != (F, C):
+        raise ValueError(f"seeds must be (n_folds, n_chains) = ({F}, {C}); got {s.shape}")
+    return s.astype(np.uint64)
+
+
+def cv_summary(y, folds, n_folds, elpd_i, mean_i, n_draws):
+    """The host summary of the module docstring from the pointwise vectors (float64)."""
+    e = np.asarray(elpd_i, dtype=np.float64)
+    m = np.asarray(mean_i, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64)
+    return {"elpd_cv": float(np.sum(e)), "se": _se(e),
+            "cv_rmse": float(np.sqrt(np.mean((y - m) ** 2))),
+            "elpd_fold": np.bincount(folds, weights=e, minlength=n_folds),
+            "n_fold": np.bincount(folds, minlength=n_folds), "n_points": int(e.shape[0]),
+            "n_folds": int(n_folds), "n_draws": int(n_draws)}
+
+
+def kfold_cv(A, y, prior_info, folds, iterations, burn=0, thin=1, n_chains=1, seed=None, seeds=None,
+             return_draws=False, device=0):
+    """Exact cross-validation over the folds named by ``folds`` (module docstring).
+
+    ``A`` is ``(n, k)`` float64 with k <= 64 (either memory order), ``y`` ``(n,)``, ``prior_info =
+    [b_mean_prior, b_mean_cov, nu0, sigma20]`` as ``gibbs_sampler`` takes it, ``folds`` ``(n,)``
+    integer labels ``0 .. F-1`` (``fold_labels``, ``group_labels``), 2 <= F <= 1024, every label
+    used and every training set of at least k rows.  Every fold runs ``n_chains`` chains of
+    ``iterations`` iterations; ``seeds`` is ``(F, n_chains)`` uint64, or derived from ``seed`` as
+    ``chains.chain_seeds(seed, f * n_chains + c)``, or drawn like ``gibbs_sampler`` draws its own.
+    Returns a dict: ``elpd_cv``, ``se``, ``cv_rmse``, ``elpd_fold``, ``n_fold``, ``n_points``,
+    ``n_folds``, ``n_draws`` (pooled kept draws per fold), the pointwise ``elpd_cv_i`` and
+    ``cv_mean_i``, ``seeds``, and with ``return_draws`` the ``draws`` ``(F, n_chains, kept, k+1)``.
+    Argument errors are ``ValueError`` before any GPU work; a fold whose training Gram is
+    numerically singular raises ``_lib.SingularFoldError`` naming it."""
+    from . import _lib
+
+    A = np.asarray(A)
+    y = np.asarray(y)
+    if A.dtype != np.float64 or y.dtype != np.float64:
+        raise ValueError("A and y must be float64")
+    iterations = _check_int("iterations", iterations, 1)
+    n_chains = _check_int("n_chains", n_chains, 1)
+    # (the draws this call will make, as the shape of samples scoring checks)
+    k1 = (A.shape[1] if A.ndim == 2 else 0) + 1
+    n, k, C, T, kept = _check_shapes(A.shape, y.shape, (n_chains, iterations, k1), burn, thin)
+    if k > MAX_K:
+        raise ValueError(f"k must be at most {MAX_K} (one lane per coefficient); got {k}")
+    if burn >= iterations:
+        raise ValueError(f"burn = {burn} leaves no draw of {iterations} iterations")
+    f, F, count = _check_folds(folds, n, k)
+    b0, C0, nu0, s20 = prior_info
+    b0 = np.asarray(b0, dtype=np.float64)
+    C0 = np.asarray(C0, dtype=np.float64)
+    if b0.shape != (k,) or C0.shape != (k, k):
+        raise ValueError(f"prior_info must hold b_mean_prior ({k},) and b_mean_cov ({k}, {k})")
+    seeds = _check_seeds(seed, seeds, F, C)
+    Ah, lda, layout = _host_matrix(A)
+    ctx = _lib.default_context(device)
+    with ctx.lock:
+        elpd_i, mean_i, draws = ctx.kfold_cv(Ah, n, k, lda, layout, np.ascontiguousarray(y), f, F, b0,
+                                             C0, nu0, s20, C, T, int(burn), int(thin), seeds.reshape(-1),
+                                             return_draws=return_draws)
+    out = cv_summary(y, f, F, elpd_i, mean_i, C * kept)
+    out.update(elpd_cv_i=elpd_i, cv_mean_i=mean_i, seeds=seeds)
+    if return_draws:
+        out["draws"] = draws
+    return out
