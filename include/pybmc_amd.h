@@ -425,6 +425,35 @@ int bmc_kfold_cv(bmc_ctx* ctx, const double* A, int64_t n, int32_t k, int64_t ld
                  int64_t burn, int64_t thin, const uint64_t* seeds, double* elpd_out,
                  double* mean_out, double* draws_out);
 
+/* ---- posterior predictive check: do data replicated from the fit look like the data? ----------
+ * Model and arguments A, y, theta as bmc_pointwise_loglik; offset [n_points] or NULL (zeros).
+ * Replicated data y_rep[i][s] = a_i . beta_s + sigma_s z[i][s] + offset_i, z[i][s] the standard
+ * normal of (seed, i, s): Philox4x32-10 keyed by seed, counter (s lo, s hi, 0x50504353,
+ * (i >> 6) * 32 + (i & 31)), Box-Muller, the cosine half to the point with bit 5 of i clear and
+ * the sine half to point i + 32.  The n_points x n_draws matrix is never stored; it is reduced
+ * over the points, per draw:
+ *   t_rep_out   [n_draws][8]: min, max, mean, sd, skew, kurt of y_rep[.][s] (central moments with
+ *               ddof 0: sd = sqrt(m2), skew = m3 / m2^1.5, kurt = m4 / m2^2 - 3; accumulated as
+ *               power sums of y_rep - center, so pass center = mean_i(y_i + offset_i)), then
+ *               sum_i z[i][s]^2 and max_i |z[i][s]|
+ *   t_obs2_out  [n_draws][2]: sum_i e^2 and max_i |e|, e = (y_i - a_i . beta_s) / sigma_s: the
+ *               observed counterparts of the last two (those of the first six do not depend on
+ *               the draw: the same functions of y + offset, left to the caller)
+ * Either output may be NULL.  The Bayesian p-value of statistic j is the share of draws with
+ * t_rep[s][j] >= t_obs[s][j].  One workgroup per 64 draws walks all points and nothing is
+ * combined across workgroups: the results depend on the arguments alone, not on the device.
+ * BMC_EINVAL as bmc_pointwise_loglik, and when n_points < 3 or n_points > 2^31.  Runs on the
+ * context's stream and leaves the problem, the prior and the predictive draws alone.
+ * bmc_ppc stages host arrays itself; the _device form reads caller-owned DEVICE memory (A, y,
+ * offset, theta); outputs are host pointers in both.  INTEGRATION.md section 12. */
+int bmc_ppc(bmc_ctx* ctx, const double* A, int64_t n_points, int32_t k, int64_t lda, int layout,
+            const double* y, const double* offset, const double* theta, int64_t n_draws,
+            int64_t ldt, uint64_t seed, double center, double* t_rep_out, double* t_obs2_out);
+int bmc_ppc_device(bmc_ctx* ctx, const void* dA, int64_t n_points, int32_t k, int64_t lda,
+                   int layout, const void* dy, const void* doffset, const void* dtheta,
+                   int64_t n_draws, int64_t ldt, uint64_t seed, double center, double* t_rep_out,
+                   double* t_obs2_out);
+
 /* ---- on-device variates (exposed so the generator itself can be tested) ----
  * normals_out [count_normal] ~ N(0,1); gammas_out [count_gamma] ~ Gamma(shape,1). */
 int bmc_rng_fill(bmc_ctx* ctx, uint64_t seed, int64_t count_normal, double* normals_out,

@@ -8,6 +8,7 @@ from .cv import fold_labels, kfold_cv
 from .data import Dataset
 from .diagnostics import chain_diagnostics
 from .inference_utils import gibbs_sampler, gibbs_sampler_simplex, USVt_hat_extraction
+from .ppc import PPC_STATS, posterior_predictive_check, ppc_summary
 from .sampling_utils import coverage, rndm_m_random_calculator
 from .scoring import pointwise_log_likelihood, psis_loo, psis_loo_predict, waic
 
@@ -26,4 +27,7 @@ __all__ = [
     "psis_loo_predict",
     "kfold_cv",
     "fold_labels",
+    "posterior_predictive_check",
+    "ppc_summary",
+    "PPC_STATS",
 ]

@@ -110,6 +110,10 @@ PROTOTYPES = {
                                C.POINTER(C.c_int64), C.c_int32, _D, _D, C.c_double, C.c_double,
                                C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_uint64), _D,
                                _D, _D]),
+    "bmc_ppc": (C.c_int, [_P, _D, C.c_int64, C.c_int32, C.c_int64, C.c_int, _D, _D, _D, C.c_int64,
+                          C.c_int64, C.c_uint64, C.c_double, _D, _D]),
+    "bmc_ppc_device": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int, _P, _P, _P,
+                                 C.c_int64, C.c_int64, C.c_uint64, C.c_double, _D, _D]),
     "bmc_rng_fill": (C.c_int, [_P, C.c_uint64, C.c_int64, _D, C.c_double, C.c_int64, _D]),
     "bmc_philox_raw": (C.c_int, [_P, C.c_uint64, C.c_uint32, C.c_int64, C.POINTER(C.c_uint32)]),
 }
@@ -608,6 +612,29 @@ class Context:
         the caller orders its producers before the call."""
         return self._score_call(self._lib.bmc_psis_loo_predict_device, self.LOO_PREDICT_KEYS, _P,
                                 dA, n, k, lda, layout, dy, dtheta, n_draws, ldt)
+
+    # -- posterior predictive check ---------------------------------------------------------------
+    def _ppc_call(self, fn, ptr, A, n, k, lda, layout, y, theta, n_draws, ldt, offset, seed, center):
+        t_rep = np.empty((int(n_draws), 8))
+        t_obs2 = np.empty((int(n_draws), 2))
+        self._check(fn(self._h, ptr(A), int(n), int(k), int(lda), int(layout), ptr(y),
+                       ptr(offset) if offset is not None else None, ptr(theta), int(n_draws),
+                       int(ldt), int(seed) & (2 ** 64 - 1), float(center), _dptr(t_rep),
+                       _dptr(t_obs2)))
+        return {"t_rep": t_rep, "t_obs2": t_obs2}
+
+    def ppc(self, A, n, k, lda, layout, y, theta, n_draws, ldt, offset, seed, center):
+        """The per-draw statistics of replicated data, t_rep (n_draws, 8), and the observed chi2
+        and max_abs_z, t_obs2 (n_draws, 2), of HOST f64 arrays (bmc_ppc); A, y and theta as
+        pointwise_loglik, offset [n] or None, center = mean(y + offset)."""
+        return self._ppc_call(self._lib.bmc_ppc, _dptr, A, n, k, lda, layout, y, theta, n_draws,
+                              ldt, offset, seed, center)
+
+    def ppc_device(self, dA, n, k, lda, layout, dy, dtheta, n_draws, ldt, doffset, seed, center):
+        """The same on DEVICE memory (bmc_ppc_device; doffset an address or None), read on the
+        context's stream: the caller orders its producers before the call."""
+        return self._ppc_call(self._lib.bmc_ppc_device, _P, dA, n, k, lda, layout, dy, dtheta,
+                              n_draws, ldt, doffset, seed, center)
 
     # -- exact K-fold / leave-group-out cross-validation --------------------------------------------
     def kfold_cv(self, A, n, k, lda, layout, y, fold, n_folds, b0, C0, nu0, sigma20, n_chains, iters,

@@ -331,6 +331,42 @@ class BayesianModelCombination:
         out["lppd"] = pw["lppd"]
         return out
 
+    def posterior_predictive_check(self, X=None, burn=0, seed=None):
+        """Posterior predictive check of the last ``train()`` (not in the reference;
+        ``pybmc_amd.ppc.posterior_predictive_check``): Bayesian p-values of eight test quantities
+        of data replicated from every draw against the observed data.  Without ``X`` on the
+        training data of ``loo()`` (``U_hat``, ``centered_experiment_train``), with the row mean of
+        the model predictions as the offset, so that ``min``, ``max``, ``mean``, ``sd``, ``skew`` and
+        ``kurt`` are in the truth's units.  With a DataFrame ``X`` (model columns and the truth
+        column) on held-out data, built as ``log_predictive_density`` builds it: design
+        ``preds Vt_hat'``, target ``truth - mean(preds)``, offset ``mean(preds)``.  ``burn`` more
+        draws are dropped from the start of each chain; ``seed`` fixes the replicated noise (None:
+        drawn from numpy's global stream and returned).  Returns that function's dict."""
+        from .ppc import posterior_predictive_check
+        if X is None:
+            if self.samples is None or self.U_hat is None:
+                raise ValueError("Must call `orthogonalize()` and `train()` before a posterior "
+                                 "predictive check.")
+            A = self.U_hat
+            y = np.asarray(self.centered_experiment_train, dtype=np.float64)
+            offset = np.asarray(self._predictions_mean_train, dtype=np.float64)
+        else:
+            if self.samples is None or self.Vt_hat is None:
+                raise ValueError("Must call `orthogonalize()` and `train()` before a posterior "
+                                 "predictive check.")
+            if not isinstance(X, pd.DataFrame):
+                raise ValueError(
+                    "X must be a pandas DataFrame containing model predictions and the truth column.")
+            if self.truth_column_name not in X.columns:
+                raise ValueError(f"X must contain the truth column '{self.truth_column_name}'.")
+            preds = np.asarray(X[self.models].values, dtype=np.float64)
+            truth = np.asarray(X[self.truth_column_name].values, dtype=np.float64)
+            A = preds @ np.asarray(self.Vt_hat, dtype=np.float64).T
+            offset = preds.mean(axis=1)
+            y = truth - offset
+        return posterior_predictive_check(A, y, self._chains(), burn=burn, offset=offset, seed=seed,
+                                          device=self.device)
+
     # ----------------------------------------------------------------- predict
     def _require_trained(self):
         if self.samples is None or self.Vt_hat is None:

@@ -95,6 +95,8 @@ struct bmc_ctx : CtxHandles {
     // PSIS-LOO (bmc_psis_loo*, bmc_psis_loo_predict*): the select state and candidate slots,
     // besides the score buffers
     DevBuf looWork;
+    // posterior predictive check (bmc_ppc*): the staged offset, the padded operands and the results
+    DevBuf ppcOff, ppcWork;
     double predict_ms[4] = {0, 0, 0, 0};   // last bmc_predict: h2d, gemm, order statistics, device
     // pooling over GPUs (bmc_comm_*): RCCL communicator bound to this context's device
     ncclComm_t comm = nullptr;

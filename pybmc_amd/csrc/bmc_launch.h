@@ -302,4 +302,25 @@ hipError_t launch_loo(const LooArgs& a, const LooPlan& p, hipStream_t s);
 double* loo_predict_out(const LooArgs& a, const LooPredictPlan& p);
 hipError_t launch_loo_predict(const LooArgs& a, const LooPredictPlan& p, hipStream_t s);
 
+// ---- posterior predictive check (kernels_ppc.hip; plan_ppc in bmc_plan.h) -------------------------
+// Replicated data y_rep[i][s] = a_i . beta_s + sigma_s z[i][s] + offset_i of the model and
+// arguments of launch_score, z from the STREAM_PPC variates of `seed`, reduced over
+// the points per draw and never stored.  t_rep [S][PPC_STATS]: min, max, mean, sd, skew, kurt of
+// y_rep[.][s] (moments with ddof 0, from the power sums of y_rep - center), sum_i z^2, max_i |z|;
+// t_obs2 [S][PPC_OBS]: sum_i ((y_i - a_i . beta_s) / sigma_s)^2 and max_i |y_i - a_i . beta_s| /
+// sigma_s.  offset may be NULL (zeros).  Work buffers (device, sized by ppc_buffers for the plan):
+// Ap, yo, Tp, sg.  No atomics, one workgroup per 64 draws: the bits depend on the arguments alone.
+struct PpcArgs {
+    const double* A;
+    const double* y;
+    const double* offset;
+    const double* theta;
+    int64_t n, lda, S, ldt;
+    int32_t k, col_major;
+    uint64_t seed;
+    double center;
+    double *Ap, *yo, *Tp, *sg, *t_rep, *t_obs2;
+};
+hipError_t launch_ppc(const PpcArgs& a, const PpcPlan& p, hipStream_t s);
+
 }  // namespace bmc

@@ -7,7 +7,8 @@
 // Also here: plan_score, the draw-split plan of the pointwise log-likelihood kernels
 // (kernels_waic.hip; tests/score_plan_check.cpp), and plan_loo, the pass and candidate plan of
 // the PSIS-LOO kernels (kernels_loo.hip; tests/loo_plan_check.cpp), with plan_loo_predict for the
-// leave-one-out predictive moments (tests/loo_predict_plan_check.cpp).
+// leave-one-out predictive moments (tests/loo_predict_plan_check.cpp), and plan_ppc, the plan of
+// the posterior predictive check (kernels_ppc.hip; tests/ppc_plan_check.cpp).
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -834,6 +835,64 @@ inline LooPredictBuffers loo_predict_buffers(const LooPredictPlan& p, int64_t n_
     b.pay = up(sp * n_pad * LOO_PREDICT_SUMS * 8);
     b.bucket = up(sp * n_pad * LOO_BUCKET_SUMS * 8);
     b.out = up((size_t)n_points * LOO_PREDICT_OUTS * 8);
+    return b;
+}
+
+// ---- posterior predictive check (kernels_ppc.hip) -------------------------------
+// The same never-stored points x draws matrix, reduced over the POINTS, per draw: a workgroup owns
+// SCORE_TILE draws and walks every point tile, so the roles of plan_score are swapped and there
+// is no split: one workgroup per draw tile, whatever the CU count (fewer than 64 x CUs draws leave
+// CUs idle; the bits do not depend on the device).  Both operands are padded to whole tiles: the
+// draws [S_pad][k_pad] (with sigma_s and 1 / sigma_s per draw) and the design [n_pad][k_pad] (with
+// y and the offset per point).  Refused (ok = false): fewer than PPC_MIN_POINTS points (skew and
+// kurt of fewer are constants), fewer than 2 draws, k outside 1 .. SCORE_MAX_K, more points than
+// PPC_MAX_POINTS (the noise counter carries the point pair in one 32-bit word).
+constexpr int PPC_STATS = 8;      // min, max, mean, sd, skew, kurt, chi2, max_abs_z (replicated)
+constexpr int PPC_OBS = 2;        // chi2, max_abs_z (observed: the two that depend on the draw)
+constexpr int64_t PPC_MIN_POINTS = 3;
+constexpr int64_t PPC_MAX_POINTS = (int64_t)1 << 31;
+
+struct PpcPlan {
+    int64_t point_tiles, draw_tiles;   // ceil(n / 64), ceil(S / 64)
+    int64_t n_pad, S_pad;              // whole tiles
+    int32_t k_pad;                     // whole 16-column slabs
+    int64_t grid;                      // workgroups: draw_tiles
+    int64_t rounds;                    // ceil(grid / (SCORE_GROUPS_PER_CU * n_cu)): 1 = one wave of groups
+    bool ok;
+};
+
+inline PpcPlan plan_ppc(int64_t n_points, int64_t n_draws, int32_t k, int n_cu) {
+    PpcPlan p{};
+    p.ok = n_points >= PPC_MIN_POINTS && n_points <= PPC_MAX_POINTS && n_draws >= 2 && k >= 1 &&
+           k <= SCORE_MAX_K && (n_draws + SCORE_TILE - 1) / SCORE_TILE <= 0x7fffffffll;
+    if (!p.ok) return p;
+    p.point_tiles = (n_points + SCORE_TILE - 1) / SCORE_TILE;
+    p.draw_tiles = (n_draws + SCORE_TILE - 1) / SCORE_TILE;
+    p.n_pad = p.point_tiles * SCORE_TILE;
+    p.S_pad = p.draw_tiles * SCORE_TILE;
+    p.k_pad = (k + 15) / 16 * 16;
+    p.grid = p.draw_tiles;
+    const int64_t slots = (int64_t)SCORE_GROUPS_PER_CU * (n_cu > 0 ? n_cu : 1);
+    p.rounds = (p.grid + slots - 1) / slots;
+    return p;
+}
+
+// Device work space of launch_ppc, in bytes
+struct PpcBuffers {
+    size_t Ap;    // [n_pad][k_pad] f64: the design, zero in the padding
+    size_t yo;    // [2][n_pad] f64: y, then the offset
+    size_t Tp;    // [S_pad][k_pad] f64: the coefficients of every draw, zero in the padding
+    size_t sg;    // [2][S_pad] f64: sigma_s, then 1 / sigma_s (1 in the padding)
+    size_t out;   // [S][PPC_STATS] then [S][PPC_OBS] f64
+    size_t total() const { return Ap + yo + Tp + sg + out; }
+};
+inline PpcBuffers ppc_buffers(const PpcPlan& p, int64_t n_draws) {
+    PpcBuffers b;
+    b.Ap = (size_t)p.n_pad * (size_t)p.k_pad * 8;
+    b.yo = (size_t)p.n_pad * 2 * 8;
+    b.Tp = (size_t)p.S_pad * (size_t)p.k_pad * 8;
+    b.sg = (size_t)p.S_pad * 2 * 8;
+    b.out = (size_t)n_draws * (PPC_STATS + PPC_OBS) * 8;
     return b;
 }
 

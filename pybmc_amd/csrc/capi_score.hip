@@ -1,6 +1,8 @@
 // C ABI, scoring a fit: the pointwise log predictive density (kernels_waic.hip),
 // PSIS-LOO and its predictive moments (kernels_loo.hip).  The three families
 // differ in their plan, their launcher and where their results lie; score_entry is the rest.
+// Also the posterior predictive check (kernels_ppc.hip): the same operands and
+// checks, results per draw instead of per point (ppc_entry).
 #include "bmc_ctx.h"
 
 namespace {
@@ -136,6 +138,58 @@ int score_entry(bmc_ctx* c, ScoreIn in, bool on_host, ScoreFamily family,
     return BMC_OK;
 }
 
+// One posterior predictive check: host operands are staged first (offset may be NULL: zeros),
+// then the plan, the launch, the two result blocks to the host and one sync.
+int ppc_entry(bmc_ctx* c, ScoreIn in, const void* offset, bool on_host, uint64_t seed, double center,
+              double* t_rep_out, double* t_obs2_out) {
+    int rc = check_score_args(c, in.A, in.n, in.k, in.lda, in.layout, in.y, in.theta, in.S, in.ldt);
+    if (rc) return rc;
+    const PpcPlan plan = plan_ppc(in.n, in.S, in.k, c->n_cu);
+    if (!plan.ok)
+        return fail(c, BMC_EINVAL, "n_points must be between " + std::to_string(PPC_MIN_POINTS) + " and " +
+                                       std::to_string(PPC_MAX_POINTS) + " for a posterior predictive check");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (on_host) {
+        if ((rc = score_stage(c, in))) return rc;
+        if (offset) {
+            if ((rc = ensure(c, c->ppcOff, (size_t)in.n * 8))) return rc;
+            HIPCHK(c, hipMemcpyAsync(c->ppcOff.p, offset, (size_t)in.n * 8, hipMemcpyHostToDevice, c->stream));
+            offset = c->ppcOff.p;
+        }
+    }
+    const PpcBuffers pb = ppc_buffers(plan, in.S);
+    if ((rc = ensure(c, c->ppcWork, pb.total()))) return rc;
+    char* w = (char*)c->ppcWork.p;
+    PpcArgs a;
+    a.A = (const double*)in.A;
+    a.y = (const double*)in.y;
+    a.offset = (const double*)offset;
+    a.theta = (const double*)in.theta;
+    a.n = in.n;
+    a.lda = in.lda;
+    a.S = in.S;
+    a.ldt = in.ldt;
+    a.k = in.k;
+    a.col_major = in.layout == BMC_COL_MAJOR;
+    a.seed = seed;
+    a.center = center;
+    a.Ap = (double*)w;
+    a.yo = (double*)(w += pb.Ap);
+    a.Tp = (double*)(w += pb.yo);
+    a.sg = (double*)(w += pb.Tp);
+    a.t_rep = (double*)(w += pb.sg);
+    a.t_obs2 = a.t_rep + (size_t)in.S * PPC_STATS;
+    HIPCHK(c, launch_ppc(a, plan, c->stream));
+    if (t_rep_out)
+        HIPCHK(c, hipMemcpyAsync(t_rep_out, a.t_rep, (size_t)in.S * PPC_STATS * 8, hipMemcpyDeviceToHost,
+                                 c->stream));
+    if (t_obs2_out)
+        HIPCHK(c, hipMemcpyAsync(t_obs2_out, a.t_obs2, (size_t)in.S * PPC_OBS * 8, hipMemcpyDeviceToHost,
+                                 c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return BMC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -187,6 +241,20 @@ int bmc_psis_loo_predict_device(bmc_ctx* c, const void* dA, int64_t n_points, in
     return score_entry(c, {dA, dy, dtheta, n_points, lda, n_draws, ldt, k, layout}, false,
                        loo_predict_family, {elpd_loo_out, pareto_k_out, lppd_out, loo_mean_out,
                                             loo_sd_out, loo_pit_out, ess_out});
+}
+
+int bmc_ppc(bmc_ctx* c, const double* A, int64_t n_points, int32_t k, int64_t lda, int layout,
+            const double* y, const double* offset, const double* theta, int64_t n_draws, int64_t ldt,
+            uint64_t seed, double center, double* t_rep_out, double* t_obs2_out) {
+    return ppc_entry(c, {A, y, theta, n_points, lda, n_draws, ldt, k, layout}, offset, true, seed, center,
+                     t_rep_out, t_obs2_out);
+}
+
+int bmc_ppc_device(bmc_ctx* c, const void* dA, int64_t n_points, int32_t k, int64_t lda, int layout,
+                   const void* dy, const void* doffset, const void* dtheta, int64_t n_draws, int64_t ldt,
+                   uint64_t seed, double center, double* t_rep_out, double* t_obs2_out) {
+    return ppc_entry(c, {dA, dy, dtheta, n_points, lda, n_draws, ldt, k, layout}, doffset, false, seed,
+                     center, t_rep_out, t_obs2_out);
 }
 
 }  // extern "C"

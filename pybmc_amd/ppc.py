@@ -1,0 +1,110 @@
+"""Posterior predictive checks of a sampled fit on the GPU: do data replicated from the fitted
+model look like the observed data?
+
+The reference package has no such check; this is a capability of this build.  The model is the
+one the samplers draw from, ``y_i ~ N(a_i . beta, sigma^2)``.  For design rows ``A`` (n x k),
+targets ``y``, offsets and S posterior draws ``(beta_s, sigma_s)``, replicated data are
+
+    y_rep[i, s] = a_i . beta_s + sigma_s z[i, s] + offset_i
+
+with ``z[i, s]`` a standard normal that depends on ``(seed, i, s)`` alone (the
+fifth variate stream: Philox4x32-10 keyed by the seed, counter ``(s lo, s hi, "PPCS", pair(i))``,
+``pair(i) = (i >> 6) * 32 + (i & 31)``, Box-Muller, the cosine half to the point with bit 5 of i
+clear, the sine half to point i + 32).  Eight test quantities are taken per draw, ``PPC_STATS``:
+
+* ``min``, ``max``, ``mean``, ``sd``, ``skew``, ``kurt``: ``T_rep[s]`` of ``y_rep[:, s]``, ``T_obs`` the
+  same function of ``y + offset`` (constant in s; host, float64).  With ``m_r = mean((x - mean x)^r)``
+  (ddof 0): ``sd = sqrt(m2)``, ``skew = m3 / m2^1.5``, ``kurt = m4 / m2^2 - 3``.
+* ``chi2``: ``T_rep[s] = sum_i z[i, s]^2``, ``T_obs[s] = sum_i ((y_i - a_i . beta_s) / sigma_s)^2``.
+* ``max_abs_z``: ``T_rep[s] = max_i |z[i, s]|``, ``T_obs[s] = max_i |y_i - a_i . beta_s| / sigma_s``.
+
+The Bayesian p-value of a quantity is ``mean_s 1[T_rep[s] >= T_obs[s]]`` (A. Gelman, X.-L. Meng,
+H. Stern, "Posterior predictive assessment of model fitness via realized discrepancies",
+Statistica Sinica 6, 1996): values near 0 or 1 say that the data are unlike what the fit
+replicates -- a noise model too narrow (``chi2``, ``sd`` near 0) or too wide (near 1), skewed or
+heavy-tailed residuals (``skew``, ``kurt``), a single outlier (``max_abs_z``, ``min``, ``max``).
+At least 3 points are needed; with exactly 3 ``kurt`` is -3/2 for any data, so its p-value compares
+two equal numbers and says nothing.
+
+On the device (``kernels_ppc.hip``) the n x S matrix is never stored: the f64 MFMA GEMM of the
+scoring kernels with the noise made in the epilogue and the tile reduced over the points, per
+draw; one workgroup per 64 draws and no combine across workgroups, so the result does not depend
+on the device.
+
+Out of scope: per-point posterior predictive p-values.  They reduce along the other axis, and they
+use every point twice (to fit and to check); ``psis_loo_predict()["loo_pit"]`` is the honest
+version of those.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from .scoring import _pointwise_call
+
+PPC_STATS = ("min", "max", "mean", "sd", "skew", "kurt", "chi2", "max_abs_z")
+MIN_POINTS = 3
+
+
+def marginal_stats(x):
+    """``min, max, mean, sd, skew, kurt`` of a vector as defined in the module docstring (host,
+    float64, moments about the mean with ddof 0)."""
+    x = np.asarray(x, dtype=np.float64)
+    mean = float(np.mean(x))
+    d = x - mean
+    m2, m3, m4 = (float(np.mean(d ** r)) for r in (2, 3, 4))
+    return np.array([np.min(x), np.max(x), mean, np.sqrt(m2), m3 / m2 ** 1.5, m4 / m2 ** 2 - 3.0])
+
+
+def ppc_summary(t_rep, t_obs):
+    """``{name: p-value}`` for the columns of ``t_rep`` and ``t_obs`` (both ``(S, 8)``, columns
+    ``PPC_STATS``): the share of draws with ``t_rep >= t_obs`` (host)."""
+    t_rep = np.asarray(t_rep, dtype=np.float64)
+    t_obs = np.asarray(t_obs, dtype=np.float64)
+    if t_rep.ndim != 2 or t_rep.shape[1] != len(PPC_STATS) or t_obs.shape != t_rep.shape:
+        raise ValueError(f"t_rep and t_obs must both be (n_draws, {len(PPC_STATS)}); got "
+                         f"{t_rep.shape} and {t_obs.shape}")
+    if t_rep.shape[0] < 1:
+        raise ValueError("t_rep must hold at least one draw")
+    return {name: float(np.mean(t_rep[:, j] >= t_obs[:, j])) for j, name in enumerate(PPC_STATS)}
+
+
+def _draw_seed():
+    # (as sampling_utils.rndm_m_random_calculator: 64 bits of numpy's global stream)
+    return int(np.random.randint(0, 2 ** 32, dtype=np.uint64)) << 32 | int(
+        np.random.randint(0, 2 ** 32, dtype=np.uint64))
+
+
+def posterior_predictive_check(A, y, samples, burn=0, thin=1, offset=None, seed=None, device=0):
+    """Posterior predictive check of a fit (module docstring).
+
+    ``A``, ``y``, ``samples``, ``burn``, ``thin`` and ``device`` as
+    ``pointwise_log_likelihood``, with at least 3 points.  ``offset`` is ``(n_points,)`` float64
+    (default zeros): added to the replicated and to the observed data of the six marginal
+    quantities, so that they can be read in the units of an un-centred target.  ``seed`` (uint64)
+    fixes the replicated noise; None draws one from numpy's global stream, and it is returned.
+
+    Returns a dict: ``p_value`` (``{name: p}`` for ``PPC_STATS``), ``t_rep`` and ``t_obs``
+    (``(n_draws, 8)``; the marginal columns of ``t_obs`` repeat one value), ``stats``
+    (``PPC_STATS``), ``n_points``, ``n_draws``, ``seed``.  Per-point p-values are out of scope:
+    see ``psis_loo_predict()["loo_pit"]``."""
+    if seed is None:
+        seed = _draw_seed()
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 2 ** 64:
+        raise ValueError("seed must be an integer in [0, 2^64) or None")
+    seed = int(seed)
+
+    def center(A, y, off):
+        return float(np.mean(y if off is None else y + off))
+
+    out = _pointwise_call("ppc", "ppc_device", A, y, samples, burn, thin, device,
+                          min_points=MIN_POINTS, vectors=(("offset", offset),),
+                          scalars=(seed, center))
+    y = np.asarray(y)
+    obs = marginal_stats(y if offset is None else y + np.asarray(offset))
+    t_rep = out["t_rep"]
+    t_obs = np.empty_like(t_rep)
+    t_obs[:, :6] = obs
+    t_obs[:, 6:] = out["t_obs2"]
+    return {"p_value": ppc_summary(t_rep, t_obs), "t_rep": t_rep, "t_obs": t_obs,
+            "stats": PPC_STATS, "n_points": int(y.shape[0]), "n_draws": int(t_rep.shape[0]),
+            "seed": seed}

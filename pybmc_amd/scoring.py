@@ -91,7 +91,7 @@ def kept_draws(T, burn, thin):
     return max(0, -(-(T - burn) // thin))
 
 
-def _check_shapes(a_shape, y_shape, s_shape, burn, thin):
+def _check_shapes(a_shape, y_shape, s_shape, burn, thin, min_points=1):
     """(n, k, C, T, kept per chain) of valid arguments; ValueError otherwise (no GPU needed)."""
     burn = _check_int("burn", burn, 0)
     thin = _check_int("thin", thin, 1)
@@ -100,6 +100,8 @@ def _check_shapes(a_shape, y_shape, s_shape, burn, thin):
     n, k = a_shape
     if n < 1:
         raise ValueError("A must hold at least one point")
+    if n < min_points:
+        raise ValueError(f"A must hold at least {min_points} points; got {n}")
     if k < 1 or k > MAX_K:
         raise ValueError(f"k must be between 1 and {MAX_K}; got {k}")
     if tuple(y_shape) != (n,):
@@ -133,11 +135,33 @@ def _host_matrix(A):
     return A, k, BMC_ROW_MAJOR
 
 
-def _pointwise_call(host_call, device_call, A, y, samples, burn, thin, device):
-    """The argument handling ``pointwise_log_likelihood`` and ``psis_loo`` share: checks, burn /
-    thin / pooling in place where the strides allow it, then the context method named
-    ``host_call`` (numpy draws) or ``device_call`` (CUDA tensor draws)."""
+def _point_vectors(vectors, n):
+    """The extra per-point vectors of ``_pointwise_call``: each None or float64 ``(n,)``."""
+    out = []
+    for name, v in vectors:
+        if v is not None:
+            v = np.asarray(v)
+            if v.dtype != np.float64:
+                raise ValueError(f"{name} must be float64; got {v.dtype}")
+            if v.shape != (n,):
+                raise ValueError(f"{name} must be ({n},); got {v.shape}")
+            v = np.ascontiguousarray(v)
+        out.append(v)
+    return out
+
+
+def _pointwise_call(host_call, device_call, A, y, samples, burn, thin, device, min_points=1,
+                    vectors=(), scalars=()):
+    """The argument handling the scoring calls and the posterior predictive check share: checks,
+    burn / thin / pooling in place where the strides allow it, then the context method named
+    ``host_call`` (numpy draws) or ``device_call`` (CUDA tensor draws).  ``vectors`` are further
+    ``(name, array or None)`` per-point inputs, checked like ``y`` and handed over after the
+    common arguments as host arrays or device addresses; ``scalars`` follow them, either plain
+    values or functions of the checked ``(A, y, *vectors)``."""
     from . import _lib
+
+    def tail(A, y, vecs):
+        return [f(A, y, *vecs) if callable(f) else f for f in scalars]
 
     if _is_torch(samples) and not samples.is_cuda:
         samples = samples.numpy()
@@ -149,7 +173,9 @@ def _pointwise_call(host_call, device_call, A, y, samples, burn, thin, device):
         import torch
         if samples.dtype != torch.float64:
             raise ValueError(f"samples must be float64; got {samples.dtype}")
-        n, k, C, T, kept = _check_shapes(A.shape, y.shape, tuple(samples.shape), burn, thin)
+        n, k, C, T, kept = _check_shapes(A.shape, y.shape, tuple(samples.shape), burn, thin,
+                                         min_points)
+        vecs = _point_vectors(vectors, n)
         t = samples if samples.dim() == 3 else samples.unsqueeze(0)
         if t.stride(2) != 1 or t.stride(1) < k + 1:
             raise ValueError("a device tensor must have a contiguous last dimension")
@@ -162,17 +188,21 @@ def _pointwise_call(host_call, device_call, A, y, samples, burn, thin, device):
         ctx = _lib.default_context(dev.index if dev.index is not None else device)
         Ad = torch.as_tensor(np.ascontiguousarray(A), device=dev)
         yd = torch.as_tensor(np.ascontiguousarray(y), device=dev)
+        vd = [None if v is None else torch.as_tensor(v, device=dev) for v in vecs]
         # the library reads on its own stream: what torch queued (the uploads above, the
         # producer of `samples`) must be done first (cf. diagnostics.chain_diagnostics)
         torch.cuda.current_stream(dev).synchronize()
         with ctx.lock:
             return getattr(ctx, device_call)(Ad.data_ptr(), n, k, k, _lib.BMC_ROW_MAJOR,
-                                             yd.data_ptr(), t.data_ptr(), C * kept, ld)
+                                             yd.data_ptr(), t.data_ptr(), C * kept, ld,
+                                             *(None if v is None else v.data_ptr() for v in vd),
+                                             *tail(A, y, vecs))
 
     s = np.asarray(samples)
     if s.dtype != np.float64:
         raise ValueError(f"samples must be float64; got {s.dtype}")
-    n, k, C, T, kept = _check_shapes(A.shape, y.shape, s.shape, burn, thin)
+    n, k, C, T, kept = _check_shapes(A.shape, y.shape, s.shape, burn, thin, min_points)
+    vecs = _point_vectors(vectors, n)
     s = (s if s.ndim == 3 else s[None])[:, burn::thin]
     st = s.strides
     if st[2] == 8 and st[1] % 8 == 0 and st[1] >= 8 * (k + 1) and (C == 1 or st[0] == kept * st[1]):
@@ -184,7 +214,8 @@ def _pointwise_call(host_call, device_call, A, y, samples, burn, thin, device):
     y = np.ascontiguousarray(y)
     ctx = _lib.default_context(device)
     with ctx.lock:
-        return getattr(ctx, host_call)(A, n, k, lda, layout, y, s, C * kept, ld)
+        return getattr(ctx, host_call)(A, n, k, lda, layout, y, s, C * kept, ld, *vecs,
+                                       *tail(A, y, vecs))
 
 
 def pointwise_log_likelihood(A, y, samples, burn=0, thin=1, device=0):
