@@ -8,7 +8,9 @@
 // (kernels_waic.hip; tests/score_plan_check.cpp), and plan_loo, the pass and candidate plan of
 // the PSIS-LOO kernels (kernels_loo.hip; tests/loo_plan_check.cpp), with plan_loo_predict for the
 // leave-one-out predictive moments (tests/loo_predict_plan_check.cpp), and plan_ppc, the plan of
-// the posterior predictive check (kernels_ppc.hip; tests/ppc_plan_check.cpp).
+// the posterior predictive check (kernels_ppc.hip; tests/ppc_plan_check.cpp), and
+// plan_predict_orderstat, the sort / selection route of the posterior predictive's order
+// statistics (kernels_predict.hip; tests/predict_plan_check.cpp).
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -894,6 +896,76 @@ inline PpcBuffers ppc_buffers(const PpcPlan& p, int64_t n_draws) {
     b.sg = (size_t)p.S_pad * 2 * 8;
     b.out = (size_t)n_draws * (PPC_STATS + PPC_OBS) * 8;
     return b;
+}
+
+// ---- posterior predictive order statistics (kernels_predict.hip) ----------------
+// Which kernels read the requested ranks off the S draws of each of M points, and with what grid,
+// block and LDS.  Two routes:
+//   sort     predict_orderstat_kernel<nsort>: bitonic sort in LDS over nsort = the power of two
+//            >= max(S, 64), one thread per pair up to 1024 threads and never fewer than 128 (thread
+//            t < n_q writes a percentile, thread 64 + c counts interval c: 128 threads serve the
+//            request limits n_q = n_cov = 64).
+//   select   predict_select_kernel<vpt>: SEL_THREADS threads keep vpt draws each in registers
+//            (vpt = ceil(S / SEL_THREADS) rounded up to 8, 12, .. 32), histogram them over SEL_BINS
+//            bins and rank only the members of the requested bins (<= SEL_CAP each).  Taken for
+//            2048 <= S <= 32 SEL_THREADS and at most PREDICT_SELECT_MAX_RANKS requested ranks
+//            (2 n_q + 2 n_cov: every rank owns a list of SEL_CAP doubles in LDS).  Points it cannot
+//            resolve are handed to the sort kernel, which then runs second over that list with
+//            fewer workgroups.
+// Both kernels walk the points with a stride of their grid.  Refused (ok = false): S outside
+// 1 .. PREDICT_MAX_DRAWS (the sort holds a point's draws in LDS), n_q or n_cov outside
+// 0 .. PREDICT_MAX_Q / PREDICT_MAX_COV, no points.  `launch` is false when nothing is asked.
+#ifndef BMC_SEL_BINS
+#define BMC_SEL_BINS 4096
+#endif
+constexpr int SEL_BINS = BMC_SEL_BINS, SEL_CAP = 64, SEL_THREADS = 512;
+constexpr int PREDICT_MAX_DRAWS = 16384;          // 128 KiB of doubles in LDS; 32 draws x SEL_THREADS
+constexpr int PREDICT_MAX_Q = 64, PREDICT_MAX_COV = 64;
+constexpr int PREDICT_SELECT_MIN_DRAWS = 2048;
+constexpr int PREDICT_SELECT_MAX_VPT = 32;
+constexpr int PREDICT_SELECT_MAX_RANKS = 128;
+constexpr int64_t PREDICT_MAX_BLOCKS = 2048;      // workgroups of the first (or only) pass
+constexpr int64_t PREDICT_FALLBACK_BLOCKS = 256;  // workgroups of the sort behind the selection
+
+struct PredictOrderstatPlan {
+    bool ok, launch, select;
+    int vpt;                              // draws per thread of the selection (8 .. 32), or 0
+    int nsort, sort_threads;              // the sort: primary, or second pass behind the selection
+    int64_t blocks_select, blocks_sort;   // workgroups (blocks_select = 0 without the selection)
+    size_t lds_select, lds_sort;          // dynamic LDS, bytes
+};
+
+inline PredictOrderstatPlan plan_predict_orderstat(int32_t S, int32_t n_q, int32_t n_cov, int64_t M,
+                                                   bool have_fail_list = true) {
+    PredictOrderstatPlan p{};
+    p.ok = S >= 1 && S <= PREDICT_MAX_DRAWS && n_q >= 0 && n_q <= PREDICT_MAX_Q && n_cov >= 0 &&
+           n_cov <= PREDICT_MAX_COV && M >= 1;
+    if (!p.ok) return p;
+    p.launch = n_q > 0 || n_cov > 0;
+    p.nsort = 64;
+    while (p.nsort < S) p.nsort <<= 1;
+    p.sort_threads = p.nsort / 2 < 1024 ? (p.nsort / 2 < 128 ? 128 : p.nsort / 2) : 1024;
+    p.lds_sort = (size_t)p.nsort * sizeof(double);
+    // selection when there are many draws and few requested ranks, otherwise the sort
+    const int n_t = 2 * n_q + 2 * n_cov;
+    p.select = S >= PREDICT_SELECT_MIN_DRAWS && S <= PREDICT_SELECT_MAX_VPT * SEL_THREADS &&
+               n_t <= PREDICT_SELECT_MAX_RANKS && have_fail_list;
+    int64_t blocks = M < PREDICT_MAX_BLOCKS ? M : PREDICT_MAX_BLOCKS;
+    if (blocks < 1) blocks = 1;
+    p.blocks_sort = blocks;
+    if (p.select) {
+        // hist + slot | min / max per wave | wave totals + flag | prefix per thread | cnt, tbin, tk,
+        // trank per rank | alignment | one list per rank
+        p.lds_select = (size_t)SEL_BINS * 8 + 16 * 8 + 16 * 4 + SEL_THREADS * 4 + (size_t)n_t * 16 + 16 +
+                       (size_t)n_t * SEL_CAP * 8;
+        // draws per thread in steps of 4 (10 000 draws: 20, not 24 -- the slots past the row
+        // cost every per-draw step of the kernel)
+        const int vpt = (S + SEL_THREADS - 1) / SEL_THREADS;
+        p.vpt = vpt <= 8 ? 8 : (vpt + 3) / 4 * 4;
+        p.blocks_select = blocks;
+        p.blocks_sort = blocks < PREDICT_FALLBACK_BLOCKS ? blocks : PREDICT_FALLBACK_BLOCKS;
+    }
+    return p;
 }
 
 }  // namespace bmc

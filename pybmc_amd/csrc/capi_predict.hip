@@ -11,8 +11,9 @@ int bmc_predict(bmc_ctx* c, const double* preds, int64_t M, int32_t Km, const do
     if (!c) return BMC_EINVAL;
     if (!preds || !theta || !Vt_hat) return fail(c, BMC_EINVAL, "preds/theta/Vt_hat must not be NULL");
     if (M < 1 || Km < 1 || k < 1 || S < 1) return fail(c, BMC_EINVAL, "empty predictive problem");
-    if (S > 16384) return fail(c, BMC_EINVAL, "n_draws > 16384 is not supported");
-    if (n_q < 0 || n_q > 64 || n_cov < 0 || n_cov > 64)
+    // (the limits of plan_predict_orderstat, bmc_plan.h)
+    if (S > PREDICT_MAX_DRAWS) return fail(c, BMC_EINVAL, "n_draws > 16384 is not supported");
+    if (n_q < 0 || n_q > PREDICT_MAX_Q || n_cov < 0 || n_cov > PREDICT_MAX_COV)
         return fail(c, BMC_EINVAL, "n_q and n_cov must be in 0..64");
     if (n_q > 0 && (!q_index || !q_gamma || !bands_out))
         return fail(c, BMC_EINVAL, "order statistics requested without index/gamma/output");

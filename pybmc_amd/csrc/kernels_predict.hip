@@ -321,10 +321,7 @@ __global__ __launch_bounds__(1024) void predict_orderstat_kernel(
 // through `fail_points`.
 // (bins: same-box A/B of the C5 order statistics with 2048 / 4096 / 8192 bins: 1.88 / 1.62 / 2.59 ms --
 // half the draws per requested bin halve the rank counting; 8192 bins leave one workgroup per CU)
-#ifndef BMC_SEL_BINS
-#define BMC_SEL_BINS 4096
-#endif
-constexpr int SEL_BINS = BMC_SEL_BINS, SEL_CAP = 64, SEL_THREADS = 512;
+// (SEL_BINS, SEL_CAP and SEL_THREADS live in bmc_plan.h with the route: plan_predict_orderstat)
 constexpr int SEL_BPT = SEL_BINS / SEL_THREADS;   // consecutive bins per thread in the prefix sums
 
 __device__ __forceinline__ int sel_bin(double x, double mn, double scale) {
@@ -583,59 +580,53 @@ hipError_t launch_predict(const PredictArgs& a, hipStream_t s) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (a.ev_mid && (e = hipEventRecord(a.ev_mid, s)) != hipSuccess) return e;
-    if (a.n_q > 0 || a.n_cov > 0) {
-        int nsort = 64;
-        while (nsort < a.S) nsort <<= 1;
-        // selection when there are many draws and few requested ranks, otherwise the sort
-        const int n_t = 2 * a.n_q + 2 * a.n_cov;
-        const bool select = a.S >= 2048 && a.S <= 32 * SEL_THREADS && n_t <= 128 && a.fail_points;
+    // which kernels, grids, blocks and LDS: plan_predict_orderstat (bmc_plan.h)
+    const PredictOrderstatPlan pl =
+        plan_predict_orderstat(a.S, a.n_q, a.n_cov, a.M, a.fail_points != nullptr);
+    if (!pl.ok) return hipErrorInvalidValue;
+    if (pl.launch) {
         const int32_t* plist = nullptr;
         const int32_t* pcount = nullptr;
-        int64_t blocks = a.M < 2048 ? a.M : 2048;
-        if (blocks < 1) blocks = 1;
-        if (select) {
-            const size_t lds = (size_t)SEL_BINS * 8 + 16 * 8 + 16 * 4 + SEL_THREADS * 4 + (size_t)n_t * 16 + 16 +
-                               (size_t)n_t * SEL_CAP * 8;
+        if (pl.select) {
+            const size_t lds = pl.lds_select;
 #define BMC_SEL(V)                                                                             \
     do {                                                                                       \
         e = hipFuncSetAttribute((const void*)predict_select_kernel<V>,                          \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);         \
         if (e != hipSuccess) return e;                                                         \
-        hipLaunchKernelGGL((predict_select_kernel<V>), dim3((unsigned)blocks),                 \
+        hipLaunchKernelGGL((predict_select_kernel<V>), dim3((unsigned)pl.blocks_select),       \
                            dim3(SEL_THREADS), lds, s, (const double*)a.R, a.S, a.S_pad, a.M,   \
                            a.q_index, a.q_gamma, a.n_q, a.truth, a.cov_lo, a.cov_hi, a.n_cov,  \
                            a.bands, a.hits, a.fail_points, a.fail_count);                      \
     } while (0)
-            const int vpt = (a.S + SEL_THREADS - 1) / SEL_THREADS;
-            // draws per thread in steps of 4 (10 000 draws: 20, not 24 -- the slots past the row
-            // cost every per-draw step of the kernel)
-            if (vpt <= 8) BMC_SEL(8);
-            else if (vpt <= 12) BMC_SEL(12);
-            else if (vpt <= 16) BMC_SEL(16);
-            else if (vpt <= 20) BMC_SEL(20);
-            else if (vpt <= 24) BMC_SEL(24);
-            else if (vpt <= 28) BMC_SEL(28);
-            else BMC_SEL(32);
+            switch (pl.vpt) {
+                case 8: BMC_SEL(8); break;
+                case 12: BMC_SEL(12); break;
+                case 16: BMC_SEL(16); break;
+                case 20: BMC_SEL(20); break;
+                case 24: BMC_SEL(24); break;
+                case 28: BMC_SEL(28); break;
+                case 32: BMC_SEL(32); break;
+                default: return hipErrorInvalidValue;
+            }
 #undef BMC_SEL
             e = hipGetLastError();
             if (e != hipSuccess) return e;
             plist = a.fail_points;   // second pass: whatever the selection handed back
             pcount = a.fail_count;
-            blocks = blocks < 256 ? blocks : 256;
         }
-        const size_t lds = (size_t)nsort * sizeof(double);
+        const size_t lds = pl.lds_sort;
 #define BMC_OS(NS)                                                                            \
     do {                                                                                      \
         e = hipFuncSetAttribute((const void*)predict_orderstat_kernel<NS>,                    \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);        \
         if (e != hipSuccess) return e;                                                        \
-        hipLaunchKernelGGL((predict_orderstat_kernel<NS>), dim3((unsigned)blocks),            \
-                           dim3(NS / 2 < 1024 ? (NS / 2 < 128 ? 128 : NS / 2) : 1024), lds, s, \
-                           (const double*)a.R, a.S, a.S_pad, a.M, a.q_index, a.q_gamma, a.n_q, \
-                           a.truth, a.cov_lo, a.cov_hi, a.n_cov, a.bands, a.hits, plist,       \
-                           pcount);                                                            \
+        hipLaunchKernelGGL((predict_orderstat_kernel<NS>), dim3((unsigned)pl.blocks_sort),    \
+                           dim3((unsigned)pl.sort_threads), lds, s, (const double*)a.R, a.S,  \
+                           a.S_pad, a.M, a.q_index, a.q_gamma, a.n_q, a.truth, a.cov_lo,      \
+                           a.cov_hi, a.n_cov, a.bands, a.hits, plist, pcount);                \
     } while (0)
-        switch (nsort) {
+        switch (pl.nsort) {
             case 64: BMC_OS(64); break;
             case 128: BMC_OS(128); break;
             case 256: BMC_OS(256); break;
