@@ -321,6 +321,51 @@ int bmc_chain_diagnostics_device(bmc_ctx* ctx, const void* d_samples, int32_t n_
                                  double* mean_out, double* sd_out, double* rhat_out,
                                  double* ess_out, double* mcse_out, int64_t* max_lag_out);
 
+/* ---- rank-normalised diagnostics and quantiles (a capability the reference lacks) -------------
+ * The rank-normalised, folded split R-hat, the bulk and tail ESS of the same paper (Stan's and
+ * ArviZ's defaults) and interpolated quantiles; the estimator is written out in INTEGRATION.md
+ * section 13.  samples, n_chains, iters, n_cols, ld and burn are those of bmc_chain_diagnostics;
+ * the S = 2 n_chains n split draws of a column (n = (iters - burn) / 2; the middle draw of an
+ * odd iters - burn takes no part) are ranked exactly on the device, ties sharing their mean
+ * rank and -0 tying with +0, and z = ndtri((rank - 3/8) / (S + 1/4)).  Per column (every
+ * output but quantiles_out is [n_cols]; any may be NULL):
+ *   mean_out, sd_out   bit-equal to bmc_chain_diagnostics's
+ *   quantiles_out      [n_probs][n_cols]: numpy's method="linear" quantile of the S split draws
+ *                      at probs[t] (1 <= n_probs <= 16, each in [0, 1])
+ *   rhat_out           max of the split R-hat of z(x) and of z(|x - median|)
+ *   ess_bulk_out       ESS of z(x);   mcse_out  sd / sqrt(ess_bulk)
+ *   ess_tail_out       min of the ESS of 1[x <= q05] and of 1[x <= q95]
+ * A column with any non-finite value gets NaN in every rank-based output and quantile; a derived
+ * series that is constant within every half (W = 0: an all-equal column) gives NaN for the
+ * outputs built on it: values, not errors.  cols_per_batch: columns ranked together (0: as many
+ * as the free device memory holds); the results do not depend on it.  BMC_EINVAL outside the
+ * limits above, when 2 n_chains n > 2^31 - 1, and wherever bmc_chain_diagnostics returns it;
+ * BMC_ENOMEM when one column does not fit.  Results are deterministic: the only atomics are
+ * integer counters and masks.  The _device form reads caller-owned DEVICE memory on the
+ * context's stream.
+ *   bmc_rank_normalize*   z alone: z_out is HOST [2 n_chains][n][n_cols], sequence 2c + h the
+ *                         h-th half of chain c; folded != 0 ranks |x - median| instead of x.
+ *                         A column with a non-finite value is all NaN.
+ *   bmc_rank_last_timing  device milliseconds of the last bmc_rank_diagnostics* on ctx: the
+ *                         sorts (gather and fold included), the rank / quantile / indicator
+ *                         kernels, the classic leg on the derived series, the mean / sd pass */
+int bmc_rank_diagnostics(bmc_ctx* ctx, const double* samples, int32_t n_chains, int64_t iters,
+                         int32_t n_cols, int64_t ld, int64_t burn, const double* probs,
+                         int32_t n_probs, int32_t cols_per_batch, double* mean_out, double* sd_out,
+                         double* quantiles_out, double* rhat_out, double* ess_bulk_out,
+                         double* ess_tail_out, double* mcse_out);
+int bmc_rank_diagnostics_device(bmc_ctx* ctx, const void* d_samples, int32_t n_chains,
+                                int64_t iters, int32_t n_cols, int64_t ld, int64_t burn,
+                                const double* probs, int32_t n_probs, int32_t cols_per_batch,
+                                double* mean_out, double* sd_out, double* quantiles_out,
+                                double* rhat_out, double* ess_bulk_out, double* ess_tail_out,
+                                double* mcse_out);
+int bmc_rank_normalize(bmc_ctx* ctx, const double* samples, int32_t n_chains, int64_t iters,
+                       int32_t n_cols, int64_t ld, int64_t burn, int folded, double* z_out);
+int bmc_rank_normalize_device(bmc_ctx* ctx, const void* d_samples, int32_t n_chains, int64_t iters,
+                              int32_t n_cols, int64_t ld, int64_t burn, int folded, double* z_out);
+int bmc_rank_last_timing(bmc_ctx* ctx, double ms_out[4]);
+
 /* ---- pointwise log predictive density of a sampled fit (WAIC; not in the reference) ----------
  * The model the samplers draw from: y_i ~ N(a_i . beta, sigma^2).  A is n_points x k (lda / layout
  * as in bmc_set_problem: BMC_COL_MAJOR is what U_hat is), y [n_points], theta holds n_draws rows

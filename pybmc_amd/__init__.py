@@ -9,6 +9,7 @@ from .data import Dataset
 from .diagnostics import chain_diagnostics
 from .inference_utils import gibbs_sampler, gibbs_sampler_simplex, USVt_hat_extraction
 from .ppc import PPC_STATS, posterior_predictive_check, ppc_summary
+from .rankdiag import rank_diagnostics, rank_normalize
 from .sampling_utils import coverage, rndm_m_random_calculator
 from .scoring import pointwise_log_likelihood, psis_loo, psis_loo_predict, waic
 
@@ -21,6 +22,8 @@ __all__ = [
     "coverage",
     "rndm_m_random_calculator",
     "chain_diagnostics",
+    "rank_diagnostics",
+    "rank_normalize",
     "pointwise_log_likelihood",
     "waic",
     "psis_loo",

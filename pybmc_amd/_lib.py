@@ -94,6 +94,16 @@ PROTOTYPES = {
     "bmc_chain_diagnostics_device": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int64,
                                                C.c_int64, _D, _D, _D, _D, _D,
                                                C.POINTER(C.c_int64)]),
+    "bmc_rank_diagnostics": (C.c_int, [_P, _D, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_int64,
+                                       _D, C.c_int32, C.c_int32, _D, _D, _D, _D, _D, _D, _D]),
+    "bmc_rank_diagnostics_device": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int64,
+                                              C.c_int64, _D, C.c_int32, C.c_int32, _D, _D, _D, _D, _D,
+                                              _D, _D]),
+    "bmc_rank_normalize": (C.c_int, [_P, _D, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_int64,
+                                     C.c_int, _D]),
+    "bmc_rank_normalize_device": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int64,
+                                            C.c_int64, C.c_int, _D]),
+    "bmc_rank_last_timing": (C.c_int, [_P, _D]),
     "bmc_pointwise_loglik": (C.c_int, [_P, _D, C.c_int64, C.c_int32, C.c_int64, C.c_int, _D, _D,
                                        C.c_int64, C.c_int64, _D, _D, _D]),
     "bmc_pointwise_loglik_device": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int, _P,
@@ -561,6 +571,56 @@ class Context:
         stream: the caller orders its producer before the call."""
         return self._diag_call(self._lib.bmc_chain_diagnostics_device, _P(d_ptr), n_chains, iters,
                                n_cols, ld, burn)
+
+    # -- rank-normalised diagnostics -------------------------------------------------------------
+    RANK_KEYS = ("mean", "sd", "mcse_mean", "ess_bulk", "ess_tail", "r_hat")
+
+    def _rank_call(self, fn, ptr, n_chains, iters, n_cols, ld, burn, probs, cols_per_batch):
+        probs = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+        out = {k: np.empty(n_cols) for k in self.RANK_KEYS}
+        quant = np.empty((len(probs), n_cols))
+        self._check(fn(self._h, ptr, int(n_chains), int(iters), int(n_cols), int(ld), int(burn),
+                       _dptr(probs), len(probs), int(cols_per_batch), _dptr(out["mean"]),
+                       _dptr(out["sd"]), _dptr(quant), _dptr(out["r_hat"]), _dptr(out["ess_bulk"]),
+                       _dptr(out["ess_tail"]), _dptr(out["mcse_mean"])))
+        out["quantiles"] = quant
+        return out
+
+    def rank_diagnostics(self, samples, n_chains, iters, n_cols, ld, burn=0, probs=(0.05, 0.5, 0.95),
+                         cols_per_batch=0):
+        """Rank-normalised R-hat, bulk / tail ESS and quantiles of a HOST f64 array laid out as
+        for chain_diagnostics (bmc_rank_diagnostics).  Returns a dict of [n_cols] arrays and
+        ``quantiles`` [len(probs), n_cols]."""
+        return self._rank_call(self._lib.bmc_rank_diagnostics, samples.ctypes.data_as(_D), n_chains,
+                               iters, n_cols, ld, burn, probs, cols_per_batch)
+
+    def rank_diagnostics_device(self, d_ptr, n_chains, iters, n_cols, ld, burn=0,
+                                probs=(0.05, 0.5, 0.95), cols_per_batch=0):
+        """The same on DEVICE memory (bmc_rank_diagnostics_device), read on the context's stream."""
+        return self._rank_call(self._lib.bmc_rank_diagnostics_device, _P(d_ptr), n_chains, iters,
+                               n_cols, ld, burn, probs, cols_per_batch)
+
+    def _rank_normalize(self, fn, ptr, n_chains, iters, n_cols, ld, burn, folded):
+        z = np.empty((2 * n_chains, (iters - burn) // 2, n_cols))
+        self._check(fn(self._h, ptr, int(n_chains), int(iters), int(n_cols), int(ld), int(burn),
+                       1 if folded else 0, _dptr(z)))
+        return z
+
+    def rank_normalize(self, samples, n_chains, iters, n_cols, ld, burn=0, folded=False):
+        """z-scores of the exact ranks of a HOST f64 array's split draws (bmc_rank_normalize):
+        (2 n_chains, n, n_cols)."""
+        return self._rank_normalize(self._lib.bmc_rank_normalize, samples.ctypes.data_as(_D), n_chains,
+                                    iters, n_cols, ld, burn, folded)
+
+    def rank_normalize_device(self, d_ptr, n_chains, iters, n_cols, ld, burn=0, folded=False):
+        return self._rank_normalize(self._lib.bmc_rank_normalize_device, _P(d_ptr), n_chains, iters,
+                                    n_cols, ld, burn, folded)
+
+    def rank_last_timing(self):
+        """Device milliseconds of the last rank_diagnostics* call: sort, rank, classic, moments."""
+        ms = np.zeros(4)
+        self._check(self._lib.bmc_rank_last_timing(self._h, _dptr(ms)))
+        return dict(zip(("sort_ms", "rank_ms", "classic_ms", "moments_ms"), ms.tolist()))
 
     # -- scoring: pointwise log predictive density, PSIS-LOO and its predictive moments -----------
     SCORE_KEYS = ("lppd", "p_waic", "mean_ll")

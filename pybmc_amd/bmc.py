@@ -198,6 +198,26 @@ class BayesianModelCombination:
         from .diagnostics import KEYS
         return pd.DataFrame({key: np.asarray(d[key]) for key in KEYS}, index=index)
 
+    def summary(self, burn=0, probs=(0.05, 0.5, 0.95)):
+        """Posterior summary of the last ``train()`` with the rank-normalised diagnostics (not in
+        the reference; ``pybmc_amd.rankdiag``): over ``beta_i``, ``sigma`` and the model weights,
+        the rows of ``diagnostics()`` formed the same way, the columns ``mean``, ``sd``, one
+        quantile per entry of ``probs`` (``q5``, ``q50``, ``q95``), ``mcse_mean``, ``ess_bulk``,
+        ``ess_tail`` and ``r_hat`` (folded, rank-normalised), computed on the GPU."""
+        if self.samples is None or self.Vt_hat is None:
+            raise ValueError("Must call `orthogonalize()` and `train()` before computing a summary.")
+        from .rankdiag import quantile_names, rank_diagnostics
+        s = self._chains()
+        d = rank_diagnostics(_series_tensor(s, self.Vt_hat, self.device), burn=burn, probs=probs,
+                             device=self.device)
+        index = [f"beta_{i}" for i in range(s.shape[-1] - 1)] + ["sigma"] + list(self.models)
+        cols = {"mean": d["mean"], "sd": d["sd"]}
+        for name, row in zip(quantile_names(probs), d["quantiles"]):
+            cols[name] = row
+        for key in ("mcse_mean", "ess_bulk", "ess_tail", "r_hat"):
+            cols[key] = d[key]
+        return pd.DataFrame({k: np.asarray(v) for k, v in cols.items()}, index=index)
+
     # ----------------------------------------------------------------- scoring
     def _chains(self):
         s = np.asarray(self.samples)
@@ -442,16 +462,21 @@ class BayesianModelCombination:
                                    device=self.device)
 
 
-def _series_diagnostics(samples, Vt_hat, burn, device):
-    """Diagnostics of [beta, sigma, weights] per draw: ONE upload of the (C, T, k+1) samples, the
-    weights beta Vt_hat + 1/K formed next to them on the device (torch matmul), and the
-    ``chain_diagnostics`` kernels on the concatenated (C, T, k+1+K) tensor."""
+def _series_tensor(samples, Vt_hat, device):
+    """[beta, sigma, weights] per draw as one device tensor (C, T, k+1+K): ONE upload of the
+    (C, T, k+1) samples, the weights beta Vt_hat + 1/K formed next to them (torch matmul)."""
     import torch
-
-    from .diagnostics import chain_diagnostics
 
     dev = torch.device("cuda", device)
     s = torch.as_tensor(np.ascontiguousarray(samples, dtype=np.float64), device=dev)
     V = torch.as_tensor(np.ascontiguousarray(Vt_hat, dtype=np.float64), device=dev)
     w = torch.matmul(s[..., :-1], V) + 1.0 / V.shape[1]
-    return chain_diagnostics(torch.cat([s, w], dim=-1), burn=burn, device=device)
+    return torch.cat([s, w], dim=-1)
+
+
+def _series_diagnostics(samples, Vt_hat, burn, device):
+    """Diagnostics of [beta, sigma, weights] per draw: the ``chain_diagnostics`` kernels on the
+    concatenated tensor of ``_series_tensor``."""
+    from .diagnostics import chain_diagnostics
+
+    return chain_diagnostics(_series_tensor(samples, Vt_hat, device), burn=burn, device=device)

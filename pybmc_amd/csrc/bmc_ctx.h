@@ -90,6 +90,10 @@ struct bmc_ctx : CtxHandles {
     DevBuf oFc, oMu, oW, oOut;
     // chain diagnostics (bmc_chain_diagnostics*)
     DevBuf dgIn, dgPart, dgMean, dgM2, dgCols, dgAcovPart, dgAcov;
+    // rank-normalised diagnostics (bmc_rank_*): the two (key, index) buffers of the sort, its
+    // histograms, the derived series, and the quantiles / masks / flags of a batch
+    DevBuf rkKey[2], rkIdx[2], rkHist, rkDer, rkSmall;
+    double rank_ms[4] = {0, 0, 0, 0};      // last bmc_rank_diagnostics*: sort, rank, classic, moments
     // pointwise log-likelihood (bmc_pointwise_loglik*)
     DevBuf scA, scY, scTheta, scAp, scYp, scCh, scPart, scOut;
     // PSIS-LOO (bmc_psis_loo*, bmc_psis_loo_predict*): the select state and candidate slots,
@@ -135,6 +139,12 @@ Panels panels_of(const bmc_ctx* c, const void* X);
 Shape shape_of(const bmc_ctx* c);
 Chip chip_of(const bmc_ctx* c);
 uint32_t launch_nonce(bmc_ctx* c, uint64_t n_tags);
+
+// The classic split R-hat / ESS of device samples [C][iters][ld] (capi_diag.hip):
+// what bmc_chain_diagnostics* run after their argument checks.  Every output is host [P] or NULL.
+int diag_run(bmc_ctx* c, const double* dx, int32_t C, int64_t iters, int32_t P, int64_t ld,
+             int64_t burn, double* mean_out, double* sd_out, double* rhat_out, double* ess_out,
+             double* mcse_out, int64_t* max_lag_out);
 
 // milliseconds from c->ev[from] to c->ev[to]
 int event_ms(bmc_ctx* c, int from, int to, double* ms);

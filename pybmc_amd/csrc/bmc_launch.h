@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "bmc_plan.h"
+#include "bmc_rank_plan.h"
 
 namespace bmc {
 
@@ -260,6 +261,46 @@ size_t diag_acov_scratch(const DiagShape& d, int32_t n_active, int64_t n_lags);
 hipError_t launch_diag_acov(const DiagShape& d, const double* mean, const int32_t* cols,
                             int32_t n_active, int64_t t0, int64_t n_lags, double* scratch,
                             double* acov_out, hipStream_t s);
+
+// ---- rank normalisation (kernels_rank.hip; plan_rank in bmc_rank_plan.h) -----------------------------
+// A batch of Pb columns col0 .. col0 + Pb - 1 of the samples of a DiagShape.  Split draw e < S = 2 C n
+// of a column is draw e % n of sequence e / n (sequence 2c + h as above); e is also its row in a
+// derived buffer [C][2n][ld_d].  Segment jb of a key / index buffer is [jb * S, (jb + 1) * S).
+// Outputs per draw go to out[jb * seg_stride + e * ld_d + col]: seg_stride = S * ld_d gives every
+// column a buffer [C][2n][ld_d] of its own, seg_stride = 1 and ld_d = Pb one [S][Pb] array.
+struct RankShape {
+    const double* x;
+    int64_t iters, ld, burn, n, half_off, S, tiles;
+    int32_t C, col0, Pb;
+};
+// keys[jb][e] = rank_key(x), idx[jb][e] = e; flags[jb] = 1 when the column holds a non-finite value;
+// or_and[jb] = {OR, AND} of the segment's keys (integer atomics: the result is order-free)
+hipError_t launch_rank_gather(const RankShape& r, uint64_t* keys, uint32_t* idx, uint64_t* or_and,
+                              uint32_t* flags, hipStream_t s);
+// One stable counting pass on digit `digit` (bits 8 digit .. 8 digit + 7) of every segment, from
+// (kin, iin) to (kout, iout).  hist: [Pb][tiles][256] u32 of scratch.
+hipError_t launch_rank_sort_pass(const RankShape& r, int digit, const uint64_t* kin, const uint32_t* iin,
+                                 uint64_t* kout, uint32_t* iout, uint32_t* hist, hipStream_t s);
+// From SORTED segments: the output of draw idx is ndtri((rank - 3/8) / (S + 1/4)), rank the
+// 1-based average rank of the key's run of equal keys (runs may cross tiles)
+hipError_t launch_rank_z(const RankShape& r, const uint64_t* keys, const uint32_t* idx, double* out,
+                         int64_t seg_stride, int64_t ld_d, int32_t col, hipStream_t s);
+// Order statistics of SORTED segments: q[jb][t] = lerp(x_(index[t]), x_(index[t] + 1), weight[t]),
+// t < n, with the interpolation of the predictive leg; q is [Pb][RANK_Q_SLOTS]
+struct RankQuantiles {
+    int32_t n;
+    int32_t index[RANK_Q_SLOTS];
+    double weight[RANK_Q_SLOTS];
+};
+hipError_t launch_rank_pick(const RankShape& r, const uint64_t* keys, const RankQuantiles& rq, double* q,
+                            hipStream_t s);
+// In place: key -> rank_key(|x - q[jb][med_slot]|), x the value of the key; or_and as in the gather
+hipError_t launch_rank_fold(const RankShape& r, uint64_t* keys, const double* q, int32_t med_slot,
+                            uint64_t* or_and, hipStream_t s);
+// the outputs of draw e at col_lo and col_hi: x <= q[jb][slot_lo] ? 1.0 : 0.0, and the same with slot_hi
+hipError_t launch_rank_indicators(const RankShape& r, const double* q, int32_t slot_lo, int32_t slot_hi,
+                                  double* out, int64_t seg_stride, int64_t ld_d, int32_t col_lo, int32_t col_hi,
+                                  hipStream_t s);
 
 // ---- pointwise log-likelihood (kernels_waic.hip; plan_score in bmc_plan.h) ---------------------
 // ll[i][s] = -1/2 log(2 pi) - log sigma_s - (y_i - a_i . beta_s)^2 / (2 sigma_s^2) for design rows

@@ -108,4 +108,68 @@ BMC_HD void box_muller_pair(double u1, double u2, double& z0, double& z1) {
     z1 = rad * sn;
 }
 
+// Inverse of the standard normal CDF for 0 < p < 1 with min(p, 1 - p) a normal double: Wichura's
+// AS 241, routine PPND16 (Applied Statistics 37(3), 1988; about 1e-16 relative).  Three rational
+// approximations of degree 7: |p - 1/2| <= 0.425 in q^2, the tails in r = sqrt(-log(min(p, 1 - p))),
+// split at r = 5.  Odd about 1/2 by construction: the two sides differ in the sign alone wherever
+// 1 - p is exact.  The logarithm is log_normal_arg, so the CPU build gives the device's bits.
+BMC_HD double ndtri(double p) {
+    const double q = p - 0.5;
+    if (fabs(q) <= 0.425) {
+        const double r = 0.180625 - q * q;
+        const double num = fma(fma(fma(fma(fma(fma(fma(2.5090809287301226727e3, r,
+            3.3430575583588128105e4), r, 6.7265770927008700853e4), r, 4.5921953931549871457e4), r,
+            1.3731693765509461125e4), r, 1.9715909503065514427e3), r, 1.3314166789178437745e2), r,
+            3.3871328727963666080);
+        const double den = fma(fma(fma(fma(fma(fma(fma(5.2264952788528545610e3, r,
+            2.8729085735721942674e4), r, 3.9307895800092710610e4), r, 2.1213794301586595867e4), r,
+            5.3941960214247511077e3), r, 6.8718700749205790830e2), r, 4.2313330701600911252e1), r,
+            1.0);
+        return q * num / den;
+    }
+    double r = q < 0 ? p : 1.0 - p;
+    r = sqrt(-log_normal_arg(r));
+    double val;
+    if (r <= 5.0) {
+        r -= 1.6;
+        const double num = fma(fma(fma(fma(fma(fma(fma(7.74545014278341407640e-4, r,
+            2.27238449892691845833e-2), r, 2.41780725177450611770e-1), r, 1.27045825245236838258), r,
+            3.64784832476320460504), r, 5.76949722146069140550), r, 4.63033784615654529590), r,
+            1.42343711074968357734);
+        const double den = fma(fma(fma(fma(fma(fma(fma(1.05075007164441684324e-9, r,
+            5.47593808499534494600e-4), r, 1.51986665636164571966e-2), r, 1.48103976427480074590e-1), r,
+            6.89767334985100004550e-1), r, 1.67638483018380384940), r, 2.05319162663775882187), r,
+            1.0);
+        val = num / den;
+    } else {
+        r -= 5.0;
+        const double num = fma(fma(fma(fma(fma(fma(fma(2.01033439929228813265e-7, r,
+            2.71155556874348757815e-5), r, 1.24266094738807843860e-3), r, 2.65321895265761230930e-2), r,
+            2.96560571828504891230e-1), r, 1.78482653991729133580), r, 5.46378491116411436990), r,
+            6.65790464350110377720);
+        const double den = fma(fma(fma(fma(fma(fma(fma(2.04426310338993978564e-15, r,
+            1.42151175831644588870e-7), r, 1.84631831751005468180e-5), r, 7.86869131145613259100e-4), r,
+            1.48753612908506148525e-2), r, 1.36929880922735805310e-1), r, 5.99832206555887937690e-1), r,
+            1.0);
+        val = num / den;
+    }
+    return q < 0 ? -val : val;
+}
+
+// The order-preserving 64-bit image of a double (the sort key of kernels_rank.hip): a < b exactly
+// when rank_key(a) < rank_key(b), and -0.0 has the key of +0.0 (equality is by value).  NaNs land
+// beyond the infinities of their sign; rank_unkey inverts it (-0.0 comes back as +0.0).
+BMC_HD uint64_t rank_key(double x) {
+    if (x == 0.0) x = 0.0;
+    uint64_t u;
+    memcpy(&u, &x, 8);
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+BMC_HD double rank_unkey(uint64_t k) {
+    const uint64_t u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
+    double x;
+    memcpy(&x, &u, 8);
+    return x;
+}
+
 }  // namespace bmc

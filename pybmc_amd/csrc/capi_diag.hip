@@ -59,6 +59,10 @@ bool ess_scan(const double* a, int64_t have, int64_t n, double W, double var_plu
     return true;
 }
 
+}  // namespace
+
+// (declared in bmc_ctx.h: bmc_rank_diagnostics* runs it on its derived series as well.  With no
+// ess, mcse or max_lag wanted the autocovariance blocks are not launched.)
 int diag_run(bmc_ctx* c, const double* dx, int32_t C, int64_t iters, int32_t P, int64_t ld,
              int64_t burn, double* mean_out, double* sd_out, double* rhat_out, double* ess_out,
              double* mcse_out, int64_t* max_lag_out) {
@@ -133,6 +137,7 @@ int diag_run(bmc_ctx* c, const double* dx, int32_t C, int64_t iters, int32_t P, 
         if (rhat_out) rhat_out[j] = ok ? std::sqrt(var_plus[j] / w) : nan;
         if (ok) active.push_back(j);
     }
+    if (!ess_out && !mcse_out && !max_lag_out) active.clear();
 
     // a(t) in blocks of lags: 64 first, then doubling, for the columns whose scan ran off the end
     std::vector<std::vector<double>> acov(P);
@@ -172,8 +177,6 @@ int diag_run(bmc_ctx* c, const double* dx, int32_t C, int64_t iters, int32_t P, 
     }
     return BMC_OK;
 }
-
-}  // namespace
 
 extern "C" {
 

@@ -1,7 +1,8 @@
 """Convergence diagnostics of sampled chains on the GPU: split R-hat and effective sample size.
 
 The reference package has no diagnostics; this is a capability of this build.  The estimator is
-the classic (not rank-normalised) split R-hat and the "mean" ESS of
+the classic (not rank-normalised) split R-hat and the "mean" ESS (the rank-normalised ones built
+on it are in ``rankdiag.py``) of
 
     A. Vehtari, A. Gelman, D. Simpson, B. Carpenter, P.-C. Buerkner, "Rank-normalization,
     folding, and localization: an improved R-hat for assessing convergence of MCMC",
@@ -65,14 +66,10 @@ def _check_shape(shape, burn):
     return C, T, P
 
 
-def chain_diagnostics(samples, burn=0, device=0):
-    """Split R-hat, ESS and Monte-Carlo standard error of every column of ``samples``.
-
-    ``samples`` is a float64 array ``(T, P)`` (one chain) or ``(C, T, P)``: a numpy array, or a
-    CUDA torch tensor whose last dimension is contiguous (read in place, row stride passed as
-    ``ld``: the route for ``chains.run_chains`` output; ``device`` is then the tensor's).
-    Returns a dict of ``[P]`` arrays: ``mean``, ``sd``, ``mcse_mean``, ``ess``, ``r_hat``,
-    ``max_lag``.  The estimator is the module docstring's."""
+def _prepare(samples, burn, device):
+    """The input rules of ``chain_diagnostics``: (context, on_device, array or tensor, C, T, P, ld).
+    A numpy array is read in place when it is a column subset of a C-ordered array, else copied;
+    a CUDA tensor is always read in place (and whatever torch queued on it is waited for)."""
     from . import _lib
 
     if _is_torch(samples) and not samples.is_cuda:
@@ -91,8 +88,7 @@ def chain_diagnostics(samples, burn=0, device=0):
         # the library reads on its own stream: whatever torch queued that writes `t` (a sampler
         # run, an RCCL gather, a matmul) must be done first (cf. chains.pool_samples)
         torch.cuda.current_stream(t.device).synchronize()
-        with ctx.lock:
-            return _order(ctx.chain_diagnostics_device(t.data_ptr(), C, T, P, ld, int(burn)))
+        return ctx, True, t, C, T, P, ld
 
     a = np.asarray(samples)
     if a.dtype != np.float64:
@@ -105,8 +101,21 @@ def chain_diagnostics(samples, burn=0, device=0):
     else:
         a = np.ascontiguousarray(a)
         ld = P
-    ctx = _lib.default_context(device)
+    return _lib.default_context(device), False, a, C, T, P, ld
+
+
+def chain_diagnostics(samples, burn=0, device=0):
+    """Split R-hat, ESS and Monte-Carlo standard error of every column of ``samples``.
+
+    ``samples`` is a float64 array ``(T, P)`` (one chain) or ``(C, T, P)``: a numpy array, or a
+    CUDA torch tensor whose last dimension is contiguous (read in place, row stride passed as
+    ``ld``: the route for ``chains.run_chains`` output; ``device`` is then the tensor's).
+    Returns a dict of ``[P]`` arrays: ``mean``, ``sd``, ``mcse_mean``, ``ess``, ``r_hat``,
+    ``max_lag``.  The estimator is the module docstring's."""
+    ctx, on_device, a, C, T, P, ld = _prepare(samples, burn, device)
     with ctx.lock:
+        if on_device:
+            return _order(ctx.chain_diagnostics_device(a.data_ptr(), C, T, P, ld, int(burn)))
         return _order(ctx.chain_diagnostics(a, C, T, P, ld, int(burn)))
 
 
