@@ -470,6 +470,30 @@ int bmc_kfold_cv(bmc_ctx* ctx, const double* A, int64_t n, int32_t k, int64_t ld
                  int64_t burn, int64_t thin, const uint64_t* seeds, double* elpd_out,
                  double* mean_out, double* draws_out);
 
+/* ---- the component path: bmc_kfold_cv for every candidate component count in one call ---------
+ * Arguments as bmc_kfold_cv, A with k <= 64 columns, plus comps [n_comps]: strictly increasing
+ * candidate counts in 1 .. k.  Candidate k_j is the model on the LEADING k_j columns of A under the
+ * prior (b0[0 .. k_j), the leading k_j x k_j block of C0 (row-major, leading dimension k), nu0,
+ * sigma20): the exact marginal of the Gaussian prior.  seeds [n_folds * n_chains] serve every
+ * candidate: chain (j, f, c) consumes the streams of seeds[f * n_chains + c] and is the chain
+ * bmc_kfold_cv runs on those k_j columns under that seed.  Every training set must hold at least
+ * comps[n_comps - 1] rows.
+ *   elpd_out, mean_out   [n_comps][n] row-major: row j is bmc_kfold_cv's vector for candidate j
+ *   draws_out            candidate after candidate, each [n_folds][n_chains][kept][k_j + 1]; may be NULL
+ * One gather and one Gram pass at the widest candidate serve all of them (the training Gram of
+ * candidate k_j is the leading block); the n_comps * n_folds * n_chains chains run one wave each,
+ * in launches of one kernel width (8 / 16 / 32 / 64 columns) and at most 2048 chains, in as many
+ * batches of whole (candidate, fold) problems as the free device memory asks for.  The resident
+ * problem and prior of the context are not touched.  Deterministic.
+ * BMC_EINVAL for bad arguments, BMC_ESINGULAR when a leading block of C0 or the training Gram of a
+ * (candidate, fold) is numerically singular (the message names the fold and the component count),
+ * BMC_ENOMEM when the chains of one problem do not fit the device.  INTEGRATION.md section 11.1. */
+int bmc_cv_path(bmc_ctx* ctx, const double* A, int64_t n, int32_t k, int64_t lda, int layout,
+                const double* y, const int64_t* fold, int32_t n_folds, const double* b0,
+                const double* C0, double nu0, double sigma20, int32_t n_chains, int64_t iters,
+                int64_t burn, int64_t thin, const uint64_t* seeds, const int32_t* comps,
+                int32_t n_comps, double* elpd_out, double* mean_out, double* draws_out);
+
 /* ---- posterior predictive check: do data replicated from the fit look like the data? ----------
  * Model and arguments A, y, theta as bmc_pointwise_loglik; offset [n_points] or NULL (zeros).
  * Replicated data y_rep[i][s] = a_i . beta_s + sigma_s z[i][s] + offset_i, z[i][s] the standard

@@ -4,7 +4,7 @@ Public names follow the reference package (pybmc/__init__.py:11-24); the
 nonexistent ``Model`` of its ``__all__`` is dropped.
 """
 from .bmc import BayesianModelCombination
-from .cv import fold_labels, kfold_cv
+from .cv import cv_component_path, fold_labels, kfold_cv, path_summary
 from .data import Dataset
 from .diagnostics import chain_diagnostics
 from .inference_utils import gibbs_sampler, gibbs_sampler_simplex, USVt_hat_extraction
@@ -30,6 +30,8 @@ __all__ = [
     "psis_loo_predict",
     "kfold_cv",
     "fold_labels",
+    "cv_component_path",
+    "path_summary",
     "posterior_predictive_check",
     "ppc_summary",
     "PPC_STATS",

@@ -120,6 +120,10 @@ PROTOTYPES = {
                                C.POINTER(C.c_int64), C.c_int32, _D, _D, C.c_double, C.c_double,
                                C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_uint64), _D,
                                _D, _D]),
+    "bmc_cv_path": (C.c_int, [_P, _D, C.c_int64, C.c_int32, C.c_int64, C.c_int, _D,
+                              C.POINTER(C.c_int64), C.c_int32, _D, _D, C.c_double, C.c_double,
+                              C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_uint64),
+                              C.POINTER(C.c_int32), C.c_int32, _D, _D, _D]),
     "bmc_ppc": (C.c_int, [_P, _D, C.c_int64, C.c_int32, C.c_int64, C.c_int, _D, _D, _D, C.c_int64,
                           C.c_int64, C.c_uint64, C.c_double, _D, _D]),
     "bmc_ppc_device": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int, _P, _P, _P,
@@ -193,8 +197,9 @@ class BmcError(RuntimeError):
 
 
 class SingularFoldError(BmcError, np.linalg.LinAlgError):
-    """A fold of ``kfold_cv`` whose training Gram is numerically singular (BMC_ESINGULAR): the
-    library's error, and the ``LinAlgError`` a refit of that fold would raise."""
+    """A fold of ``kfold_cv``, or a (candidate, fold) of ``cv_component_path``, whose training Gram is
+    numerically singular (BMC_ESINGULAR): the library's error, and the ``LinAlgError`` a refit of
+    that fold would raise."""
 
 
 class Context:
@@ -718,6 +723,40 @@ class Context:
             raise SingularFoldError(
                 (self._lib.bmc_last_error(self._h) or b"").decode("utf-8", "replace"))
         self._check(rc)
+        return elpd, mean, draws
+
+    def cv_path(self, A, n, k, lda, layout, y, fold, n_folds, b0, C0, nu0, sigma20, n_chains, iters,
+                burn, thin, seeds, comps, return_draws=False):
+        """bmc_cv_path of HOST arrays: the arguments of ``kfold_cv`` and comps [m] int32 candidate
+        component counts.  Returns (elpd_cv_i [m, n], cv_mean_i [m, n], draws: a list of m arrays
+        (n_folds, n_chains, kept, k_j + 1), or None).  A singular (candidate, fold) raises
+        SingularFoldError."""
+        kept = max(0, -(-(int(iters) - int(burn)) // int(thin)))
+        comps = np.ascontiguousarray(comps, dtype=np.int32)
+        m = int(comps.shape[0])
+        elpd, mean = np.empty((m, n)), np.empty((m, n))
+        sizes = [n_folds * n_chains * kept * (int(kj) + 1) for kj in comps]
+        flat = np.empty(sum(sizes)) if return_draws else None
+        b0 = np.ascontiguousarray(b0, dtype=np.float64)
+        C0 = np.ascontiguousarray(C0, dtype=np.float64)
+        fold = np.ascontiguousarray(fold, dtype=np.int64)
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+        rc = self._lib.bmc_cv_path(
+            self._h, _dptr(A), int(n), int(k), int(lda), int(layout), _dptr(y),
+            fold.ctypes.data_as(C.POINTER(C.c_int64)), int(n_folds), _dptr(b0), _dptr(C0),
+            float(nu0), float(sigma20), int(n_chains), int(iters), int(burn), int(thin),
+            seeds.ctypes.data_as(C.POINTER(C.c_uint64)), comps.ctypes.data_as(C.POINTER(C.c_int32)), m,
+            _dptr(elpd), _dptr(mean), _dptr(flat))
+        if rc == BMC_ESINGULAR:
+            raise SingularFoldError(
+                (self._lib.bmc_last_error(self._h) or b"").decode("utf-8", "replace"))
+        self._check(rc)
+        draws = None
+        if return_draws:
+            draws, at = [], 0
+            for kj, size in zip(comps, sizes):
+                draws.append(flat[at:at + size].reshape(n_folds, n_chains, kept, int(kj) + 1).copy())
+                at += size
         return elpd, mean, draws
 
     # -- variates -----------------------------------------------------------------------

@@ -266,6 +266,33 @@ class BayesianModelCombination:
         out["residual"] = y - out["loo_mean"]
         return out
 
+    def _cv_arguments(self, what, n_folds, groups, training_options, seed):
+        """(options, y, fold labels, group values or None, prior) of ``cross_validate`` and
+        ``component_path``; ValueError for what neither accepts."""
+        if self.U_hat is None:
+            raise ValueError("Must call `orthogonalize()` before cross-validating.")
+        opts = training_options if training_options is not None else {}
+        if opts.get("sampler", "gibbs_sampling") == "simplex":
+            raise ValueError(f'{what} supports the Gibbs sampler only (sampler == "simplex")')
+        from .cv import fold_labels, group_labels
+        y = np.asarray(self.centered_experiment_train, dtype=np.float64)
+        n, kc = self.U_hat.shape
+        values = None
+        if groups is not None:
+            if isinstance(groups, str):
+                if self._train_df is None or groups not in self._train_df.columns:
+                    raise ValueError(f"groups: the training frame has no column '{groups}'")
+                groups = self._train_df[groups].values
+            groups = np.asarray(groups)
+            if groups.shape != (n,):
+                raise ValueError(f"groups must have one entry per training row ({n},); got {groups.shape}")
+            folds, values = group_labels(groups)
+        else:
+            folds = fold_labels(n, n_folds, seed)
+        prior = [opts.get("b_mean_prior", np.zeros(kc)), opts.get("b_mean_cov", np.diag(self.S_hat ** 2)),
+                 opts.get("nu0_chosen", 1.0), opts.get("sigma20_chosen", 0.02)]
+        return opts, y, folds, values, prior
+
     def cross_validate(self, n_folds=10, groups=None, training_options=None, seed=None):
         """Exact K-fold or leave-group-out cross-validation of the combination (not in the
         reference; ``pybmc_amd.cv.kfold_cv``): for every fold the Gibbs sampler is run on
@@ -291,28 +318,9 @@ class BayesianModelCombination:
         ``folds`` (the labels), ``groups`` (the distinct values, with ``groups``) and, in the
         truth's units as ``loo_predict()``, ``predicted = cv_mean_i +`` the row mean of the model
         predictions, ``truth`` and ``residual = truth - predicted``."""
-        if self.U_hat is None:
-            raise ValueError("Must call `orthogonalize()` before cross-validating.")
-        opts = training_options if training_options is not None else {}
-        if opts.get("sampler", "gibbs_sampling") == "simplex":
-            raise ValueError('cross_validate supports the Gibbs sampler only (sampler == "simplex")')
-        from .cv import fold_labels, group_labels, kfold_cv
-        y = np.asarray(self.centered_experiment_train, dtype=np.float64)
-        n, kc = self.U_hat.shape
-        values = None
-        if groups is not None:
-            if isinstance(groups, str):
-                if self._train_df is None or groups not in self._train_df.columns:
-                    raise ValueError(f"groups: the training frame has no column '{groups}'")
-                groups = self._train_df[groups].values
-            groups = np.asarray(groups)
-            if groups.shape != (n,):
-                raise ValueError(f"groups must have one entry per training row ({n},); got {groups.shape}")
-            folds, values = group_labels(groups)
-        else:
-            folds = fold_labels(n, n_folds, seed)
-        prior = [opts.get("b_mean_prior", np.zeros(kc)), opts.get("b_mean_cov", np.diag(self.S_hat ** 2)),
-                 opts.get("nu0_chosen", 1.0), opts.get("sigma20_chosen", 0.02)]
+        from .cv import kfold_cv
+        opts, y, folds, values, prior = self._cv_arguments("cross_validate", n_folds, groups,
+                                                          training_options, seed)
         out = kfold_cv(np.asarray(self.U_hat, dtype=np.float64), y, prior, folds,
                        opts.get("iterations", 50000), burn=opts.get("burn", 10000),
                        thin=opts.get("thin", 1), n_chains=int(opts.get("n_chains", 1)), seed=seed,
@@ -324,6 +332,44 @@ class BayesianModelCombination:
         out["predicted"] = out["cv_mean_i"] + mu
         out["truth"] = y + mu
         out["residual"] = y - out["cv_mean_i"]
+        return out
+
+    def component_path(self, n_folds=10, groups=None, components=None, training_options=None, seed=None):
+        """Choose ``components_kept`` by cross-validation (not in the reference;
+        ``pybmc_amd.cv.cv_component_path``): ``cross_validate()`` for every candidate number of
+        components in one call on the GPU.  Call it after ``orthogonalize(..., components_kept=k_max)``
+        with the largest count worth considering; no ``train()`` is needed.  Candidate k is the model
+        on the leading k columns of ``U_hat`` -- what ``orthogonalize(..., components_kept=k)`` would
+        keep -- under the leading block of the prior (the default ``diag(S_hat ** 2)`` is the one
+        ``train()`` would use).  ``components`` is a strictly increasing sequence in ``1 .. k_max``
+        (default: all); ``n_folds``, ``groups``, ``training_options`` and ``seed`` as in
+        ``cross_validate()``, Gibbs sampler only (``sampler == "simplex"`` raises ``ValueError``).
+
+        The SVD basis is held fixed: ``U_hat`` is the basis ``orthogonalize()`` made from ALL
+        training rows and is not recomputed per fold.  That basis depends on the model predictions
+        only, never on the truth, so no held-out truth reaches a fold's fit; it is the same
+        conditioning as ``loo()``, whose ``elpd_loo`` is therefore comparable with ``elpd_cv``.
+
+        Returns the dict of ``cv_component_path`` (per candidate ``elpd_cv``, ``se``, ``cv_rmse``,
+        ``elpd_fold``, ``elpd_cv_i``, ``cv_mean_i``; ``k_best``, ``k_1se``, ``elpd_diff``,
+        ``se_diff``; ...), ``folds`` (the labels), ``groups`` (the distinct values, with ``groups``)
+        and ``table``: a DataFrame indexed by ``components`` with the columns ``elpd_cv``, ``se``,
+        ``elpd_diff``, ``se_diff`` and ``cv_rmse``.  Then call
+        ``orthogonalize(..., components_kept=out["k_1se"])`` (the most parsimonious count
+        indistinguishable from the best; or ``out["k_best"]``) followed by ``train()``."""
+        from .cv import cv_component_path
+        opts, y, folds, values, prior = self._cv_arguments("component_path", n_folds, groups,
+                                                          training_options, seed)
+        out = cv_component_path(np.asarray(self.U_hat, dtype=np.float64), y, prior, folds,
+                                opts.get("iterations", 50000), components=components,
+                                burn=opts.get("burn", 10000), thin=opts.get("thin", 1),
+                                n_chains=int(opts.get("n_chains", 1)), seed=seed, device=self.device)
+        out["folds"] = folds
+        if values is not None:
+            out["groups"] = values
+        out["table"] = pd.DataFrame({key: out[key] for key in ("elpd_cv", "se", "elpd_diff", "se_diff",
+                                                               "cv_rmse")},
+                                    index=pd.Index(out["components"], name="components"))
         return out
 
     def log_predictive_density(self, X, burn=0):

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "bmc_cv_plan.h"
+#include "bmc_cvpath_plan.h"
 
 namespace bmc {
 
@@ -59,8 +60,25 @@ hipError_t launch_cv_unrotate(const double* u, const double* WT, int32_t k, int3
 hipError_t launch_cv_colmean(const double* draws, int32_t k, int64_t S, int32_t folds, int32_t fold0,
                              double* bbar, hipStream_t s);
 
-// mean[r] = Z[r][0..k) . bbar[row_fold[r]]
-hipError_t launch_cv_mean(const double* Z, int32_t k, const int32_t* row_fold, const double* bbar,
-                          int64_t n_pad, double* mean, hipStream_t s);
+// mean[r] = Z[r][0..k) . bbar[row_fold[r]]; ldz the leading dimension of Z (cv_ldz of the width it
+// was gathered at)
+hipError_t launch_cv_mean(const double* Z, int32_t ldz, int32_t k, const int32_t* row_fold,
+                          const double* bbar, int64_t n_pad, double* mean, hipStream_t s);
+
+// The chains of a component path (bmc_cv_path; the plan in bmc_cvpath_plan.h): block b of the launch
+// is local chain l = chain0 + b of the batch, chain l % chains_per_problem of problem
+// l / chains_per_problem, and runs the body of cv_gram_kernel<kmax> on what desc[] names.  Every
+// chain of a launch has cv_kmax(k) == kmax.
+struct CvPathArgs {
+    const CvPathDesc* desc;   // [problems of the batch], device
+    int32_t chains_per_problem, kmax;
+    int64_t chain0;
+    const double *G, *lam, *c1, *c2, *u0, *g0, *scal;   // set-up arrays of all problems
+    const double *xi, *gam;   // the batch's variates
+    double* uout;             // the batch's rotated draws
+    int64_t iters;
+    int32_t n_chains;         // chains in THIS launch
+};
+hipError_t launch_cv_path(const CvPathArgs& a, hipStream_t s);
 
 }  // namespace bmc

@@ -9,6 +9,8 @@
 //                           coefficient vectors at once: non-negative sums, nothing cancels;
 //   * cv_gram_kernel        gibbs_gram_kernel for F x C chains of F different problems, one wave
 //                           per chain, every per-problem quantity indexed by the chain's fold;
+//   * cv_path_kernel        the same chain body for problems of different widths (the component
+//                           path, bmc_cv_path): each chain finds its problem through a descriptor;
 //   * cv_unrotate_kernel    the kept draws back in the coefficient basis, per-fold W;
 //   * cv_colmean_kernel, cv_mean_kernel   the held-out predictive mean a_i . mean_s beta_s.
 // The held-out log predictive densities come from the score kernels (kernels_waic.hip) on a fold's
@@ -159,31 +161,29 @@ __global__ __launch_bounds__(64) void cv_block_rss_kernel(const double* __restri
 
 // ---- all chains of all folds ----------------------------------------------------------------------------
 // gibbs_gram_kernel (kernels_gibbs.hip explains the iteration, the 64-row output staging and the
-// deferred sigma roots) with every per-problem quantity taken from the chain's fold; the base
-// pointers are formed once, in front of the loop.
+// deferred sigma roots) for ONE chain of width K <= KMAX, one wave: its variates xi [T][K] and gam
+// [T], its rotated draws uout [T][K+1], and its problem's G [K][K], k-vectors and scal (rss0,
+// sigma2_init, nu0 * sigma20).  The body of cv_gram_kernel and cv_path_kernel: a chain of the
+// component path is the chain bmc_kfold_cv runs on the leading columns, operation for operation.
 template <int KMAX>
-__global__ __launch_bounds__(64) void cv_gram_kernel(CvGramArgs a) {
+__device__ __forceinline__ void cv_chain(const int K, const int64_t T_it, const double* __restrict__ xi,
+                                         const double* __restrict__ gam, double* __restrict__ uout,
+                                         const double* __restrict__ Gf, const double* __restrict__ lamv,
+                                         const double* __restrict__ c1v, const double* __restrict__ c2v,
+                                         const double* __restrict__ u0v, const double* __restrict__ g0v,
+                                         const double* __restrict__ scal) {
     __shared__ double d_lds[64];
     __shared__ double rows[64 * (KMAX + 1)];
-    const int lane = threadIdx.x, K = a.k;
-    if ((int)blockIdx.x >= a.n_chains) return;
-    const int64_t fold = (a.chain0 + blockIdx.x) / a.chains_per_fold;
-    const int64_t local = a.local0 + blockIdx.x;
-    const int64_t T_it = a.iters;
-    const double* xi = a.xi + local * T_it * K;
-    const double* gam = a.gam + local * T_it;
-    double* uout = a.uout + local * T_it * (K + 1);
-    const double* Gf = a.G + fold * K * K;
-    const int64_t fl = fold * K + lane;   // the lane's element of the fold's k-vectors
+    const int lane = threadIdx.x;
     const bool act = lane < K;
     double grow[KMAX];   // row `lane` of G
 #pragma unroll
     for (int i = 0; i < KMAX; ++i) grow[i] = (act && i < K) ? Gf[(size_t)lane * K + i] : 0.0;
-    const double lam = act ? a.lam[fl] : 0.0, c1 = act ? a.c1[fl] : 0.0;
-    const double c2 = act ? a.c2[fl] : 0.0, u0 = act ? a.u0[fl] : 0.0;
-    const double g0x2 = act ? 2.0 * a.g0[fl] : 0.0;
-    const double rss0 = a.scal[fold * 4 + 0], sigma2_init = a.scal[fold * 4 + 1];
-    const double nu0_s20 = a.scal[fold * 4 + 2];
+    const double lam = act ? lamv[lane] : 0.0, c1 = act ? c1v[lane] : 0.0;
+    const double c2 = act ? c2v[lane] : 0.0, u0 = act ? u0v[lane] : 0.0;
+    const double g0x2 = act ? 2.0 * g0v[lane] : 0.0;
+    const double rss0 = scal[0], sigma2_init = scal[1];
+    const double nu0_s20 = scal[2];
     d_lds[lane] = 0.0;
     double sp_eff = sigma2_init, g_eff = 1.0;
     double sp_cap = 1.0, g_cap = 1.0;   // lane i: the (sp, g) pair behind staged row i
@@ -229,6 +229,35 @@ __global__ __launch_bounds__(64) void cv_gram_kernel(CvGramArgs a) {
             for (int idx = lane; idx < nrows * K1; idx += 64) dst[idx] = rows[idx];
         }
     }
+}
+
+// F x C chains of F problems of one width: every per-problem quantity is the chain's fold's; the
+// base pointers are formed once, in front of the loop.
+template <int KMAX>
+__global__ __launch_bounds__(64) void cv_gram_kernel(CvGramArgs a) {
+    const int K = a.k;
+    if ((int)blockIdx.x >= a.n_chains) return;
+    const int64_t fold = (a.chain0 + blockIdx.x) / a.chains_per_fold;
+    const int64_t local = a.local0 + blockIdx.x;
+    const int64_t T_it = a.iters;
+    const int64_t fk = fold * K;
+    cv_chain<KMAX>(K, T_it, a.xi + local * T_it * K, a.gam + local * T_it, a.uout + local * T_it * (K + 1),
+                   a.G + fk * K, a.lam + fk, a.c1 + fk, a.c2 + fk, a.u0 + fk, a.g0 + fk, a.scal + fold * 4);
+}
+
+// The chains of a component path: problems of DIFFERENT widths within one width class, each
+// found through its descriptor (bmc_cvpath_plan.h).
+template <int KMAX>
+__global__ __launch_bounds__(64) void cv_path_kernel(CvPathArgs a) {
+    if ((int)blockIdx.x >= a.n_chains) return;
+    const int64_t l = a.chain0 + blockIdx.x;
+    const int64_t p = l / a.chains_per_problem, c = l - p * a.chains_per_problem;
+    const CvPathDesc d = a.desc[p];
+    const int K = d.k;
+    const int64_t T_it = a.iters;
+    cv_chain<KMAX>(K, T_it, a.xi + d.xi_off + c * T_it * K, a.gam + d.gam_off + c * T_it,
+                   a.uout + d.u_off + c * T_it * (K + 1), a.G + d.g_off, a.lam + d.v_off, a.c1 + d.v_off,
+                   a.c2 + d.v_off, a.u0 + d.v_off, a.g0 + d.v_off, a.scal + d.s_off);
 }
 
 // ---- kept draws in the coefficient basis ------------------------------------------------------------------
@@ -375,10 +404,26 @@ hipError_t launch_cv_colmean(const double* draws, int32_t k, int64_t S, int32_t 
     return hipGetLastError();
 }
 
-hipError_t launch_cv_mean(const double* Z, int32_t k, const int32_t* row_fold, const double* bbar,
-                          int64_t n_pad, double* mean, hipStream_t s) {
+hipError_t launch_cv_mean(const double* Z, int32_t ldz, int32_t k, const int32_t* row_fold,
+                          const double* bbar, int64_t n_pad, double* mean, hipStream_t s) {
+    if (k < 1 || ldz < k) return hipErrorInvalidValue;
     hipLaunchKernelGGL(cv_mean_kernel, dim3(blocks_for(n_pad, 256, (int64_t)1 << 30)), dim3(256), 0, s, Z,
-                       cv_ldz(k), k, row_fold, bbar, n_pad, mean);
+                       ldz, k, row_fold, bbar, n_pad, mean);
+    return hipGetLastError();
+}
+
+hipError_t launch_cv_path(const CvPathArgs& a, hipStream_t s) {
+    if (!a.desc || a.n_chains < 1 || a.n_chains > CV_MAX_CHAINS_PER_LAUNCH || a.chains_per_problem < 1 ||
+        a.chain0 < 0 || a.iters < 1)
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)a.n_chains), block(64);
+    switch (a.kmax) {
+    case 8: hipLaunchKernelGGL(cv_path_kernel<8>, grid, block, 0, s, a); break;
+    case 16: hipLaunchKernelGGL(cv_path_kernel<16>, grid, block, 0, s, a); break;
+    case 32: hipLaunchKernelGGL(cv_path_kernel<32>, grid, block, 0, s, a); break;
+    case 64: hipLaunchKernelGGL(cv_path_kernel<64>, grid, block, 0, s, a); break;
+    default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 

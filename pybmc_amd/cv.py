@@ -24,6 +24,11 @@ On the device (``kernels_cv.hip``): the rows are gathered into fold order once, 
 matrix cores gives the Gram of every fold's own rows, and the training statistics of fold f are the
 total minus its own.  The F x C chains then run from those statistics alone, one wave each, in
 launches of at most 2048 chains.  At most 64 columns and 1024 folds.
+
+``cv_component_path`` answers "how many components?": the model with k components is the leading k
+columns of the same matrix, so one gather and one Gram pass serve every candidate k and all
+candidates' chains share the device; ``path_summary`` picks ``k_best`` and, by the
+one-standard-error rule, ``k_1se``.
 """
 from __future__ import annotations
 
@@ -150,4 +155,111 @@ def kfold_cv(A, y, prior_info, folds, iterations, burn=0, thin=1, n_chains=1, se
     out.update(elpd_cv_i=elpd_i, cv_mean_i=mean_i, seeds=seeds)
     if return_draws:
         out["draws"] = draws
+    return out
+
+
+def _check_components(components, k_max):
+    """int32 candidates of a valid ``components`` (None: 1 .. k_max); ValueError otherwise."""
+    if components is None:
+        return np.arange(1, k_max + 1, dtype=np.int32)
+    try:
+        items = list(components)
+    except TypeError:
+        raise ValueError("components must be a sequence of integers") from None
+    if not items:
+        raise ValueError("components must name at least one candidate")
+    for v in items:
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"components must be integers; got {v!r}")
+        if v < 1 or v > k_max:
+            raise ValueError(f"components must lie in 1 .. {k_max}; got {int(v)}")
+    if any(b <= a for a, b in zip(items, items[1:])):
+        raise ValueError("components must be strictly increasing, without repeats")
+    return np.asarray(items, dtype=np.int32)
+
+
+def path_summary(components, elpd_cv_i):
+    """Which candidate?  ``components`` ``(m,)`` and the pointwise ``elpd_cv_i`` ``(m, n)`` of the
+    same rows under every candidate give
+
+    * ``k_best``: the candidate of largest ``elpd_cv`` (the smallest such on a tie);
+    * ``elpd_diff[j] = elpd_cv[best] - elpd_cv[j]``;
+    * ``se_diff[j] = sqrt(n var_i(elpd_cv_i[best] - elpd_cv_i[j], ddof=1))``, the paired standard
+      error of that difference (0 at ``best``);
+    * ``k_1se``: the smallest candidate with ``elpd_diff[j] <= se_diff[j]`` -- the
+      one-standard-error rule: the most parsimonious model indistinguishable from the best.
+
+    Host, float64; no GPU."""
+    comps = np.asarray(components)
+    e = np.asarray(elpd_cv_i, dtype=np.float64)
+    if comps.ndim != 1 or e.ndim != 2 or e.shape[0] != comps.shape[0] or comps.shape[0] < 1:
+        raise ValueError(f"need components (m,) and elpd_cv_i (m, n); got {comps.shape} and {e.shape}")
+    elpd = e.sum(axis=1)
+    best = int(np.argmax(elpd))          # (the first of equal maxima: the smallest candidate)
+    elpd_diff = elpd[best] - elpd
+    se_diff = np.array([_se(e[best] - e[j]) if j != best else 0.0 for j in range(e.shape[0])])
+    within = np.nonzero(elpd_diff <= se_diff)[0]
+    return {"k_best": int(comps[best]), "k_1se": int(comps[within.min()]), "elpd_diff": elpd_diff,
+            "se_diff": se_diff}
+
+
+def cv_component_path(A, y, prior_info, folds, iterations, components=None, burn=0, thin=1, n_chains=1,
+                      seed=None, seeds=None, return_draws=False, device=0):
+    """``kfold_cv`` for every candidate component count in one call.
+
+    ``A`` is ``(n, k_max)`` float64 with k_max <= 64 (either memory order); ``components`` a
+    strictly increasing sequence of integers in ``1 .. k_max`` (default: all of them).  Candidate k
+    is the model with design ``A[:, :k]`` and prior ``[b0[:k], C0[:k, :k], nu0, sigma20]`` -- the
+    exact marginal of the Gaussian prior.  ``y``, ``prior_info``, ``folds``, ``iterations``,
+    ``burn``, ``thin`` and ``n_chains`` as in ``kfold_cv``; every training set must hold at least
+    ``max(components)`` rows.  ``seeds`` ``(F, n_chains)`` (or derived from ``seed`` as ``kfold_cv``
+    derives them) serve every candidate: chain (k, f, c) consumes the streams of ``seeds[f, c]``
+    exactly as ``kfold_cv(A[:, :k], ..., seeds=seeds)`` does, and the result of candidate k is that
+    call's.
+
+    Returns a dict, m = ``len(components)``: ``components`` ``(m,)``; ``elpd_cv``, ``se``,
+    ``cv_rmse`` ``(m,)`` and ``elpd_fold`` ``(m, F)``; ``n_fold``, ``n_points``, ``n_folds``,
+    ``n_draws``; the pointwise ``elpd_cv_i`` and ``cv_mean_i`` ``(m, n)``; ``seeds``; with
+    ``return_draws`` ``draws``, a list of m arrays ``(F, n_chains, kept, k + 1)``; and the selection
+    of ``path_summary``: ``k_best``, ``k_1se``, ``elpd_diff``, ``se_diff``.  Argument errors are
+    ``ValueError`` before any GPU work; a (candidate, fold) whose training Gram is numerically
+    singular raises ``_lib.SingularFoldError`` naming the fold and the component count."""
+    from . import _lib
+
+    A = np.asarray(A)
+    y = np.asarray(y)
+    if A.dtype != np.float64 or y.dtype != np.float64:
+        raise ValueError("A and y must be float64")
+    if A.ndim == 2 and A.shape[1] > MAX_K:
+        raise ValueError(f"k_max must be at most {MAX_K} (one lane per coefficient); got {A.shape[1]}")
+    iterations = _check_int("iterations", iterations, 1)
+    n_chains = _check_int("n_chains", n_chains, 1)
+    k1 = (A.shape[1] if A.ndim == 2 else 0) + 1
+    n, k_max, C, T, kept = _check_shapes(A.shape, y.shape, (n_chains, iterations, k1), burn, thin)
+    if burn >= iterations:
+        raise ValueError(f"burn = {burn} leaves no draw of {iterations} iterations")
+    comps = _check_components(components, k_max)
+    f, F, count = _check_folds(folds, n, int(comps[-1]))
+    b0, C0, nu0, s20 = prior_info
+    b0 = np.asarray(b0, dtype=np.float64)
+    C0 = np.asarray(C0, dtype=np.float64)
+    if b0.shape != (k_max,) or C0.shape != (k_max, k_max):
+        raise ValueError(f"prior_info must hold b_mean_prior ({k_max},) and b_mean_cov ({k_max}, {k_max})")
+    seeds = _check_seeds(seed, seeds, F, C)
+    Ah, lda, layout = _host_matrix(A)
+    ctx = _lib.default_context(device)
+    with ctx.lock:
+        elpd_i, mean_i, draws = ctx.cv_path(Ah, n, k_max, lda, layout, np.ascontiguousarray(y), f, F, b0,
+                                            C0, nu0, s20, C, T, int(burn), int(thin), seeds.reshape(-1),
+                                            comps, return_draws=return_draws)
+    per = [cv_summary(y, f, F, elpd_i[j], mean_i[j], C * kept) for j in range(len(comps))]
+    out = {"components": comps.astype(np.int64)}
+    for key in ("elpd_cv", "se", "cv_rmse", "elpd_fold"):
+        out[key] = np.array([p[key] for p in per])
+    for key in ("n_fold", "n_points", "n_folds", "n_draws"):
+        out[key] = per[0][key]
+    out.update(elpd_cv_i=elpd_i, cv_mean_i=mean_i, seeds=seeds)
+    if return_draws:
+        out["draws"] = draws
+    out.update(path_summary(out["components"], elpd_i))
     return out
