@@ -523,6 +523,59 @@ int bmc_ppc_device(bmc_ctx* ctx, const void* dA, int64_t n_points, int32_t k, in
                    int64_t n_draws, int64_t ldt, uint64_t seed, double center, double* t_rep_out,
                    double* t_obs2_out);
 
+/* ---- power-scaling sensitivity: does the answer depend on the prior? (not in the reference) -----
+ * Model and arguments A, y, theta as bmc_pointwise_loglik (n_draws >= 2 pooled draws, row s =
+ * (beta_s, sigma_s)); the prior of bmc_set_prior: b0 [k], C0 [k][k] (row-major, symmetric positive
+ * definite; factored on the host), nu0, sigma20 -- HOST pointers in both forms, as are Vt
+ * [k][n_models] (row-major; NULL with n_models = 0) and alphas [n_alphas] (1 .. 66 values, each
+ * > 0, finite and != 1).  Per draw, additive constants dropped:
+ *   lp_beta   = -1/2 (beta - b0)' C0^-1 (beta - b0)
+ *   lp_sigma2 = -(nu0/2 + 1) log sigma^2 - nu0 sigma20 / (2 sigma^2)
+ *   loglik    = -(n/2) log 2 pi - n log sigma - sum_i (y_i - a_i . beta)^2 / (2 sigma^2)
+ * (all three NaN for a draw with a non-finite coefficient or without a finite sigma > 0).
+ * `components` is a mask of bit 0 prior = lp_beta + lp_sigma2, bit 1 likelihood = loglik, bit 2
+ * prior_beta, bit 3 prior_sigma2; the set bits in that order are the components c, and weight
+ * vector w = c * n_alphas + a is that of (component c, alphas[a]): lw = (alpha - 1) lp_c shifted
+ * to a largest of 0, Pareto-smoothed as bmc_psis_loo smooths its weights (tail of
+ * M = min(floor(S / 5), ceil(3 sqrt S)) draws in ascending lw with ties in draw order, no fit when
+ * M < 5 or the tail is one value), truncated at 0, normalised to sum 1.  The quantity columns are
+ * q = 0 .. k-1 the coefficients, q = k sigma, q = k+1 .. k+n_models the model weights
+ * beta . Vt + 1 / n_models; Q = k + 1 + n_models.  For column q and vector w, with the draws sorted
+ * by (value, draw), P_j = j / S and Q_j the running sum of the weights: the cumulative
+ * Jensen-Shannon distance cjs = sqrt((cjs_PQ + cjs_QP) / (I_P + I_Q)) (0 for
+ * a constant column) and the weighted mean and sd.  Outputs (host; any may be NULL):
+ *   logdens_out   [3][n_draws]: lp_beta, lp_sigma2, loglik
+ *   pareto_k_out  [W], W = n_components * n_alphas; +inf where nothing was smoothed
+ *   mean_out, sd_out, cjs_out   [W][Q]
+ *   weights_out   [n_draws][W]: the normalised weights, in draw order
+ *   flags_out     [n_components + Q]: 1 for a component with a non-finite log density (its
+ *                 pareto_k, weights and every mean / sd / cjs are NaN) and for a column with a
+ *                 non-finite value (its mean / sd / cjs are NaN), else 0
+ * Every vector is sorted once, whatever n_alphas; the columns are sorted in batches of
+ * cols_per_batch (0: as many as the free device memory holds).  Results are deterministic and do
+ * not depend on cols_per_batch or on which other alphas are in the call.  BMC_EINVAL for bad
+ * arguments (k outside 1..256, n_models > 4096, n_draws > 2^31 - 2), BMC_ESINGULAR when C0 is not
+ * positive definite, BMC_ENOMEM when one column does not fit.  The _device form reads
+ * caller-owned DEVICE memory (A, y, theta).  bmc_sens_last_timing: device milliseconds of the last
+ * call: log densities, sorts, Pareto smoothing, distances. */
+int bmc_power_sensitivity(bmc_ctx* ctx, const double* A, int64_t n_points, int32_t k, int64_t lda,
+                          int layout, const double* y, const double* theta, int64_t n_draws,
+                          int64_t ldt, const double* b0, const double* C0, double nu0,
+                          double sigma20, const double* Vt, int32_t n_models, const double* alphas,
+                          int32_t n_alphas, uint32_t components, int32_t cols_per_batch,
+                          double* logdens_out, double* pareto_k_out, double* mean_out,
+                          double* sd_out, double* cjs_out, double* weights_out,
+                          uint32_t* flags_out);
+int bmc_power_sensitivity_device(bmc_ctx* ctx, const void* dA, int64_t n_points, int32_t k,
+                                 int64_t lda, int layout, const void* dy, const void* dtheta,
+                                 int64_t n_draws, int64_t ldt, const double* b0, const double* C0,
+                                 double nu0, double sigma20, const double* Vt, int32_t n_models,
+                                 const double* alphas, int32_t n_alphas, uint32_t components,
+                                 int32_t cols_per_batch, double* logdens_out, double* pareto_k_out,
+                                 double* mean_out, double* sd_out, double* cjs_out,
+                                 double* weights_out, uint32_t* flags_out);
+int bmc_sens_last_timing(bmc_ctx* ctx, double ms_out[4]);
+
 /* ---- on-device variates (exposed so the generator itself can be tested) ----
  * normals_out [count_normal] ~ N(0,1); gammas_out [count_gamma] ~ Gamma(shape,1). */
 int bmc_rng_fill(bmc_ctx* ctx, uint64_t seed, int64_t count_normal, double* normals_out,

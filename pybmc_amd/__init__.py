@@ -12,6 +12,7 @@ from .ppc import PPC_STATS, posterior_predictive_check, ppc_summary
 from .rankdiag import rank_diagnostics, rank_normalize
 from .sampling_utils import coverage, rndm_m_random_calculator
 from .scoring import pointwise_log_likelihood, psis_loo, psis_loo_predict, waic
+from .sensitivity import power_scale_sensitivity, power_scale_weights, sensitivity_summary
 
 __all__ = [
     "Dataset",
@@ -35,4 +36,7 @@ __all__ = [
     "posterior_predictive_check",
     "ppc_summary",
     "PPC_STATS",
+    "power_scale_sensitivity",
+    "power_scale_weights",
+    "sensitivity_summary",
 ]

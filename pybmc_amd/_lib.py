@@ -128,6 +128,16 @@ PROTOTYPES = {
                           C.c_int64, C.c_uint64, C.c_double, _D, _D]),
     "bmc_ppc_device": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int, _P, _P, _P,
                                  C.c_int64, C.c_int64, C.c_uint64, C.c_double, _D, _D]),
+    "bmc_power_sensitivity": (C.c_int, [_P, _D, C.c_int64, C.c_int32, C.c_int64, C.c_int, _D, _D,
+                                        C.c_int64, C.c_int64, _D, _D, C.c_double, C.c_double, _D,
+                                        C.c_int32, _D, C.c_int32, C.c_uint32, C.c_int32, _D, _D, _D,
+                                        _D, _D, _D, C.POINTER(C.c_uint32)]),
+    "bmc_power_sensitivity_device": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int, _P,
+                                               _P, C.c_int64, C.c_int64, _D, _D, C.c_double,
+                                               C.c_double, _D, C.c_int32, _D, C.c_int32, C.c_uint32,
+                                               C.c_int32, _D, _D, _D, _D, _D, _D,
+                                               C.POINTER(C.c_uint32)]),
+    "bmc_sens_last_timing": (C.c_int, [_P, _D]),
     "bmc_rng_fill": (C.c_int, [_P, C.c_uint64, C.c_int64, _D, C.c_double, C.c_int64, _D]),
     "bmc_philox_raw": (C.c_int, [_P, C.c_uint64, C.c_uint32, C.c_int64, C.POINTER(C.c_uint32)]),
 }
@@ -700,6 +710,65 @@ class Context:
         context's stream: the caller orders its producers before the call."""
         return self._ppc_call(self._lib.bmc_ppc_device, _P, dA, n, k, lda, layout, dy, dtheta,
                               n_draws, ldt, doffset, seed, center)
+
+    # -- power-scaling sensitivity ----------------------------------------------------------------
+    SENS_COMPONENTS = ("prior", "likelihood", "prior_beta", "prior_sigma2")   # bit order of the mask
+
+    def _sens_call(self, fn, ptr, A, n, k, lda, layout, y, theta, n_draws, ldt, prior, Vt, alphas,
+                   components, cols_per_batch, want_weights):
+        b0, C0, nu0, sigma20 = prior
+        b0 = np.ascontiguousarray(b0, dtype=np.float64).reshape(-1)
+        C0 = np.ascontiguousarray(C0, dtype=np.float64)
+        if b0.shape != (k,) or C0.shape != (k, k):
+            raise ValueError(f"the prior must hold b0 ({k},) and C0 ({k}, {k})")
+        if Vt is not None and (np.ndim(Vt) != 2 or np.shape(Vt)[0] != k):
+            raise ValueError(f"Vt must be ({k}, n_models)")
+        alphas = np.ascontiguousarray(alphas, dtype=np.float64).reshape(-1)
+        n_models = 0
+        if Vt is not None:
+            Vt = np.ascontiguousarray(Vt, dtype=np.float64)
+            n_models = int(Vt.shape[1])
+        S, mask = int(n_draws), int(components)
+        n_comp = bin(mask).count("1")
+        W, Q = n_comp * len(alphas), int(k) + 1 + n_models
+        out = {"logdens": np.empty((3, S)), "pareto_k": np.empty((n_comp, len(alphas))),
+               "mean": np.empty((n_comp, len(alphas), Q)), "sd": np.empty((n_comp, len(alphas), Q)),
+               "cjs": np.empty((n_comp, len(alphas), Q)),
+               "weights": np.empty((S, W)) if want_weights else None}
+        flags = np.zeros(n_comp + Q, dtype=np.uint32)
+        self._check(fn(self._h, ptr(A), int(n), int(k), int(lda), int(layout), ptr(y), ptr(theta), S,
+                       int(ldt), _dptr(b0), _dptr(C0), float(nu0), float(sigma20), _dptr(Vt), n_models,
+                       _dptr(alphas), len(alphas), mask, int(cols_per_batch), _dptr(out["logdens"]),
+                       _dptr(out["pareto_k"]), _dptr(out["mean"]), _dptr(out["sd"]), _dptr(out["cjs"]),
+                       _dptr(out["weights"]), flags.ctypes.data_as(C.POINTER(C.c_uint32))))
+        out["component_flags"] = flags[:n_comp].astype(bool)
+        out["column_flags"] = flags[n_comp:].astype(bool)
+        return out
+
+    def power_sensitivity(self, A, n, k, lda, layout, y, theta, n_draws, ldt, prior, Vt, alphas,
+                          components, cols_per_batch=0, want_weights=False):
+        """bmc_power_sensitivity of HOST f64 arrays: A, y and theta as pointwise_loglik, prior =
+        (b0, C0, nu0, sigma20), Vt (k, n_models) or None, alphas, components a bit mask in the
+        order of SENS_COMPONENTS.  Returns a dict: ``logdens`` (3, S), ``pareto_k`` (c, a),
+        ``mean`` / ``sd`` / ``cjs`` (c, a, Q), ``weights`` (S, c * a) or None, and the boolean
+        ``component_flags`` (c,) and ``column_flags`` (Q,)."""
+        return self._sens_call(self._lib.bmc_power_sensitivity, _dptr, A, n, k, lda, layout, y, theta,
+                               n_draws, ldt, prior, Vt, alphas, components, cols_per_batch, want_weights)
+
+    def power_sensitivity_device(self, dA, n, k, lda, layout, dy, dtheta, n_draws, ldt, prior, Vt,
+                                 alphas, components, cols_per_batch=0, want_weights=False):
+        """The same on DEVICE memory for A, y and theta (bmc_power_sensitivity_device), read on the
+        context's stream: the caller orders its producers before the call."""
+        return self._sens_call(self._lib.bmc_power_sensitivity_device, _P, dA, n, k, lda, layout, dy,
+                               dtheta, n_draws, ldt, prior, Vt, alphas, components, cols_per_batch,
+                               want_weights)
+
+    def sens_last_timing(self):
+        """Device milliseconds of the last power_sensitivity* call: log densities, sorts, Pareto
+        smoothing, distances."""
+        ms = np.zeros(4)
+        self._check(self._lib.bmc_sens_last_timing(self._h, _dptr(ms)))
+        return dict(zip(("logdens_ms", "sort_ms", "psis_ms", "cjs_ms"), ms.tolist()))
 
     # -- exact K-fold / leave-group-out cross-validation --------------------------------------------
     def kfold_cv(self, A, n, k, lda, layout, y, fold, n_folds, b0, C0, nu0, sigma20, n_chains, iters,

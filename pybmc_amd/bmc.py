@@ -48,6 +48,7 @@ class BayesianModelCombination:
         self._train_df = None
         self.last_stats = None
         self._device_problem = None
+        self._trained_with = None   # (sampler, [b0, C0, nu0, sigma20]) of the last train()
 
     # ------------------------------------------------------------------ set-up
     def orthogonalize(self, property, train_df, components_kept, method="auto"):
@@ -134,6 +135,8 @@ class BayesianModelCombination:
         nu0 = get_option("nu0_chosen", 1.0)
         sigma20 = get_option("sigma20_chosen", 0.02)
 
+        self._trained_with = ("simplex" if sampler == "simplex" else "gibbs",
+                              [b_mean_prior, b_mean_cov, nu0, sigma20])
         if sampler == "simplex":
             devices = opts.get("devices")
             if devices is not None and list(devices) != [self.device]:
@@ -265,6 +268,31 @@ class BayesianModelCombination:
         out["truth"] = y + mu
         out["residual"] = y - out["loo_mean"]
         return out
+
+    def prior_sensitivity(self, burn=0, alphas=None, training_options=None):
+        """Power-scaling sensitivity of the last ``train()`` to its prior and its likelihood (not in
+        the reference; ``pybmc_amd.sensitivity.power_scale_sensitivity``): for every coefficient,
+        ``sigma`` and every model weight ``beta Vt_hat + 1/K``, how far the posterior marginal moves
+        when the prior, or the likelihood, is raised to a power near 1 -- from the draws already
+        taken.  The priors are those ``train()`` used; ``training_options`` (the keys
+        ``b_mean_prior``, ``b_mean_cov``, ``nu0_chosen``, ``sigma20_chosen``) overrides them.
+        ``burn`` more draws are dropped from the start of each chain.  Gibbs sampler only: after
+        ``sampler == "simplex"`` it raises ``ValueError`` (that sampler's target is not this
+        posterior).  Returns that function's dict; ``sensitivity.sensitivity_summary`` makes the
+        table."""
+        if self.samples is None or self.U_hat is None or self._trained_with is None:
+            raise ValueError("Must call `orthogonalize()` and `train()` before the prior sensitivity.")
+        sampler, prior = self._trained_with
+        opts = training_options if training_options is not None else {}
+        if sampler == "simplex" or opts.get("sampler", "gibbs_sampling") == "simplex":
+            raise ValueError('prior_sensitivity supports the Gibbs sampler only (sampler == "simplex")')
+        prior = [opts.get("b_mean_prior", prior[0]), opts.get("b_mean_cov", prior[1]),
+                 opts.get("nu0_chosen", prior[2]), opts.get("sigma20_chosen", prior[3])]
+        from .sensitivity import power_scale_sensitivity
+        return power_scale_sensitivity(
+            self.U_hat, np.asarray(self.centered_experiment_train, dtype=np.float64), self._chains(),
+            prior, Vt_hat=self.Vt_hat, burn=burn, alphas=alphas, device=self.device,
+            models=self.models)
 
     def _cv_arguments(self, what, n_folds, groups, training_options, seed):
         """(options, y, fold labels, group values or None, prior) of ``cross_validate`` and

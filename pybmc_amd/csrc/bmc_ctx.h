@@ -101,6 +101,10 @@ struct bmc_ctx : CtxHandles {
     DevBuf looWork;
     // posterior predictive check (bmc_ppc*): the staged offset, the padded operands and the results
     DevBuf ppcOff, ppcWork;
+    // power-scaling sensitivity (bmc_power_sensitivity*): staged operands, log densities, weights
+    // and the scan's partials (the sort reuses the rank buffers)
+    DevBuf snStage, snWork, snPart;
+    double sens_ms[4] = {0, 0, 0, 0};      // last bmc_power_sensitivity*: log densities, sorts, PSIS, CJS
     double predict_ms[4] = {0, 0, 0, 0};   // last bmc_predict: h2d, gemm, order statistics, device
     // pooling over GPUs (bmc_comm_*): RCCL communicator bound to this context's device
     ncclComm_t comm = nullptr;

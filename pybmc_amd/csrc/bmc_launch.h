@@ -7,6 +7,7 @@
 
 #include "bmc_plan.h"
 #include "bmc_rank_plan.h"
+#include "bmc_sens_plan.h"
 
 namespace bmc {
 
@@ -363,5 +364,48 @@ struct PpcArgs {
     double *Ap, *yo, *Tp, *sg, *t_rep, *t_obs2;
 };
 hipError_t launch_ppc(const PpcArgs& a, const PpcPlan& p, hipStream_t s);
+
+// ---- power-scaling sensitivity (kernels_sens.hip; plan_sens in bmc_sens_plan.h) -----------------
+// A (n x k, either layout) and y -> Ap [n_pad][k_pad], yo [n_pad], zero in the padding
+hipError_t launch_sens_pad_points(const double* A, const double* y, int64_t n, int32_t k, int64_t lda,
+                                  int32_t col_major, int64_t n_pad, int32_t k_pad, double* Ap, double* yo,
+                                  hipStream_t s);
+// Per draw s of theta (row s at theta + s*ldt: k coefficients, then sigma_s):
+//   lp[0][s] = -1/2 |Lp beta_s - Ly|^2   (Lp = L^-1, Ly = L^-1 b0 for C0 = L L', padded as Ap / yo)
+//   lp[1][s] = -(nu0/2 + 1) log sigma_s^2 - nu0 sigma20 / (2 sigma_s^2)
+//   lp[2][s] = -(n/2) log 2 pi - n log sigma_s - sum_i (y_i - a_i . beta_s)^2 / (2 sigma_s^2)
+// all NaN for a draw with a non-finite coefficient or without a finite sigma_s > 0; comps [.][S]:
+// the vectors of the set bits of `components` in bit order (lp0 + lp1, lp2, lp0, lp1); omega
+// [S][n_models] = beta_s . Vt + 1 / n_models (Vt [k][n_models]).  Work: Tp [S_pad][k_pad], rss [2][S].
+struct SensLogdensArgs {
+    const double *theta, *Ap, *yo, *Lp, *Ly, *Vt;
+    int64_t S, S_pad, ldt, n, n_pad, q_pad;
+    int32_t k, k_pad, n_models;
+    uint32_t components;
+    double nu0, sigma20;
+    double *Tp, *rss, *lp, *comps, *omega;
+};
+hipError_t launch_sens_logdens(const SensLogdensArgs& a, hipStream_t s);
+// Column j of a batch is p0[e * rs0 + j] for j < n0, else p1[e * rs1 + (j - n0) * cs1], e < S
+struct SensSource {
+    const double *p0, *p1;
+    int64_t rs0, rs1, cs1;
+    int32_t n0;
+};
+// As launch_rank_gather on segments of sens_padded(S) pairs: the S draws in draw order and, when
+// S is odd, one pad key that no real key exceeds (it stays last under the stable sort and adds no
+// live pass); or_and and flags over the real keys
+hipError_t launch_sens_gather(const SensSource& src, int64_t S, int32_t col0, int32_t Pb, uint64_t* keys,
+                              uint32_t* idx, uint64_t* or_and, uint32_t* flags, hipStream_t s);
+// keys / idx: the SORTED segments of the n_components component vectors.  Workgroup
+// w = c * n_alphas + a: Wt[s][w] = the Pareto-smoothed normalised weight of draw s, khat[w] its
+// pareto_k (+inf: nothing smoothed).  W = n_components * n_alphas; xs: [W][max(M, 1)] f64 scratch.
+hipError_t launch_sens_psis(const uint64_t* keys, const uint32_t* idx, int64_t S, int32_t n_components,
+                            int32_t n_alphas, const double* d_alphas, double* xs, double* Wt, double* khat,
+                            hipStream_t s);
+// keys / idx: the SORTED segments of Pb quantity columns.  out[jb][w][3] = cjs, weighted mean,
+// weighted sd of column jb under weight vector w.  offs [Pb][W][chunks], part [Pb][W][chunks][SENS_PART].
+hipError_t launch_sens_cjs(const uint64_t* keys, const uint32_t* idx, int64_t S, int32_t Pb, int32_t W,
+                           const double* Wt, double* offs, double* part, double* out, hipStream_t s);
 
 }  // namespace bmc
