@@ -576,6 +576,44 @@ int bmc_power_sensitivity_device(bmc_ctx* ctx, const void* dA, int64_t n_points,
                                  double* weights_out, uint32_t* flags_out);
 int bmc_sens_last_timing(bmc_ctx* ctx, double ms_out[4]);
 
+/* ---- Student-t (outlier-robust) Gibbs sampler, many chains per launch (not in the reference) ----
+ * The resident problem of bmc_set_problem (f64 storage, either layout, 1 <= k <= 32, n < 2^32) and
+ * the prior of bmc_set_prior, with the likelihood y_n | beta, sigma2, lambda_n ~ N(x_n . beta,
+ * sigma2 / lambda_n), lambda_n ~ Gamma(nu/2, rate nu/2): marginally t_nu(x_n . beta, sigma2); nu > 0
+ * is fixed.  Start: lambda = 1, sigma2 = the OLS start of bmc_set_prior.  Sweep t = 0, 1, ..., burn-in
+ * included (L = diag(lambda), P = inv(C0)):
+ *   1. Q = X'LX / sigma2 + P + 1e-6 I = L_c L_c';  beta = Q^-1 (P b0 + X'Ly / sigma2) + L_c^-T xi_t
+ *   2. r = y - X beta;  sigma2 = max(((nu0 sigma20 + sum lambda_n r_n^2) / 2) / G_t, 1e-6)
+ *   3. lambda_n = g_{t,n} / ((nu + r_n^2 / sigma2) / 2)
+ *   4. row t - burn of samples_out = [beta, sqrt(sigma2)] and lambda added to the rows' running sums
+ *      (t >= burn)
+ * with xi_t k standard normals, G_t ~ Gamma((nu0 + n) / 2, 1), g_{t,n} ~ Gamma((nu + 1) / 2, 1).
+ * rng_mode BMC_RNG_DEVICE: seeds [n_chains]; xi and G are elements t k + j and t of the normal and
+ *   gamma streams of bmc_rng_fill(seed), g_{t,n} is drawn in the kernel by Marsaglia-Tsang on the
+ *   Philox counters (n, t lo, 0x524F4253, ((t >> 32) << 8) | attempt) (xi, g, gl must be NULL).
+ * rng_mode BMC_RNG_REPLAY: xi [n_chains][burn+iters][k], g [n_chains][burn+iters] and
+ *   gl [n_chains][burn+iters][n] are the caller's (meant for tests at small n; BMC_ENOMEM when gl
+ *   does not fit the device).
+ * samples_out [n_chains][iters][k+1]; row_weight_out [n_chains][n], the mean of lambda_n over the kept
+ * sweeps (a per-row outlier score: far below 1 for a row the Gaussian model cannot reach), or NULL.
+ * One workgroup per chain, all chains of a call side by side (launches of at most 1024); a chain
+ * waits for no other workgroup.  CONTRACT: the order of every sum is fixed by (n, k) alone, so chain
+ * c of any call is bit for bit the one-chain call with seeds[c] (or its replay streams), whatever
+ * its index, its launch or the device, and identical calls agree bit for bit.
+ * BMC_EINVAL (nothing is launched) for k > 32, a problem stored in f32, nu <= 0, n_chains < 1,
+ * iters < 0, burn < 0.  A Cholesky pivot that is not positive and finite stops that chain (its later
+ * rows and weights are NaN): BMC_ESINGULAR, bmc_last_error names the first such chain "(chain c)",
+ * the other chains' results are still written.  stats: rng_ms, loop_ms, total_ms, iterations
+ * (burn + iters), n_chains, launches.  bmc_robust_run_device is the device-RNG form writing
+ * caller-owned DEVICE buffers (d_row_weight_out may be NULL); it returns after the stream has
+ * drained. */
+int bmc_robust_run(bmc_ctx* ctx, double nu, int32_t n_chains, int64_t iters, int64_t burn,
+                   int rng_mode, const uint64_t* seeds, const double* xi, const double* g,
+                   const double* gl, double* samples_out, double* row_weight_out, bmc_stats* stats);
+int bmc_robust_run_device(bmc_ctx* ctx, double nu, int32_t n_chains, int64_t iters, int64_t burn,
+                          const uint64_t* seeds, void* d_samples_out, void* d_row_weight_out,
+                          bmc_stats* stats);
+
 /* ---- on-device variates (exposed so the generator itself can be tested) ----
  * normals_out [count_normal] ~ N(0,1); gammas_out [count_gamma] ~ Gamma(shape,1). */
 int bmc_rng_fill(bmc_ctx* ctx, uint64_t seed, int64_t count_normal, double* normals_out,

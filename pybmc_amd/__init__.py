@@ -7,7 +7,8 @@ from .bmc import BayesianModelCombination
 from .cv import cv_component_path, fold_labels, kfold_cv, path_summary
 from .data import Dataset
 from .diagnostics import chain_diagnostics
-from .inference_utils import gibbs_sampler, gibbs_sampler_simplex, USVt_hat_extraction
+from .inference_utils import (gibbs_sampler, gibbs_sampler_robust, gibbs_sampler_simplex,
+                              USVt_hat_extraction)
 from .ppc import PPC_STATS, posterior_predictive_check, ppc_summary
 from .rankdiag import rank_diagnostics, rank_normalize
 from .sampling_utils import coverage, rndm_m_random_calculator
@@ -18,6 +19,7 @@ __all__ = [
     "Dataset",
     "BayesianModelCombination",
     "gibbs_sampler",
+    "gibbs_sampler_robust",
     "gibbs_sampler_simplex",
     "USVt_hat_extraction",
     "coverage",

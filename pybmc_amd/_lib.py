@@ -138,6 +138,10 @@ PROTOTYPES = {
                                                C.c_int32, _D, _D, _D, _D, _D, _D,
                                                C.POINTER(C.c_uint32)]),
     "bmc_sens_last_timing": (C.c_int, [_P, _D]),
+    "bmc_robust_run": (C.c_int, [_P, C.c_double, C.c_int32, C.c_int64, C.c_int64, C.c_int,
+                                 C.POINTER(C.c_uint64), _D, _D, _D, _D, _D, C.POINTER(Stats)]),
+    "bmc_robust_run_device": (C.c_int, [_P, C.c_double, C.c_int32, C.c_int64, C.c_int64,
+                                        C.POINTER(C.c_uint64), _P, _P, C.POINTER(Stats)]),
     "bmc_rng_fill": (C.c_int, [_P, C.c_uint64, C.c_int64, _D, C.c_double, C.c_int64, _D]),
     "bmc_philox_raw": (C.c_int, [_P, C.c_uint64, C.c_uint32, C.c_int64, C.POINTER(C.c_uint32)]),
 }
@@ -432,6 +436,43 @@ class Context:
         self._check(self._lib.bmc_gibbs_run_device(
             self._h, n_chains, iters, sd.ctypes.data_as(C.POINTER(C.c_uint64)), _P(out_ptr),
             C.byref(st)))
+        return st.as_dict()
+
+    # -- Student-t (outlier-robust) sampler ------------------------------------------------------
+    def robust_run(self, nu, n_chains, iters, burn=0, seeds=None, xi=None, g=None, gl=None,
+                   want_weights=True):
+        """``n_chains`` Student-t chains on the resident problem and prior (bmc_robust_run).
+        Device mode: ``seeds`` (n_chains,).  Replay mode: ``xi`` (n_chains, burn+iters, k), ``g``
+        (n_chains, burn+iters), ``gl`` (n_chains, burn+iters, n).  Returns (samples (n_chains,
+        iters, k+1), mean row weights (n_chains, n) or None, stats dict)."""
+        n_chains, iters, burn = int(n_chains), int(iters), int(burn)
+        if n_chains < 1 or iters < 0:
+            raise ValueError("need n_chains >= 1 and iters >= 0")
+        out = np.empty((n_chains, iters, self.k + 1))
+        w = np.empty((n_chains, self.n)) if want_weights else None
+        st = Stats()
+        if xi is not None or g is not None or gl is not None:
+            tt = burn + iters
+            xi = np.ascontiguousarray(xi, dtype=np.float64).reshape(n_chains, tt, self.k)
+            g = np.ascontiguousarray(g, dtype=np.float64).reshape(n_chains, tt)
+            gl = np.ascontiguousarray(gl, dtype=np.float64).reshape(n_chains, tt, self.n)
+            rc = self._lib.bmc_robust_run(self._h, float(nu), n_chains, iters, burn, BMC_RNG_REPLAY,
+                                          None, _dptr(xi), _dptr(g), _dptr(gl), _dptr(out), _dptr(w),
+                                          C.byref(st))
+        else:
+            sd = np.ascontiguousarray(seeds, dtype=np.uint64).reshape(n_chains)
+            rc = self._lib.bmc_robust_run(self._h, float(nu), n_chains, iters, burn, BMC_RNG_DEVICE,
+                                          sd.ctypes.data_as(C.POINTER(C.c_uint64)), None, None, None,
+                                          _dptr(out), _dptr(w), C.byref(st))
+        self._check(rc)
+        return out, w, st.as_dict()
+
+    def robust_run_device(self, nu, n_chains, iters, burn, seeds, out_ptr, weight_ptr=None):
+        sd = np.ascontiguousarray(seeds, dtype=np.uint64).reshape(n_chains)
+        st = Stats()
+        self._check(self._lib.bmc_robust_run_device(
+            self._h, float(nu), int(n_chains), int(iters), int(burn),
+            sd.ctypes.data_as(C.POINTER(C.c_uint64)), _P(out_ptr), _P(weight_ptr or 0), C.byref(st)))
         return st.as_dict()
 
     # -- simplex sampler --------------------------------------------------------------------

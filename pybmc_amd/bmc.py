@@ -11,7 +11,8 @@ import numpy as np
 import pandas as pd
 
 from .data import apply_domain_filters
-from .inference_utils import USVt_hat_extraction, gibbs_sampler, gibbs_sampler_simplex
+from .inference_utils import (USVt_hat_extraction, gibbs_sampler, gibbs_sampler_robust,
+                              gibbs_sampler_simplex)
 from .sampling_utils import predictive_coverage, rndm_m_random_calculator
 
 
@@ -48,7 +49,8 @@ class BayesianModelCombination:
         self._train_df = None
         self.last_stats = None
         self._device_problem = None
-        self._trained_with = None   # (sampler, [b0, C0, nu0, sigma20]) of the last train()
+        self._trained_with = None   # (sampler, [b0, C0, nu0, sigma20][, nu]) of the last train()
+        self.row_weights = None     # (N,) mean latent weight per training row ("student_t" only)
 
     # ------------------------------------------------------------------ set-up
     def orthogonalize(self, property, train_df, components_kept, method="auto"):
@@ -107,8 +109,15 @@ class BayesianModelCombination:
     # ------------------------------------------------------------------- train
     def train(self, training_options=None):
         """Sample the posterior (reference bmc.py:132-193).  Options and their defaults
-        are the reference's; any sampler string other than ``"simplex"`` selects the
-        Gibbs sampler (quirk Q6).  Extra optional keys (defaults keep the reference behaviour):
+        are the reference's; any sampler string other than ``"simplex"`` and ``"student_t"``
+        selects the Gibbs sampler (quirk Q6).  ``{"sampler": "student_t", "nu": 4.0}`` (not in the
+        reference) runs the outlier-robust sampler ``gibbs_sampler_robust``: Student-t likelihood
+        with ``nu`` degrees of freedom, ``n_chains`` and ``seeds`` honoured, ``burn`` sweeps dropped
+        per chain only when the caller gives ``burn`` (default 0), ``devices`` other than this GPU a
+        ``ValueError``; afterwards ``row_weights`` holds the mean latent weight of every training
+        row, averaged over chains (far below 1: an outlier), and the predictive noise of
+        ``predict``, ``predict2`` and ``evaluate`` is ``sigma t_nu``.  Extra optional keys (defaults
+        keep the reference behaviour):
         ``n_chains`` (pooled along the sample axis), ``seeds``, ``dtype`` (``"float32"`` stores
         U_hat and y in float32 on the device, sums stay float64 -- BASELINE configs[3]),
         ``devices`` (list of GPU ids: the chains are split over them, one host thread and one
@@ -137,7 +146,26 @@ class BayesianModelCombination:
 
         self._trained_with = ("simplex" if sampler == "simplex" else "gibbs",
                               [b_mean_prior, b_mean_cov, nu0, sigma20])
-        if sampler == "simplex":
+        self.row_weights = None
+        if sampler == "student_t":
+            devices = opts.get("devices")
+            if devices is not None and list(devices) != [self.device]:
+                raise ValueError('"devices" is for the Gibbs sampler: Student-t chains run on one '
+                                 'GPU (use n_chains for several chains on this device)')
+            nu = float(opts.get("nu", 4.0))
+            n_chains = int(opts.get("n_chains", 1))
+            prior = [b_mean_prior, b_mean_cov, nu0, sigma20]
+            self._trained_with = ("student_t", prior, nu)
+            self._device_problem = None   # this path sets its own problem
+            res, w, stats = gibbs_sampler_robust(
+                self.centered_experiment_train, self.U_hat, iterations, prior, nu,
+                burn=int(opts.get("burn", 0)), n_chains=n_chains, seeds=opts.get("seeds"),
+                device=self.device, return_row_weights=True, return_stats=True)
+            self.last_stats = stats
+            self.samples = res if res.ndim == 2 else res.reshape(-1, res.shape[-1])
+            self.row_weights = w if w.ndim == 1 else w.mean(axis=0)
+            self.n_chains = n_chains
+        elif sampler == "simplex":
             devices = opts.get("devices")
             if devices is not None and list(devices) != [self.device]:
                 raise ValueError('"devices" is for the Gibbs sampler: simplex chains run on one '
@@ -221,6 +249,18 @@ class BayesianModelCombination:
             cols[key] = d[key]
         return pd.DataFrame({k: np.asarray(v) for k, v in cols.items()}, index=index)
 
+    def _require_gaussian(self, what, training_options=None):
+        """The scoring, checking and cross-validation kernels hard-code the Gaussian density."""
+        opts = training_options if training_options is not None else {}
+        trained = self._trained_with[0] if self._trained_with is not None else None
+        if opts.get("sampler", trained) == "student_t":
+            raise ValueError(f'{what} supports the Gaussian Gibbs sampler only (sampler == "student_t")')
+
+    def _noise_df(self):
+        """Degrees of freedom of the predictive noise: None (normal) unless the fit was Student-t."""
+        tw = self._trained_with
+        return tw[2] if tw is not None and tw[0] == "student_t" else None
+
     # ----------------------------------------------------------------- scoring
     def _chains(self):
         s = np.asarray(self.samples)
@@ -235,6 +275,7 @@ class BayesianModelCombination:
         ``lppd``, ``p_waic_i``, ``mean_ll``, ``elpd_waic_i``."""
         if self.samples is None or self.U_hat is None:
             raise ValueError("Must call `orthogonalize()` and `train()` before computing WAIC.")
+        self._require_gaussian("waic")
         from .scoring import waic
         return waic(self.U_hat, np.asarray(self.centered_experiment_train, dtype=np.float64),
                     self._chains(), burn=burn, device=self.device)
@@ -248,6 +289,7 @@ class BayesianModelCombination:
         ``elpd_loo_i``, ``p_loo_i``, ``pareto_k``, ``lppd``."""
         if self.samples is None or self.U_hat is None:
             raise ValueError("Must call `orthogonalize()` and `train()` before computing LOO.")
+        self._require_gaussian("loo")
         from .scoring import psis_loo
         return psis_loo(self.U_hat, np.asarray(self.centered_experiment_train, dtype=np.float64),
                         self._chains(), burn=burn, device=self.device)
@@ -260,6 +302,7 @@ class BayesianModelCombination:
         model predictions, ``truth`` and ``residual = truth - predicted``."""
         if self.samples is None or self.U_hat is None:
             raise ValueError("Must call `orthogonalize()` and `train()` before computing LOO.")
+        self._require_gaussian("loo_predict")
         from .scoring import psis_loo_predict
         y = np.asarray(self.centered_experiment_train, dtype=np.float64)
         out = psis_loo_predict(self.U_hat, y, self._chains(), burn=burn, device=self.device)
@@ -282,7 +325,8 @@ class BayesianModelCombination:
         table."""
         if self.samples is None or self.U_hat is None or self._trained_with is None:
             raise ValueError("Must call `orthogonalize()` and `train()` before the prior sensitivity.")
-        sampler, prior = self._trained_with
+        self._require_gaussian("prior_sensitivity", training_options)
+        sampler, prior = self._trained_with[:2]
         opts = training_options if training_options is not None else {}
         if sampler == "simplex" or opts.get("sampler", "gibbs_sampling") == "simplex":
             raise ValueError('prior_sensitivity supports the Gibbs sampler only (sampler == "simplex")')
@@ -300,6 +344,7 @@ class BayesianModelCombination:
         if self.U_hat is None:
             raise ValueError("Must call `orthogonalize()` before cross-validating.")
         opts = training_options if training_options is not None else {}
+        self._require_gaussian(what, training_options)
         if opts.get("sampler", "gibbs_sampling") == "simplex":
             raise ValueError(f'{what} supports the Gibbs sampler only (sampler == "simplex")')
         from .cv import fold_labels, group_labels
@@ -415,6 +460,7 @@ class BayesianModelCombination:
                 "X must be a pandas DataFrame containing model predictions and the truth column.")
         if self.truth_column_name not in X.columns:
             raise ValueError(f"X must contain the truth column '{self.truth_column_name}'.")
+        self._require_gaussian("log_predictive_density")
         from .scoring import elpd_summary, pointwise_log_likelihood
         preds = np.asarray(X[self.models].values, dtype=np.float64)
         truth = np.asarray(X[self.truth_column_name].values, dtype=np.float64)
@@ -437,6 +483,7 @@ class BayesianModelCombination:
         draws are dropped from the start of each chain; ``seed`` fixes the replicated noise (None:
         drawn from numpy's global stream and returned).  Returns that function's dict."""
         from .ppc import posterior_predictive_check
+        self._require_gaussian("posterior_predictive_check")
         if X is None:
             if self.samples is None or self.U_hat is None:
                 raise ValueError("Must call `orthogonalize()` and `train()` before a posterior "
@@ -485,7 +532,8 @@ class BayesianModelCombination:
                 "X must be a pandas DataFrame containing model predictions and domain info.")
         domain_keys = [c for c in X.columns if c not in self.models]
         rndm_m, (lo, med, up) = rndm_m_random_calculator(
-            X[self.models].values, self.samples, self.Vt_hat, device=self.device)
+            X[self.models].values, self.samples, self.Vt_hat, device=self.device,
+            noise_df=self._noise_df())
         lo_df, med_df, up_df = self._band_frames(X[domain_keys].reset_index(drop=True),
                                                  lo, med, up)
         return rndm_m, lo_df, med_df, up_df
@@ -518,7 +566,8 @@ class BayesianModelCombination:
             raise ValueError("No available trained models are present in prediction DataFrame.")
         idx = [self.models.index(m) for m in available]
         rndm_m, (lo, med, up) = rndm_m_random_calculator(
-            df[available].values, self.samples, self.Vt_hat[:, idx], device=self.device)
+            df[available].values, self.samples, self.Vt_hat[:, idx], device=self.device,
+            noise_df=self._noise_df())
         lo_df, med_df, up_df = self._band_frames(df[domain_keys].reset_index(drop=True),
                                                  lo, med, up)
         return rndm_m, lo_df, med_df, up_df
@@ -533,7 +582,7 @@ class BayesianModelCombination:
         df = apply_domain_filters(self.data_dict[self.current_property], domain_filter)
         return predictive_coverage(np.arange(0, 101, 5), df[self.models].to_numpy(), self.samples,
                                    self.Vt_hat, df[self.truth_column_name].to_numpy(),
-                                   device=self.device)
+                                   device=self.device, noise_df=self._noise_df())
 
 
 def _series_tensor(samples, Vt_hat, device):

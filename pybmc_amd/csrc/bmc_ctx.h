@@ -67,6 +67,7 @@ struct bmc_ctx : CtxHandles {
     // prior / basis (host copies)
     std::vector<double> W, lam, c1, c2, b0;
     double nu0 = 0, s20 = 0, sigma2_init = 0;
+    std::vector<double> Pprec, Pb0;   // inv(C0) and inv(C0) b0 (the Student-t sampler's operands)
     DevBuf dW, dWT, dLam, dC1, dC2;
     // sufficient statistics in the rotated basis (rss_mode 1; host part made by bmc_set_prior
     // when k <= 64, device part on first use)
@@ -104,6 +105,9 @@ struct bmc_ctx : CtxHandles {
     // power-scaling sensitivity (bmc_power_sensitivity*): staged operands, log densities, weights
     // and the scan's partials (the sort reuses the rank buffers)
     DevBuf snStage, snWork, snPart;
+    // Student-t sampler (bmc_robust_run*): the packed operand, the prior, per-chain row state, the
+    // replayed weights' variates, the mean weights
+    DevBuf rbZ, rbPrior, rbWs, rbGl, rbWsum;
     double sens_ms[4] = {0, 0, 0, 0};      // last bmc_power_sensitivity*: log densities, sorts, PSIS, CJS
     double predict_ms[4] = {0, 0, 0, 0};   // last bmc_predict: h2d, gemm, order statistics, device
     // pooling over GPUs (bmc_comm_*): RCCL communicator bound to this context's device

@@ -1,0 +1,39 @@
+// Launchers of the Student-t (outlier-robust) Gibbs sampler (kernels_robust.hip).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "bmc_launch.h"
+#include "bmc_robust_plan.h"
+
+namespace bmc {
+
+struct RobustArgs {
+    const double* Z;      // [rows_padded][ldz]: X row-major, zero-padded columns and rows
+    const double* yv;     // [rows_padded]: y, zero-padded
+    int64_t n;            // true rows
+    int32_t k;
+    int64_t rows_per_wave;   // robust_rows_per_wave(n)
+    const double* P;      // [k][k] prior precision inv(C0) (its lower triangle is read)
+    const double* Pb0;    // [k] P b0
+    double nu, shape_l;   // degrees of freedom; (nu + 1) / 2
+    double nu0_s20, sigma2_init;
+    int64_t iters, burn;
+    int32_t n_chains;
+    // per-chain arrays, chain 0 of the launch first
+    const uint64_t* seeds;   // device RNG: the keys of the STREAM_ROBUST variates; NULL in replay mode
+    const double* xi;     // [C][burn + iters][k]
+    const double* gam;    // [C][burn + iters]
+    const double* gl;     // replay mode: [C][burn + iters][n]
+    double* ws;           // [C][n][2]: r_n, lambda_n
+    double* samples;      // [C][iters][k + 1]
+    double* wsum;         // [C][n]: mean of lambda_n over the kept sweeps
+    int32_t* status;      // [C]: 1 = a Cholesky pivot was not positive and finite
+};
+
+// panels (f64) -> Z, yv
+hipError_t launch_robust_pack(const Panels& P, double* Z, double* yv, hipStream_t s);
+// one workgroup per chain, a.n_chains <= ROBUST_MAX_CHAINS_PER_LAUNCH
+hipError_t launch_robust(const RobustArgs& a, hipStream_t s);
+
+}  // namespace bmc

@@ -455,6 +455,8 @@ int bmc_set_prior(bmc_ctx* c, const double* b0, const double* C0, double nu0, do
         c->c2[j] = (double)s2l;
     }
     c->b0.assign(b0, b0 + k);
+    c->Pprec.assign(P.begin(), P.end());
+    c->Pb0 = Pb0;
     c->nu0 = nu0;
     c->s20 = sigma20;
     // rss_mode 1 (k <= 64): G = W'AW (= diag(lam) up to rounding), the least-squares point u0 in

@@ -1,0 +1,160 @@
+// The Student-t (outlier-robust) Gibbs sampler behind the C ABI: bmc_robust_run*.
+#include <cstring>
+
+#include "bmc_ctx.h"
+#include "bmc_robust.h"
+
+namespace {
+
+int robust_common(bmc_ctx* c, double nu, int32_t n_chains, int64_t iters, int64_t burn, int rng_mode,
+                  const uint64_t* seeds, const double* xi, const double* g, const double* gl,
+                  double* samples_host, void* samples_dev, double* weight_host, void* weight_dev,
+                  bmc_stats* stats) {
+    if (!c->have_problem || !c->have_prior)
+        return fail(c, BMC_ESTATE, "bmc_set_problem and bmc_set_prior must be called first");
+    const std::string why = robust_check(c->n, c->k, c->f32, nu, n_chains, iters, burn);
+    if (!why.empty()) return fail(c, BMC_EINVAL, "bmc_robust_run: " + why);
+    if (rng_mode == BMC_RNG_DEVICE) {
+        if (!seeds) return fail(c, BMC_EINVAL, "seeds required in device RNG mode");
+        if (xi || g || gl) return fail(c, BMC_EINVAL, "xi/g/gl must be NULL in device RNG mode");
+    } else if (rng_mode == BMC_RNG_REPLAY) {
+        if (!xi || !g || !gl) return fail(c, BMC_EINVAL, "xi, g and gl required in replay mode");
+    } else {
+        return fail(c, BMC_EINVAL, "rng_mode must be 0 or 1");
+    }
+    const int K = c->k;
+    const int64_t N = c->n;
+    const size_t C = (size_t)n_chains, Tt = (size_t)(burn + iters), T = (size_t)iters;
+    int rc;
+    if (rng_mode == BMC_RNG_REPLAY && Tt > 0) {
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
+        const size_t need = robust_gl_bytes(N, n_chains, (int64_t)Tt);
+        if (need > c->rbGl.cap && need - c->rbGl.cap > free_b)
+            return fail(c, BMC_ENOMEM, "bmc_robust_run: the replayed weight variates gl (" +
+                                           std::to_string(need) + " bytes) do not fit the device");
+        if ((rc = ensure(c, c->rbGl, need))) return rc;
+    }
+    const size_t n_pad = (size_t)robust_rows_padded(N);
+    if ((rc = ensure_all(c, {{c->xi, C * Tt * K * 8}, {c->gam, C * Tt * 8},
+                             {c->rbZ, robust_packed_bytes(N, K)},
+                             {c->rbPrior, (size_t)(K * K + K) * 8},
+                             {c->rbWs, robust_workspace_bytes(N, n_chains)},
+                             {c->rbWsum, C * (size_t)N * 8},
+                             {c->status, C * sizeof(int32_t)}, {c->seeds, C * sizeof(uint64_t)}})))
+        return rc;
+    double* d_samples = (double*)samples_dev;
+    if (!d_samples) {
+        if ((rc = ensure(c, c->samples, C * T * (K + 1) * 8))) return rc;
+        d_samples = (double*)c->samples.p;
+    }
+    double* d_weight = weight_dev ? (double*)weight_dev : (double*)c->rbWsum.p;
+    double* dP = (double*)c->rbPrior.p;
+    HIPCHK(c, hipMemsetAsync(c->status.p, 0, C * sizeof(int32_t), c->stream));
+    HIPCHK(c, hipMemcpyAsync(dP, c->Pprec.data(), (size_t)K * K * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dP + (size_t)K * K, c->Pb0.data(), (size_t)K * 8, hipMemcpyHostToDevice,
+                             c->stream));
+    double* Z = (double*)c->rbZ.p;
+    double* yv = Z + n_pad * (size_t)robust_ldz(K);
+    HIPCHK(c, launch_robust_pack(panels_of(c, c->Xraw.p), Z, yv, c->stream));
+    HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
+    if (Tt > 0) {
+        if (rng_mode == BMC_RNG_DEVICE) {
+            HIPCHK(c, hipMemcpyAsync(c->seeds.p, seeds, C * sizeof(uint64_t), hipMemcpyHostToDevice,
+                                     c->stream));
+            HIPCHK(c, launch_rng_fill((const uint64_t*)c->seeds.p, n_chains, (int64_t)Tt * K,
+                                      (double*)c->xi.p, (c->nu0 + (double)N) / 2.0, (int64_t)Tt,
+                                      (double*)c->gam.p, c->stream));
+        } else {
+            HIPCHK(c, hipMemcpyAsync(c->xi.p, xi, C * Tt * K * 8, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(c->gam.p, g, C * Tt * 8, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(c->rbGl.p, gl, C * Tt * (size_t)N * 8, hipMemcpyHostToDevice,
+                                     c->stream));
+        }
+    }
+    HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
+    RobustArgs a;
+    a.Z = Z;
+    a.yv = yv;
+    a.n = N;
+    a.k = K;
+    a.rows_per_wave = robust_rows_per_wave(N);
+    a.P = dP;
+    a.Pb0 = dP + (size_t)K * K;
+    a.nu = nu;
+    a.shape_l = (nu + 1.0) / 2.0;
+    a.nu0_s20 = c->nu0 * c->s20;
+    a.sigma2_init = c->sigma2_init;
+    a.iters = iters;
+    a.burn = burn;
+    const std::vector<RobustLaunch> plan = robust_launches(n_chains);
+    for (const RobustLaunch& l : plan) {
+        const size_t c0 = (size_t)l.c0;
+        a.n_chains = l.n_chains;
+        a.seeds = rng_mode == BMC_RNG_DEVICE ? (const uint64_t*)c->seeds.p + c0 : nullptr;
+        a.xi = (const double*)c->xi.p + c0 * Tt * K;
+        a.gam = (const double*)c->gam.p + c0 * Tt;
+        a.gl = rng_mode == BMC_RNG_REPLAY ? (const double*)c->rbGl.p + c0 * Tt * (size_t)N : nullptr;
+        a.ws = (double*)c->rbWs.p + c0 * (size_t)N * 2;
+        a.samples = d_samples + c0 * T * (K + 1);
+        a.wsum = d_weight + c0 * (size_t)N;
+        a.status = (int32_t*)c->status.p + c0;
+        HIPCHK(c, launch_robust(a, c->stream));
+    }
+    HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
+    std::vector<int32_t> st(C, 0);
+    HIPCHK(c, hipMemcpyAsync(st.data(), c->status.p, C * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (samples_host && iters > 0)
+        if ((rc = copy_to_host(c, samples_host, d_samples, C * T * (K + 1) * 8, C * T * (K + 1) * 8, 1)))
+            return rc;
+    if (weight_host)
+        if ((rc = copy_to_host(c, weight_host, d_weight, C * (size_t)N * 8, C * (size_t)N * 8, 1))) return rc;
+    if (stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        if ((rc = event_ms(c, 0, 1, &stats->rng_ms)) || (rc = event_ms(c, 1, 2, &stats->loop_ms)) ||
+            (rc = event_ms(c, 0, 2, &stats->total_ms)))
+            return rc;
+        stats->iterations = burn + iters;
+        stats->n_chains = n_chains;
+        stats->launches = (int32_t)plan.size();
+        stats->groups_per_chain = 1;
+        stats->waves_per_group = ROBUST_WAVES;
+        stats->chains_per_pass = 1;
+        stats->residency = 3;
+        stats->bytes_per_pass = (N * K + N) * 8;
+        stats->passes = 2 * (burn + iters) * (int64_t)n_chains;
+    }
+    for (size_t i = 0; i < C; ++i)
+        if (st[i] != 0)
+            return fail(c, BMC_ESINGULAR,
+                        "bmc_robust_run: a Cholesky pivot of X'LX / sigma2 + inv(C0) + 1e-6 I was not "
+                        "positive and finite (chain " + std::to_string(i) + ")");
+    return BMC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bmc_robust_run(bmc_ctx* c, double nu, int32_t n_chains, int64_t iters, int64_t burn, int rng_mode,
+                   const uint64_t* seeds, const double* xi, const double* g, const double* gl,
+                   double* samples_out, double* row_weight_out, bmc_stats* stats) {
+    if (!c) return BMC_EINVAL;
+    if (!samples_out && iters > 0) return fail(c, BMC_EINVAL, "samples_out must not be NULL");
+    HIPCHK(c, hipSetDevice(c->device));
+    return robust_common(c, nu, n_chains, iters, burn, rng_mode, seeds, xi, g, gl, samples_out, nullptr,
+                         row_weight_out, nullptr, stats);
+}
+
+int bmc_robust_run_device(bmc_ctx* c, double nu, int32_t n_chains, int64_t iters, int64_t burn,
+                          const uint64_t* seeds, void* d_samples_out, void* d_row_weight_out,
+                          bmc_stats* stats) {
+    if (!c) return BMC_EINVAL;
+    if (!d_samples_out && iters > 0) return fail(c, BMC_EINVAL, "d_samples_out must not be NULL");
+    HIPCHK(c, hipSetDevice(c->device));
+    return robust_common(c, nu, n_chains, iters, burn, BMC_RNG_DEVICE, seeds, nullptr, nullptr, nullptr,
+                         nullptr, d_samples_out, nullptr, d_row_weight_out, stats);
+}
+
+}  // extern "C"

@@ -7,6 +7,7 @@
 //   rng_fill      Philox4x32-10 -> N(0,1) and Gamma(a,1)           (reference inference_utils.py:45,52)
 #include "bmc_dev.h"
 #include "bmc_launch.h"
+#include "bmc_rng.h"
 
 namespace bmc {
 
@@ -761,10 +762,6 @@ hipError_t launch_unrotate(const double* uout, const double* WT, int32_t k, int6
 // from Philox counter (pair_lo, pair_hi, STREAM_NORMAL, 0) under the chain's key,
 // so a chain's variates depend on (seed, e) only -- not on the launch geometry,
 // the chain's index or the number of GPUs.
-__device__ __forceinline__ void box_muller(u32x4 r, double& z0, double& z1) {
-    box_muller_pair(u53_open0(r.x, r.y), u53_open0(r.z, r.w), z0, z1);   // bmc_math.h
-}
-
 __global__ __launch_bounds__(256) void normal_fill_kernel(const uint64_t* __restrict__ seeds,
                                                           int64_t per_chain,
                                                           double* __restrict__ out) {
@@ -784,36 +781,7 @@ __global__ __launch_bounds__(256) void normal_fill_kernel(const uint64_t* __rest
     }
 }
 
-// Gamma(a, 1), Marsaglia & Tsang (2000).  Attempt m of element t uses Philox
-// counters (t_lo, t_hi, STREAM_GAMMA, 2m) and (.., 2m+1).  For a < 1 the usual
-// boost Gamma(a) = Gamma(a+1) * U^(1/a) is applied.
-__device__ inline double gamma_mt(double a, uint64_t t, uint32_t k0, uint32_t k1) {
-    const bool boost = a < 1.0;
-    const double aa = boost ? a + 1.0 : a;
-    const double d = aa - 1.0 / 3.0;
-    const double c = 1.0 / sqrt(9.0 * d);
-    double res = d;
-    for (uint32_t m = 0; m < 64; ++m) {
-        const u32x4 r0 = philox4x32_10(u32x4{(uint32_t)t, (uint32_t)(t >> 32), STREAM_GAMMA, 2 * m},
-                                       k0, k1);
-        const u32x4 r1 = philox4x32_10(
-            u32x4{(uint32_t)t, (uint32_t)(t >> 32), STREAM_GAMMA, 2 * m + 1}, k0, k1);
-        double x, unused;
-        box_muller(r0, x, unused);
-        const double u = u53_open0(r1.x, r1.y);
-        double v = 1.0 + c * x;
-        if (v <= 0.0) continue;
-        v = v * v * v;
-        const double x2 = x * x;
-        if (u < 1.0 - 0.0331 * x2 * x2 || log(u) < 0.5 * x2 + d * (1.0 - v + log(v))) {
-            res = d * v;
-            if (boost) res *= pow(u53_open0(r1.z, r1.w), 1.0 / a);
-            break;
-        }
-    }
-    return res;
-}
-
+// (box_muller and gamma_mt: bmc_rng.h, shared with the Student-t sampler)
 __global__ __launch_bounds__(256) void gamma_fill_kernel(const uint64_t* __restrict__ seeds,
                                                          double shape, int64_t per_chain,
                                                          double* __restrict__ out) {

@@ -58,6 +58,62 @@ def gibbs_sampler(y, X, iterations, prior_info, *, n_chains=1, seeds=None, devic
     return (res, stats) if return_stats else res
 
 
+ROBUST_MAX_K = 32   # bmc_robust_plan.h
+
+
+def gibbs_sampler_robust(y, X, iterations, prior_info, nu=4.0, *, burn=0, n_chains=1, seeds=None,
+                         device=0, return_row_weights=False, return_stats=False):
+    """Outlier-robust Gibbs sampling on the GPU (not in the reference): ``gibbs_sampler``'s model
+    and priors with a Student-t likelihood ``y_n ~ t_nu(x_n . beta, sigma^2)``, written as a scale
+    mixture of normals with one latent weight ``lambda_n ~ Gamma(nu/2, rate nu/2)`` per row.
+    ``nu > 0`` is fixed (default 4).  ``prior_info`` is that of ``gibbs_sampler``.
+
+    Every chain runs ``burn + iterations`` sweeps from ``lambda = 1`` and the OLS ``sigma^2`` and
+    keeps the last ``iterations``.  Returns ``(iterations, k+1)`` rows ``[beta, sigma]``, or
+    ``(n_chains, iterations, k+1)``; with ``return_row_weights`` also the posterior mean of
+    ``lambda_n`` over the kept sweeps, ``(N,)`` or ``(n_chains, N)``: a per-row outlier score (about
+    1 for a row the model reaches, far below 1 for an outlier).  ``seeds`` fixes the per-chain
+    Philox keys; chain c is bit for bit the one-chain run with ``seeds[c]``.  At most 32 columns,
+    float64 storage.  ``ValueError`` for ``nu <= 0``, ``burn < 0``, ``n_chains < 1``, a wrong number of
+    seeds or more than 32 columns; ``numpy.linalg.LinAlgError`` where ``gibbs_sampler`` raises it, and
+    when a chain's conditional precision stops being positive definite."""
+    nu = float(nu)
+    if not nu > 0 or not np.isfinite(nu):
+        raise ValueError("nu must be positive and finite")
+    if burn < 0:
+        raise ValueError("Burn-in iterations must be non-negative.")
+    n_chains = int(n_chains)
+    if n_chains < 1:
+        raise ValueError("n_chains must be >= 1")
+    if int(iterations) < 0:
+        raise ValueError("iterations must be non-negative")
+    if seeds is not None:
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint64).reshape(-1)
+        if seeds.shape[0] != n_chains:
+            raise ValueError(f"seeds has {seeds.shape[0]} entries for n_chains = {n_chains}")
+    X = np.asarray(X)
+    if X.ndim != 2:
+        raise ValueError("X must be (n, k)")
+    if X.shape[1] > ROBUST_MAX_K:
+        raise ValueError(f"gibbs_sampler_robust supports at most {ROBUST_MAX_K} columns; "
+                         f"got {X.shape[1]}")
+    b0, C0, nu0, s20 = prior_info
+    ctx = _lib.default_context(device)
+    with ctx.lock:
+        ctx.set_problem(y, X, dtype=np.float64)
+        ctx.set_prior(b0, C0, nu0, s20)
+        if seeds is None:
+            seeds = _draw_seeds(n_chains)
+        out, w, stats = ctx.robust_run(nu, n_chains, int(iterations), int(burn), seeds=seeds,
+                                       want_weights=return_row_weights)
+    res = [out[0] if n_chains == 1 else out]
+    if return_row_weights:
+        res.append(w[0] if n_chains == 1 else w)
+    if return_stats:
+        res.append(stats)
+    return res[0] if len(res) == 1 else tuple(res)
+
+
 def USVt_hat_extraction(U, S, Vt, components_kept):
     """Truncate an SVD to ``components_kept`` components
     (reference inference_utils.py:147-168).  ``U_hat`` is returned column-major

@@ -8,8 +8,19 @@ from . import _lib
 N_PREDICTIVE_DRAWS = 10000  # reference sampling_utils.py:57
 
 
+def _t_noise(rng, noise_df, n_points):
+    """Student-t predictive noise for the replay ``noise=`` argument of ``Context.predict``, drawn on
+    the host from the generator that made the ``choice``, right after it.  This path is
+    host-bound: 80 kB of variates per point are generated and uploaded (on-device t noise in the
+    predictive kernels is a follow-up)."""
+    noise_df = float(noise_df)
+    if not noise_df > 0:
+        raise ValueError("noise_df must be positive")
+    return rng.standard_t(noise_df, (N_PREDICTIVE_DRAWS, n_points))
+
+
 def rndm_m_random_calculator(filtered_model_predictions, samples, Vt_hat, *, seed=None,
-                             device=0):
+                             device=0, noise_df=None):
     """Posterior-predictive draws and 2.5/50/97.5 % bands on the GPU
     (reference sampling_utils.py:40-84).
 
@@ -17,6 +28,12 @@ def rndm_m_random_calculator(filtered_model_predictions, samples, Vt_hat, *, see
     ``(10000, n_points)`` (C-ordered, like the reference's: sampling_utils.py:77).  Needs at least 10000 posterior samples, like the
     reference (``ValueError`` otherwise, :57).  The reference's side effect of
     re-seeding numpy's global stream (:54, quirk Q2) is not reproduced.
+
+    ``noise_df`` (after a Student-t fit, ``gibbs_sampler_robust``): the predictive noise is
+    ``sigma_s * t_nu`` instead of ``sigma_s * z``, with
+    ``Generator(PCG64(seed)).standard_t(noise_df, (10000, n_points))`` taken from the generator
+    that made the ``choice``, right after it, and replayed through the predictive kernels.  That
+    path is host-bound (80 kB of variates per point).
     """
     preds = np.ascontiguousarray(filtered_model_predictions, dtype=np.float64)
     samples = np.ascontiguousarray(samples, dtype=np.float64)
@@ -29,16 +46,18 @@ def rndm_m_random_calculator(filtered_model_predictions, samples, Vt_hat, *, see
     ctx = _lib.default_context(device)
     rng = np.random.Generator(np.random.PCG64(seed))
     theta = rng.choice(samples, N_PREDICTIVE_DRAWS, replace=False)     # :57
+    noise = None if noise_df is None else _t_noise(rng, noise_df, preds.shape[0])
     with ctx.lock:
-        rndm_m, bands, _ = ctx.predict(preds, theta, Vt_hat, seed=seed)
+        rndm_m, bands, _ = ctx.predict(preds, theta, Vt_hat, seed=seed, noise=noise)
     return rndm_m, [bands[0], bands[1], bands[2]]
 
 
 def predictive_coverage(percentiles, filtered_model_predictions, samples, Vt_hat, truth, *,
-                        seed=None, device=0):
+                        seed=None, device=0, noise_df=None):
     """``coverage(percentiles, rndm_m_random_calculator(...)[0], ...)`` fused on the GPU:
     the draws are sorted where they were produced and only the hit counts come back
-    (what ``BayesianModelCombination.evaluate`` needs, reference bmc.py:366-376)."""
+    (what ``BayesianModelCombination.evaluate`` needs, reference bmc.py:366-376).  ``noise_df``:
+    Student-t noise as in ``rndm_m_random_calculator`` (host-bound)."""
     preds = np.ascontiguousarray(filtered_model_predictions, dtype=np.float64)
     samples = np.ascontiguousarray(samples, dtype=np.float64)
     if samples.shape[0] < N_PREDICTIVE_DRAWS:
@@ -48,9 +67,10 @@ def predictive_coverage(percentiles, filtered_model_predictions, samples, Vt_hat
             np.random.randint(0, 2 ** 32, dtype=np.uint64))
     rng = np.random.Generator(np.random.PCG64(seed))
     theta = rng.choice(samples, N_PREDICTIVE_DRAWS, replace=False)
+    noise = None if noise_df is None else _t_noise(rng, noise_df, preds.shape[0])
     ctx = _lib.default_context(device)
     with ctx.lock:
-        _, _, cov = ctx.predict(preds, theta, Vt_hat, seed=seed, q=(), truth=truth,
+        _, _, cov = ctx.predict(preds, theta, Vt_hat, seed=seed, noise=noise, q=(), truth=truth,
                                 cov_percentiles=list(percentiles), want_draws=False)
     return cov
 
