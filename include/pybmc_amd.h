@@ -421,6 +421,31 @@ int bmc_psis_loo_device(bmc_ctx* ctx, const void* dA, int64_t n_points, int32_t 
                         int64_t ldt, double* elpd_loo_out, double* pareto_k_out,
                         double* lppd_out);
 
+/* ---- the same scores under a Student-t likelihood (not in the reference) -----------------------
+ * For a fit of bmc_robust_run*: y_i ~ a_i . beta + sigma t_nu with nu fixed, the latent row weights
+ * integrated out.  Everything as bmc_pointwise_loglik / bmc_psis_loo (arguments, outputs, the
+ * estimators, determinism, non-finite input, BMC_EINVAL) with
+ *   ll[i][s] = lgamma((nu + 1)/2) - lgamma(nu/2) - 1/2 log(nu pi) - log sigma_s
+ *              - (nu + 1)/2 log1p((y_i - a_i . beta_s)^2 / (nu sigma_s^2))
+ * (an infinity in row i of A or in y_i makes point i's outputs non-finite: NaN, where the Gaussian
+ * density gives -inf).  BMC_EINVAL also when nu is not positive and finite; the context stays
+ * usable.  INTEGRATION.md section 16. */
+int bmc_pointwise_loglik_t(bmc_ctx* ctx, const double* A, int64_t n_points, int32_t k, int64_t lda,
+                           int layout, const double* y, const double* theta, int64_t n_draws,
+                           int64_t ldt, double nu, double* lppd_out, double* pwaic_out,
+                           double* mean_ll_out);
+int bmc_pointwise_loglik_t_device(bmc_ctx* ctx, const void* dA, int64_t n_points, int32_t k,
+                                  int64_t lda, int layout, const void* dy, const void* dtheta,
+                                  int64_t n_draws, int64_t ldt, double nu, double* lppd_out,
+                                  double* pwaic_out, double* mean_ll_out);
+int bmc_psis_loo_t(bmc_ctx* ctx, const double* A, int64_t n_points, int32_t k, int64_t lda,
+                   int layout, const double* y, const double* theta, int64_t n_draws, int64_t ldt,
+                   double nu, double* elpd_loo_out, double* pareto_k_out, double* lppd_out);
+int bmc_psis_loo_t_device(bmc_ctx* ctx, const void* dA, int64_t n_points, int32_t k, int64_t lda,
+                          int layout, const void* dy, const void* dtheta, int64_t n_draws,
+                          int64_t ldt, double nu, double* elpd_loo_out, double* pareto_k_out,
+                          double* lppd_out);
+
 /* ---- PSIS-LOO predictive moments: what the fit would have predicted for y_i without it -------
  * Arguments, weights, elpd_loo_out, pareto_k_out and lppd_out as bmc_psis_loo.  With W_s the
  * truncated (smoothed or raw) weight of draw s for point i, every draw of a run of equal ll[i][s]

@@ -12,7 +12,7 @@ from .inference_utils import (gibbs_sampler, gibbs_sampler_robust, gibbs_sampler
 from .ppc import PPC_STATS, posterior_predictive_check, ppc_summary
 from .rankdiag import rank_diagnostics, rank_normalize
 from .sampling_utils import coverage, rndm_m_random_calculator
-from .scoring import pointwise_log_likelihood, psis_loo, psis_loo_predict, waic
+from .scoring import compare_elpd, pointwise_log_likelihood, psis_loo, psis_loo_predict, waic
 from .sensitivity import power_scale_sensitivity, power_scale_weights, sensitivity_summary
 
 __all__ = [
@@ -31,6 +31,7 @@ __all__ = [
     "waic",
     "psis_loo",
     "psis_loo_predict",
+    "compare_elpd",
     "kfold_cv",
     "fold_labels",
     "cv_component_path",

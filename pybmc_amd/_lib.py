@@ -112,6 +112,14 @@ PROTOTYPES = {
                                C.c_int64, _D, _D, _D]),
     "bmc_psis_loo_device": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int, _P, _P,
                                       C.c_int64, C.c_int64, _D, _D, _D]),
+    "bmc_pointwise_loglik_t": (C.c_int, [_P, _D, C.c_int64, C.c_int32, C.c_int64, C.c_int, _D, _D,
+                                         C.c_int64, C.c_int64, C.c_double, _D, _D, _D]),
+    "bmc_pointwise_loglik_t_device": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int, _P,
+                                                _P, C.c_int64, C.c_int64, C.c_double, _D, _D, _D]),
+    "bmc_psis_loo_t": (C.c_int, [_P, _D, C.c_int64, C.c_int32, C.c_int64, C.c_int, _D, _D, C.c_int64,
+                                 C.c_int64, C.c_double, _D, _D, _D]),
+    "bmc_psis_loo_t_device": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int, _P, _P,
+                                        C.c_int64, C.c_int64, C.c_double, _D, _D, _D]),
     "bmc_psis_loo_predict": (C.c_int, [_P, _D, C.c_int64, C.c_int32, C.c_int64, C.c_int, _D, _D,
                                        C.c_int64, C.c_int64, _D, _D, _D, _D, _D, _D, _D]),
     "bmc_psis_loo_predict_device": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int, _P,
@@ -683,12 +691,14 @@ class Context:
     LOO_KEYS = ("elpd_loo", "pareto_k", "lppd")
     LOO_PREDICT_KEYS = LOO_KEYS + ("loo_mean", "loo_sd", "loo_pit", "ess")
 
-    def _score_call(self, fn, keys, ptr, A, n, k, lda, layout, y, theta, n_draws, ldt):
+    def _score_call(self, fn, keys, ptr, A, n, k, lda, layout, y, theta, n_draws, ldt, nu=None):
         """One scoring entry point: `ptr` turns A, y and theta into what it takes (_dptr: host
-        arrays, _P: device addresses), one [n] output vector per key."""
+        arrays, _P: device addresses), one [n] output vector per key.  `nu`: the degrees of
+        freedom the Student-t (_t) entry points take behind ldt."""
         out = {key: np.empty(n) for key in keys}
+        lik = () if nu is None else (float(nu),)
         self._check(fn(self._h, ptr(A), int(n), int(k), int(lda), int(layout), ptr(y), ptr(theta),
-                       int(n_draws), int(ldt), *(_dptr(out[key]) for key in keys)))
+                       int(n_draws), int(ldt), *lik, *(_dptr(out[key]) for key in keys)))
         return out
 
     def pointwise_loglik(self, A, n, k, lda, layout, y, theta, n_draws, ldt):
@@ -715,6 +725,27 @@ class Context:
         caller orders its producers before the call."""
         return self._score_call(self._lib.bmc_psis_loo_device, self.LOO_KEYS, _P,
                                 dA, n, k, lda, layout, dy, dtheta, n_draws, ldt)
+
+    def pointwise_loglik_t(self, A, n, k, lda, layout, y, theta, n_draws, ldt, nu):
+        """pointwise_loglik under the Student-t likelihood with `nu` degrees of freedom
+        (bmc_pointwise_loglik_t)."""
+        return self._score_call(self._lib.bmc_pointwise_loglik_t, self.SCORE_KEYS, _dptr,
+                                A, n, k, lda, layout, y, theta, n_draws, ldt, nu)
+
+    def pointwise_loglik_t_device(self, dA, n, k, lda, layout, dy, dtheta, n_draws, ldt, nu):
+        """The same on DEVICE memory (bmc_pointwise_loglik_t_device)."""
+        return self._score_call(self._lib.bmc_pointwise_loglik_t_device, self.SCORE_KEYS, _P,
+                                dA, n, k, lda, layout, dy, dtheta, n_draws, ldt, nu)
+
+    def psis_loo_t(self, A, n, k, lda, layout, y, theta, n_draws, ldt, nu):
+        """psis_loo under the Student-t likelihood with `nu` degrees of freedom (bmc_psis_loo_t)."""
+        return self._score_call(self._lib.bmc_psis_loo_t, self.LOO_KEYS, _dptr,
+                                A, n, k, lda, layout, y, theta, n_draws, ldt, nu)
+
+    def psis_loo_t_device(self, dA, n, k, lda, layout, dy, dtheta, n_draws, ldt, nu):
+        """The same on DEVICE memory (bmc_psis_loo_t_device)."""
+        return self._score_call(self._lib.bmc_psis_loo_t_device, self.LOO_KEYS, _P,
+                                dA, n, k, lda, layout, dy, dtheta, n_draws, ldt, nu)
 
     def psis_loo_predict(self, A, n, k, lda, layout, y, theta, n_draws, ldt):
         """What psis_loo returns and the leave-one-out predictive loo_mean_i, loo_sd_i, loo_pit_i

@@ -250,7 +250,8 @@ class BayesianModelCombination:
         return pd.DataFrame({k: np.asarray(v) for k, v in cols.items()}, index=index)
 
     def _require_gaussian(self, what, training_options=None):
-        """The scoring, checking and cross-validation kernels hard-code the Gaussian density."""
+        """The checking and cross-validation kernels hard-code the Gaussian density, and the scoring
+        methods that call this one keep to it (``score()`` takes the fit's own likelihood)."""
         opts = training_options if training_options is not None else {}
         trained = self._trained_with[0] if self._trained_with is not None else None
         if opts.get("sampler", trained) == "student_t":
@@ -293,6 +294,46 @@ class BayesianModelCombination:
         from .scoring import psis_loo
         return psis_loo(self.U_hat, np.asarray(self.centered_experiment_train, dtype=np.float64),
                         self._chains(), burn=burn, device=self.device)
+
+    def score(self, method="loo", X=None, burn=0):
+        """Score the last ``train()`` under the likelihood it sampled from (not in the reference;
+        ``pybmc_amd.scoring``): Gaussian, or after ``{"sampler": "student_t"}`` the Student-t
+        density with that fit's ``nu`` -- the one scoring method that accepts a Student-t fit.
+        ``method`` is ``"loo"`` (``psis_loo``) or ``"waic"`` (``waic``) on the training data of
+        ``loo()`` and ``waic()``.  With a DataFrame ``X`` (model columns and the truth column) it is
+        the log predictive density of held-out data instead, built as ``log_predictive_density``
+        builds it (``elpd``, ``se``, ``n_points``, ``lppd``; ``method`` is not used).  ``burn`` more
+        draws are dropped from the start of each chain.  The result also carries ``likelihood``
+        (``"gaussian"`` or ``"student_t"``) and ``nu`` (None for the Gaussian one); the results of
+        two fits of the same data feed ``pybmc_amd.compare_elpd`` directly."""
+        if method not in ("loo", "waic"):
+            raise ValueError(f'method must be "loo" or "waic"; got {method!r}')
+        nu = self._noise_df()
+        from . import scoring
+        if X is not None:
+            if self.samples is None or self.Vt_hat is None:
+                raise ValueError("Must call `orthogonalize()` and `train()` before scoring.")
+            if not isinstance(X, pd.DataFrame):
+                raise ValueError(
+                    "X must be a pandas DataFrame containing model predictions and the truth column.")
+            if self.truth_column_name not in X.columns:
+                raise ValueError(f"X must contain the truth column '{self.truth_column_name}'.")
+            preds = np.asarray(X[self.models].values, dtype=np.float64)
+            truth = np.asarray(X[self.truth_column_name].values, dtype=np.float64)
+            A = preds @ np.asarray(self.Vt_hat, dtype=np.float64).T
+            pw = scoring.pointwise_log_likelihood(A, truth - preds.mean(axis=1), self._chains(),
+                                                  burn=burn, device=self.device, nu=nu)
+            out = scoring.elpd_summary(pw["lppd"])
+            out["lppd"] = pw["lppd"]
+        else:
+            if self.samples is None or self.U_hat is None:
+                raise ValueError("Must call `orthogonalize()` and `train()` before scoring.")
+            fn = scoring.psis_loo if method == "loo" else scoring.waic
+            out = fn(self.U_hat, np.asarray(self.centered_experiment_train, dtype=np.float64),
+                     self._chains(), burn=burn, device=self.device, nu=nu)
+        out["likelihood"] = "gaussian" if nu is None else "student_t"
+        out["nu"] = nu
+        return out
 
     def loo_predict(self, burn=0):
         """What the combination would have predicted for every training point had that point not

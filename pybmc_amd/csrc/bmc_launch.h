@@ -311,6 +311,9 @@ hipError_t launch_rank_indicators(const RankShape& r, const double* q, int32_t s
 // (out is [3][n], device).  The n x S matrix is never stored.  Work buffers (device, sized by
 // score_buffers for the plan): Ap [n_pad][k_pad] and yp [n_pad], the operands padded to whole
 // tiles; ch [2][S], the per-draw constants; part [splits][n_pad][5], the per-split partials.
+// nu > 0 selects the Student-t density with nu degrees of freedom (bmc_score_tile.h, TileDrawsT):
+// ll[i][s] = lgamma((nu + 1)/2) - lgamma(nu/2) - 1/2 log(nu pi) - log sigma_s
+//            - (nu + 1)/2 log1p((y_i - a_i . beta_s)^2 / (nu sigma_s^2));  nu = 0 is the Gaussian one.
 struct ScorePlan;
 struct ScoreArgs {
     const double* A;
@@ -319,6 +322,7 @@ struct ScoreArgs {
     int64_t n, lda, S, ldt;
     int32_t k, col_major;
     double *Ap, *yp, *ch, *part, *out;
+    double nu = 0.0;   // host-only: the likelihood (0: Gaussian; else positive and finite)
 };
 struct ScoreBuffers {
     size_t Ap, yp, ch, part;   // bytes
@@ -330,7 +334,7 @@ hipError_t launch_score(const ScoreArgs& a, const ScorePlan& p, hipStream_t s);
 // Pareto-smoothed importance-sampling leave-one-out of the same model and arguments as
 // launch_score (whose kernels run first, into `score`'s buffers: score.out[0][i] = lppd_i).  work:
 // loo_buffers(plan, n).total() bytes (device, 256-byte aligned); its `out` part, at loo_out(),
-// receives elpd_loo_i [n] then pareto_k [n].
+// receives elpd_loo_i [n] then pareto_k [n].  The likelihood is score.nu.
 struct LooArgs {
     ScoreArgs score;
     void* work;
@@ -340,7 +344,7 @@ hipError_t launch_loo(const LooArgs& a, const LooPlan& p, hipStream_t s);
 
 // The leave-one-out predictive moments of every point with the same weights.
 // work: loo_predict_buffers(plan, n).total() bytes; at loo_predict_out(): elpd_loo_i, pareto_k,
-// loo_mean, loo_sd, loo_pit, ess, [n] each.
+// loo_mean, loo_sd, loo_pit, ess, [n] each.  Gaussian only: score.nu != 0 is hipErrorInvalidValue.
 double* loo_predict_out(const LooArgs& a, const LooPredictPlan& p);
 hipError_t launch_loo_predict(const LooArgs& a, const LooPredictPlan& p, hipStream_t s);
 

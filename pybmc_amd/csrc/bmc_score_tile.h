@@ -137,4 +137,22 @@ struct TileDraws {
     }
 };
 
+// The same view under the Student-t density with nu degrees of freedom, the latent row weights
+// integrated out: ll = c_s - (nu + 1)/2 log1p(g_s r^2), with ch = [2][S] holding
+// c_s = lgamma((nu + 1)/2) - lgamma(nu/2) - 1/2 log(nu pi) - log sigma_s in place of the Gaussian
+// constant and g_s = 1 / (nu sigma_s^2) in place of h_s (so hs[] is g_s here); hn = (nu + 1)/2 is
+// the likelihood's one kernel scalar.  The kernels that walk the matrix are templates on the draws
+// type <D, L...>: L... are the scalars D's constructor takes behind TileDraws' own, none for
+// TileDraws (those instantiations have the arguments and the code of the untemplated kernels).
+struct TileDrawsT : TileDraws {
+    double hn;
+    __device__ __forceinline__ TileDrawsT(const double* __restrict__ ch, int64_t S, int64_t s0, int cl,
+                                          double half_nu1)
+        : TileDraws(ch, S, s0, cl), hn(half_nu1) {}
+    __device__ __forceinline__ double ll(double y, double dot, int t) const {
+        const double res = y - dot;
+        return fma(-hn, log1p_nonneg((res * res) * hs[t]), cs[t]);
+    }
+};
+
 }  // namespace bmc

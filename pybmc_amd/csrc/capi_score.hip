@@ -12,11 +12,14 @@ struct ScoreIn {
     const void *A, *y, *theta;   // host or device
     int64_t n, lda, S, ldt;
     int32_t k, layout;
+    double nu = 0.0;   // the likelihood: 0 Gaussian, else Student-t with nu degrees of freedom
 };
 
 int check_score_args(bmc_ctx* c, const void* A, int64_t n, int32_t k, int64_t lda, int layout,
-                     const void* y, const void* theta, int64_t S, int64_t ldt) {
+                     const void* y, const void* theta, int64_t S, int64_t ldt, double nu = 0.0) {
     if (!c) return BMC_EINVAL;
+    if (!(nu >= 0.0 && nu < INFINITY))   // (the _t entry points have turned a nu of 0 into NaN)
+        return fail(c, BMC_EINVAL, "nu must be positive and finite");
     if (!A || !y || !theta) return fail(c, BMC_EINVAL, "A, y and theta must not be NULL");
     if (n < 1) return fail(c, BMC_EINVAL, "n_points must be >= 1");
     if (k < 1 || k > SCORE_MAX_K)
@@ -45,6 +48,7 @@ int score_args(bmc_ctx* c, const ScorePlan& plan, const ScoreIn& in, ScoreArgs& 
     a.ldt = in.ldt;
     a.k = in.k;
     a.col_major = in.layout == BMC_COL_MAJOR;
+    a.nu = in.nu;
     a.Ap = (double*)c->scAp.p;
     a.yp = (double*)c->scYp.p;
     a.ch = (double*)c->scCh.p;
@@ -122,7 +126,8 @@ int loo_predict_family(bmc_ctx* c, const ScoreIn& in, const double** src) {
 // own: the resident problem, the prior and the predictive draws are not touched.
 int score_entry(bmc_ctx* c, ScoreIn in, bool on_host, ScoreFamily family,
                 std::initializer_list<double*> dst) {
-    int rc = check_score_args(c, in.A, in.n, in.k, in.lda, in.layout, in.y, in.theta, in.S, in.ldt);
+    int rc = check_score_args(c, in.A, in.n, in.k, in.lda, in.layout, in.y, in.theta, in.S, in.ldt,
+                              in.nu);
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     if (on_host && (rc = score_stage(c, in))) return rc;
@@ -190,6 +195,10 @@ int ppc_entry(bmc_ctx* c, ScoreIn in, const void* offset, bool on_host, uint64_t
     return BMC_OK;
 }
 
+// nu of a _t entry point as ScoreIn carries it: what is not positive (0 would mean Gaussian there)
+// becomes NaN, which check_score_args refuses
+double t_nu(double nu) { return nu > 0.0 ? nu : NAN; }
+
 }  // namespace
 
 extern "C" {
@@ -221,6 +230,36 @@ int bmc_psis_loo_device(bmc_ctx* c, const void* dA, int64_t n_points, int32_t k,
                         double* elpd_loo_out, double* pareto_k_out, double* lppd_out) {
     return score_entry(c, {dA, dy, dtheta, n_points, lda, n_draws, ldt, k, layout}, false, loo_family,
                        {elpd_loo_out, pareto_k_out, lppd_out});
+}
+
+int bmc_pointwise_loglik_t(bmc_ctx* c, const double* A, int64_t n_points, int32_t k, int64_t lda,
+                           int layout, const double* y, const double* theta, int64_t n_draws,
+                           int64_t ldt, double nu, double* lppd_out, double* pwaic_out,
+                           double* mean_ll_out) {
+    return score_entry(c, {A, y, theta, n_points, lda, n_draws, ldt, k, layout, t_nu(nu)}, true,
+                       pointwise_family, {lppd_out, pwaic_out, mean_ll_out});
+}
+
+int bmc_pointwise_loglik_t_device(bmc_ctx* c, const void* dA, int64_t n_points, int32_t k, int64_t lda,
+                                  int layout, const void* dy, const void* dtheta, int64_t n_draws,
+                                  int64_t ldt, double nu, double* lppd_out, double* pwaic_out,
+                                  double* mean_ll_out) {
+    return score_entry(c, {dA, dy, dtheta, n_points, lda, n_draws, ldt, k, layout, t_nu(nu)}, false,
+                       pointwise_family, {lppd_out, pwaic_out, mean_ll_out});
+}
+
+int bmc_psis_loo_t(bmc_ctx* c, const double* A, int64_t n_points, int32_t k, int64_t lda, int layout,
+                   const double* y, const double* theta, int64_t n_draws, int64_t ldt, double nu,
+                   double* elpd_loo_out, double* pareto_k_out, double* lppd_out) {
+    return score_entry(c, {A, y, theta, n_points, lda, n_draws, ldt, k, layout, t_nu(nu)}, true,
+                       loo_family, {elpd_loo_out, pareto_k_out, lppd_out});
+}
+
+int bmc_psis_loo_t_device(bmc_ctx* c, const void* dA, int64_t n_points, int32_t k, int64_t lda,
+                          int layout, const void* dy, const void* dtheta, int64_t n_draws, int64_t ldt,
+                          double nu, double* elpd_loo_out, double* pareto_k_out, double* lppd_out) {
+    return score_entry(c, {dA, dy, dtheta, n_points, lda, n_draws, ldt, k, layout, t_nu(nu)}, false,
+                       loo_family, {elpd_loo_out, pareto_k_out, lppd_out});
 }
 
 int bmc_psis_loo_predict(bmc_ctx* c, const double* A, int64_t n_points, int32_t k, int64_t lda,

@@ -30,6 +30,11 @@
 // that are sorted before use.  A point with a non-finite ll (a NaN or infinity in a_i, y_i or any
 // draw, a sigma_s <= 0) is flagged by loo_range and gets NaN; its keys are never used as an index
 // (digits are masked, slots are bounded by the cap).
+//
+// The likelihood enters through the draws type alone (bmc_score_tile.h): the passes that compute ll
+// (range, select, the non-PREDICT append) are templates <D, L...> on it, TileDraws for the Gaussian
+// density and TileDrawsT with its scalar for the Student-t one (ScoreArgs::nu > 0); init, scan and
+// fit see values of ll only.  The PREDICT variants and loo_bucket are Gaussian only.
 #include "bmc_dev.h"
 #include "bmc_launch.h"
 #include "bmc_plan.h"
@@ -79,7 +84,9 @@ struct PassArgs {
     uint32_t point_tiles;
 };
 
-__global__ __launch_bounds__(256) void loo_range_kernel(PassArgs a, uint64_t* __restrict__ range) {
+template <class D, class... L>
+__global__ __launch_bounds__(256) void loo_range_kernel(PassArgs a, uint64_t* __restrict__ range,
+                                                        L... lik) {
     __shared__ double As[SC_LDS_DOUBLES];
     __shared__ double Bs[SC_LDS_DOUBLES];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, cl = lane & 15, kq = lane >> 4;
@@ -95,7 +102,7 @@ __global__ __launch_bounds__(256) void loo_range_kernel(PassArgs a, uint64_t* __
     }
     score_tile_loop(a.Ap, a.theta, a.S, a.ldt, a.k, a.k_pad, pos.p0, pos.dt0, pos.dt1, As, Bs,
                     [&](int64_t s0, const f64x4(&acc)[4]) {
-        const TileDraws d(a.ch, a.S, s0, cl);
+        const D d(a.ch, a.S, s0, cl, lik...);
 #pragma unroll
         for (int r = 0; r < 4; ++r)
 #pragma unroll
@@ -165,10 +172,11 @@ __global__ __launch_bounds__(256) void loo_init_kernel(const uint64_t* __restric
     meta[i] = m;
 }
 
+template <class D, class... L>
 __global__ __launch_bounds__(256) void loo_select_kernel(PassArgs a,
                                                          const uint64_t* __restrict__ prefix,
                                                          const uint4* __restrict__ meta,
-                                                         uint32_t* __restrict__ hist) {
+                                                         uint32_t* __restrict__ hist, L... lik) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     double* As = (double*)smem_raw;
     double* Bs = As + SC_LDS_DOUBLES;
@@ -199,7 +207,7 @@ __global__ __launch_bounds__(256) void loo_select_kernel(PassArgs a,
     __syncthreads();
     score_tile_loop(a.Ap, a.theta, a.S, a.ldt, a.k, a.k_pad, pos.p0, pos.dt0, pos.dt1, As, Bs,
                     [&](int64_t s0, const f64x4(&acc)[4]) {
-        const TileDraws d(a.ch, a.S, s0, cl);
+        const D d(a.ch, a.S, s0, cl, lik...);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             if (!live[r]) continue;
@@ -268,8 +276,8 @@ __device__ __forceinline__ double draw_phi(double res, double sqrt_h) {
 
 // PREDICT: besides sum w (body), pay[split][point][4] = sum w r, sum w (sigma^2 + r^2),
 // sum w Phi(r / sigma), sum w^2 over the keys above the bucket, each in the order of `body`; and
-// the draw index of every candidate next to its value.
-template <bool PREDICT>
+// the draw index of every candidate next to its value (TileDraws only: it reads h_s).
+template <bool PREDICT, class D, class... L>
 __global__ __launch_bounds__(256) void loo_append_kernel(PassArgs a,
                                                          const uint64_t* __restrict__ prefix,
                                                          const uint64_t* __restrict__ kmin,
@@ -278,7 +286,7 @@ __global__ __launch_bounds__(256) void loo_append_kernel(PassArgs a,
                                                          double* __restrict__ cand,
                                                          double* __restrict__ body,
                                                          uint32_t* __restrict__ candidx,
-                                                         double* __restrict__ pay) {
+                                                         double* __restrict__ pay, L... lik) {
     __shared__ double As[SC_LDS_DOUBLES];
     __shared__ double Bs[SC_LDS_DOUBLES];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, cl = lane & 15, kq = lane >> 4;
@@ -304,7 +312,7 @@ __global__ __launch_bounds__(256) void loo_append_kernel(PassArgs a,
     }
     score_tile_loop(a.Ap, a.theta, a.S, a.ldt, a.k, a.k_pad, pos.p0, pos.dt0, pos.dt1, As, Bs,
                     [&](int64_t s0, const f64x4(&acc)[4]) {
-        const TileDraws d(a.ch, a.S, s0, cl);
+        const D d(a.ch, a.S, s0, cl, lik...);
         double s2[4], sq[4];
         if constexpr (PREDICT)
 #pragma unroll
@@ -790,7 +798,8 @@ hipError_t launch_loo_passes(const LooArgs& a, const LooPlan& p, const LooPredic
     const ScoreArgs& sa = a.score;
     const ScorePlan& sp = p.score;
     if (!p.ok || !a.work || sa.S - p.tail < 1 || p.cap < 2 * (p.tail + 1) || p.cap > LOO_MAX_CAP ||
-        (p.cap & (p.cap - 1)) != 0 || p.tail != loo_tail(sa.S) || sa.n > 0x7fffffffll)
+        (p.cap & (p.cap - 1)) != 0 || p.tail != loo_tail(sa.S) || sa.n > 0x7fffffffll ||
+        (pp && sa.nu != 0.0))
         return hipErrorInvalidValue;   // (the fit's grid is one workgroup per point)
     hipError_t e = launch_score(sa, sp, s);   // (checks the shapes and the split plan)
     if (e != hipSuccess) return e;
@@ -814,25 +823,34 @@ hipError_t launch_loo_passes(const LooArgs& a, const LooPlan& p, const LooPredic
     pa.k_pad = sp.k_pad;
     pa.point_tiles = (uint32_t)sp.point_tiles;
 
+    // a pass over the matrix under the call's likelihood (launch_score has checked sa.nu)
+    const bool student = sa.nu > 0.0;
+    const double hn = 0.5 * (sa.nu + 1.0);
+    auto pass = [&](auto gauss, auto student_t, size_t lds, auto... args) {
+        if (student) hipLaunchKernelGGL(student_t, dim3(groups), dim3(256), lds, s, pa, args..., hn);
+        else hipLaunchKernelGGL(gauss, dim3(groups), dim3(256), lds, s, pa, args...);
+    };
+
     if ((e = hipMemsetAsync(w.hist, 0, lb.hist, s)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(w.count, 0, lb.count, s)) != hipSuccess) return e;
-    hipLaunchKernelGGL(loo_range_kernel, dim3(groups), dim3(256), 0, s, pa, w.range);
+    pass(loo_range_kernel<TileDraws>, loo_range_kernel<TileDrawsT, double>, 0, w.range);
     hipLaunchKernelGGL(loo_init_kernel, dim3(pblocks), dim3(256), 0, s, (const uint64_t*)w.range,
                        n_pad, sp.splits, sa.S, M, cap, w.prefix, w.kmin, w.meta);
     if (p.select_passes > 0) {
-        e = hipFuncSetAttribute((const void*)loo_select_kernel,
+        e = hipFuncSetAttribute(student ? (const void*)loo_select_kernel<TileDrawsT, double>
+                                        : (const void*)loo_select_kernel<TileDraws>,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)LOO_SELECT_LDS);
         if (e != hipSuccess) return e;
-        for (int pass = 0; pass < p.select_passes; ++pass) {
-            hipLaunchKernelGGL(loo_select_kernel, dim3(groups), dim3(256), LOO_SELECT_LDS, s, pa,
-                               (const uint64_t*)w.prefix, (const uint4*)w.meta, w.hist);
+        for (int sel = 0; sel < p.select_passes; ++sel) {
+            pass(loo_select_kernel<TileDraws>, loo_select_kernel<TileDrawsT, double>, LOO_SELECT_LDS,
+                 (const uint64_t*)w.prefix, (const uint4*)w.meta, w.hist);
             hipLaunchKernelGGL(loo_scan_kernel, dim3(pblocks), dim3(256), 0, s, n_pad, M, cap,
                                w.prefix, w.meta, w.hist);
         }
     }
     if (pp) {
         const PredictWork pw(w, loo_predict_buffers(*pp, sa.n));
-        hipLaunchKernelGGL(loo_append_kernel<true>, dim3(groups), dim3(256), 0, s, pa,
+        hipLaunchKernelGGL((loo_append_kernel<true, TileDraws>), dim3(groups), dim3(256), 0, s, pa,
                            (const uint64_t*)w.prefix, (const uint64_t*)w.kmin,
                            (const uint4*)w.meta, (uint32_t)cap, w.count, w.cand, w.body, pw.candidx,
                            pw.pay);
@@ -860,9 +878,9 @@ hipError_t launch_loo_passes(const LooArgs& a, const LooPlan& p, const LooPredic
                            M, cap, pw.out, fp);
         return hipGetLastError();
     }
-    hipLaunchKernelGGL(loo_append_kernel<false>, dim3(groups), dim3(256), 0, s, pa,
-                       (const uint64_t*)w.prefix, (const uint64_t*)w.kmin, (const uint4*)w.meta,
-                       (uint32_t)cap, w.count, w.cand, w.body, (uint32_t*)nullptr, (double*)nullptr);
+    pass(loo_append_kernel<false, TileDraws>, loo_append_kernel<false, TileDrawsT, double>, 0,
+         (const uint64_t*)w.prefix, (const uint64_t*)w.kmin, (const uint4*)w.meta, (uint32_t)cap,
+         w.count, w.cand, w.body, (uint32_t*)nullptr, (double*)nullptr);
     const size_t fit_lds = (size_t)cap * 8;
     e = hipFuncSetAttribute((const void*)loo_fit_kernel<false>,
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)fit_lds);

@@ -6,6 +6,7 @@
 //   score_pad      A (either layout, any lda) and y -> whole 64-point tiles and 16-column slabs,
 //                  zero in the padding
 //   score_consts   per draw: c_s = -1/2 log(2 pi) - log sigma_s,  h_s = 1 / (2 sigma_s^2)
+//                  (score_consts_t: the constants of the Student-t density, ScoreArgs::nu > 0)
 //   score_tile     workgroup = 64 points x the draw tiles of one split.  a_i . beta_s on
 //                  v_mfma_f64_16x16x4_f64 (the tile loop of bmc_score_tile.h, shared with
 //                  kernels_loo.hip); the tile is reduced in the epilogue
@@ -74,6 +75,18 @@ __global__ __launch_bounds__(256) void score_consts_kernel(const double* __restr
     ch[S + s] = 1.0 / (2.0 * sg * sg);
 }
 
+// the Student-t constants of TileDrawsT: cnu = lgamma((nu + 1)/2) - lgamma(nu/2) - 1/2 log(nu pi)
+__global__ __launch_bounds__(256) void score_consts_t_kernel(const double* __restrict__ theta,
+                                                             int64_t S, int64_t ldt, int32_t k,
+                                                             double cnu, double nu,
+                                                             double* __restrict__ ch) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= S) return;
+    const double sg = theta[s * ldt + k];
+    ch[s] = cnu - log(sg);
+    ch[S + s] = 1.0 / (nu * sg * sg);
+}
+
 // The running state of one point in one lane; the count is the lane's (the same for its 4 points).
 struct LlRun {
     double m, L, mean, M2;
@@ -115,11 +128,13 @@ __device__ __forceinline__ void score_fold(LlRun& st, const double (&x)[4], cons
 // grid: splits * point_tiles, point tile fastest: the workgroups that run together walk the SAME
 // draws (one split) over different points, so each XCD's L2 fetches a slab of theta once for
 // all of them; the A tiles (64 x k_pad each) stay in L2 for the whole launch.
+// <D, L...>: the draws type and its scalars lik (bmc_score_tile.h).
+template <class D, class... L>
 __global__ __launch_bounds__(256) void score_tile_kernel(
     const double* __restrict__ Ap, const double* __restrict__ yp, const double* __restrict__ theta,
     const double* __restrict__ ch, int64_t S, int64_t ldt, int32_t k, int32_t k_pad,
     uint32_t point_tiles, int64_t tiles_per_split, int64_t draw_tiles, int64_t n_pad,
-    double* __restrict__ part) {
+    double* __restrict__ part, L... lik) {
     __shared__ double As[SC_LDS_DOUBLES];
     __shared__ double Bs[SC_LDS_DOUBLES];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -141,11 +156,11 @@ __global__ __launch_bounds__(256) void score_tile_kernel(
         st[r] = LlRun{-__builtin_inf(), 0.0, 0.0, 0.0};
     }
 
-    // epilogue: ll = c_s - h_s r^2 for the lane's 4 points x 4 draws, folded into the running
-    // state of each point
+    // epilogue: ll (D::ll) for the lane's 4 points x 4 draws, folded into the running state of
+    // each point
     score_tile_loop(Ap, theta, S, ldt, k, k_pad, p0, dt0, dt1, As, Bs,
                     [&](int64_t s0, const f64x4(&acc)[4]) {
-        const TileDraws d(ch, S, s0, cl);
+        const D d(ch, S, s0, cl, lik...);
         const bool full = s0 + SC_TM <= S;   // wave-uniform
         const double nb = (double)((int)d.ok[0] + (int)d.ok[1] + (int)d.ok[2] + (int)d.ok[3]);
         if (nb > 0.0) {   // (not a lane whose draws of the last tile are all past S)
@@ -218,7 +233,8 @@ ScoreBuffers score_buffers(const ScorePlan& p, int64_t n_draws) {
 
 hipError_t launch_score(const ScoreArgs& a, const ScorePlan& p, hipStream_t s) {
     if (a.n < 1 || a.S < 2 || a.k < 1 || a.k > SCORE_MAX_K || a.ldt < a.k + 1 ||
-        a.lda < (a.col_major ? a.n : (int64_t)a.k) || p.k_pad < a.k || p.k_pad % SC_KT != 0 ||
+        a.lda < (a.col_major ? a.n : (int64_t)a.k) || !(a.nu >= 0.0 && a.nu < __builtin_inf()) ||
+        p.k_pad < a.k || p.k_pad % SC_KT != 0 ||
         p.point_tiles != (a.n + SC_TM - 1) / SC_TM || p.draw_tiles != (a.S + SC_TM - 1) / SC_TM ||
         p.splits < 1 || p.tiles_per_split < 1 || p.splits * p.tiles_per_split < p.draw_tiles ||
         (p.splits - 1) * p.tiles_per_split >= p.draw_tiles)
@@ -235,13 +251,28 @@ hipError_t launch_score(const ScoreArgs& a, const ScorePlan& p, hipStream_t s) {
     {
         const int64_t blocks = (a.S + 255) / 256;
         if (blocks > 0x7fffffffll) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(score_consts_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a.theta, a.S,
-                           a.ldt, a.k, a.ch);
+        if (a.nu > 0.0) {
+            // in long double: the difference of the two lgamma loses digits as nu grows
+            const long double nu = (long double)a.nu;
+            const long double cnu = lgammal(0.5L * (nu + 1.0L)) - lgammal(0.5L * nu) -
+                                    0.5L * logl(nu * 3.14159265358979323846264338327950288L);
+            hipLaunchKernelGGL(score_consts_t_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a.theta,
+                               a.S, a.ldt, a.k, (double)cnu, a.nu, a.ch);
+        } else {
+            hipLaunchKernelGGL(score_consts_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a.theta,
+                               a.S, a.ldt, a.k, a.ch);
+        }
     }
-    hipLaunchKernelGGL(score_tile_kernel, dim3((unsigned)groups), dim3(256), 0, s,
-                       (const double*)a.Ap, (const double*)a.yp, a.theta, (const double*)a.ch, a.S,
-                       a.ldt, a.k, p.k_pad, (uint32_t)p.point_tiles, p.tiles_per_split,
-                       p.draw_tiles, n_pad, a.part);
+    if (a.nu > 0.0)
+        hipLaunchKernelGGL((score_tile_kernel<TileDrawsT, double>), dim3((unsigned)groups), dim3(256), 0,
+                           s, (const double*)a.Ap, (const double*)a.yp, a.theta, (const double*)a.ch,
+                           a.S, a.ldt, a.k, p.k_pad, (uint32_t)p.point_tiles, p.tiles_per_split,
+                           p.draw_tiles, n_pad, a.part, 0.5 * (a.nu + 1.0));
+    else
+        hipLaunchKernelGGL(score_tile_kernel<TileDraws>, dim3((unsigned)groups), dim3(256), 0, s,
+                           (const double*)a.Ap, (const double*)a.yp, a.theta, (const double*)a.ch, a.S,
+                           a.ldt, a.k, p.k_pad, (uint32_t)p.point_tiles, p.tiles_per_split,
+                           p.draw_tiles, n_pad, a.part);
     hipLaunchKernelGGL(score_merge_kernel, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, s,
                        (const double*)a.part, a.n, n_pad, p.splits, a.S, a.out);
     return hipGetLastError();

@@ -18,6 +18,18 @@ and, on the host in float64 from the pointwise vectors,
   ``n_high_p = #{i : p_waic_i > 0.4}`` (the ``loo`` package's warning threshold);
 * for held-out data there is no penalty: ``elpd = sum_i lppd_i``, ``se`` from ``lppd_i``.
 
+With ``nu=`` the same estimators score a Student-t fit (``gibbs_sampler_robust``,
+``train({"sampler": "student_t"})``): ``y_i ~ a_i . beta + sigma t_nu`` with ``nu`` fixed, and, for
+``r = y_i - a_i . beta_s``,
+
+    ll[i, s] = lgamma((nu + 1)/2) - lgamma(nu/2) - 1/2 log(nu pi) - log sigma_s
+               - (nu + 1)/2 log1p(r^2 / (nu sigma_s^2))
+
+the marginal t density, the latent row weights integrated out: what leave-one-out needs, since the
+``(beta, sigma)`` rows that sampler returns are draws from that marginal posterior.  Everything
+downstream of ``ll`` is unchanged.  ``compare_elpd`` puts the scores of several fits of the same
+data side by side with the paired standard error of their differences.
+
 S. Watanabe, "Asymptotic equivalence of Bayes cross validation and widely applicable information
 criterion in singular learning theory", JMLR 11, 2010; A. Gelman, J. Hwang, A. Vehtari,
 "Understanding predictive information criteria for Bayesian models", Stat. Comput. 24, 2014.
@@ -218,7 +230,27 @@ def _pointwise_call(host_call, device_call, A, y, samples, burn, thin, device, m
                                        *tail(A, y, vecs))
 
 
-def pointwise_log_likelihood(A, y, samples, burn=0, thin=1, device=0):
+def _check_nu(nu):
+    """None (the Gaussian likelihood) or the Student-t degrees of freedom as a float; ValueError
+    for anything not positive and finite (no GPU needed)."""
+    if nu is None:
+        return None
+    if isinstance(nu, bool) or not isinstance(nu, (int, float, np.integer, np.floating)):
+        raise ValueError(f"nu must be None or a positive finite number; got {nu!r}")
+    nu = float(nu)
+    if not (0.0 < nu < float("inf")):
+        raise ValueError(f"nu must be None or a positive finite number; got {nu}")
+    return nu
+
+
+def _likelihood_call(name, nu):
+    """(host method, device method, trailing scalars) of a scoring call under the likelihood."""
+    if nu is None:
+        return name, name + "_device", ()
+    return name + "_t", name + "_t_device", (nu,)
+
+
+def pointwise_log_likelihood(A, y, samples, burn=0, thin=1, device=0, nu=None):
     """``lppd_i``, ``p_waic_i`` and ``mean_ll_i`` of every row of ``A`` (module docstring).
 
     ``A`` is ``(n_points, k)`` float64 (either memory order: ``U_hat`` is Fortran-ordered), ``y``
@@ -226,9 +258,10 @@ def pointwise_log_likelihood(A, y, samples, burn=0, thin=1, device=0):
     (last column sigma): a numpy array, or a CUDA torch tensor whose last dimension is contiguous
     (read in place; ``device`` is then the tensor's).  The first ``burn`` draws of every chain are
     dropped, every ``thin``-th of the rest kept, and the chains pooled.  Returns a dict of
-    ``[n_points]`` arrays ``lppd``, ``p_waic``, ``mean_ll``."""
-    return _pointwise_call("pointwise_loglik", "pointwise_loglik_device", A, y, samples, burn,
-                           thin, device)
+    ``[n_points]`` arrays ``lppd``, ``p_waic``, ``mean_ll``.  ``nu=None`` is the Gaussian
+    likelihood; a positive finite number the Student-t one with that many degrees of freedom."""
+    host, dev, scalars = _likelihood_call("pointwise_loglik", _check_nu(nu))
+    return _pointwise_call(host, dev, A, y, samples, burn, thin, device, scalars=scalars)
 
 
 def _se(v):
@@ -253,11 +286,11 @@ def elpd_summary(lppd):
     return {"elpd": float(np.sum(lppd)), "se": _se(lppd), "n_points": int(lppd.shape[0])}
 
 
-def waic(A, y, samples, burn=0, thin=1, device=0):
+def waic(A, y, samples, burn=0, thin=1, device=0, nu=None):
     """WAIC of a fit on its training data: ``elpd_waic``, ``p_waic``, ``waic``, ``se``,
     ``n_high_p``, ``n_points`` and the pointwise ``lppd``, ``p_waic_i``, ``mean_ll``,
     ``elpd_waic_i``.  Arguments as ``pointwise_log_likelihood``."""
-    pw = pointwise_log_likelihood(A, y, samples, burn=burn, thin=thin, device=device)
+    pw = pointwise_log_likelihood(A, y, samples, burn=burn, thin=thin, device=device, nu=nu)
     out = waic_summary(pw["lppd"], pw["p_waic"])
     out.update(lppd=pw["lppd"], p_waic_i=pw["p_waic"], mean_ll=pw["mean_ll"],
                elpd_waic_i=pw["lppd"] - pw["p_waic"])
@@ -278,14 +311,15 @@ def loo_summary(elpd_loo_i, lppd, pareto_k, n_draws):
             "n_draws": int(n_draws)}
 
 
-def psis_loo(A, y, samples, burn=0, thin=1, device=0):
+def psis_loo(A, y, samples, burn=0, thin=1, device=0, nu=None):
     """PSIS-LOO of a fit on its training data (module docstring): ``elpd_loo``, ``p_loo``,
     ``looic``, ``se``, ``n_high_k``, ``k_threshold``, ``n_above_threshold``, ``n_points``,
     ``n_draws`` and the pointwise ``elpd_loo_i``, ``p_loo_i``, ``pareto_k``, ``lppd``.  Arguments
-    as ``pointwise_log_likelihood``.  The relative efficiency r_eff of the draws is taken as 1, as
+    as ``pointwise_log_likelihood``, ``nu`` included.  The relative efficiency r_eff of the draws is taken as 1, as
     ``loo::psis`` does when none is given.  ``pareto_k`` is ``+inf`` where nothing was smoothed
     (fewer than 25 draws, a tail of equal values, a non-finite fit)."""
-    pw = _pointwise_call("psis_loo", "psis_loo_device", A, y, samples, burn, thin, device)
+    host, dev, scalars = _likelihood_call("psis_loo", _check_nu(nu))
+    pw = _pointwise_call(host, dev, A, y, samples, burn, thin, device, scalars=scalars)
     sh = tuple(samples.shape)
     C, T = (1, sh[0]) if len(sh) == 2 else sh[:2]
     out = loo_summary(pw["elpd_loo"], pw["lppd"], pw["pareto_k"], C * kept_draws(T, burn, thin))
@@ -324,3 +358,54 @@ def psis_loo_predict(A, y, samples, burn=0, thin=1, device=0):
                loo_sd=pw["loo_sd"], loo_pit=pw["loo_pit"], ess=pw["ess"])
     out.update(loo_predict_summary(np.asarray(y), pw["loo_mean"], pw["loo_pit"], pw["ess"]))
     return out
+
+
+ELPD_KINDS = (("elpd_loo_i", "elpd_loo"), ("elpd_waic_i", "elpd_waic"), ("elpd_cv_i", "elpd_cv"),
+              ("lppd", "elpd"))
+
+
+def compare_elpd(fits):
+    """Compare fits of the same data by their expected log predictive density (host, float64).
+
+    ``fits`` maps a name to a result dict of ``psis_loo``, ``waic``, ``kfold_cv`` or
+    ``log_predictive_density`` (``BayesianModelCombination.score`` returns the first, second or
+    last); the pointwise vector is ``elpd_loo_i``, ``elpd_waic_i``, ``elpd_cv_i`` or ``lppd``.
+    Every entry must be of the same kind and the same length, else ``ValueError``.  Returns a dict:
+    ``names`` ordered by ``elpd`` descending (ties in input order), ``elpd`` and ``se`` in that
+    order, ``elpd_diff[j] = elpd[best] - elpd[j]``, ``se_diff[j] = sqrt(n var_i(e_best,i - e_j,i,
+    ddof=1))`` (0 at the best: the paired standard error, as ``cv.path_summary``), ``kind`` (the
+    name of the pointwise vector) and ``n_points``.  NaNs propagate."""
+    if not isinstance(fits, dict) or not fits:
+        raise ValueError("fits must be a non-empty dict of name -> result dict")
+    kind, vectors = None, []
+    for name, res in fits.items():
+        found = None
+        if isinstance(res, dict):
+            # (a psis_loo or waic result carries lppd too: the first match names the kind)
+            found = next((key for key, total in ELPD_KINDS if key in res and total in res), None)
+        if found is None:
+            raise ValueError(f"fits[{name!r}] is not a result of psis_loo, waic, kfold_cv or "
+                             "log_predictive_density")
+        if kind is not None and found != kind:
+            raise ValueError(f"fits[{name!r}] holds {found}, the entries before it {kind}: "
+                             "only scores of the same kind compare")
+        kind = found
+        v = np.asarray(res[found], dtype=np.float64)
+        if v.ndim != 1 or (vectors and v.shape != vectors[0].shape):
+            raise ValueError(f"fits[{name!r}][{found!r}] must be a vector of the length of the "
+                             "other entries (the same data points)")
+        vectors.append(v)
+    e = np.stack(vectors)                                   # (fits, n)
+    n = e.shape[1]
+    elpd = e.sum(axis=1)
+    # descending, ties in input order; a NaN elpd sorts last
+    order = sorted(range(len(vectors)), key=lambda j: (np.isnan(elpd[j]), -elpd[j]))
+    e, elpd = e[order], elpd[order]
+    d = e[0][None, :] - e
+    with np.errstate(invalid="ignore"):
+        se = np.sqrt(n * np.var(e, axis=1, ddof=1)) if n > 1 else np.full(len(order), np.nan)
+        se_diff = np.sqrt(n * np.var(d, axis=1, ddof=1)) if n > 1 else np.full(len(order), np.nan)
+    se_diff[0] = 0.0
+    names = list(fits)
+    return {"names": [names[j] for j in order], "elpd": elpd, "se": se, "elpd_diff": elpd[0] - elpd,
+            "se_diff": se_diff, "kind": kind, "n_points": int(n)}
