@@ -134,6 +134,25 @@ inline int choose_vec(int64_t n, int32_t k, int f32) {
     return vec;
 }
 
+// ---- set-up kernels (kernels_setup.hip): the launch classes a shape reaches -------------------
+// residual_rss: workgroups of 4 wave slots; slot w walks panels w, w + 4 G, ...
+// 4 workgroups per CU: measured best all-round on MI355X (52 MB: 12.1 us/pass,
+// 520 MB: 95 us/pass = 5.5 TB/s); more groups only add ramp-up and tail
+inline int32_t rss_groups_of(int32_t npanels) {
+    int32_t g = (npanels + 3) / 4;
+    if (g > 1024) g = 1024;
+    if (g < 1) g = 1;
+    return g;
+}
+constexpr unsigned RSS_FLAT_TICKET_MAX = 256;   // more workgroups than this draw tickets in two levels
+// the most panels one wave slot of residual_rss walks
+inline int32_t rss_trips_of(int32_t npanels) {
+    const int32_t slots = 4 * rss_groups_of(npanels);
+    return npanels > 0 ? (npanels + slots - 1) / slots : 0;
+}
+// rotate: column groups per panel (a workgroup of 4 waves x jt output columns each)
+inline uint32_t rotate_col_groups(int32_t ko, int32_t jt) { return (uint32_t)((ko + 4 * jt - 1) / (4 * jt)); }
+
 struct Geometry {
     int chains_per_launch, G, waves, ppg, mode, ppw, nslot;
     int one_wave;   // the chain runs in ONE wave (gibbs_wave_kernel)

@@ -429,7 +429,7 @@ template <typename T>
 static hipError_t rotate_dispatch(const Panels& P, const double* W, int32_t ko, void* Xrot,
                                   hipStream_t s) {
     constexpr int jt = 8;
-    const uint32_t ncg = (uint32_t)((ko + 4 * jt - 1) / (4 * jt));   // column groups per panel
+    const uint32_t ncg = rotate_col_groups(ko, jt);   // column groups per panel
     const dim3 grid((unsigned)(((P.npanels + 7) / 8) * 8) * ncg);
 #define BMC_ROT(V, J)                                                                       \
     hipLaunchKernelGGL((rotate_kernel<T, V, J>), grid, dim3(256), 0, s, (const T*)P.X, W, P.k, \
@@ -666,14 +666,7 @@ __global__ __launch_bounds__(256) void residual_rss_kernel(
         __hip_atomic_store(ticket_word, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-int32_t rss_groups(const Panels& P) {
-    int32_t g = (P.npanels + 3) / 4;
-    // 4 workgroups per CU: measured best all-round on MI355X (52 MB: 12.1 us/pass,
-    // 520 MB: 95 us/pass = 5.5 TB/s); more groups only add ramp-up and tail
-    if (g > 1024) g = 1024;
-    if (g < 1) g = 1;
-    return g;
-}
+int32_t rss_groups(const Panels& P) { return rss_groups_of(P.npanels); }
 
 template <typename T, int VEC>
 static hipError_t rss_dispatch(const Panels& P, const double* coef, int32_t nb, double* partial,

@@ -16,6 +16,12 @@
 //   replan FILE    re-plans every recipe of such a table: "name | the launches in order, joined by
 //                  ;, each kernel@first chain+chains:chains per pass | the same had the device
 //                  given the other pack answer"
+//   setup N K F32 [N K F32 ...]
+//                  per triple the launch class of the set-up kernels (kernels_setup.hip) for an
+//                  (N x K) problem of that storage type: rows per lane (choose_vec), panels, rows
+//                  of the last panel; residual_rss: workgroups, flat or two-level ticket, the most
+//                  panels one wave slot walks; rotate to K output columns: column groups per
+//                  panel and the columns of the last wave (tests/test_setup_plan.py)
 #include "../pybmc_amd/csrc/bmc_plan.h"
 
 #include <cstdio>
@@ -375,8 +381,25 @@ static int replan(const char* file) {
     return 0;
 }
 
+// ---- setup: the launch class of the set-up kernels for one (n, k, f32) ------------------------
+static void setup_class(int64_t n, int k, int f32) {
+    const Shape s = shape_of(n, k, f32);
+    const int32_t G = rss_groups_of(s.npanels);
+    std::printf("setup n=%lld k=%d f32=%d: vec=%d np=%d rows_per_panel=%d last_rows=%lld | rss G=%d ticket=%s "
+                "trips=%d | rotate ncg=%u last_wave_cols=%d\n",
+                (long long)n, k, f32, s.vec, s.npanels, 64 * s.vec,
+                (long long)(n - (int64_t)(s.npanels - 1) * 64 * s.vec), G,
+                (unsigned)G > RSS_FLAT_TICKET_MAX ? "two-level" : "flat", rss_trips_of(s.npanels),
+                rotate_col_groups(k, 8), (k - 1) % 8 + 1);
+}
+
 int main(int argc, char** argv) {
     static constexpr KernelKeys keys = loop_kernel_keys();
+    if (argc > 4 && (argc - 2) % 3 == 0 && std::strcmp(argv[1], "setup") == 0) {
+        for (int a = 2; a + 2 < argc; a += 3)
+            setup_class(std::atoll(argv[a]), std::atoi(argv[a + 1]), std::atoi(argv[a + 2]));
+        return 0;
+    }
     if (argc > 1 && std::strcmp(argv[1], "census") == 0) {
         census(keys);
         return 0;
