@@ -91,22 +91,43 @@ __device__ __forceinline__ void granule_put(gu64* g, unsigned epoch, unsigned va
 #ifndef BMC_REGMULTI_DEPTH_BIG
 #define BMC_REGMULTI_DEPTH_BIG 3
 #endif
-#ifndef BMC_POLL_DEPTH2
-#define BMC_POLL_DEPTH2 2
-#endif
-// Gather n2 <= 64 granules of `epoch`, one per lane (the usual case: G <= 32).  Two reads are
-// kept in flight, so the epoch is seen half a load round trip after it lands instead of up
-// to a full one (three or four in flight were slower: same-box A/B).  Returns false when the
-// bounded spin expired.  Lanes >= n2 get 0.
-template <int DEPTH = 2, int STRIDE = GRAN_PAIR_STRIDE>
+// N wait states (s_nop: 4.3 shader cycles each on MI355X, scripts/micro/pollsched.hip).  The wave
+// idles without touching a counter, so loads already in flight keep returning.
+template <int N>
+__device__ __forceinline__ void wait_states() {
+    if constexpr (N >= 16) {
+        asm volatile("s_nop 15");
+        wait_states<N - 16>();
+    } else if constexpr (N > 0) {
+        asm volatile("s_nop %0" ::"n"(N - 1));
+    }
+}
+
+struct NoPollSpacing {
+    __device__ __forceinline__ void operator()() const {}
+};
+
+// Gather n2 <= 64 granules of `epoch`, one per lane (the usual case: G <= 32).  DEPTH reads are
+// kept in flight; each is re-issued when its predecessor has been tested, so the reads keep the
+// distance they were first issued at.  `space` runs between the first DEPTH reads: issued back to
+// back the pair samples L2 twice at almost the same instant and then not for a full load round
+// trip (~260 cycles); half a round trip apart it samples every half round trip (PollSched in
+// bmc_plan.h, measured in scripts/micro/pollsched.hip; three or four in flight were slower, spaced
+// or not).  Returns false when the bounded spin expired.  Lanes >= n2 get 0.
+template <int DEPTH = 2, int STRIDE = GRAN_PAIR_STRIDE, typename S = NoPollSpacing>
 __device__ __forceinline__ bool granule_gather1(const gu64* gp, int n2, unsigned epoch, int lane,
-                                                gu64& x STAMP_PARAMS) {
+                                                gu64& x STAMP_PARAMS, S space = S()) {
     unsigned long long t_start = 0;
     const bool have = lane < n2;
     const gu64* p = gp + gran_at<STRIDE>(have ? lane : 0);
+    // the lanes whose tag decides: the test is the compare's own lane mask against this one
+    const gu64 need = __builtin_amdgcn_ballot_w64(have);
     gu64 q[DEPTH];
 #pragma unroll
-    for (int d = 0; d < DEPTH - 1; ++d) q[d] = granule_load(p);
+    for (int d = 0; d < DEPTH - 1; ++d) {
+        q[d] = granule_load(p);
+        space();
+    }
     for (unsigned spins = 0;; ++spins) {
 #pragma unroll
         for (int d = 0; d < DEPTH; ++d) {
@@ -115,7 +136,8 @@ __device__ __forceinline__ bool granule_gather1(const gu64* gp, int n2, unsigned
             if (stamping) acc_[9] += 1;
 #endif
             const gu64 w = q[d];
-            if (__all(!have || (unsigned)(w >> 32) == epoch)) { x = have ? w : 0; return true; }
+            const gu64 hit = __builtin_amdgcn_ballot_w64((unsigned)(w >> 32) == epoch);
+            if ((hit & need) == need) { x = have ? w : 0; return true; }
         }
         if ((spins & 0x7f) == 0x7f) {
             const unsigned long long now = __builtin_amdgcn_s_memrealtime();
@@ -748,7 +770,9 @@ struct NoIdleWork {
 // most 32 groups and runs one of two copies of its loop, chosen once after the placement check:
 // with both run-time tests and the dead two-level code out of the loop an iteration at C2 is
 // 3 % shorter (1.090 -> 1.059 us, same-box A/B).
-template <bool RELAY = false, int TEAMS = -1, int LOCAL = -1, typename F = NoIdleWork>
+// SPACED: the first level polls by the spaced schedule of its scope (bmc_plan.h); false (and the
+// RELAY passes) keep the two reads back to back.
+template <bool RELAY = false, int TEAMS = -1, int LOCAL = -1, bool SPACED = true, typename F = NoIdleWork>
 __device__ __forceinline__ double exchange_sum(double s, gu64* gp, int G, int g, int lane,
                                                unsigned epoch, bool local, bool& ok STAMP_PARAMS,
                                                F idle = F()) {
@@ -770,7 +794,16 @@ __device__ __forceinline__ double exchange_sum(double s, gu64* gp, int G, int g,
     // of 128 / 256 / 384 cycles before the first poll -- 64 chains at C2 2.333 / 2.346 / 2.382 against
     // 2.319 us per iteration without; gpurun_out/r3_ab5.log)
     gu64 x;
-    ok = granule_gather1(gp1, 2 * members, epoch, lane, x STAMP_ARGS);
+    // first level: the schedule of this use (bmc_plan.h)
+    constexpr bool PLAIN = RELAY || !SPACED;
+    constexpr PollSched SL = PLAIN ? POLL_PLAIN : POLL_LOCAL, SA = PLAIN ? POLL_PLAIN : POLL_AGENT;
+    static_assert(SL.depth == SA.depth, "one gather, two spacings");
+    if (local) wait_states<SL.first>();
+    else wait_states<SA.first>();
+    ok = granule_gather1<SL.depth>(gp1, 2 * members, epoch, lane, x STAMP_ARGS, [&] {
+        if (local) wait_states<SL.gap>();
+        else wait_states<SA.gap>();
+    });
     GSTAMP(5);
     // (the expired spin leaves at once: as `ok ? sum : 0` the flag travelled through the whole
     // serial path as set / test / branch pairs -- tried, rejected: part of the three changes
@@ -784,7 +817,7 @@ __device__ __forceinline__ double exchange_sum(double s, gu64* gp, int G, int g,
         gu64* gp3 = gp2 + (size_t)(8 + team) * GRAN_L2_STRIDE;
         if (rank == 0) publish_pair<false, GRAN_L2_STRIDE>(gp2, team, lane, epoch, tot);
         if (!RELAY || rank == 0) {
-            ok = granule_gather1<BMC_POLL_DEPTH2, GRAN_L2_STRIDE>(gp2, 16, epoch, lane, x STAMP_ARGS);
+            ok = granule_gather1<POLL_LEVEL2.depth, GRAN_L2_STRIDE>(gp2, 16, epoch, lane, x STAMP_ARGS);
             if (__builtin_expect(!ok, 0)) return 0.0;
             tot = granule_sum1(x, lane);
             if (RELAY) {
@@ -792,7 +825,7 @@ __device__ __forceinline__ double exchange_sum(double s, gu64* gp, int G, int g,
                 else publish_pair<false, GRAN_L2_STRIDE>(gp3, 0, lane, epoch, tot);
             }
         } else {
-            ok = granule_gather1<2, GRAN_L2_STRIDE>(gp3, 2, epoch, lane, x STAMP_ARGS);
+            ok = granule_gather1<POLL_LEVEL2.depth, GRAN_L2_STRIDE>(gp3, 2, epoch, lane, x STAMP_ARGS);
             if (__builtin_expect(!ok, 0)) return 0.0;
             tot = granule_sum1(x, lane);   // the relayed double itself (+ zeros)
         }
@@ -815,7 +848,7 @@ __device__ __forceinline__ double exchange_sum(double s, gu64* gp, int G, int g,
 // (right behind the residual pass, ahead of its other work in front of the barrier).
 // `idle`: work of the leader placed between publishing the group total and the first poll.
 template <bool SINGLE = false, bool LANEWISE = false, int TEAMS = -1, int LOCAL = -1, int ROLE = -1,
-          bool PREWRITTEN = false, typename F = NoIdleWork>
+          bool PREWRITTEN = false, bool SPACED = true, typename F = NoIdleWork>
 __device__ __forceinline__ double group_allreduce(double s, double* red, gu64* gp, int G, int g,
                                                   int wave, int nw, int lane, unsigned epoch,
                                                   bool local, bool& ok STAMP_PARAMS, F idle = F()) {
@@ -833,7 +866,7 @@ __device__ __forceinline__ double group_allreduce(double s, double* red, gu64* g
     s = LANEWISE ? sum_wave_rows(red, lane) : sum_wave_slots(red, lane);
     GSTAMP(4);
     if constexpr (SINGLE) return s;
-    return exchange_sum<false, TEAMS, LOCAL>(s, gp, G, g, lane, epoch, local, ok STAMP_ARGS, idle);
+    return exchange_sum<false, TEAMS, LOCAL, SPACED>(s, gp, G, g, lane, epoch, local, ok STAMP_ARGS, idle);
 }
 
 // ---- several chains per pass (streaming / LDS residency) ---------------------------------

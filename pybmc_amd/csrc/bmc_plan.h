@@ -27,6 +27,45 @@ constexpr size_t LDS_LIMIT = 160 * 1024;
 constexpr int MAX_KCH = 4;        // K <= 256 columns (64 per lane-chunk)
 constexpr int MAX_GROUPS = 256;   // 8 teams of <= 32 groups (exchange_sum)
 
+// ---- poll schedule of the granule gather (bmc_loop.h: granule_gather1, exchange_sum) ---------
+// A group publishes its total and then polls with `depth` reads in flight.  Read d of the first
+// `depth` is issued poll_issue_state(s, d) wait states (s_nop; 4.3 shader cycles each on MI355X)
+// behind the publication; every later read is issued when its predecessor has been tested, so the
+// reads keep that distance for the whole spin.  One schedule per use, each chosen by a same-box
+// A/B of the product after the table of scripts/micro/pollsched.hip:
+//   POLL_LOCAL   first level, workgroup-scope store (the groups share an XCD), one chain per
+//                pass: the first read ~140 cycles behind the store (an earlier one is certain to
+//                miss: every group publishes at about the same time and the store needs longer
+//                to land), the second ~100 cycles behind the first, so that the pair samples L2
+//                every ~half load round trip (~260 cycles) instead of twice at the same instant
+//   POLL_AGENT   first level, agent-scope store, one chain per pass: reads that arrive while the
+//                write-through is under way delay it, so the first one waits ~280 cycles
+//   POLL_PLAIN   first level of the passes that serve 4 or 8 chains (their leaders share a CU)
+//                and of the simplex sampler: back to back, as before (the spaced pair was 1.9 %
+//                slower for 32 chains at C2 and no faster for the simplex sampler)
+//   POLL_LEVEL2  team totals and relay of chains over more than 32 groups: back to back, as
+//                before (no spaced or delayed schedule was faster in the micro benchmark)
+struct PollSched {
+    int depth, first, gap;
+};
+constexpr int poll_issue_state(PollSched s, int d) { return s.first + d * s.gap; }
+#ifndef BMC_POLL_DEPTH2
+#define BMC_POLL_DEPTH2 2
+#endif
+#ifndef BMC_POLL_FIRST_LOCAL
+#define BMC_POLL_FIRST_LOCAL 32
+#endif
+#ifndef BMC_POLL_GAP_LOCAL
+#define BMC_POLL_GAP_LOCAL 24
+#endif
+#ifndef BMC_POLL_FIRST_AGENT
+#define BMC_POLL_FIRST_AGENT 64
+#endif
+constexpr PollSched POLL_LOCAL{2, BMC_POLL_FIRST_LOCAL, BMC_POLL_GAP_LOCAL};
+constexpr PollSched POLL_AGENT{2, BMC_POLL_FIRST_AGENT, 0};
+constexpr PollSched POLL_PLAIN{2, 0, 0};
+constexpr PollSched POLL_LEVEL2{BMC_POLL_DEPTH2, 0, 0};
+
 // ---- capacity rules (host plan and kernel instantiations) ------------------------------------
 constexpr int reg_kmax(int k) { return k <= 8 ? 8 : k <= 16 ? 16 : k <= 32 ? 32 : k <= 64 ? 64 : 0; }
 

@@ -951,7 +951,9 @@ __global__ __launch_bounds__(512) void simplex_loop_kernel(SimplexArgs a) {
 #endif
             // (a chain in ONE workgroup has nothing to exchange: without SINGLE it published its
             // total and polled it back through L2 -- N = 629: 1.55 -> 1.32 us per step)
-            const double rss_prop = group_allreduce<SINGLE, (MODE == MODE_REG && VEC == 1)>(
+            // (SPACED = false: the spaced poll schedule of the Gibbs loop was no faster here, and
+            // 2 % slower on one of two boxes: same-box A/B at the C2 size)
+            const double rss_prop = group_allreduce<SINGLE, (MODE == MODE_REG && VEC == 1), -1, -1, -1, false, false>(
                 part, red, gr + (size_t)(nex & 1) * a.gran_stride, G, g, wave, nw, lane,
                 nex + 1 + a.epoch0, local, got STAMP_ARGS);
             ++nex;

@@ -83,6 +83,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--groups", type=int, default=0)
     ap.add_argument("--waves", type=int, default=0)
+    ap.add_argument("--agent", action="store_true", help="force agent-scope exchange stores")
     args = ap.parse_args()
     import ctypes
     _lib._share_hip_runtime_with_torch()
@@ -96,8 +97,8 @@ def main():
             c = _lib.Context(0, lib=lib)
             c.set_problem(y, X, dtype=dt)
             c.set_prior(*prior)
-            if args.groups or args.waves:
-                c.set_tuning(args.groups, args.waves)
+            if args.groups or args.waves or args.agent:
+                c.set_tuning(args.groups, args.waves, force_agent_scope=int(args.agent))
             if chains > 0:
                 c.gibbs_run(chains, max(50, iters // 20), seeds=np.arange(chains) + 1)   # warm
             ctxs.append((name, c))
