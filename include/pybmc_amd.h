@@ -446,6 +446,36 @@ int bmc_psis_loo_t_device(bmc_ctx* ctx, const void* dA, int64_t n_points, int32_
                           int64_t ldt, double nu, double* elpd_loo_out, double* pareto_k_out,
                           double* lppd_out);
 
+/* ---- the same with degrees of freedom of each draw's own (not in the reference) -----------------
+ * For a fit of bmc_robust_run_nu*: draw s is (beta_s, sigma_s, nu_s).  Everything as the _t entry
+ * points with nu_s in place of nu in ll[i][s].  The caller gives the distinct values nu_values
+ * [n_values] (HOST in all four forms) and nu_index [n_draws] (int32; host, or DEVICE in the _device
+ * forms): nu_s = nu_values[nu_index[s]].  The constant lgamma((nu + 1)/2) - lgamma(nu/2) -
+ * 1/2 log(nu pi) is computed once per table entry with the expression of the _t entry points, so a
+ * table of one value returns their bits.  BMC_EINVAL for n_values < 1, a table entry that is not
+ * positive and finite, or an index outside 0 .. n_values - 1: a host index is checked before any
+ * launch; a device index is clamped into range where it is read (nothing is read out of bounds)
+ * and reported after the run, whose outputs are then not valid.  The context stays usable. */
+int bmc_pointwise_loglik_tv(bmc_ctx* ctx, const double* A, int64_t n_points, int32_t k, int64_t lda,
+                            int layout, const double* y, const double* theta, int64_t n_draws,
+                            int64_t ldt, const double* nu_values, int32_t n_values,
+                            const int32_t* nu_index, double* lppd_out, double* pwaic_out,
+                            double* mean_ll_out);
+int bmc_pointwise_loglik_tv_device(bmc_ctx* ctx, const void* dA, int64_t n_points, int32_t k,
+                                   int64_t lda, int layout, const void* dy, const void* dtheta,
+                                   int64_t n_draws, int64_t ldt, const double* nu_values,
+                                   int32_t n_values, const void* d_nu_index, double* lppd_out,
+                                   double* pwaic_out, double* mean_ll_out);
+int bmc_psis_loo_tv(bmc_ctx* ctx, const double* A, int64_t n_points, int32_t k, int64_t lda,
+                    int layout, const double* y, const double* theta, int64_t n_draws, int64_t ldt,
+                    const double* nu_values, int32_t n_values, const int32_t* nu_index,
+                    double* elpd_loo_out, double* pareto_k_out, double* lppd_out);
+int bmc_psis_loo_tv_device(bmc_ctx* ctx, const void* dA, int64_t n_points, int32_t k, int64_t lda,
+                           int layout, const void* dy, const void* dtheta, int64_t n_draws,
+                           int64_t ldt, const double* nu_values, int32_t n_values,
+                           const void* d_nu_index, double* elpd_loo_out, double* pareto_k_out,
+                           double* lppd_out);
+
 /* ---- PSIS-LOO predictive moments: what the fit would have predicted for y_i without it -------
  * Arguments, weights, elpd_loo_out, pareto_k_out and lppd_out as bmc_psis_loo.  With W_s the
  * truncated (smoothed or raw) weight of draw s for point i, every draw of a run of equal ll[i][s]
@@ -638,6 +668,47 @@ int bmc_robust_run(bmc_ctx* ctx, double nu, int32_t n_chains, int64_t iters, int
 int bmc_robust_run_device(bmc_ctx* ctx, double nu, int32_t n_chains, int64_t iters, int64_t burn,
                           const uint64_t* seeds, void* d_samples_out, void* d_row_weight_out,
                           bmc_stats* stats);
+
+/* ---- The same sampler with the degrees of freedom estimated (not in the reference) ----
+ * nu takes one of n_grid <= 64 values nu_grid[0] < ... < nu_grid[n_grid-1] (positive, finite) with
+ * prior weights nu_weight[g] >= 0 (finite, at least one positive); it starts at nu_grid[nu_init], whose
+ * weight must be positive.  Sweep t is steps 1-4 of bmc_robust_run with the nu in force (g_{t,n} ~
+ * Gamma((nu + 1) / 2, 1) at that nu), then
+ *   5. T_t = sum_n (log lambda_n - lambda_n) over the weights just drawn (the summation order of
+ *      step 2's sum);
+ *   6. l_g = fma(h_g, T_t, c_g), h_g = nu_g / 2, c_g = n (h_g log h_g - lgamma(h_g)) + log w_g (host,
+ *      double; -inf where w_g = 0); m = max l_g; p_g = exp(l_g - m); P_0 = p_0, P_g = P_{g-1} + p_g
+ *      strictly left to right; the new index is the number of g < n_grid - 1 with P_g < u_t P_{G-1}.
+ *      A T_t that is not finite leaves the index where it was.
+ *   7. nu_idx_out[c][t - burn] = the new index, tstat_out[c][t - burn] = T_t (t >= burn).
+ * The state reported for sweep t is (beta_t, sigma_t, lambda_t, nu_t); nu_t shapes the weights of
+ * sweep t + 1.
+ * rng_mode BMC_RNG_DEVICE: as bmc_robust_run; u_t is the first uniform ((0, 1], 53 bits of words 0
+ *   and 1) of Philox counter (t lo, t hi, 0x4E554446, 0) under the chain's key (u_nu, nu_path NULL).
+ * rng_mode BMC_RNG_REPLAY: also u_nu [n_chains][burn+iters] and a FORCED path nu_path
+ *   [n_chains][burn+iters] of grid indices: nu_path[t] is the index in force after sweep t, so the
+ *   weights of sweep t are drawn at nu_grid[nu_path[t-1]] (nu_init for t = 0) and gl must hold gamma
+ *   variates of those shapes.  The index the kernel would have picked from u_t is still computed and
+ *   written to nu_idx_out; the chain continues on the forced path.
+ * nu_idx_out [n_chains][iters] (rows a stopped chain never reached hold -1); tstat_out
+ * [n_chains][iters] or NULL.  BMC_EINVAL (nothing is launched) for whatever bmc_robust_run refuses,
+ * n_grid outside 1 .. 64, a grid that is not strictly increasing, positive and finite, weights that
+ * are negative, not finite or all zero, nu_init out of range or of weight zero, a nu_path entry out of
+ * range.  Everything else -- statuses, stats, launches of at most 1024 chains, chain c bit for bit its
+ * one-chain call -- is as bmc_robust_run; a grid of one value gives the bits of bmc_robust_run at
+ * that nu.  bmc_robust_run_nu_device writes caller-owned DEVICE buffers (d_nu_idx_out int32;
+ * d_row_weight_out and d_tstat_out may be NULL). */
+int bmc_robust_run_nu(bmc_ctx* ctx, const double* nu_grid, const double* nu_weight, int32_t n_grid,
+                      int32_t nu_init, int32_t n_chains, int64_t iters, int64_t burn, int rng_mode,
+                      const uint64_t* seeds, const double* xi, const double* g, const double* gl,
+                      const double* u_nu, const int32_t* nu_path, double* samples_out,
+                      double* row_weight_out, int32_t* nu_idx_out, double* tstat_out,
+                      bmc_stats* stats);
+int bmc_robust_run_nu_device(bmc_ctx* ctx, const double* nu_grid, const double* nu_weight,
+                             int32_t n_grid, int32_t nu_init, int32_t n_chains, int64_t iters,
+                             int64_t burn, const uint64_t* seeds, void* d_samples_out,
+                             void* d_row_weight_out, void* d_nu_idx_out, void* d_tstat_out,
+                             bmc_stats* stats);
 
 /* ---- on-device variates (exposed so the generator itself can be tested) ----
  * normals_out [count_normal] ~ N(0,1); gammas_out [count_gamma] ~ Gamma(shape,1). */

@@ -120,6 +120,16 @@ PROTOTYPES = {
                                  C.c_int64, C.c_double, _D, _D, _D]),
     "bmc_psis_loo_t_device": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int, _P, _P,
                                         C.c_int64, C.c_int64, C.c_double, _D, _D, _D]),
+    "bmc_pointwise_loglik_tv": (C.c_int, [_P, _D, C.c_int64, C.c_int32, C.c_int64, C.c_int, _D, _D,
+                                          C.c_int64, C.c_int64, _D, C.c_int32, C.POINTER(C.c_int32),
+                                          _D, _D, _D]),
+    "bmc_pointwise_loglik_tv_device": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int, _P,
+                                                 _P, C.c_int64, C.c_int64, _D, C.c_int32, _P, _D, _D,
+                                                 _D]),
+    "bmc_psis_loo_tv": (C.c_int, [_P, _D, C.c_int64, C.c_int32, C.c_int64, C.c_int, _D, _D, C.c_int64,
+                                  C.c_int64, _D, C.c_int32, C.POINTER(C.c_int32), _D, _D, _D]),
+    "bmc_psis_loo_tv_device": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int, _P, _P,
+                                         C.c_int64, C.c_int64, _D, C.c_int32, _P, _D, _D, _D]),
     "bmc_psis_loo_predict": (C.c_int, [_P, _D, C.c_int64, C.c_int32, C.c_int64, C.c_int, _D, _D,
                                        C.c_int64, C.c_int64, _D, _D, _D, _D, _D, _D, _D]),
     "bmc_psis_loo_predict_device": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int, _P,
@@ -150,6 +160,13 @@ PROTOTYPES = {
                                  C.POINTER(C.c_uint64), _D, _D, _D, _D, _D, C.POINTER(Stats)]),
     "bmc_robust_run_device": (C.c_int, [_P, C.c_double, C.c_int32, C.c_int64, C.c_int64,
                                         C.POINTER(C.c_uint64), _P, _P, C.POINTER(Stats)]),
+    "bmc_robust_run_nu": (C.c_int, [_P, _D, _D, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
+                                    C.c_int, C.POINTER(C.c_uint64), _D, _D, _D, _D,
+                                    C.POINTER(C.c_int32), _D, _D, C.POINTER(C.c_int32), _D,
+                                    C.POINTER(Stats)]),
+    "bmc_robust_run_nu_device": (C.c_int, [_P, _D, _D, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
+                                           C.c_int64, C.POINTER(C.c_uint64), _P, _P, _P, _P,
+                                           C.POINTER(Stats)]),
     "bmc_rng_fill": (C.c_int, [_P, C.c_uint64, C.c_int64, _D, C.c_double, C.c_int64, _D]),
     "bmc_philox_raw": (C.c_int, [_P, C.c_uint64, C.c_uint32, C.c_int64, C.POINTER(C.c_uint32)]),
 }
@@ -448,14 +465,24 @@ class Context:
 
     # -- Student-t (outlier-robust) sampler ------------------------------------------------------
     def robust_run(self, nu, n_chains, iters, burn=0, seeds=None, xi=None, g=None, gl=None,
-                   want_weights=True):
+                   want_weights=True, nu_grid=None, nu_weight=None, nu_init=None, u_nu=None,
+                   nu_path=None, want_tstat=False):
         """``n_chains`` Student-t chains on the resident problem and prior (bmc_robust_run).
         Device mode: ``seeds`` (n_chains,).  Replay mode: ``xi`` (n_chains, burn+iters, k), ``g``
         (n_chains, burn+iters), ``gl`` (n_chains, burn+iters, n).  Returns (samples (n_chains,
-        iters, k+1), mean row weights (n_chains, n) or None, stats dict)."""
+        iters, k+1), mean row weights (n_chains, n) or None, stats dict).
+
+        With ``nu_grid`` (``nu`` is ignored) the degrees of freedom are drawn from the grid every
+        sweep (bmc_robust_run_nu): ``nu_weight`` the prior weights, ``nu_init`` the starting index;
+        replay mode also takes ``u_nu`` (n_chains, burn+iters) and the forced path ``nu_path``
+        (n_chains, burn+iters) of grid indices.  Returns (samples, weights or None, grid indices
+        (n_chains, iters) int32, T_t (n_chains, iters) or None, stats dict)."""
         n_chains, iters, burn = int(n_chains), int(iters), int(burn)
         if n_chains < 1 or iters < 0:
             raise ValueError("need n_chains >= 1 and iters >= 0")
+        if nu_grid is not None:
+            return self._robust_run_nu(nu_grid, nu_weight, nu_init, n_chains, iters, burn, seeds, xi, g,
+                                       gl, u_nu, nu_path, want_weights, want_tstat)
         out = np.empty((n_chains, iters, self.k + 1))
         w = np.empty((n_chains, self.n)) if want_weights else None
         st = Stats()
@@ -474,6 +501,53 @@ class Context:
                                           _dptr(out), _dptr(w), C.byref(st))
         self._check(rc)
         return out, w, st.as_dict()
+
+    def _robust_run_nu(self, nu_grid, nu_weight, nu_init, n_chains, iters, burn, seeds, xi, g, gl, u_nu,
+                       nu_path, want_weights, want_tstat):
+        grid = np.ascontiguousarray(nu_grid, dtype=np.float64).reshape(-1)
+        wt = np.ascontiguousarray(nu_weight, dtype=np.float64).reshape(-1)
+        if wt.shape != grid.shape:
+            raise ValueError("nu_weight must have one entry per grid value")
+        if nu_init is None:
+            raise ValueError("nu_init (an index of nu_grid) is required with nu_grid")
+        out = np.empty((n_chains, iters, self.k + 1))
+        w = np.empty((n_chains, self.n)) if want_weights else None
+        idx = np.empty((n_chains, iters), dtype=np.int32)
+        ts = np.empty((n_chains, iters)) if want_tstat else None
+        st = Stats()
+        i32p = C.POINTER(C.c_int32)
+        head = (self._h, _dptr(grid), _dptr(wt), grid.shape[0], int(nu_init), n_chains, iters, burn)
+        tail = (_dptr(out), _dptr(w), idx.ctypes.data_as(i32p), _dptr(ts), C.byref(st))
+        if xi is not None or g is not None or gl is not None:
+            tt = burn + iters
+            xi = np.ascontiguousarray(xi, dtype=np.float64).reshape(n_chains, tt, self.k)
+            g = np.ascontiguousarray(g, dtype=np.float64).reshape(n_chains, tt)
+            gl = np.ascontiguousarray(gl, dtype=np.float64).reshape(n_chains, tt, self.n)
+            u_nu = np.ascontiguousarray(u_nu, dtype=np.float64).reshape(n_chains, tt)
+            nu_path = np.ascontiguousarray(nu_path, dtype=np.int32).reshape(n_chains, tt)
+            rc = self._lib.bmc_robust_run_nu(*head, BMC_RNG_REPLAY, None, _dptr(xi), _dptr(g), _dptr(gl),
+                                             _dptr(u_nu), nu_path.ctypes.data_as(i32p), *tail)
+        else:
+            sd = np.ascontiguousarray(seeds, dtype=np.uint64).reshape(n_chains)
+            rc = self._lib.bmc_robust_run_nu(*head, BMC_RNG_DEVICE,
+                                             sd.ctypes.data_as(C.POINTER(C.c_uint64)), None, None, None,
+                                             None, None, *tail)
+        self._check(rc)
+        return out, w, idx, ts, st.as_dict()
+
+    def robust_run_nu_device(self, nu_grid, nu_weight, nu_init, n_chains, iters, burn, seeds, out_ptr,
+                             idx_ptr, weight_ptr=None, tstat_ptr=None):
+        grid = np.ascontiguousarray(nu_grid, dtype=np.float64).reshape(-1)
+        wt = np.ascontiguousarray(nu_weight, dtype=np.float64).reshape(-1)
+        if wt.shape != grid.shape:
+            raise ValueError("nu_weight must have one entry per grid value")
+        sd = np.ascontiguousarray(seeds, dtype=np.uint64).reshape(n_chains)
+        st = Stats()
+        self._check(self._lib.bmc_robust_run_nu_device(
+            self._h, _dptr(grid), _dptr(wt), grid.shape[0], int(nu_init), int(n_chains), int(iters),
+            int(burn), sd.ctypes.data_as(C.POINTER(C.c_uint64)), _P(out_ptr), _P(weight_ptr or 0),
+            _P(idx_ptr), _P(tstat_ptr or 0), C.byref(st)))
+        return st.as_dict()
 
     def robust_run_device(self, nu, n_chains, iters, burn, seeds, out_ptr, weight_ptr=None):
         sd = np.ascontiguousarray(seeds, dtype=np.uint64).reshape(n_chains)
@@ -746,6 +820,46 @@ class Context:
         """The same on DEVICE memory (bmc_psis_loo_t_device)."""
         return self._score_call(self._lib.bmc_psis_loo_t_device, self.LOO_KEYS, _P,
                                 dA, n, k, lda, layout, dy, dtheta, n_draws, ldt, nu)
+
+    def _score_call_tv(self, fn, keys, ptr, A, n, k, lda, layout, y, theta, n_draws, ldt, nu_values,
+                       nu_index):
+        """A _tv entry point: `nu_values` the distinct degrees of freedom (host), `nu_index` every
+        draw's index into them, a host int32 array (ptr is _dptr) or a device address (_P)."""
+        out = {key: np.empty(n) for key in keys}
+        vals = np.ascontiguousarray(nu_values, dtype=np.float64).reshape(-1)
+        if ptr is _dptr:
+            nu_index = np.ascontiguousarray(nu_index, dtype=np.int32).reshape(-1)
+            if nu_index.shape[0] != int(n_draws):
+                raise ValueError("nu_index must have one entry per draw")
+            idx = nu_index.ctypes.data_as(C.POINTER(C.c_int32))
+        else:
+            idx = _P(nu_index)
+        self._check(fn(self._h, ptr(A), int(n), int(k), int(lda), int(layout), ptr(y), ptr(theta),
+                       int(n_draws), int(ldt), _dptr(vals), vals.shape[0], idx,
+                       *(_dptr(out[key]) for key in keys)))
+        return out
+
+    def pointwise_loglik_tv(self, A, n, k, lda, layout, y, theta, n_draws, ldt, nu_values, nu_index):
+        """pointwise_loglik under the Student-t likelihood with nu_values[nu_index[s]] degrees of
+        freedom for draw s (bmc_pointwise_loglik_tv)."""
+        return self._score_call_tv(self._lib.bmc_pointwise_loglik_tv, self.SCORE_KEYS, _dptr, A, n, k,
+                                   lda, layout, y, theta, n_draws, ldt, nu_values, nu_index)
+
+    def pointwise_loglik_tv_device(self, dA, n, k, lda, layout, dy, dtheta, n_draws, ldt, nu_values,
+                                   d_nu_index):
+        """The same on DEVICE memory, the int32 index included (bmc_pointwise_loglik_tv_device)."""
+        return self._score_call_tv(self._lib.bmc_pointwise_loglik_tv_device, self.SCORE_KEYS, _P, dA, n,
+                                   k, lda, layout, dy, dtheta, n_draws, ldt, nu_values, d_nu_index)
+
+    def psis_loo_tv(self, A, n, k, lda, layout, y, theta, n_draws, ldt, nu_values, nu_index):
+        """psis_loo under the Student-t likelihood with a nu per draw (bmc_psis_loo_tv)."""
+        return self._score_call_tv(self._lib.bmc_psis_loo_tv, self.LOO_KEYS, _dptr, A, n, k, lda, layout,
+                                   y, theta, n_draws, ldt, nu_values, nu_index)
+
+    def psis_loo_tv_device(self, dA, n, k, lda, layout, dy, dtheta, n_draws, ldt, nu_values, d_nu_index):
+        """The same on DEVICE memory, the int32 index included (bmc_psis_loo_tv_device)."""
+        return self._score_call_tv(self._lib.bmc_psis_loo_tv_device, self.LOO_KEYS, _P, dA, n, k, lda,
+                                   layout, dy, dtheta, n_draws, ldt, nu_values, d_nu_index)
 
     def psis_loo_predict(self, A, n, k, lda, layout, y, theta, n_draws, ldt):
         """What psis_loo returns and the leave-one-out predictive loo_mean_i, loo_sd_i, loo_pit_i

@@ -51,6 +51,7 @@ class BayesianModelCombination:
         self._device_problem = None
         self._trained_with = None   # (sampler, [b0, C0, nu0, sigma20][, nu]) of the last train()
         self.row_weights = None     # (N,) mean latent weight per training row ("student_t" only)
+        self.nu_samples = None      # draws of nu, one per row of samples ("nu": "estimate" only)
 
     # ------------------------------------------------------------------ set-up
     def orthogonalize(self, property, train_df, components_kept, method="auto"):
@@ -116,7 +117,11 @@ class BayesianModelCombination:
         per chain only when the caller gives ``burn`` (default 0), ``devices`` other than this GPU a
         ``ValueError``; afterwards ``row_weights`` holds the mean latent weight of every training
         row, averaged over chains (far below 1: an outlier), and the predictive noise of
-        ``predict``, ``predict2`` and ``evaluate`` is ``sigma t_nu``.  Extra optional keys (defaults
+        ``predict``, ``predict2`` and ``evaluate`` is ``sigma t_nu``.  ``"nu": "estimate"`` (with the
+        optional ``nu_grid``, ``nu_prior``, ``nu_init`` of ``gibbs_sampler_robust``) draws ``nu`` from
+        a discrete prior in every sweep: ``nu_samples`` then holds its draws, pooled in chain order
+        like ``samples``, ``diagnostics()`` and ``summary()`` gain a row ``nu`` after ``sigma``, and
+        the predictive noise of draw s is ``sigma_s t_{nu_s}``.  Extra optional keys (defaults
         keep the reference behaviour):
         ``n_chains`` (pooled along the sample axis), ``seeds``, ``dtype`` (``"float32"`` stores
         U_hat and y in float32 on the device, sums stay float64 -- BASELINE configs[3]),
@@ -147,20 +152,28 @@ class BayesianModelCombination:
         self._trained_with = ("simplex" if sampler == "simplex" else "gibbs",
                               [b_mean_prior, b_mean_cov, nu0, sigma20])
         self.row_weights = None
+        self.nu_samples = None
         if sampler == "student_t":
             devices = opts.get("devices")
             if devices is not None and list(devices) != [self.device]:
                 raise ValueError('"devices" is for the Gibbs sampler: Student-t chains run on one '
                                  'GPU (use n_chains for several chains on this device)')
-            nu = float(opts.get("nu", 4.0))
+            nu = opts.get("nu", 4.0)
+            estimate = isinstance(nu, str)
+            nu = nu if estimate else float(nu)
             n_chains = int(opts.get("n_chains", 1))
             prior = [b_mean_prior, b_mean_cov, nu0, sigma20]
             self._trained_with = ("student_t", prior, nu)
             self._device_problem = None   # this path sets its own problem
-            res, w, stats = gibbs_sampler_robust(
+            extra = {key: opts.get(key) for key in ("nu_grid", "nu_prior", "nu_init") if key in opts}
+            got = gibbs_sampler_robust(
                 self.centered_experiment_train, self.U_hat, iterations, prior, nu,
                 burn=int(opts.get("burn", 0)), n_chains=n_chains, seeds=opts.get("seeds"),
-                device=self.device, return_row_weights=True, return_stats=True)
+                device=self.device, return_row_weights=True, return_stats=True,
+                return_nu=estimate, **extra)
+            res, w, stats = got[0], got[1], got[-1]
+            if estimate:
+                self.nu_samples = np.ascontiguousarray(got[2]).reshape(-1)   # pooled in chain order
             self.last_stats = stats
             self.samples = res if res.ndim == 2 else res.reshape(-1, res.shape[-1])
             self.row_weights = w if w.ndim == 1 else w.mean(axis=0)
@@ -224,8 +237,8 @@ class BayesianModelCombination:
         k1 = s.shape[-1]
         chains = int(self.n_chains or 1)
         s = s.reshape(chains, -1, k1)
-        d = _series_diagnostics(s, self.Vt_hat, burn, self.device)
-        index = [f"beta_{i}" for i in range(k1 - 1)] + ["sigma"] + list(self.models)
+        d = _series_diagnostics(s, self.Vt_hat, burn, self.device, **self._nu_series())
+        index = [f"beta_{i}" for i in range(k1 - 1)] + ["sigma"] + self._nu_row() + list(self.models)
         from .diagnostics import KEYS
         return pd.DataFrame({key: np.asarray(d[key]) for key in KEYS}, index=index)
 
@@ -239,9 +252,9 @@ class BayesianModelCombination:
             raise ValueError("Must call `orthogonalize()` and `train()` before computing a summary.")
         from .rankdiag import quantile_names, rank_diagnostics
         s = self._chains()
-        d = rank_diagnostics(_series_tensor(s, self.Vt_hat, self.device), burn=burn, probs=probs,
-                             device=self.device)
-        index = [f"beta_{i}" for i in range(s.shape[-1] - 1)] + ["sigma"] + list(self.models)
+        d = rank_diagnostics(_series_tensor(s, self.Vt_hat, self.device, **self._nu_series()), burn=burn,
+                             probs=probs, device=self.device)
+        index = [f"beta_{i}" for i in range(s.shape[-1] - 1)] + ["sigma"] + self._nu_row() + list(self.models)
         cols = {"mean": d["mean"], "sd": d["sd"]}
         for name, row in zip(quantile_names(probs), d["quantiles"]):
             cols[name] = row
@@ -258,9 +271,30 @@ class BayesianModelCombination:
             raise ValueError(f'{what} supports the Gaussian Gibbs sampler only (sampler == "student_t")')
 
     def _noise_df(self):
-        """Degrees of freedom of the predictive noise: None (normal) unless the fit was Student-t."""
+        """Degrees of freedom of the predictive noise: None (normal) unless the fit was Student-t;
+        the draws ``nu_samples`` (one per row of ``samples``) when ``nu`` was estimated."""
         tw = self._trained_with
-        return tw[2] if tw is not None and tw[0] == "student_t" else None
+        if tw is None or tw[0] != "student_t":
+            return None
+        return self.nu_samples if self._nu_estimated() else tw[2]
+
+    def _nu_estimated(self):
+        tw = self._trained_with
+        return (tw is not None and tw[0] == "student_t" and isinstance(tw[2], str)
+                and getattr(self, "nu_samples", None) is not None)
+
+    def _nu_chains(self):
+        """(n_chains, T) draws of nu of a fit that estimated it, else None."""
+        if not self._nu_estimated():
+            return None
+        return np.asarray(self.nu_samples, dtype=np.float64).reshape(int(self.n_chains or 1), -1)
+
+    def _nu_series(self):
+        """The extra keyword of the series helpers: the nu column of a fit that estimated it."""
+        return {"nu": self._nu_chains()} if self._nu_estimated() else {}
+
+    def _nu_row(self):
+        return ["nu"] if self._nu_estimated() else []
 
     # ----------------------------------------------------------------- scoring
     def _chains(self):
@@ -304,11 +338,15 @@ class BayesianModelCombination:
         the log predictive density of held-out data instead, built as ``log_predictive_density``
         builds it (``elpd``, ``se``, ``n_points``, ``lppd``; ``method`` is not used).  ``burn`` more
         draws are dropped from the start of each chain.  The result also carries ``likelihood``
-        (``"gaussian"`` or ``"student_t"``) and ``nu`` (None for the Gaussian one); the results of
+        (``"gaussian"`` or ``"student_t"``) and ``nu`` (None for the Gaussian one; after
+        ``"nu": "estimate"`` every draw is scored with its own ``nu``, ``nu`` is the mean over the
+        scored draws and ``nu_estimated`` is True); the results of
         two fits of the same data feed ``pybmc_amd.compare_elpd`` directly."""
         if method not in ("loo", "waic"):
             raise ValueError(f'method must be "loo" or "waic"; got {method!r}')
         nu = self._noise_df()
+        estimated = self._nu_estimated()
+        lik = {"nu_draws": self._nu_chains()} if estimated else {"nu": nu}
         from . import scoring
         if X is not None:
             if self.samples is None or self.Vt_hat is None:
@@ -322,7 +360,7 @@ class BayesianModelCombination:
             truth = np.asarray(X[self.truth_column_name].values, dtype=np.float64)
             A = preds @ np.asarray(self.Vt_hat, dtype=np.float64).T
             pw = scoring.pointwise_log_likelihood(A, truth - preds.mean(axis=1), self._chains(),
-                                                  burn=burn, device=self.device, nu=nu)
+                                                  burn=burn, device=self.device, **lik)
             out = scoring.elpd_summary(pw["lppd"])
             out["lppd"] = pw["lppd"]
         else:
@@ -330,9 +368,13 @@ class BayesianModelCombination:
                 raise ValueError("Must call `orthogonalize()` and `train()` before scoring.")
             fn = scoring.psis_loo if method == "loo" else scoring.waic
             out = fn(self.U_hat, np.asarray(self.centered_experiment_train, dtype=np.float64),
-                     self._chains(), burn=burn, device=self.device, nu=nu)
+                     self._chains(), burn=burn, device=self.device, **lik)
         out["likelihood"] = "gaussian" if nu is None else "student_t"
-        out["nu"] = nu
+        if estimated:    # the mean over the scored draws
+            out["nu"] = float(np.mean(lik["nu_draws"][:, int(burn):]))
+            out["nu_estimated"] = True
+        else:
+            out["nu"] = nu
         return out
 
     def loo_predict(self, burn=0):
@@ -626,21 +668,25 @@ class BayesianModelCombination:
                                    device=self.device, noise_df=self._noise_df())
 
 
-def _series_tensor(samples, Vt_hat, device):
+def _series_tensor(samples, Vt_hat, device, nu=None):
     """[beta, sigma, weights] per draw as one device tensor (C, T, k+1+K): ONE upload of the
-    (C, T, k+1) samples, the weights beta Vt_hat + 1/K formed next to them (torch matmul)."""
+    (C, T, k+1) samples, the weights beta Vt_hat + 1/K formed next to them (torch matmul).  With
+    ``nu`` (C, T) its column stands between sigma and the weights."""
     import torch
 
     dev = torch.device("cuda", device)
     s = torch.as_tensor(np.ascontiguousarray(samples, dtype=np.float64), device=dev)
     V = torch.as_tensor(np.ascontiguousarray(Vt_hat, dtype=np.float64), device=dev)
     w = torch.matmul(s[..., :-1], V) + 1.0 / V.shape[1]
+    if nu is not None:
+        col = torch.as_tensor(np.ascontiguousarray(nu, dtype=np.float64), device=dev)
+        return torch.cat([s, col.reshape(s.shape[0], s.shape[1], 1), w], dim=-1)
     return torch.cat([s, w], dim=-1)
 
 
-def _series_diagnostics(samples, Vt_hat, burn, device):
+def _series_diagnostics(samples, Vt_hat, burn, device, nu=None):
     """Diagnostics of [beta, sigma, weights] per draw: the ``chain_diagnostics`` kernels on the
     concatenated tensor of ``_series_tensor``."""
     from .diagnostics import chain_diagnostics
 
-    return chain_diagnostics(_series_tensor(samples, Vt_hat, device), burn=burn, device=device)
+    return chain_diagnostics(_series_tensor(samples, Vt_hat, device, nu), burn=burn, device=device)

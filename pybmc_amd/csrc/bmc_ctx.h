@@ -97,6 +97,7 @@ struct bmc_ctx : CtxHandles {
     double rank_ms[4] = {0, 0, 0, 0};      // last bmc_rank_diagnostics*: sort, rank, classic, moments
     // pointwise log-likelihood (bmc_pointwise_loglik*)
     DevBuf scA, scY, scTheta, scAp, scYp, scCh, scPart, scOut;
+    DevBuf scNu;   // the _tv entry points: the table of distinct nu, the staged index, the flag word
     // PSIS-LOO (bmc_psis_loo*, bmc_psis_loo_predict*): the select state and candidate slots,
     // besides the score buffers
     DevBuf looWork;
@@ -108,6 +109,7 @@ struct bmc_ctx : CtxHandles {
     // Student-t sampler (bmc_robust_run*): the packed operand, the prior, per-chain row state, the
     // replayed weights' variates, the mean weights
     DevBuf rbZ, rbPrior, rbWs, rbGl, rbWsum;
+    DevBuf rbNu;   // bmc_robust_run_nu*: the grid's table, T_t, the pick's uniforms, the indices, the path
     double sens_ms[4] = {0, 0, 0, 0};      // last bmc_power_sensitivity*: log densities, sorts, PSIS, CJS
     double predict_ms[4] = {0, 0, 0, 0};   // last bmc_predict: h2d, gemm, order statistics, device
     // pooling over GPUs (bmc_comm_*): RCCL communicator bound to this context's device

@@ -2,6 +2,7 @@
 // launch_gibbs / launch_simplex are chosen on the host (bmc_plan.h, gibbs_kernel_key); gibbs_kernel /
 // simplex_kernel below return the chosen instantiation for the residency and packing queries.
 #pragma once
+#include <cmath>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -323,7 +324,22 @@ struct ScoreArgs {
     int32_t k, col_major;
     double *Ap, *yp, *ch, *part, *out;
     double nu = 0.0;   // host-only: the likelihood (0: Gaussian; else positive and finite)
+    // host-only: n_nu > 0 selects the Student-t density with a nu per draw (TileDrawsTV; nu stays 0).
+    // All three are DEVICE pointers: nu_tab [2][n_nu] = cnu of every distinct value (student_t_cnu),
+    // then the values; nu_index [S] int32 into them (clamped into range in the kernel); nu_flag one
+    // int32 word the caller has zeroed, set to 1 when an index was out of range.
+    int32_t n_nu = 0;
+    const double* nu_tab = nullptr;
+    const int32_t* nu_index = nullptr;
+    int32_t* nu_flag = nullptr;
 };
+// lgamma((nu + 1)/2) - lgamma(nu/2) - 1/2 log(nu pi), the constant of the t_nu density, in long
+// double: the difference of the two lgamma loses digits as nu grows
+inline double student_t_cnu(double nu_) {
+    const long double nu = (long double)nu_;
+    return (double)(lgammal(0.5L * (nu + 1.0L)) - lgammal(0.5L * nu) -
+                    0.5L * logl(nu * 3.14159265358979323846264338327950288L));
+}
 struct ScoreBuffers {
     size_t Ap, yp, ch, part;   // bytes
 };

@@ -29,11 +29,20 @@ struct RobustArgs {
     double* samples;      // [C][iters][k + 1]
     double* wsum;         // [C][n]: mean of lambda_n over the kept sweeps
     int32_t* status;      // [C]: 1 = a Cholesky pivot was not positive and finite
+    // nu on a grid (launch_robust_nu only; the fixed-nu kernels read none of these)
+    const double* nu_tab; // [4][n_grid]: robust_nu_table
+    int32_t n_grid, nu_init;
+    const double* u_nu;   // replay mode: [C][burn + iters] uniforms of the pick; NULL in device RNG mode
+    const int32_t* nu_path;  // replay mode: [C][burn + iters] the index in force after each sweep
+    int32_t* nu_idx;      // [C][iters]: the index picked in each kept sweep
+    double* tstat;        // [C][iters]: T_t = sum_n (log lambda_n - lambda_n), or NULL
 };
 
 // panels (f64) -> Z, yv
 hipError_t launch_robust_pack(const Panels& P, double* Z, double* yv, hipStream_t s);
 // one workgroup per chain, a.n_chains <= ROBUST_MAX_CHAINS_PER_LAUNCH
 hipError_t launch_robust(const RobustArgs& a, hipStream_t s);
+// the same with nu drawn from its grid every sweep, 1 <= a.n_grid <= ROBUST_MAX_NU_GRID
+hipError_t launch_robust_nu(const RobustArgs& a, hipStream_t s);
 
 }  // namespace bmc

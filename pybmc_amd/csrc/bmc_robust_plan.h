@@ -86,4 +86,44 @@ inline std::string robust_check(int64_t n, int32_t k, int f32, double nu, int32_
     return "";
 }
 
+// ---- nu on a grid (bmc_robust_run_nu) --------------------------------------------------
+constexpr int ROBUST_MAX_NU_GRID = 64;              // one lane of wave 0 per grid value
+
+// "" when (grid, weight, nu_init) describe a valid discrete prior, else the reason
+inline std::string robust_nu_check(const double* grid, const double* weight, int32_t n_grid,
+                                   int32_t nu_init) {
+    if (n_grid < 1 || n_grid > ROBUST_MAX_NU_GRID)
+        return "the nu grid needs 1 <= n_grid <= " + std::to_string(ROBUST_MAX_NU_GRID) + " values; got " +
+               std::to_string(n_grid);
+    if (!grid || !weight) return "nu_grid and nu_weight must not be NULL";
+    bool any = false;
+    for (int32_t g = 0; g < n_grid; ++g) {
+        if (!(grid[g] > 0) || !std::isfinite(grid[g])) return "the nu grid must be positive and finite";
+        if (g > 0 && !(grid[g] > grid[g - 1])) return "the nu grid must be strictly increasing";
+        if (!(weight[g] >= 0) || !std::isfinite(weight[g]))
+            return "the nu prior weights must be non-negative and finite";
+        any = any || weight[g] > 0;
+    }
+    if (!any) return "at least one nu prior weight must be positive";
+    if (nu_init < 0 || nu_init >= n_grid) return "nu_init must index the nu grid";
+    if (!(weight[nu_init] > 0)) return "nu_init must have a positive prior weight";
+    return "";
+}
+
+// The four rows [4][n_grid] that the kernel keeps in LDS: nu_g, the shape (nu_g + 1) / 2 of the weight
+// variates, h_g = nu_g / 2 and c_g = n (h_g log h_g - lgamma(h_g)) + log w_g (-inf where w_g = 0).
+// log p(nu_g | lambda) = h_g T + c_g + const with T = sum_n (log lambda_n - lambda_n).
+inline void robust_nu_table(const double* grid, const double* weight, int32_t n_grid, int64_t n,
+                            double* table) {
+    for (int32_t g = 0; g < n_grid; ++g) {
+        const double nu = grid[g], h = nu / 2.0;
+        table[g] = nu;
+        table[n_grid + g] = (nu + 1.0) / 2.0;
+        table[2 * n_grid + g] = h;
+        table[3 * n_grid + g] = weight[g] > 0
+                                    ? (double)n * (h * std::log(h) - std::lgamma(h)) + std::log(weight[g])
+                                    : -HUGE_VAL;
+    }
+}
+
 }  // namespace bmc

@@ -155,4 +155,24 @@ struct TileDrawsT : TileDraws {
     }
 };
 
+// The Student-t view with degrees of freedom of each draw's own (a fit that estimated nu): ch =
+// [3][S] holds c_s and g_s = 1 / (nu_s sigma_s^2) as TileDrawsT reads them at nu = nu_s, and
+// hn_s = (nu_s + 1)/2 in its third row; no kernel scalar.  With one nu for all draws the three rows
+// and the arithmetic are TileDrawsT's.
+struct TileDrawsTV : TileDraws {
+    double hn[4];
+    __device__ __forceinline__ TileDrawsTV(const double* __restrict__ ch, int64_t S, int64_t s0, int cl)
+        : TileDraws(ch, S, s0, cl) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const int64_t sd = s0 + cl + 16 * t;
+            hn[t] = ch[2 * S + (sd < S ? sd : S - 1)];
+        }
+    }
+    __device__ __forceinline__ double ll(double y, double dot, int t) const {
+        const double res = y - dot;
+        return fma(-hn[t], log1p_nonneg((res * res) * hs[t]), cs[t]);
+    }
+};
+
 }  // namespace bmc

@@ -6,19 +6,47 @@
 
 namespace {
 
-int robust_common(bmc_ctx* c, double nu, int32_t n_chains, int64_t iters, int64_t burn, int rng_mode,
+// nu on a grid (bmc_robust_run_nu*): the prior, the replay inputs and the outputs.  Exactly one of
+// idx_host / idx_dev is set; tstat_host / tstat_dev may both be NULL.
+struct NuSpec {
+    const double* grid;
+    const double* weight;
+    int32_t n_grid, nu_init;
+    const double* u_nu;        // replay: [n_chains][burn + iters]
+    const int32_t* nu_path;    // replay: [n_chains][burn + iters]
+    int32_t* idx_host;
+    void* idx_dev;
+    double* tstat_host;
+    void* tstat_dev;
+};
+
+int robust_common(bmc_ctx* c, double nu, const NuSpec* ns, int32_t n_chains, int64_t iters, int64_t burn, int rng_mode,
                   const uint64_t* seeds, const double* xi, const double* g, const double* gl,
                   double* samples_host, void* samples_dev, double* weight_host, void* weight_dev,
                   bmc_stats* stats) {
     if (!c->have_problem || !c->have_prior)
         return fail(c, BMC_ESTATE, "bmc_set_problem and bmc_set_prior must be called first");
-    const std::string why = robust_check(c->n, c->k, c->f32, nu, n_chains, iters, burn);
-    if (!why.empty()) return fail(c, BMC_EINVAL, "bmc_robust_run: " + why);
+    const std::string name = ns ? "bmc_robust_run_nu: " : "bmc_robust_run: ";
+    std::string why = ns ? robust_nu_check(ns->grid, ns->weight, ns->n_grid, ns->nu_init) : "";
+    if (!why.empty()) return fail(c, BMC_EINVAL, name + why);
+    if (ns) nu = ns->grid[ns->nu_init];
+    why = robust_check(c->n, c->k, c->f32, nu, n_chains, iters, burn);
+    if (!why.empty()) return fail(c, BMC_EINVAL, name + why);
     if (rng_mode == BMC_RNG_DEVICE) {
         if (!seeds) return fail(c, BMC_EINVAL, "seeds required in device RNG mode");
         if (xi || g || gl) return fail(c, BMC_EINVAL, "xi/g/gl must be NULL in device RNG mode");
+        if (ns && (ns->u_nu || ns->nu_path))
+            return fail(c, BMC_EINVAL, "u_nu/nu_path must be NULL in device RNG mode");
     } else if (rng_mode == BMC_RNG_REPLAY) {
         if (!xi || !g || !gl) return fail(c, BMC_EINVAL, "xi, g and gl required in replay mode");
+        if (ns) {
+            if (!ns->u_nu || !ns->nu_path)
+                return fail(c, BMC_EINVAL, "u_nu and nu_path required in replay mode");
+            const size_t cells = (size_t)n_chains * (size_t)(burn + iters);
+            for (size_t i = 0; i < cells; ++i)
+                if (ns->nu_path[i] < 0 || ns->nu_path[i] >= ns->n_grid)
+                    return fail(c, BMC_EINVAL, name + "nu_path must index the nu grid");
+        }
     } else {
         return fail(c, BMC_EINVAL, "rng_mode must be 0 or 1");
     }
@@ -49,6 +77,31 @@ int robust_common(bmc_ctx* c, double nu, int32_t n_chains, int64_t iters, int64_
         d_samples = (double*)c->samples.p;
     }
     double* d_weight = weight_dev ? (double*)weight_dev : (double*)c->rbWsum.p;
+    // nu on a grid: [table 4 G f64][tstat C T f64][u C Tt f64][idx C T i32][path C Tt i32]
+    const bool replay_nu = ns && rng_mode == BMC_RNG_REPLAY;
+    double *d_tab = nullptr, *d_tstat = nullptr, *d_unu = nullptr;
+    int32_t *d_idx = nullptr, *d_path = nullptr;
+    if (ns) {
+        const size_t G = (size_t)ns->n_grid;
+        if ((rc = ensure(c, c->rbNu, (4 * G + C * T + C * Tt) * 8 + (C * T + C * Tt) * 4))) return rc;
+        d_tab = (double*)c->rbNu.p;
+        double* own_tstat = d_tab + 4 * G;
+        d_unu = own_tstat + C * T;
+        int32_t* own_idx = (int32_t*)(d_unu + C * Tt);
+        d_path = own_idx + C * T;
+        d_idx = ns->idx_dev ? (int32_t*)ns->idx_dev : own_idx;
+        d_tstat = ns->tstat_dev ? (double*)ns->tstat_dev : (ns->tstat_host ? own_tstat : nullptr);
+        std::vector<double> tab(4 * G);
+        robust_nu_table(ns->grid, ns->weight, ns->n_grid, c->n, tab.data());
+        // pageable source: the copy is staged before hipMemcpyAsync returns
+        HIPCHK(c, hipMemcpyAsync(d_tab, tab.data(), 4 * G * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (T > 0) HIPCHK(c, hipMemsetAsync(d_idx, 0xff, C * T * 4, c->stream));   // -1: never drawn
+        if (replay_nu && Tt > 0) {
+            HIPCHK(c, hipMemcpyAsync(d_unu, ns->u_nu, C * Tt * 8, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(d_path, ns->nu_path, C * Tt * 4, hipMemcpyHostToDevice, c->stream));
+        }
+    }
     double* dP = (double*)c->rbPrior.p;
     HIPCHK(c, hipMemsetAsync(c->status.p, 0, C * sizeof(int32_t), c->stream));
     HIPCHK(c, hipMemcpyAsync(dP, c->Pprec.data(), (size_t)K * K * 8, hipMemcpyHostToDevice, c->stream));
@@ -83,6 +136,9 @@ int robust_common(bmc_ctx* c, double nu, int32_t n_chains, int64_t iters, int64_
     a.Pb0 = dP + (size_t)K * K;
     a.nu = nu;
     a.shape_l = (nu + 1.0) / 2.0;
+    a.nu_tab = d_tab;
+    a.n_grid = ns ? ns->n_grid : 0;
+    a.nu_init = ns ? ns->nu_init : 0;
     a.nu0_s20 = c->nu0 * c->s20;
     a.sigma2_init = c->sigma2_init;
     a.iters = iters;
@@ -99,7 +155,11 @@ int robust_common(bmc_ctx* c, double nu, int32_t n_chains, int64_t iters, int64_
         a.samples = d_samples + c0 * T * (K + 1);
         a.wsum = d_weight + c0 * (size_t)N;
         a.status = (int32_t*)c->status.p + c0;
-        HIPCHK(c, launch_robust(a, c->stream));
+        a.u_nu = replay_nu ? d_unu + c0 * Tt : nullptr;
+        a.nu_path = replay_nu ? d_path + c0 * Tt : nullptr;
+        a.nu_idx = ns ? d_idx + c0 * T : nullptr;
+        a.tstat = d_tstat ? d_tstat + c0 * T : nullptr;
+        HIPCHK(c, ns ? launch_robust_nu(a, c->stream) : launch_robust(a, c->stream));
     }
     HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
     std::vector<int32_t> st(C, 0);
@@ -110,6 +170,11 @@ int robust_common(bmc_ctx* c, double nu, int32_t n_chains, int64_t iters, int64_
             return rc;
     if (weight_host)
         if ((rc = copy_to_host(c, weight_host, d_weight, C * (size_t)N * 8, C * (size_t)N * 8, 1))) return rc;
+    if (ns && iters > 0) {
+        if (ns->idx_host && (rc = copy_to_host(c, ns->idx_host, d_idx, C * T * 4, C * T * 4, 1))) return rc;
+        if (ns->tstat_host && (rc = copy_to_host(c, ns->tstat_host, d_tstat, C * T * 8, C * T * 8, 1)))
+            return rc;
+    }
     if (stats) {
         std::memset(stats, 0, sizeof(*stats));
         if ((rc = event_ms(c, 0, 1, &stats->rng_ms)) || (rc = event_ms(c, 1, 2, &stats->loop_ms)) ||
@@ -143,7 +208,7 @@ int bmc_robust_run(bmc_ctx* c, double nu, int32_t n_chains, int64_t iters, int64
     if (!c) return BMC_EINVAL;
     if (!samples_out && iters > 0) return fail(c, BMC_EINVAL, "samples_out must not be NULL");
     HIPCHK(c, hipSetDevice(c->device));
-    return robust_common(c, nu, n_chains, iters, burn, rng_mode, seeds, xi, g, gl, samples_out, nullptr,
+    return robust_common(c, nu, nullptr, n_chains, iters, burn, rng_mode, seeds, xi, g, gl, samples_out, nullptr,
                          row_weight_out, nullptr, stats);
 }
 
@@ -153,8 +218,37 @@ int bmc_robust_run_device(bmc_ctx* c, double nu, int32_t n_chains, int64_t iters
     if (!c) return BMC_EINVAL;
     if (!d_samples_out && iters > 0) return fail(c, BMC_EINVAL, "d_samples_out must not be NULL");
     HIPCHK(c, hipSetDevice(c->device));
-    return robust_common(c, nu, n_chains, iters, burn, BMC_RNG_DEVICE, seeds, nullptr, nullptr, nullptr,
+    return robust_common(c, nu, nullptr, n_chains, iters, burn, BMC_RNG_DEVICE, seeds, nullptr, nullptr, nullptr,
                          nullptr, d_samples_out, nullptr, d_row_weight_out, stats);
+}
+
+int bmc_robust_run_nu(bmc_ctx* c, const double* nu_grid, const double* nu_weight, int32_t n_grid,
+                      int32_t nu_init, int32_t n_chains, int64_t iters, int64_t burn, int rng_mode,
+                      const uint64_t* seeds, const double* xi, const double* g, const double* gl,
+                      const double* u_nu, const int32_t* nu_path, double* samples_out,
+                      double* row_weight_out, int32_t* nu_idx_out, double* tstat_out, bmc_stats* stats) {
+    if (!c) return BMC_EINVAL;
+    if ((!samples_out || !nu_idx_out) && iters > 0)
+        return fail(c, BMC_EINVAL, "samples_out and nu_idx_out must not be NULL");
+    HIPCHK(c, hipSetDevice(c->device));
+    const NuSpec ns{nu_grid, nu_weight, n_grid, nu_init, u_nu, nu_path, nu_idx_out, nullptr, tstat_out,
+                    nullptr};
+    return robust_common(c, 0.0, &ns, n_chains, iters, burn, rng_mode, seeds, xi, g, gl, samples_out,
+                         nullptr, row_weight_out, nullptr, stats);
+}
+
+int bmc_robust_run_nu_device(bmc_ctx* c, const double* nu_grid, const double* nu_weight, int32_t n_grid,
+                             int32_t nu_init, int32_t n_chains, int64_t iters, int64_t burn,
+                             const uint64_t* seeds, void* d_samples_out, void* d_row_weight_out,
+                             void* d_nu_idx_out, void* d_tstat_out, bmc_stats* stats) {
+    if (!c) return BMC_EINVAL;
+    if ((!d_samples_out || !d_nu_idx_out) && iters > 0)
+        return fail(c, BMC_EINVAL, "d_samples_out and d_nu_idx_out must not be NULL");
+    HIPCHK(c, hipSetDevice(c->device));
+    const NuSpec ns{nu_grid, nu_weight, n_grid, nu_init, nullptr, nullptr, nullptr, d_nu_idx_out, nullptr,
+                    d_tstat_out};
+    return robust_common(c, 0.0, &ns, n_chains, iters, burn, BMC_RNG_DEVICE, seeds, nullptr, nullptr,
+                         nullptr, nullptr, d_samples_out, nullptr, d_row_weight_out, stats);
 }
 
 }  // extern "C"

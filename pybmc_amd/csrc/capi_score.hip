@@ -13,6 +13,11 @@ struct ScoreIn {
     int64_t n, lda, S, ldt;
     int32_t k, layout;
     double nu = 0.0;   // the likelihood: 0 Gaussian, else Student-t with nu degrees of freedom
+    // the _tv entry points (Student-t, a nu per draw; nu stays 0): the distinct values (host) and
+    // every draw's index into them (int32; host or device, as A)
+    int32_t n_nu = 0;
+    const double* nu_values = nullptr;
+    const void* nu_index = nullptr;
 };
 
 int check_score_args(bmc_ctx* c, const void* A, int64_t n, int32_t k, int64_t lda, int layout,
@@ -49,6 +54,12 @@ int score_args(bmc_ctx* c, const ScorePlan& plan, const ScoreIn& in, ScoreArgs& 
     a.k = in.k;
     a.col_major = in.layout == BMC_COL_MAJOR;
     a.nu = in.nu;
+    if (in.n_nu > 0) {   // score_nu has laid scNu out: [2][n_nu] f64, [S] i32 staged index, the flag
+        a.n_nu = in.n_nu;
+        a.nu_tab = (const double*)c->scNu.p;
+        a.nu_index = (const int32_t*)in.nu_index;
+        a.nu_flag = (int32_t*)((char*)c->scNu.p + (size_t)in.n_nu * 16 + (size_t)in.S * 4);
+    }
     a.Ap = (double*)c->scAp.p;
     a.yp = (double*)c->scYp.p;
     a.ch = (double*)c->scCh.p;
@@ -67,6 +78,37 @@ int score_stage(bmc_ctx* c, ScoreIn& in) {
     HIPCHK(c, hipMemcpyAsync(c->scY.p, in.y, (size_t)in.n * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->scTheta.p, in.theta, tbytes, hipMemcpyHostToDevice, c->stream));
     in.A = c->scA.p, in.y = c->scY.p, in.theta = c->scTheta.p;
+    return BMC_OK;
+}
+
+// The _tv calls: the table of distinct nu with its constants and the zeroed flag word go to scNu; a
+// host index is checked here and staged (`in` then names the staged copy).  BMC_EINVAL for a table
+// entry that is not positive and finite, n_values < 1, a NULL pointer or a host index out of range.
+int score_nu(bmc_ctx* c, ScoreIn& in, bool on_host) {
+    if (in.n_nu < 1) return fail(c, BMC_EINVAL, "n_values must be >= 1");
+    if (!in.nu_values || !in.nu_index) return fail(c, BMC_EINVAL, "nu_values and nu_index must not be NULL");
+    const size_t V = (size_t)in.n_nu, S = (size_t)in.S;
+    std::vector<double> tab(2 * V);
+    for (size_t v = 0; v < V; ++v) {
+        const double nu = in.nu_values[v];
+        if (!(nu > 0.0 && nu < INFINITY)) return fail(c, BMC_EINVAL, "nu_values must be positive and finite");
+        tab[v] = student_t_cnu(nu);
+        tab[V + v] = nu;
+    }
+    if (on_host) {
+        const int32_t* idx = (const int32_t*)in.nu_index;
+        for (size_t s = 0; s < S; ++s)
+            if (idx[s] < 0 || idx[s] >= in.n_nu) return fail(c, BMC_EINVAL, "nu_index must index nu_values");
+    }
+    if (int rc = ensure(c, c->scNu, V * 16 + S * 4 + 4)) return rc;
+    char* base = (char*)c->scNu.p;
+    HIPCHK(c, hipMemcpyAsync(base, tab.data(), V * 16, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // tab is a local
+    HIPCHK(c, hipMemsetAsync(base + V * 16 + S * 4, 0, 4, c->stream));
+    if (on_host) {
+        HIPCHK(c, hipMemcpyAsync(base + V * 16, in.nu_index, S * 4, hipMemcpyHostToDevice, c->stream));
+        in.nu_index = base + V * 16;
+    }
     return BMC_OK;
 }
 
@@ -131,8 +173,14 @@ int score_entry(bmc_ctx* c, ScoreIn in, bool on_host, ScoreFamily family,
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     if (on_host && (rc = score_stage(c, in))) return rc;
+    const bool per_draw = in.nu_values || in.nu_index || in.n_nu != 0;
+    if (per_draw && (rc = score_nu(c, in, on_host))) return rc;
     const double* src[7] = {};
     if ((rc = family(c, in, src))) return rc;
+    int32_t flag = 0;
+    if (per_draw)
+        HIPCHK(c, hipMemcpyAsync(&flag, (char*)c->scNu.p + (size_t)in.n_nu * 16 + (size_t)in.S * 4, 4,
+                                 hipMemcpyDeviceToHost, c->stream));
     int f = 0;
     for (double* out : dst) {
         if (out)
@@ -140,6 +188,7 @@ int score_entry(bmc_ctx* c, ScoreIn in, bool on_host, ScoreFamily family,
         ++f;
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (flag) return fail(c, BMC_EINVAL, "nu_index must index nu_values (the results are not valid)");
     return BMC_OK;
 }
 
@@ -260,6 +309,42 @@ int bmc_psis_loo_t_device(bmc_ctx* c, const void* dA, int64_t n_points, int32_t 
                           double nu, double* elpd_loo_out, double* pareto_k_out, double* lppd_out) {
     return score_entry(c, {dA, dy, dtheta, n_points, lda, n_draws, ldt, k, layout, t_nu(nu)}, false,
                        loo_family, {elpd_loo_out, pareto_k_out, lppd_out});
+}
+
+int bmc_pointwise_loglik_tv(bmc_ctx* c, const double* A, int64_t n_points, int32_t k, int64_t lda,
+                            int layout, const double* y, const double* theta, int64_t n_draws,
+                            int64_t ldt, const double* nu_values, int32_t n_values,
+                            const int32_t* nu_index, double* lppd_out, double* pwaic_out,
+                            double* mean_ll_out) {
+    return score_entry(c, {A, y, theta, n_points, lda, n_draws, ldt, k, layout, 0.0, n_values, nu_values,
+                           nu_index}, true, pointwise_family, {lppd_out, pwaic_out, mean_ll_out});
+}
+
+int bmc_pointwise_loglik_tv_device(bmc_ctx* c, const void* dA, int64_t n_points, int32_t k, int64_t lda,
+                                   int layout, const void* dy, const void* dtheta, int64_t n_draws,
+                                   int64_t ldt, const double* nu_values, int32_t n_values,
+                                   const void* d_nu_index, double* lppd_out, double* pwaic_out,
+                                   double* mean_ll_out) {
+    return score_entry(c, {dA, dy, dtheta, n_points, lda, n_draws, ldt, k, layout, 0.0, n_values,
+                           nu_values, d_nu_index}, false, pointwise_family,
+                       {lppd_out, pwaic_out, mean_ll_out});
+}
+
+int bmc_psis_loo_tv(bmc_ctx* c, const double* A, int64_t n_points, int32_t k, int64_t lda, int layout,
+                    const double* y, const double* theta, int64_t n_draws, int64_t ldt,
+                    const double* nu_values, int32_t n_values, const int32_t* nu_index,
+                    double* elpd_loo_out, double* pareto_k_out, double* lppd_out) {
+    return score_entry(c, {A, y, theta, n_points, lda, n_draws, ldt, k, layout, 0.0, n_values, nu_values,
+                           nu_index}, true, loo_family, {elpd_loo_out, pareto_k_out, lppd_out});
+}
+
+int bmc_psis_loo_tv_device(bmc_ctx* c, const void* dA, int64_t n_points, int32_t k, int64_t lda,
+                           int layout, const void* dy, const void* dtheta, int64_t n_draws, int64_t ldt,
+                           const double* nu_values, int32_t n_values, const void* d_nu_index,
+                           double* elpd_loo_out, double* pareto_k_out, double* lppd_out) {
+    return score_entry(c, {dA, dy, dtheta, n_points, lda, n_draws, ldt, k, layout, 0.0, n_values,
+                           nu_values, d_nu_index}, false, loo_family,
+                       {elpd_loo_out, pareto_k_out, lppd_out});
 }
 
 int bmc_psis_loo_predict(bmc_ctx* c, const double* A, int64_t n_points, int32_t k, int64_t lda,

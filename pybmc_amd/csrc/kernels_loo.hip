@@ -33,7 +33,8 @@
 //
 // The likelihood enters through the draws type alone (bmc_score_tile.h): the passes that compute ll
 // (range, select, the non-PREDICT append) are templates <D, L...> on it, TileDraws for the Gaussian
-// density and TileDrawsT with its scalar for the Student-t one (ScoreArgs::nu > 0); init, scan and
+// density, TileDrawsT with its scalar for the Student-t one (ScoreArgs::nu > 0) and TileDrawsTV for
+// the Student-t one with a nu per draw (ScoreArgs::n_nu > 0); init, scan and
 // fit see values of ll only.  The PREDICT variants and loo_bucket are Gaussian only.
 #include "bmc_dev.h"
 #include "bmc_launch.h"
@@ -799,7 +800,7 @@ hipError_t launch_loo_passes(const LooArgs& a, const LooPlan& p, const LooPredic
     const ScorePlan& sp = p.score;
     if (!p.ok || !a.work || sa.S - p.tail < 1 || p.cap < 2 * (p.tail + 1) || p.cap > LOO_MAX_CAP ||
         (p.cap & (p.cap - 1)) != 0 || p.tail != loo_tail(sa.S) || sa.n > 0x7fffffffll ||
-        (pp && sa.nu != 0.0))
+        (pp && (sa.nu != 0.0 || sa.n_nu != 0)))
         return hipErrorInvalidValue;   // (the fit's grid is one workgroup per point)
     hipError_t e = launch_score(sa, sp, s);   // (checks the shapes and the split plan)
     if (e != hipSuccess) return e;
@@ -824,25 +825,29 @@ hipError_t launch_loo_passes(const LooArgs& a, const LooPlan& p, const LooPredic
     pa.point_tiles = (uint32_t)sp.point_tiles;
 
     // a pass over the matrix under the call's likelihood (launch_score has checked sa.nu)
-    const bool student = sa.nu > 0.0;
+    const bool student = sa.nu > 0.0, per_draw = sa.n_nu > 0;
     const double hn = 0.5 * (sa.nu + 1.0);
-    auto pass = [&](auto gauss, auto student_t, size_t lds, auto... args) {
-        if (student) hipLaunchKernelGGL(student_t, dim3(groups), dim3(256), lds, s, pa, args..., hn);
+    auto pass = [&](auto gauss, auto student_t, auto student_tv, size_t lds, auto... args) {
+        if (per_draw) hipLaunchKernelGGL(student_tv, dim3(groups), dim3(256), lds, s, pa, args...);
+        else if (student) hipLaunchKernelGGL(student_t, dim3(groups), dim3(256), lds, s, pa, args..., hn);
         else hipLaunchKernelGGL(gauss, dim3(groups), dim3(256), lds, s, pa, args...);
     };
 
     if ((e = hipMemsetAsync(w.hist, 0, lb.hist, s)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(w.count, 0, lb.count, s)) != hipSuccess) return e;
-    pass(loo_range_kernel<TileDraws>, loo_range_kernel<TileDrawsT, double>, 0, w.range);
+    pass(loo_range_kernel<TileDraws>, loo_range_kernel<TileDrawsT, double>, loo_range_kernel<TileDrawsTV>, 0,
+         w.range);
     hipLaunchKernelGGL(loo_init_kernel, dim3(pblocks), dim3(256), 0, s, (const uint64_t*)w.range,
                        n_pad, sp.splits, sa.S, M, cap, w.prefix, w.kmin, w.meta);
     if (p.select_passes > 0) {
-        e = hipFuncSetAttribute(student ? (const void*)loo_select_kernel<TileDrawsT, double>
-                                        : (const void*)loo_select_kernel<TileDraws>,
+        e = hipFuncSetAttribute(per_draw  ? (const void*)loo_select_kernel<TileDrawsTV>
+                                : student ? (const void*)loo_select_kernel<TileDrawsT, double>
+                                          : (const void*)loo_select_kernel<TileDraws>,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)LOO_SELECT_LDS);
         if (e != hipSuccess) return e;
         for (int sel = 0; sel < p.select_passes; ++sel) {
-            pass(loo_select_kernel<TileDraws>, loo_select_kernel<TileDrawsT, double>, LOO_SELECT_LDS,
+            pass(loo_select_kernel<TileDraws>, loo_select_kernel<TileDrawsT, double>,
+                 loo_select_kernel<TileDrawsTV>, LOO_SELECT_LDS,
                  (const uint64_t*)w.prefix, (const uint4*)w.meta, w.hist);
             hipLaunchKernelGGL(loo_scan_kernel, dim3(pblocks), dim3(256), 0, s, n_pad, M, cap,
                                w.prefix, w.meta, w.hist);
@@ -878,7 +883,8 @@ hipError_t launch_loo_passes(const LooArgs& a, const LooPlan& p, const LooPredic
                            M, cap, pw.out, fp);
         return hipGetLastError();
     }
-    pass(loo_append_kernel<false, TileDraws>, loo_append_kernel<false, TileDrawsT, double>, 0,
+    pass(loo_append_kernel<false, TileDraws>, loo_append_kernel<false, TileDrawsT, double>,
+         loo_append_kernel<false, TileDrawsTV>, 0,
          (const uint64_t*)w.prefix, (const uint64_t*)w.kmin, (const uint4*)w.meta, (uint32_t)cap,
          w.count, w.cand, w.body, (uint32_t*)nullptr, (double*)nullptr);
     const size_t fit_lds = (size_t)cap * 8;

@@ -23,6 +23,12 @@
 //   L  lambda_n = g_{t,n} / ((nu + r_n^2 / sigma2) / 2), added to the row's running sum when the
 //      sweep is kept.  g_{t,n}: Marsaglia-Tsang at shape (nu + 1) / 2 on the STREAM_ROBUST counters
 //      (n, t lo, STREAM_ROBUST, ((t >> 32) << 8) | attempt), or the caller's array (replay).
+//   N  (robust_chain_kernel<KC, true> only: nu on a grid, bmc_robust_run_nu)  phase L also sums
+//      log lambda_n - lambda_n in the order of S; after the sweep's last barrier wave 0, lane g = grid
+//      value g, forms l_g = fma(nu_g / 2, T, c_g), p_g = exp(l_g - max l), the running sums P_g strictly
+//      left to right (one v_readlane per grid value) and picks #{g < G - 1 : P_g < u P_{G-1}}, u from
+//      Philox counter (t lo, t hi, STREAM_NU, 0) or the caller's array.  The index lives in LDS; phase L
+//      of the next sweep reads nu and (nu + 1) / 2 from the grid's LDS table, three barriers later.
 // Every sum's order is fixed by (N, k): a chain's bits do not depend on its index, its launch, its
 // neighbours or the device.
 #include "bmc_dev.h"
@@ -50,7 +56,25 @@ __global__ __launch_bounds__(256) void robust_pack_kernel(const double* __restri
     }
 }
 
-template <int KC>
+// a wave-uniform double held in scalar registers
+__device__ __forceinline__ double uniform_f64(double v) {
+    const int lo = __builtin_amdgcn_readfirstlane(__double2loint(v));
+    const int hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
+    return __hiloint2double(hi, lo);
+}
+
+// max over the 64 lanes, the same bits in every lane (a maximum has no order to fix)
+__device__ __forceinline__ double wave_max(double v) {   // the data movement of wave_sum
+    v = fmax(v, dpp_mov_f64<0xB1>(v));
+    v = fmax(v, dpp_mov_f64<0x4E>(v));
+    v = fmax(v, dpp_mov_f64<0x141>(v));
+    v = fmax(v, dpp_mov_f64<0x140>(v));
+    return fmax(fmax(readlane_f64(v, 0), readlane_f64(v, 16)), fmax(readlane_f64(v, 32), readlane_f64(v, 48)));
+}
+
+// NU_FREE = false: nu is a.nu in every sweep.  NU_FREE = true: nu is a value of the grid a.nu_tab,
+// drawn anew at the end of every sweep (steps 5 and 6 of bmc_robust_run_nu).
+template <int KC, bool NU_FREE>
 __global__ __launch_bounds__(ROBUST_THREADS) void robust_chain_kernel(const RobustArgs a) {
     constexpr int NT = KC > 16 ? 2 : 1, NP = NT * (NT + 1) / 2, LDZ = 16 * NT, LDL = KC + 1;
     __shared__ double s_part[ROBUST_WAVES][NP][256];
@@ -59,6 +83,10 @@ __global__ __launch_bounds__(ROBUST_THREADS) void robust_chain_kernel(const Robu
     __shared__ double s_rhs[KC], s_w[KC], s_beta[KC];
     __shared__ double s_wsum[ROBUST_WAVES];
     __shared__ int s_fail;
+    // NU_FREE only: the grid's four rows, the waves' partials of T_t, the grid index in force
+    __shared__ double s_nu[NU_FREE ? 4 * ROBUST_MAX_NU_GRID : 1];
+    __shared__ double s_tsum[NU_FREE ? ROBUST_WAVES : 1];
+    __shared__ int s_idx;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, kq = lane >> 4, cl = lane & 15;
     const int64_t c = blockIdx.x, N = a.n, Tt = a.burn + a.iters;
@@ -88,6 +116,10 @@ __global__ __launch_bounds__(ROBUST_THREADS) void robust_chain_kernel(const Robu
         wsum[row] = 0.0;
     }
     if (tid == 0) s_fail = 0;
+    if constexpr (NU_FREE) {
+        if (tid < 4 * a.n_grid) s_nu[tid] = a.nu_tab[tid];
+        if (tid == 0) s_idx = a.nu_init;
+    }
     double sigma2 = a.sigma2_init;
     int64_t t_fail = -1;
     __syncthreads();
@@ -233,16 +265,70 @@ __global__ __launch_bounds__(ROBUST_THREADS) void robust_chain_kernel(const Robu
             if (keep && tid == 0) orow[k] = sqrt(sigma2);
         }
         // ---- L: the rows' weights ---------------------------------------------------------------------
+        double nu_t = a.nu, shape_t = a.shape_l;
+        if constexpr (NU_FREE) {
+            const int gi = s_idx;                    // written after the previous sweep's last barrier
+            nu_t = uniform_f64(s_nu[gi]);
+            shape_t = uniform_f64(s_nu[a.n_grid + gi]);
+        }
+        double tl = 0.0;
         for (int64_t r = slab0 + lane; r < slab1; r += 64) {
             const double res = ws[2 * r];
             const double g = gl ? gl[(size_t)t * N + r]
-                                : gamma_mt_at<STREAM_ROBUST>(a.shape_l, (uint32_t)r, (uint32_t)t,
+                                : gamma_mt_at<STREAM_ROBUST>(shape_t, (uint32_t)r, (uint32_t)t,
                                                              (uint32_t)((uint64_t)t >> 32) << 8, k0, k1);
-            const double lam = g / ((a.nu + res * res / sigma2) * 0.5);
+            const double lam = g / ((nu_t + res * res / sigma2) * 0.5);
             ws[2 * r + 1] = lam;
             if (keep) wsum[r] += lam;
+            if constexpr (NU_FREE) tl += log(lam) - lam;
+        }
+        if constexpr (NU_FREE) {
+            tl = wave_sum(tl);
+            if (lane == 0) s_tsum[wave] = tl;
         }
         __syncthreads();
+        // ---- N: nu | lambda, an exact draw from the grid (wave 0; the others go on to phase G) ---------
+        if constexpr (NU_FREE) {
+            if (wave == 0) {
+                const int G = a.n_grid, cur = s_idx;
+                const double T = ((s_tsum[0] + s_tsum[1]) + s_tsum[2]) + s_tsum[3];
+                int pick = cur;
+                if (__builtin_isfinite(T)) {
+                    const bool on = lane < G;
+                    const int gi = on ? lane : G - 1;
+                    const double l = on ? fma(s_nu[2 * G + gi], T, s_nu[3 * G + gi]) : -__builtin_huge_val();
+                    const double m = wave_max(l);
+                    const double p = on ? exp(l - m) : 0.0;
+                    // P_g = P_{g-1} + p_g, strictly in grid order.  Eight steps at a time, so that the
+                    // readlanes run ahead of the chain of additions; lanes past G hold p = 0, which
+                    // leaves the running sum as it is.
+                    double run = 0.0, P = 0.0;
+                    for (int g0 = 0; g0 < G; g0 += 8) {
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) {
+                            run = run + readlane_f64(p, g0 + j);
+                            if (lane == g0 + j) P = run;
+                        }
+                    }
+                    double u;
+                    if (a.u_nu) {
+                        u = a.u_nu[(size_t)c * Tt + t];
+                    } else {
+                        const u32x4 w = philox4x32_10(
+                            u32x4{(uint32_t)t, (uint32_t)((uint64_t)t >> 32), STREAM_NU, 0u}, k0, k1);
+                        u = u53_open0(w.x, w.y);
+                    }
+                    pick = __builtin_popcountll(__ballot(lane < G - 1 && P < u * run));
+                }
+                if (lane == 0) {
+                    if (keep) {
+                        a.nu_idx[(size_t)c * a.iters + (t - a.burn)] = pick;
+                        if (a.tstat) a.tstat[(size_t)c * a.iters + (t - a.burn)] = T;
+                    }
+                    s_idx = a.nu_path ? a.nu_path[(size_t)c * Tt + t] : pick;
+                }
+            }
+        }
     }
 
     // mean weight over the kept sweeps; a stopped chain leaves NaN from the failing sweep on
@@ -256,9 +342,9 @@ __global__ __launch_bounds__(ROBUST_THREADS) void robust_chain_kernel(const Robu
     }
 }
 
-template <int KC>
+template <int KC, bool NU_FREE>
 hipError_t launch_kc(const RobustArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL((robust_chain_kernel<KC>), dim3((unsigned)a.n_chains), dim3(ROBUST_THREADS), 0, s, a);
+    hipLaunchKernelGGL((robust_chain_kernel<KC, NU_FREE>), dim3((unsigned)a.n_chains), dim3(ROBUST_THREADS), 0, s, a);
     return hipGetLastError();
 }
 
@@ -278,10 +364,23 @@ hipError_t launch_robust(const RobustArgs& a, hipStream_t s) {
     if (a.n_chains < 1 || a.n_chains > ROBUST_MAX_CHAINS_PER_LAUNCH || a.k < 1 || a.k > ROBUST_MAX_K)
         return hipErrorInvalidValue;
     switch (robust_kc(a.k)) {
-        case 4: return launch_kc<4>(a, s);
-        case 8: return launch_kc<8>(a, s);
-        case 16: return launch_kc<16>(a, s);
-        default: return launch_kc<32>(a, s);
+        case 4: return launch_kc<4, false>(a, s);
+        case 8: return launch_kc<8, false>(a, s);
+        case 16: return launch_kc<16, false>(a, s);
+        default: return launch_kc<32, false>(a, s);
+    }
+}
+
+hipError_t launch_robust_nu(const RobustArgs& a, hipStream_t s) {
+    if (a.n_chains < 1 || a.n_chains > ROBUST_MAX_CHAINS_PER_LAUNCH || a.k < 1 || a.k > ROBUST_MAX_K ||
+        a.n_grid < 1 || a.n_grid > ROBUST_MAX_NU_GRID || a.nu_init < 0 || a.nu_init >= a.n_grid ||
+        !a.nu_tab || !a.nu_idx)
+        return hipErrorInvalidValue;
+    switch (robust_kc(a.k)) {
+        case 4: return launch_kc<4, true>(a, s);
+        case 8: return launch_kc<8, true>(a, s);
+        case 16: return launch_kc<16, true>(a, s);
+        default: return launch_kc<32, true>(a, s);
     }
 }
 

@@ -6,7 +6,8 @@
 //   score_pad      A (either layout, any lda) and y -> whole 64-point tiles and 16-column slabs,
 //                  zero in the padding
 //   score_consts   per draw: c_s = -1/2 log(2 pi) - log sigma_s,  h_s = 1 / (2 sigma_s^2)
-//                  (score_consts_t: the constants of the Student-t density, ScoreArgs::nu > 0)
+//                  (score_consts_t: the constants of the Student-t density, ScoreArgs::nu > 0;
+//                  score_consts_tv: the same at a nu per draw, ScoreArgs::n_nu > 0)
 //   score_tile     workgroup = 64 points x the draw tiles of one split.  a_i . beta_s on
 //                  v_mfma_f64_16x16x4_f64 (the tile loop of bmc_score_tile.h, shared with
 //                  kernels_loo.hip); the tile is reduced in the epilogue
@@ -85,6 +86,29 @@ __global__ __launch_bounds__(256) void score_consts_t_kernel(const double* __res
     const double sg = theta[s * ldt + k];
     ch[s] = cnu - log(sg);
     ch[S + s] = 1.0 / (nu * sg * sg);
+}
+
+// the constants of TileDrawsTV: those of score_consts_t_kernel at the draw's own nu, gathered from the
+// table of distinct values; an index out of range is clamped and reported through flag
+__global__ __launch_bounds__(256) void score_consts_tv_kernel(const double* __restrict__ theta,
+                                                              int64_t S, int64_t ldt, int32_t k,
+                                                              const double* __restrict__ tab,
+                                                              int32_t n_nu,
+                                                              const int32_t* __restrict__ index,
+                                                              int32_t* __restrict__ flag,
+                                                              double* __restrict__ ch) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= S) return;
+    int32_t iv = index[s];
+    if (iv < 0 || iv >= n_nu) {
+        *flag = 1;
+        iv = iv < 0 ? 0 : n_nu - 1;
+    }
+    const double cnu = tab[iv], nu = tab[n_nu + iv];
+    const double sg = theta[s * ldt + k];
+    ch[s] = cnu - log(sg);
+    ch[S + s] = 1.0 / (nu * sg * sg);
+    ch[2 * S + s] = 0.5 * (nu + 1.0);
 }
 
 // The running state of one point in one lane; the count is the lane's (the same for its 4 points).
@@ -226,7 +250,7 @@ ScoreBuffers score_buffers(const ScorePlan& p, int64_t n_draws) {
     ScoreBuffers b;
     b.Ap = n_pad * (size_t)p.k_pad * 8;
     b.yp = n_pad * 8;
-    b.ch = (size_t)n_draws * 2 * 8;
+    b.ch = (size_t)n_draws * 3 * 8;   // (the third row: TileDrawsTV only)
     b.part = (size_t)p.splits * n_pad * 5 * 8;
     return b;
 }
@@ -234,6 +258,7 @@ ScoreBuffers score_buffers(const ScorePlan& p, int64_t n_draws) {
 hipError_t launch_score(const ScoreArgs& a, const ScorePlan& p, hipStream_t s) {
     if (a.n < 1 || a.S < 2 || a.k < 1 || a.k > SCORE_MAX_K || a.ldt < a.k + 1 ||
         a.lda < (a.col_major ? a.n : (int64_t)a.k) || !(a.nu >= 0.0 && a.nu < __builtin_inf()) ||
+        a.n_nu < 0 || (a.n_nu > 0 && (a.nu != 0.0 || !a.nu_tab || !a.nu_index || !a.nu_flag)) ||
         p.k_pad < a.k || p.k_pad % SC_KT != 0 ||
         p.point_tiles != (a.n + SC_TM - 1) / SC_TM || p.draw_tiles != (a.S + SC_TM - 1) / SC_TM ||
         p.splits < 1 || p.tiles_per_split < 1 || p.splits * p.tiles_per_split < p.draw_tiles ||
@@ -251,19 +276,23 @@ hipError_t launch_score(const ScoreArgs& a, const ScorePlan& p, hipStream_t s) {
     {
         const int64_t blocks = (a.S + 255) / 256;
         if (blocks > 0x7fffffffll) return hipErrorInvalidValue;
-        if (a.nu > 0.0) {
-            // in long double: the difference of the two lgamma loses digits as nu grows
-            const long double nu = (long double)a.nu;
-            const long double cnu = lgammal(0.5L * (nu + 1.0L)) - lgammal(0.5L * nu) -
-                                    0.5L * logl(nu * 3.14159265358979323846264338327950288L);
+        if (a.n_nu > 0) {
+            hipLaunchKernelGGL(score_consts_tv_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a.theta,
+                               a.S, a.ldt, a.k, a.nu_tab, a.n_nu, a.nu_index, a.nu_flag, a.ch);
+        } else if (a.nu > 0.0) {
             hipLaunchKernelGGL(score_consts_t_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a.theta,
-                               a.S, a.ldt, a.k, (double)cnu, a.nu, a.ch);
+                               a.S, a.ldt, a.k, student_t_cnu(a.nu), a.nu, a.ch);
         } else {
             hipLaunchKernelGGL(score_consts_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a.theta,
                                a.S, a.ldt, a.k, a.ch);
         }
     }
-    if (a.nu > 0.0)
+    if (a.n_nu > 0)
+        hipLaunchKernelGGL(score_tile_kernel<TileDrawsTV>, dim3((unsigned)groups), dim3(256), 0, s,
+                           (const double*)a.Ap, (const double*)a.yp, a.theta, (const double*)a.ch, a.S,
+                           a.ldt, a.k, p.k_pad, (uint32_t)p.point_tiles, p.tiles_per_split,
+                           p.draw_tiles, n_pad, a.part);
+    else if (a.nu > 0.0)
         hipLaunchKernelGGL((score_tile_kernel<TileDrawsT, double>), dim3((unsigned)groups), dim3(256), 0,
                            s, (const double*)a.Ap, (const double*)a.yp, a.theta, (const double*)a.ch,
                            a.S, a.ldt, a.k, p.k_pad, (uint32_t)p.point_tiles, p.tiles_per_split,

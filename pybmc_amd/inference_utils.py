@@ -59,10 +59,44 @@ def gibbs_sampler(y, X, iterations, prior_info, *, n_chains=1, seeds=None, devic
 
 
 ROBUST_MAX_K = 32   # bmc_robust_plan.h
+ROBUST_MAX_NU_GRID = 64   # bmc_robust_plan.h
+
+
+def robust_nu_prior(nu_grid=None, nu_prior=None, nu_init=None):
+    """The discrete prior of ``gibbs_sampler_robust(nu="estimate")``: (grid, weights, start index).
+    Defaults: ``numpy.geomspace(1, 100, 64)``; the Gamma(shape 2, rate 0.1) density at the grid
+    times ``nu_g`` (the quadrature weight of a geometric grid); the grid value nearest 4 among
+    those of positive weight.  ``nu_init`` is a value of the grid.  ``ValueError`` for what
+    bmc_robust_run_nu refuses."""
+    grid = np.geomspace(1.0, 100.0, 64) if nu_grid is None else np.array(nu_grid, dtype=np.float64).reshape(-1)
+    if not 1 <= grid.shape[0] <= ROBUST_MAX_NU_GRID:
+        raise ValueError(f"nu_grid needs between 1 and {ROBUST_MAX_NU_GRID} values; got {grid.shape[0]}")
+    if not (np.all(np.isfinite(grid)) and np.all(grid > 0) and np.all(np.diff(grid) > 0)):
+        raise ValueError("nu_grid must be positive, finite and strictly increasing")
+    if nu_prior is None:
+        weight = grid * (grid * np.exp(-0.1 * grid))
+    else:
+        weight = np.array(nu_prior, dtype=np.float64).reshape(-1)
+        if weight.shape != grid.shape:
+            raise ValueError("nu_prior must have one weight per value of nu_grid")
+    if not (np.all(np.isfinite(weight)) and np.all(weight >= 0) and np.any(weight > 0)):
+        raise ValueError("nu_prior must be non-negative and finite with at least one positive weight")
+    if nu_init is None:
+        ok = np.flatnonzero(weight > 0)
+        init = int(ok[np.argmin(np.abs(grid[ok] - 4.0))])
+    else:
+        hit = np.flatnonzero(grid == float(nu_init))
+        if hit.shape[0] != 1:
+            raise ValueError("nu_init must be a value of nu_grid")
+        init = int(hit[0])
+        if not weight[init] > 0:
+            raise ValueError("nu_init must have a positive prior weight")
+    return grid, weight, init
 
 
 def gibbs_sampler_robust(y, X, iterations, prior_info, nu=4.0, *, burn=0, n_chains=1, seeds=None,
-                         device=0, return_row_weights=False, return_stats=False):
+                         device=0, return_row_weights=False, return_stats=False, nu_grid=None,
+                         nu_prior=None, nu_init=None, return_nu=False):
     """Outlier-robust Gibbs sampling on the GPU (not in the reference): ``gibbs_sampler``'s model
     and priors with a Student-t likelihood ``y_n ~ t_nu(x_n . beta, sigma^2)``, written as a scale
     mixture of normals with one latent weight ``lambda_n ~ Gamma(nu/2, rate nu/2)`` per row.
@@ -76,10 +110,26 @@ def gibbs_sampler_robust(y, X, iterations, prior_info, nu=4.0, *, burn=0, n_chai
     Philox keys; chain c is bit for bit the one-chain run with ``seeds[c]``.  At most 32 columns,
     float64 storage.  ``ValueError`` for ``nu <= 0``, ``burn < 0``, ``n_chains < 1``, a wrong number of
     seeds or more than 32 columns; ``numpy.linalg.LinAlgError`` where ``gibbs_sampler`` raises it, and
-    when a chain's conditional precision stops being positive definite."""
-    nu = float(nu)
-    if not nu > 0 or not np.isfinite(nu):
-        raise ValueError("nu must be positive and finite")
+    when a chain's conditional precision stops being positive definite.
+
+    ``nu="estimate"`` gives the degrees of freedom a discrete prior and draws them in every sweep
+    (an exact categorical draw given the row weights): ``nu_grid`` at most 64 increasing values
+    (default ``numpy.geomspace(1, 100, 64)``), ``nu_prior`` their weights (default the Gamma(2, 0.1)
+    density times ``nu_g``), ``nu_init`` the starting value (a grid value; default the one nearest
+    4).  With ``return_nu`` the draws of ``nu`` -- values, ``(iterations,)`` or ``(n_chains,
+    iterations)`` -- follow the row weights in the returned tuple.  A number for ``nu`` keeps it
+    fixed; the grid arguments and ``return_nu`` are then refused."""
+    estimate = isinstance(nu, str)
+    if estimate:
+        if nu != "estimate":
+            raise ValueError('nu must be a positive number or "estimate"')
+        grid, weight, init = robust_nu_prior(nu_grid, nu_prior, nu_init)
+    else:
+        if nu_grid is not None or nu_prior is not None or nu_init is not None or return_nu:
+            raise ValueError('nu_grid, nu_prior, nu_init and return_nu need nu="estimate"')
+        nu = float(nu)
+        if not nu > 0 or not np.isfinite(nu):
+            raise ValueError("nu must be positive and finite")
     if burn < 0:
         raise ValueError("Burn-in iterations must be non-negative.")
     n_chains = int(n_chains)
@@ -104,11 +154,19 @@ def gibbs_sampler_robust(y, X, iterations, prior_info, nu=4.0, *, burn=0, n_chai
         ctx.set_prior(b0, C0, nu0, s20)
         if seeds is None:
             seeds = _draw_seeds(n_chains)
-        out, w, stats = ctx.robust_run(nu, n_chains, int(iterations), int(burn), seeds=seeds,
-                                       want_weights=return_row_weights)
+        if estimate:
+            out, w, idx, _, stats = ctx.robust_run(None, n_chains, int(iterations), int(burn), seeds=seeds,
+                                                   want_weights=return_row_weights, nu_grid=grid,
+                                                   nu_weight=weight, nu_init=init)
+        else:
+            out, w, stats = ctx.robust_run(nu, n_chains, int(iterations), int(burn), seeds=seeds,
+                                           want_weights=return_row_weights)
     res = [out[0] if n_chains == 1 else out]
     if return_row_weights:
         res.append(w[0] if n_chains == 1 else w)
+    if return_nu:
+        nus = grid[idx]
+        res.append(nus[0] if n_chains == 1 else nus)
     if return_stats:
         res.append(stats)
     return res[0] if len(res) == 1 else tuple(res)

@@ -8,13 +8,27 @@ from . import _lib
 N_PREDICTIVE_DRAWS = 10000  # reference sampling_utils.py:57
 
 
+def _choose(rng, samples, noise_df):
+    """The 10000 rows of ``samples`` the generator picks (``choice`` picks rows by count alone), and
+    the degrees of freedom of their noise: ``noise_df`` itself, or, when it is one value per row of
+    ``samples`` (a fit with nu estimated), the chosen rows' values as a (10000, 1) column."""
+    if noise_df is None or np.ndim(noise_df) == 0:
+        return rng.choice(samples, N_PREDICTIVE_DRAWS, replace=False), noise_df     # :57
+    df = np.asarray(noise_df, dtype=np.float64).reshape(-1)
+    if df.shape[0] != samples.shape[0]:
+        raise ValueError("noise_df must be a number or one value per row of samples")
+    both = rng.choice(np.column_stack([samples, df]), N_PREDICTIVE_DRAWS, replace=False)
+    return np.ascontiguousarray(both[:, :-1]), both[:, -1:]
+
+
 def _t_noise(rng, noise_df, n_points):
     """Student-t predictive noise for the replay ``noise=`` argument of ``Context.predict``, drawn on
     the host from the generator that made the ``choice``, right after it.  This path is
     host-bound: 80 kB of variates per point are generated and uploaded (on-device t noise in the
     predictive kernels is a follow-up)."""
-    noise_df = float(noise_df)
-    if not noise_df > 0:
+    if np.ndim(noise_df) == 0:
+        noise_df = float(noise_df)
+    if not np.all(np.asarray(noise_df) > 0):
         raise ValueError("noise_df must be positive")
     return rng.standard_t(noise_df, (N_PREDICTIVE_DRAWS, n_points))
 
@@ -33,7 +47,9 @@ def rndm_m_random_calculator(filtered_model_predictions, samples, Vt_hat, *, see
     ``sigma_s * t_nu`` instead of ``sigma_s * z``, with
     ``Generator(PCG64(seed)).standard_t(noise_df, (10000, n_points))`` taken from the generator
     that made the ``choice``, right after it, and replayed through the predictive kernels.  That
-    path is host-bound (80 kB of variates per point).
+    path is host-bound (80 kB of variates per point).  ``noise_df`` may also hold one value per row
+    of ``samples`` (a fit with nu estimated): the rows are then chosen from ``samples`` with that
+    column appended, and draw s gets ``t`` noise of its own degrees of freedom.
     """
     preds = np.ascontiguousarray(filtered_model_predictions, dtype=np.float64)
     samples = np.ascontiguousarray(samples, dtype=np.float64)
@@ -45,7 +61,7 @@ def rndm_m_random_calculator(filtered_model_predictions, samples, Vt_hat, *, see
             np.random.randint(0, 2 ** 32, dtype=np.uint64))
     ctx = _lib.default_context(device)
     rng = np.random.Generator(np.random.PCG64(seed))
-    theta = rng.choice(samples, N_PREDICTIVE_DRAWS, replace=False)     # :57
+    theta, noise_df = _choose(rng, samples, noise_df)
     noise = None if noise_df is None else _t_noise(rng, noise_df, preds.shape[0])
     with ctx.lock:
         rndm_m, bands, _ = ctx.predict(preds, theta, Vt_hat, seed=seed, noise=noise)
@@ -66,7 +82,7 @@ def predictive_coverage(percentiles, filtered_model_predictions, samples, Vt_hat
         seed = int(np.random.randint(0, 2 ** 32, dtype=np.uint64)) << 32 | int(
             np.random.randint(0, 2 ** 32, dtype=np.uint64))
     rng = np.random.Generator(np.random.PCG64(seed))
-    theta = rng.choice(samples, N_PREDICTIVE_DRAWS, replace=False)
+    theta, noise_df = _choose(rng, samples, noise_df)
     noise = None if noise_df is None else _t_noise(rng, noise_df, preds.shape[0])
     ctx = _lib.default_context(device)
     with ctx.lock:

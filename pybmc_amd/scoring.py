@@ -27,7 +27,9 @@ With ``nu=`` the same estimators score a Student-t fit (``gibbs_sampler_robust``
 
 the marginal t density, the latent row weights integrated out: what leave-one-out needs, since the
 ``(beta, sigma)`` rows that sampler returns are draws from that marginal posterior.  Everything
-downstream of ``ll`` is unchanged.  ``compare_elpd`` puts the scores of several fits of the same
+downstream of ``ll`` is unchanged.  With ``nu_draws=`` (a fit that estimated ``nu``:
+``gibbs_sampler_robust(nu="estimate")``) draw s has its own ``nu_s`` in place of ``nu``.
+``compare_elpd`` puts the scores of several fits of the same
 data side by side with the paired standard error of their differences.
 
 S. Watanabe, "Asymptotic equivalence of Bayes cross validation and widely applicable information
@@ -243,14 +245,50 @@ def _check_nu(nu):
     return nu
 
 
-def _likelihood_call(name, nu):
-    """(host method, device method, trailing scalars) of a scoring call under the likelihood."""
+MAX_NU_VALUES = 4096
+
+
+def _nu_table(nu_draws, samples, burn, thin):
+    """(distinct values, int32 index per pooled kept draw) of ``nu_draws``, shaped like the leading
+    dimensions of ``samples`` and burnt, thinned and pooled like them; ValueError otherwise (no GPU
+    needed)."""
+    if _is_torch(nu_draws):
+        nu_draws = nu_draws.detach().cpu().numpy()
+    nd = np.asarray(nu_draws, dtype=np.float64)
+    lead = tuple(samples.shape)[:-1]
+    if len(lead) not in (1, 2) or nd.shape != lead:
+        raise ValueError(f"nu_draws must be shaped like the leading dimensions of samples {lead}; "
+                         f"got {nd.shape}")
+    burn = _check_int("burn", burn, 0)
+    thin = _check_int("thin", thin, 1)
+    nd = (nd if nd.ndim == 2 else nd[None])[:, burn::thin].reshape(-1)
+    if not (np.all(np.isfinite(nd)) and np.all(nd > 0)):
+        raise ValueError("nu_draws must be positive and finite")
+    values, index = np.unique(nd, return_inverse=True)
+    if values.shape[0] > MAX_NU_VALUES:
+        raise ValueError(f"nu_draws holds {values.shape[0]} distinct values; at most {MAX_NU_VALUES}")
+    return values, np.ascontiguousarray(index.reshape(-1), dtype=np.int32)
+
+
+def _likelihood_call(name, nu, nu_draws=None, samples=None, burn=0, thin=1):
+    """(host method, device method, trailing scalars, what must stay alive during the call) of a
+    scoring call under the likelihood."""
+    if nu_draws is not None:
+        if nu is not None:
+            raise ValueError("give nu (one value for all draws) or nu_draws (one per draw), not both")
+        values, index = _nu_table(nu_draws, samples, burn, thin)
+        if _is_torch(samples) and samples.is_cuda:
+            import torch
+            held = torch.as_tensor(index, device=samples.device)
+            return name + "_tv", name + "_tv_device", (values, held.data_ptr()), held
+        return name + "_tv", name + "_tv_device", (values, index), index
+    nu = _check_nu(nu)
     if nu is None:
-        return name, name + "_device", ()
-    return name + "_t", name + "_t_device", (nu,)
+        return name, name + "_device", (), None
+    return name + "_t", name + "_t_device", (nu,), None
 
 
-def pointwise_log_likelihood(A, y, samples, burn=0, thin=1, device=0, nu=None):
+def pointwise_log_likelihood(A, y, samples, burn=0, thin=1, device=0, nu=None, nu_draws=None):
     """``lppd_i``, ``p_waic_i`` and ``mean_ll_i`` of every row of ``A`` (module docstring).
 
     ``A`` is ``(n_points, k)`` float64 (either memory order: ``U_hat`` is Fortran-ordered), ``y``
@@ -259,9 +297,14 @@ def pointwise_log_likelihood(A, y, samples, burn=0, thin=1, device=0, nu=None):
     (read in place; ``device`` is then the tensor's).  The first ``burn`` draws of every chain are
     dropped, every ``thin``-th of the rest kept, and the chains pooled.  Returns a dict of
     ``[n_points]`` arrays ``lppd``, ``p_waic``, ``mean_ll``.  ``nu=None`` is the Gaussian
-    likelihood; a positive finite number the Student-t one with that many degrees of freedom."""
-    host, dev, scalars = _likelihood_call("pointwise_loglik", _check_nu(nu))
-    return _pointwise_call(host, dev, A, y, samples, burn, thin, device, scalars=scalars)
+    likelihood; a positive finite number the Student-t one with that many degrees of freedom.
+    ``nu_draws`` (instead of ``nu``) is the Student-t likelihood with a ``nu`` per draw, for a fit
+    that estimated it: an array shaped like the leading dimensions of ``samples`` (``(T,)`` or
+    ``(C, T)``), burnt, thinned and pooled like them; at most 4096 distinct values."""
+    host, dev, scalars, held = _likelihood_call("pointwise_loglik", nu, nu_draws, samples, burn, thin)
+    out = _pointwise_call(host, dev, A, y, samples, burn, thin, device, scalars=scalars)
+    del held
+    return out
 
 
 def _se(v):
@@ -286,11 +329,12 @@ def elpd_summary(lppd):
     return {"elpd": float(np.sum(lppd)), "se": _se(lppd), "n_points": int(lppd.shape[0])}
 
 
-def waic(A, y, samples, burn=0, thin=1, device=0, nu=None):
+def waic(A, y, samples, burn=0, thin=1, device=0, nu=None, nu_draws=None):
     """WAIC of a fit on its training data: ``elpd_waic``, ``p_waic``, ``waic``, ``se``,
     ``n_high_p``, ``n_points`` and the pointwise ``lppd``, ``p_waic_i``, ``mean_ll``,
     ``elpd_waic_i``.  Arguments as ``pointwise_log_likelihood``."""
-    pw = pointwise_log_likelihood(A, y, samples, burn=burn, thin=thin, device=device, nu=nu)
+    pw = pointwise_log_likelihood(A, y, samples, burn=burn, thin=thin, device=device, nu=nu,
+                                  nu_draws=nu_draws)
     out = waic_summary(pw["lppd"], pw["p_waic"])
     out.update(lppd=pw["lppd"], p_waic_i=pw["p_waic"], mean_ll=pw["mean_ll"],
                elpd_waic_i=pw["lppd"] - pw["p_waic"])
@@ -311,15 +355,16 @@ def loo_summary(elpd_loo_i, lppd, pareto_k, n_draws):
             "n_draws": int(n_draws)}
 
 
-def psis_loo(A, y, samples, burn=0, thin=1, device=0, nu=None):
+def psis_loo(A, y, samples, burn=0, thin=1, device=0, nu=None, nu_draws=None):
     """PSIS-LOO of a fit on its training data (module docstring): ``elpd_loo``, ``p_loo``,
     ``looic``, ``se``, ``n_high_k``, ``k_threshold``, ``n_above_threshold``, ``n_points``,
     ``n_draws`` and the pointwise ``elpd_loo_i``, ``p_loo_i``, ``pareto_k``, ``lppd``.  Arguments
-    as ``pointwise_log_likelihood``, ``nu`` included.  The relative efficiency r_eff of the draws is taken as 1, as
+    as ``pointwise_log_likelihood``, ``nu`` and ``nu_draws`` included.  The relative efficiency r_eff of the draws is taken as 1, as
     ``loo::psis`` does when none is given.  ``pareto_k`` is ``+inf`` where nothing was smoothed
     (fewer than 25 draws, a tail of equal values, a non-finite fit)."""
-    host, dev, scalars = _likelihood_call("psis_loo", _check_nu(nu))
+    host, dev, scalars, held = _likelihood_call("psis_loo", nu, nu_draws, samples, burn, thin)
     pw = _pointwise_call(host, dev, A, y, samples, burn, thin, device, scalars=scalars)
+    del held
     sh = tuple(samples.shape)
     C, T = (1, sh[0]) if len(sh) == 2 else sh[:2]
     out = loo_summary(pw["elpd_loo"], pw["lppd"], pw["pareto_k"], C * kept_draws(T, burn, thin))
