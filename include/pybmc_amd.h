@@ -321,6 +321,31 @@ int bmc_chain_diagnostics_device(bmc_ctx* ctx, const void* d_samples, int32_t n_
                                  double* mean_out, double* sd_out, double* rhat_out,
                                  double* ess_out, double* mcse_out, int64_t* max_lag_out);
 
+/* The raw quantities the diagnostics are built from, e.g. for autocorrelation plots: the
+ * per-sequence moments and ONE block of autocovariance lags, straight from the kernels.  samples,
+ * n_chains, iters, n_cols, ld and burn are those of bmc_chain_diagnostics.  Sequence 2c + h is
+ * half h of chain c; when T' is odd, sequences 2 n_chains + c are the chains' middle draws, so
+ * n_seq = 2 n_chains + (T' odd ? n_chains : 0).  Outputs (HOST; any may be NULL):
+ *   seq_mean_out [n_seq][n_cols]   mean of x - shift over the sequence
+ *   seq_m2_out   [n_seq][n_cols]   sum of (x - mean)^2 over the sequence (0 for a middle draw)
+ *   shift_out    [n_cols]          the column's first kept draw of chain 0
+ *   acov_out     [n_active][n_lags]  a(t) = mean over the 2 n_chains halves of
+ *                (1/n) sum_{i < n - t} (x_i - mean)(x_{i+t} - mean), t = t0 .. t0 + n_lags - 1, for
+ *                column cols[a]; a lag t >= n is 0, so t0 + n_lags may exceed n
+ * cols is HOST [n_active], each in [0, n_cols) (repeats allowed); NULL means all columns, and
+ * n_active must then be n_cols.  A non-finite value makes the column's affected outputs
+ * non-finite and touches no other column.  BMC_EINVAL wherever bmc_chain_diagnostics returns it,
+ * for a column index out of range, n_active < 1 or > 65536, t0 < 0 or > 2^40, n_lags < 1 or
+ * > 2^20.  Results are deterministic and do not depend on the order of cols. */
+int bmc_chain_autocov(bmc_ctx* ctx, const double* samples, int32_t n_chains, int64_t iters,
+                      int32_t n_cols, int64_t ld, int64_t burn, const int32_t* cols,
+                      int32_t n_active, int64_t t0, int64_t n_lags, double* seq_mean_out,
+                      double* seq_m2_out, double* shift_out, double* acov_out);
+int bmc_chain_autocov_device(bmc_ctx* ctx, const void* d_samples, int32_t n_chains, int64_t iters,
+                             int32_t n_cols, int64_t ld, int64_t burn, const int32_t* cols,
+                             int32_t n_active, int64_t t0, int64_t n_lags, double* seq_mean_out,
+                             double* seq_m2_out, double* shift_out, double* acov_out);
+
 /* ---- rank-normalised diagnostics and quantiles (a capability the reference lacks) -------------
  * The rank-normalised, folded split R-hat, the bulk and tail ESS of the same paper (Stan's and
  * ArviZ's defaults) and interpolated quantiles; the estimator is written out in INTEGRATION.md

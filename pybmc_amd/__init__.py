@@ -6,7 +6,7 @@ nonexistent ``Model`` of its ``__all__`` is dropped.
 from .bmc import BayesianModelCombination
 from .cv import cv_component_path, fold_labels, kfold_cv, path_summary
 from .data import Dataset
-from .diagnostics import chain_diagnostics
+from .diagnostics import chain_autocovariance, chain_diagnostics
 from .inference_utils import (gibbs_sampler, gibbs_sampler_robust, gibbs_sampler_simplex,
                               USVt_hat_extraction)
 from .ppc import PPC_STATS, posterior_predictive_check, ppc_summary
@@ -24,6 +24,7 @@ __all__ = [
     "USVt_hat_extraction",
     "coverage",
     "rndm_m_random_calculator",
+    "chain_autocovariance",
     "chain_diagnostics",
     "rank_diagnostics",
     "rank_normalize",

@@ -94,6 +94,12 @@ PROTOTYPES = {
     "bmc_chain_diagnostics_device": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int64,
                                                C.c_int64, _D, _D, _D, _D, _D,
                                                C.POINTER(C.c_int64)]),
+    "bmc_chain_autocov": (C.c_int, [_P, _D, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_int64,
+                                    C.POINTER(C.c_int32), C.c_int32, C.c_int64, C.c_int64, _D, _D, _D,
+                                    _D]),
+    "bmc_chain_autocov_device": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int64,
+                                           C.c_int64, C.POINTER(C.c_int32), C.c_int32, C.c_int64,
+                                           C.c_int64, _D, _D, _D, _D]),
     "bmc_rank_diagnostics": (C.c_int, [_P, _D, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_int64,
                                        _D, C.c_int32, C.c_int32, _D, _D, _D, _D, _D, _D, _D]),
     "bmc_rank_diagnostics_device": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int64,
@@ -709,6 +715,35 @@ class Context:
         stream: the caller orders its producer before the call."""
         return self._diag_call(self._lib.bmc_chain_diagnostics_device, _P(d_ptr), n_chains, iters,
                                n_cols, ld, burn)
+
+    def _autocov_call(self, fn, ptr, n_chains, iters, n_cols, ld, burn, cols, first_lag, n_lags):
+        n_seq = 2 * n_chains + (n_chains if (iters - burn) % 2 else 0)
+        if cols is None:
+            n_active, cp = n_cols, None
+        else:
+            cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
+            n_active, cp = len(cols), cols.ctypes.data_as(C.POINTER(C.c_int32))
+        out = {"seq_mean": np.empty((n_seq, n_cols)), "seq_m2": np.empty((n_seq, n_cols)),
+               "shift": np.empty(n_cols), "acov": np.empty((max(n_active, 0), max(int(n_lags), 0)))}
+        self._check(fn(self._h, ptr, int(n_chains), int(iters), int(n_cols), int(ld), int(burn), cp,
+                       n_active, int(first_lag), int(n_lags), _dptr(out["seq_mean"]),
+                       _dptr(out["seq_m2"]), _dptr(out["shift"]), _dptr(out["acov"])))
+        return out
+
+    def chain_autocov(self, samples, n_chains, iters, n_cols, ld, burn=0, cols=None, first_lag=0,
+                      n_lags=64):
+        """Per-sequence moments and the autocovariances a(first_lag .. first_lag + n_lags) of the
+        columns `cols` (None: all) of a HOST f64 array laid out as for chain_diagnostics
+        (bmc_chain_autocov).  Returns seq_mean, seq_m2 [n_seq, n_cols], shift [n_cols] and acov
+        [len(cols), n_lags]."""
+        return self._autocov_call(self._lib.bmc_chain_autocov, samples.ctypes.data_as(_D), n_chains,
+                                  iters, n_cols, ld, burn, cols, first_lag, n_lags)
+
+    def chain_autocov_device(self, d_ptr, n_chains, iters, n_cols, ld, burn=0, cols=None, first_lag=0,
+                             n_lags=64):
+        """The same on DEVICE memory (bmc_chain_autocov_device), read on the context's stream."""
+        return self._autocov_call(self._lib.bmc_chain_autocov_device, _P(d_ptr), n_chains, iters,
+                                  n_cols, ld, burn, cols, first_lag, n_lags)
 
     # -- rank-normalised diagnostics -------------------------------------------------------------
     RANK_KEYS = ("mean", "sd", "mcse_mean", "ess_bulk", "ess_tail", "r_hat")

@@ -59,13 +59,9 @@ bool ess_scan(const double* a, int64_t have, int64_t n, double W, double var_plu
     return true;
 }
 
-}  // namespace
-
-// (declared in bmc_ctx.h: bmc_rank_diagnostics* runs it on its derived series as well.  With no
-// ess, mcse or max_lag wanted the autocovariance blocks are not launched.)
-int diag_run(bmc_ctx* c, const double* dx, int32_t C, int64_t iters, int32_t P, int64_t ld,
-             int64_t burn, double* mean_out, double* sd_out, double* rhat_out, double* ess_out,
-             double* mcse_out, int64_t* max_lag_out) {
+// the split of DESIGN.md 4.4: n = T'/2 draws per half, the middle draws of an odd T' as sequences
+// of their own
+DiagShape diag_shape(const double* dx, int32_t C, int64_t iters, int32_t P, int64_t ld, int64_t burn) {
     const int64_t Tp = iters - burn, n = Tp / 2;
     DiagShape d;
     d.x = dx;
@@ -77,6 +73,76 @@ int diag_run(bmc_ctx* c, const double* dx, int32_t C, int64_t iters, int32_t P, 
     d.C = C;
     d.P = P;
     d.n_seq = 2 * C + (Tp & 1 ? C : 0);
+    return d;
+}
+
+// bmc_chain_autocov*: the moments and ONE block of lags [t0, t0 + n_lags) for the columns cols
+// (host; NULL: all), straight from launch_diag_moments and launch_diag_acov
+constexpr int32_t AUTOCOV_MAX_ACTIVE = 65536;
+constexpr int64_t AUTOCOV_MAX_LAGS = (int64_t)1 << 20, AUTOCOV_MAX_T0 = (int64_t)1 << 40;
+
+int check_autocov_args(bmc_ctx* c, int32_t n_cols, const int32_t* cols, int32_t n_active, int64_t t0,
+                       int64_t n_lags) {
+    if (n_active < 1 || n_active > AUTOCOV_MAX_ACTIVE)
+        return fail(c, BMC_EINVAL, "n_active must be between 1 and 65536");
+    if (!cols && n_active != n_cols)
+        return fail(c, BMC_EINVAL, "n_active must be n_cols when cols is NULL (all columns)");
+    for (int32_t a = 0; cols && a < n_active; ++a)
+        if (cols[a] < 0 || cols[a] >= n_cols)
+            return fail(c, BMC_EINVAL, "cols[" + std::to_string(a) + "] = " + std::to_string(cols[a]) +
+                                           " is outside [0, n_cols)");
+    if (t0 < 0 || t0 > AUTOCOV_MAX_T0) return fail(c, BMC_EINVAL, "first_lag must be between 0 and 2^40");
+    if (n_lags < 1 || n_lags > AUTOCOV_MAX_LAGS)
+        return fail(c, BMC_EINVAL, "n_lags must be between 1 and 2^20");
+    return BMC_OK;
+}
+
+int autocov_run(bmc_ctx* c, const double* dx, int32_t C, int64_t iters, int32_t P, int64_t ld,
+                int64_t burn, const int32_t* cols, int32_t n_active, int64_t t0, int64_t n_lags,
+                double* seq_mean_out, double* seq_m2_out, double* shift_out, double* acov_out) {
+    const DiagShape d = diag_shape(dx, C, iters, P, ld, burn);
+    const size_t ms = (size_t)d.n_seq * P;
+    int rc;
+    if ((rc = ensure_all(c, {{c->dgPart, diag_moments_scratch(d)}, {c->dgMean, (ms + P) * 8}, {c->dgM2, ms * 8}})))
+        return rc;
+    HIPCHK(c, launch_diag_moments(d, (double*)c->dgPart.p, (double*)c->dgMean.p, (double*)c->dgM2.p,
+                                  c->stream));
+    if (acov_out) {
+        std::vector<int32_t> all;
+        if (!cols) {
+            all.resize((size_t)P);
+            for (int32_t j = 0; j < P; ++j) all[j] = j;
+            cols = all.data();
+        }
+        const size_t stride = (size_t)((n_lags + 63) / 64 * 64);
+        if ((rc = ensure_all(c, {{c->dgCols, (size_t)n_active * 4},
+                                 {c->dgAcovPart, diag_acov_scratch(d, n_active, n_lags)},
+                                 {c->dgAcov, (size_t)n_active * stride * 8}})))
+            return rc;
+        HIPCHK(c, hipMemcpyAsync(c->dgCols.p, cols, (size_t)n_active * 4, hipMemcpyHostToDevice, c->stream));
+        // (a pageable source: the copy has left `all` when the call returns)
+        HIPCHK(c, launch_diag_acov(d, (const double*)c->dgMean.p, (const int32_t*)c->dgCols.p, n_active, t0,
+                                   n_lags, (double*)c->dgAcovPart.p, (double*)c->dgAcov.p, c->stream));
+        if ((rc = copy_to_host(c, acov_out, c->dgAcov.p, (size_t)n_lags * 8, stride * 8, (size_t)n_active)))
+            return rc;
+    }
+    if (seq_mean_out && (rc = copy_to_host(c, seq_mean_out, c->dgMean.p, ms * 8, ms * 8, 1))) return rc;
+    if (shift_out && (rc = copy_to_host(c, shift_out, (const double*)c->dgMean.p + ms, (size_t)P * 8, (size_t)P * 8, 1)))
+        return rc;
+    if (seq_m2_out && (rc = copy_to_host(c, seq_m2_out, c->dgM2.p, ms * 8, ms * 8, 1))) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return BMC_OK;
+}
+
+}  // namespace
+
+// (declared in bmc_ctx.h: bmc_rank_diagnostics* runs it on its derived series as well.  With no
+// ess, mcse or max_lag wanted the autocovariance blocks are not launched.)
+int diag_run(bmc_ctx* c, const double* dx, int32_t C, int64_t iters, int32_t P, int64_t ld,
+             int64_t burn, double* mean_out, double* sd_out, double* rhat_out, double* ess_out,
+             double* mcse_out, int64_t* max_lag_out) {
+    const DiagShape d = diag_shape(dx, C, iters, P, ld, burn);
+    const int64_t n = d.n;
     const int32_t M = 2 * C;
     const size_t ms = (size_t)d.n_seq * P;
     int rc;
@@ -203,6 +269,33 @@ int bmc_chain_diagnostics_device(bmc_ctx* c, const void* d_samples, int32_t n_ch
     HIPCHK(c, hipSetDevice(c->device));
     return diag_run(c, (const double*)d_samples, n_chains, iters, n_cols, ld, burn, mean_out, sd_out,
                     rhat_out, ess_out, mcse_out, max_lag_out);
+}
+
+int bmc_chain_autocov(bmc_ctx* c, const double* samples, int32_t n_chains, int64_t iters, int32_t n_cols,
+                      int64_t ld, int64_t burn, const int32_t* cols, int32_t n_active, int64_t t0,
+                      int64_t n_lags, double* seq_mean_out, double* seq_m2_out, double* shift_out,
+                      double* acov_out) {
+    int rc = check_diag_args(c, samples, n_chains, iters, n_cols, ld, burn);
+    if (rc) return rc;
+    if ((rc = check_autocov_args(c, n_cols, cols, n_active, t0, n_lags))) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t bytes = ((size_t)((int64_t)n_chains * iters - 1) * ld + n_cols) * 8;
+    if ((rc = ensure(c, c->dgIn, bytes))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->dgIn.p, samples, bytes, hipMemcpyHostToDevice, c->stream));
+    return autocov_run(c, (const double*)c->dgIn.p, n_chains, iters, n_cols, ld, burn, cols, n_active, t0,
+                       n_lags, seq_mean_out, seq_m2_out, shift_out, acov_out);
+}
+
+int bmc_chain_autocov_device(bmc_ctx* c, const void* d_samples, int32_t n_chains, int64_t iters,
+                             int32_t n_cols, int64_t ld, int64_t burn, const int32_t* cols,
+                             int32_t n_active, int64_t t0, int64_t n_lags, double* seq_mean_out,
+                             double* seq_m2_out, double* shift_out, double* acov_out) {
+    int rc = check_diag_args(c, d_samples, n_chains, iters, n_cols, ld, burn);
+    if (rc) return rc;
+    if ((rc = check_autocov_args(c, n_cols, cols, n_active, t0, n_lags))) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    return autocov_run(c, (const double*)d_samples, n_chains, iters, n_cols, ld, burn, cols, n_active, t0,
+                       n_lags, seq_mean_out, seq_m2_out, shift_out, acov_out);
 }
 
 }  // extern "C"

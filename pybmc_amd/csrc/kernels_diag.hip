@@ -7,17 +7,13 @@
 //                        sequences: a(t) = mean_m acov_m(t), [n_active][lags] back to the host
 // Input: samples [C][iters][ld] f64, column j < P (the samplers' layout: rows contiguous).
 // No atomics anywhere: every sum has one fixed order, so two calls return the same bits.
+// The launch plans (row splits, sequence groups, scratch sizes) are host-only: bmc_diag_plan.h.
+#include "bmc_diag_plan.h"
 #include "bmc_launch.h"
 
 namespace bmc {
 
 namespace {
-
-constexpr int DIAG_THREADS = 256;
-constexpr int DIAG_R = 128;    // rows of one acov tile
-constexpr int DIAG_CW = 16;    // columns of one acov workgroup (4 per wave)
-constexpr int DIAG_LC = 64;    // lags of one acov workgroup (one per lane)
-constexpr int DIAG_TARGET_GROUPS = 2048;
 
 // Sequence m: m < 2C is half (m & 1) of chain m >> 1 (n draws); 2C <= m < 3C is the middle draw
 // of chain m - 2C when T' = iters - burn is odd (one draw: it counts for mean and sd only).
@@ -247,80 +243,33 @@ __global__ __launch_bounds__(DIAG_THREADS) void diag_acov_reduce_kernel(
             (((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane]) / n / M;
 }
 
-int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-struct MomentPlan {
-    int32_t ncc, S;
-    int64_t rps;
-};
-MomentPlan moment_plan(const DiagShape& d) {
-    MomentPlan p;
-    p.ncc = (int32_t)cdiv(d.P, 64);
-    const int64_t units = (int64_t)d.n_seq * p.ncc;
-    int64_t S = cdiv(DIAG_TARGET_GROUPS, units);
-    const int64_t smax = cdiv(d.n, 256);   // at least 256 rows per split
-    S = S < 1 ? 1 : (S > smax ? smax : S);
-    p.rps = cdiv(d.n, S);
-    p.S = (int32_t)cdiv(d.n, p.rps);
-    return p;
-}
-
-struct AcovPlan {
-    int32_t ncc, nlc, MG, spg, S;
-    int64_t rps;
-};
-AcovPlan acov_plan(const DiagShape& d, int32_t n_active, int64_t n_lags) {
-    AcovPlan p;
-    const int32_t M = 2 * d.C;
-    p.ncc = (int32_t)cdiv(n_active, DIAG_CW);
-    p.nlc = (int32_t)cdiv(n_lags, DIAG_LC);
-    const int64_t units = (int64_t)p.ncc * p.nlc;
-    const int64_t tiles = cdiv(d.n, DIAG_R);
-    int64_t MG = 1, S = 1;
-    if (units < DIAG_TARGET_GROUPS) {
-        const int64_t want = cdiv(DIAG_TARGET_GROUPS, units);
-        MG = want < M ? want : M;
-        S = cdiv(want, MG);
-        S = S > tiles ? tiles : S;
-    }
-    p.spg = (int32_t)cdiv(M, MG);
-    p.MG = (int32_t)cdiv(M, p.spg);
-    const int64_t tps = cdiv(tiles, S);   // tiles per split
-    p.rps = tps * DIAG_R;
-    p.S = (int32_t)cdiv(tiles, tps);
-    return p;
-}
-
 }  // namespace
 
 size_t diag_moments_scratch(const DiagShape& d) {
-    const MomentPlan p = moment_plan(d);
-    return (size_t)d.n_seq * p.S * 2 * d.P * sizeof(double);
+    return moment_scratch_bytes(moment_plan(d.n_seq, d.P, d.n), d.n_seq, d.P);
 }
 
 hipError_t launch_diag_moments(const DiagShape& d, double* scratch, double* mean, double* m2,
                                hipStream_t s) {
-    const MomentPlan p = moment_plan(d);
+    const MomentPlan p = moment_plan(d.n_seq, d.P, d.n);
     hipLaunchKernelGGL(diag_moments_kernel, dim3((unsigned)((int64_t)d.n_seq * p.ncc * p.S)),
                        dim3(DIAG_THREADS), 0, s, d, p.ncc, p.S, p.rps, scratch);
     const int64_t total = (int64_t)d.n_seq * d.P;
-    hipLaunchKernelGGL(diag_moments_merge_kernel, dim3((unsigned)cdiv(total, DIAG_THREADS)),
+    hipLaunchKernelGGL(diag_moments_merge_kernel, dim3((unsigned)diag_cdiv(total, DIAG_THREADS)),
                        dim3(DIAG_THREADS), 0, s, d, p.S, p.rps, (const double*)scratch, mean, m2);
     return hipGetLastError();
 }
 
 size_t diag_acov_scratch(const DiagShape& d, int32_t n_active, int64_t n_lags) {
-    const AcovPlan p = acov_plan(d, n_active, n_lags);
-    return (size_t)p.MG * p.ncc * p.nlc * p.S * DIAG_CW * DIAG_LC * sizeof(double);
+    return acov_scratch_bytes(acov_plan(d.C, d.n, n_active, n_lags));
 }
 
 hipError_t launch_diag_acov(const DiagShape& d, const double* mean, const int32_t* cols,
                             int32_t n_active, int64_t t0, int64_t n_lags, double* scratch,
                             double* acov_out, hipStream_t s) {
-    const AcovPlan p = acov_plan(d, n_active, n_lags);
-    const int64_t groups = (int64_t)p.MG * p.ncc * p.nlc * p.S;
-    hipLaunchKernelGGL(diag_acov_kernel, dim3((unsigned)groups), dim3(DIAG_THREADS), 0, s, d, mean,
-                       cols, n_active, p.ncc, t0, p.nlc, p.spg, p.S, p.rps, scratch);
+    const AcovPlan p = acov_plan(d.C, d.n, n_active, n_lags);
+    hipLaunchKernelGGL(diag_acov_kernel, dim3((unsigned)acov_groups(p)), dim3(DIAG_THREADS), 0, s, d,
+                       mean, cols, n_active, p.ncc, t0, p.nlc, p.spg, p.S, p.rps, scratch);
     hipLaunchKernelGGL(diag_acov_reduce_kernel, dim3((unsigned)((int64_t)n_active * p.nlc)),
                        dim3(DIAG_THREADS), 0, s, (const double*)scratch, p.nlc, p.ncc, p.MG, p.S,
                        (double)d.n, (double)(2 * d.C), acov_out);

@@ -123,6 +123,44 @@ def _order(d):
     return {k: d[k] for k in KEYS}
 
 
+MAX_LAGS = 1 << 20     # of one chain_autocovariance call (the C ABI's limit)
+
+
+def chain_autocovariance(samples, burn=0, cols=None, first_lag=0, n_lags=64, device=0):
+    """The raw quantities behind ``chain_diagnostics``, e.g. for autocorrelation plots: the moments
+    of every split half-chain and one block of autocovariance lags, straight from the kernels.
+
+    ``samples``, ``burn`` and ``device`` follow ``chain_diagnostics``.  ``cols`` selects columns
+    (any order, repeats allowed; ``None``: all).  With ``M = 2C`` halves of ``n`` draws, returns a dict:
+
+    * ``seq_mean``, ``seq_m2``: ``(n_seq, P)``; sequence ``2c + h`` is half ``h`` of chain ``c``:
+      the mean of ``x - shift`` and the centred sum of squares.  When ``T - burn`` is odd, sequences
+      ``2C + c`` are the chains' middle draws (``n_seq = 3C``; their ``seq_m2`` is 0).
+    * ``shift``: ``(P,)``, the column's first kept draw of chain 0.
+    * ``acov``: ``(len(cols), n_lags)``, ``a(t) = mean_m acov_m(t)`` of the module docstring for
+      ``t = first_lag .. first_lag + n_lags - 1``; a lag ``t >= n`` is 0.
+
+    ``rho(t)`` of a column follows as ``1 - (W - a(t)) / var_plus`` with
+    ``W = mean_m seq_m2[m] / (n - 1)`` and ``var_plus = (n - 1) / n * W + var(seq_mean[:M], ddof=1)``."""
+    for name, v, lo in (("first_lag", first_lag, 0), ("n_lags", n_lags, 1)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo:
+            raise ValueError(f"{name} must be an integer >= {lo}")
+    if n_lags > MAX_LAGS:
+        raise ValueError(f"n_lags must be at most {MAX_LAGS}")
+    ctx, on_device, a, C, T, P, ld = _prepare(samples, burn, device)
+    if cols is not None:
+        cols = np.asarray(cols)
+        if cols.ndim != 1 or cols.size < 1 or cols.dtype.kind not in "iu":
+            raise ValueError("cols must be a non-empty 1-d integer array (n_active >= 1)")
+        if cols.min() < 0 or cols.max() >= P:
+            raise ValueError(f"cols must lie in [0, {P}): got {int(cols.min())} .. {int(cols.max())}")
+    with ctx.lock:
+        if on_device:
+            return ctx.chain_autocov_device(a.data_ptr(), C, T, P, ld, int(burn), cols, int(first_lag),
+                                            int(n_lags))
+        return ctx.chain_autocov(a, C, T, P, ld, int(burn), cols, int(first_lag), int(n_lags))
+
+
 def lag_blocks(max_lag, n):
     """Lag blocks a call launched, from its ``max_lag`` output and the half-chain length ``n``:
     blocks cover lags [0, 64), [64, 192), [192, 448), ... (clipped at n); one more block is

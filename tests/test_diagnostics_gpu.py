@@ -55,7 +55,10 @@ def test_odd_kept_draws_with_burn():
     check_against_reference(x, burn=0)
 
 
-@pytest.mark.parametrize("C,T,P", [(1, 500, 1), (64, 200, 33), (2, 300, 257)])
+# (256, 40, 300): 5 half-chains per autocovariance workgroup, the last group clipped by 3;
+# (32, 1400, 100): two 128-row tiles per row split (the classes: tests/test_diag_plan.py)
+@pytest.mark.parametrize("C,T,P", [(1, 500, 1), (64, 200, 33), (2, 300, 257), (256, 40, 300),
+                                   (32, 1400, 100)])
 def test_chain_and_column_counts(C, T, P):
     rng = np.random.default_rng(C * 1000 + P)
     check_against_reference(R.ar1(rng, C, T, P, 0.6), burn=10)
