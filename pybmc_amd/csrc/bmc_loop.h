@@ -114,15 +114,26 @@ struct NoPollSpacing {
 // trip (~260 cycles); half a round trip apart it samples every half round trip (PollSched in
 // bmc_plan.h, measured in scripts/micro/pollsched.hip; three or four in flight were slower, spaced
 // or not).  Returns false when the bounded spin expired.  Lanes >= n2 get 0.
+// `q` is handed out as it stands at the hit: one of its values is the granule that hit, the other
+// DEPTH - 1 are reads still in flight.  The caller keeps them live across the group sum and retires
+// them behind it (retire_polls): left to itself hipcc gives a pending read's register pair to a
+// temporary of granule_sum1 and waits for that read -- up to half a round trip more -- in the
+// middle of the sum.  (All DEPTH registers, not the DEPTH - 1 pending ones: which register is
+// pending depends on the read that hit, and picking it would be a copy of a value that has not
+// arrived, i.e. the same wait in front of the sum.)
 template <int DEPTH = 2, int STRIDE = GRAN_PAIR_STRIDE, typename S = NoPollSpacing>
 __device__ __forceinline__ bool granule_gather1(const gu64* gp, int n2, unsigned epoch, int lane,
-                                                gu64& x STAMP_PARAMS, S space = S()) {
+                                                gu64& x, gu64 (&q)[DEPTH] STAMP_PARAMS, S space = S()) {
     unsigned long long t_start = 0;
     const bool have = lane < n2;
     const gu64* p = gp + gran_at<STRIDE>(have ? lane : 0);
     // the lanes whose tag decides: the test is the compare's own lane mask against this one
-    const gu64 need = __builtin_amdgcn_ballot_w64(have);
-    gu64 q[DEPTH];
+    gu64 need = __builtin_amdgcn_ballot_w64(have);
+    // The loop has ONE way out, the test of a read.  An expired spin clears `need`, so the next
+    // test passes whatever it read, and the flag says that the value is not a total: as a second
+    // exit of its own it made hipcc carry "which exit" in lane-mask flags that were set, tested
+    // and branched on in front of the group sum and again behind it.
+    bool live = true;
 #pragma unroll
     for (int d = 0; d < DEPTH - 1; ++d) {
         q[d] = granule_load(p);
@@ -137,14 +148,26 @@ __device__ __forceinline__ bool granule_gather1(const gu64* gp, int n2, unsigned
 #endif
             const gu64 w = q[d];
             const gu64 hit = __builtin_amdgcn_ballot_w64((unsigned)(w >> 32) == epoch);
-            if ((hit & need) == need) { x = have ? w : 0; return true; }
+            if ((hit & need) == need) { x = have ? w : 0; return live; }
         }
         if ((spins & 0x7f) == 0x7f) {
             const unsigned long long now = __builtin_amdgcn_s_memrealtime();
             if (t_start == 0) t_start = now;
-            else if (now - t_start > SPIN_TIMEOUT_TICKS) return false;
+            else if (now - t_start > SPIN_TIMEOUT_TICKS) {
+                need = 0;
+                live = false;
+            }
         }
     }
+}
+
+// Retire the reads a gather left in flight, behind the sum `tot` they no longer feed: the empty
+// statement reads their registers, so hipcc places their s_waitcnt here and keeps the registers
+// out of everything before it (check_gather_tail.py holds the build to that).
+template <int DEPTH>
+__device__ __forceinline__ void retire_polls(double& tot, const gu64 (&q)[DEPTH]) {
+#pragma unroll
+    for (int d = 0; d < DEPTH; ++d) asm volatile("" : "+v"(tot) : "v"(q[d]));
 }
 
 // one granule per lane: even lane 2g' holds the high word of group g', odd lane the low
@@ -772,6 +795,8 @@ struct NoIdleWork {
 // 3 % shorter (1.090 -> 1.059 us, same-box A/B).
 // SPACED: the first level polls by the spaced schedule of its scope (bmc_plan.h); false (and the
 // RELAY passes) keep the two reads back to back.
+// When `ok` comes back false (the bounded spin expired) the return value is UNDEFINED -- the sum
+// of whatever was last read, or 0 -- and the caller must test `ok` before it uses the value.
 template <bool RELAY = false, int TEAMS = -1, int LOCAL = -1, bool SPACED = true, typename F = NoIdleWork>
 __device__ __forceinline__ double exchange_sum(double s, gu64* gp, int G, int g, int lane,
                                                unsigned epoch, bool local, bool& ok STAMP_PARAMS,
@@ -800,34 +825,41 @@ __device__ __forceinline__ double exchange_sum(double s, gu64* gp, int G, int g,
     static_assert(SL.depth == SA.depth, "one gather, two spacings");
     if (local) wait_states<SL.first>();
     else wait_states<SA.first>();
-    ok = granule_gather1<SL.depth>(gp1, 2 * members, epoch, lane, x STAMP_ARGS, [&] {
+    gu64 q1[SL.depth];
+    ok = granule_gather1<SL.depth>(gp1, 2 * members, epoch, lane, x, q1 STAMP_ARGS, [&] {
         if (local) wait_states<SL.gap>();
         else wait_states<SA.gap>();
     });
     GSTAMP(5);
-    // (the expired spin leaves at once: as `ok ? sum : 0` the flag travelled through the whole
-    // serial path as set / test / branch pairs -- tried, rejected: part of the three changes
-    // that took C2 from 0.9425 to 0.9411 us per iteration)
-    if (__builtin_expect(!ok, 0)) return 0.0;
+    // (after an expired spin the sum is taken of whatever was read and returned as it is: the
+    // caller tests `ok` once, behind the sum, and the chain is over.  Leaving here put a flag
+    // test and a branch in front of the sum; as `ok ? sum : 0` the flag travelled through the
+    // whole serial path as set / test / branch pairs -- both tried)
     double tot = granule_sum1(x, lane);
+    retire_polls(tot, q1);
     if (teams) {
+        // (an expired first level must not publish its sum as a team total)
+        if (__builtin_expect(!ok, 0)) return 0.0;
         // second level: 8 team-total pairs, then 8 relay pairs, GRAN_L2_STRIDE words (512 bytes)
         // apart: each pair is written by one XCD and polled by all (bmc_launch.h)
         gu64* gp2 = gp + (size_t)256 * GRAN_PAIR_STRIDE;
         gu64* gp3 = gp2 + (size_t)(8 + team) * GRAN_L2_STRIDE;
         if (rank == 0) publish_pair<false, GRAN_L2_STRIDE>(gp2, team, lane, epoch, tot);
+        gu64 q2[POLL_LEVEL2.depth];
         if (!RELAY || rank == 0) {
-            ok = granule_gather1<POLL_LEVEL2.depth, GRAN_L2_STRIDE>(gp2, 16, epoch, lane, x STAMP_ARGS);
+            ok = granule_gather1<POLL_LEVEL2.depth, GRAN_L2_STRIDE>(gp2, 16, epoch, lane, x, q2 STAMP_ARGS);
             if (__builtin_expect(!ok, 0)) return 0.0;
             tot = granule_sum1(x, lane);
+            retire_polls(tot, q2);
             if (RELAY) {
                 if (local) publish_pair<true, GRAN_L2_STRIDE>(gp3, 0, lane, epoch, tot);
                 else publish_pair<false, GRAN_L2_STRIDE>(gp3, 0, lane, epoch, tot);
             }
         } else {
-            ok = granule_gather1<POLL_LEVEL2.depth, GRAN_L2_STRIDE>(gp3, 2, epoch, lane, x STAMP_ARGS);
+            ok = granule_gather1<POLL_LEVEL2.depth, GRAN_L2_STRIDE>(gp3, 2, epoch, lane, x, q2 STAMP_ARGS);
             if (__builtin_expect(!ok, 0)) return 0.0;
             tot = granule_sum1(x, lane);   // the relayed double itself (+ zeros)
+            retire_polls(tot, q2);
         }
     }
     GSTAMP(8);
