@@ -1,5 +1,6 @@
 // C ABI of libpybmc_amd.so (see include/pybmc_amd.h).  Host orchestration only:
-// every O(N) step is a gfx950 kernel; the host does the one-off K x K algebra.
+// every O(N) step is a gfx950 kernel; the host does the one-off K x K algebra (the prior basis:
+// bmc_basis.h, shared with capi_cv.hip).
 // This file: the context and what every family shares (bmc_ctx.h), problem, prior, getters,
 // RSS and Gram, variates.
 #include <algorithm>
@@ -9,8 +10,8 @@
 #include <new>
 #include <thread>
 
+#include "bmc_basis.h"
 #include "bmc_ctx.h"
-#include "host_linalg.hpp"
 
 // Base of a persistent launch's exchange tags (GibbsArgs.epoch0): different for every launch
 // (splitmix64 of a per-context counter), so that words an earlier launch left behind -- in the
@@ -382,9 +383,10 @@ int bmc_set_prior(bmc_ctx* c, const double* b0, const double* C0, double nu0, do
     HIPCHK(c, hipSetDevice(c->device));
     c->have_prior = false;
     const int k = c->k, ka = k + 1;
-    // P = inv(C0)                                          (inference_utils.py:22)
-    bmc_la::Mat P(C0, C0 + (size_t)k * k);
-    if (!bmc_la::invert(P, k)) return fail(c, BMC_ESINGULAR, "Singular matrix (b_mean_cov)");
+    // P = inv(C0) and the prior's part of the basis        (inference_utils.py:22; bmc_basis.h)
+    PriorBasis pb;
+    const BasisStatus st = prior_basis(k, C0, k, b0, pb);
+    if (st == BASIS_C0_SINGULAR) return fail(c, BMC_ESINGULAR, "Singular matrix (b_mean_cov)");
     // OLS start value                                      (inference_utils.py:26-37)
     bmc_la::Mat A((size_t)k * k);
     std::vector<double> xty(k);
@@ -400,101 +402,24 @@ int bmc_set_prior(bmc_ctx* c, const double* b0, const double* C0, double nu0, do
     double s2 = rss0 / (double)c->n;
     if (!(s2 >= 1e-6)) s2 = s2 != s2 ? s2 : 1e-6;  // max(s2, 1e-6); NaN propagates
     c->sigma2_init = s2;
-    // basis: B = P + 1e-6 I = L L',  L^-1 A L^-T = Q diag(lam) Q',  W = L^-T Q
-    bmc_la::Mat B((size_t)k * k);
-    for (int i = 0; i < k; ++i)
-        for (int j = 0; j < k; ++j)
-            B[(size_t)i * k + j] = 0.5 * (P[(size_t)i * k + j] + P[(size_t)j * k + i]) +
-                                   (i == j ? 1e-6 : 0.0);
-    bmc_la::Mat L, Li;
-    if (!bmc_la::cholesky(B, k, L))
+    if (st == BASIS_NOT_PD)
         return fail(c, BMC_EINVAL, "prior precision inv(b_mean_cov) + 1e-6 I is not positive definite");
-    bmc_la::lower_inverse(L, k, Li);
-    bmc_la::Mat tmp((size_t)k * k, 0.0), M((size_t)k * k, 0.0);
-    for (int i = 0; i < k; ++i)          // tmp = Li * A
-        for (int m = 0; m <= i; ++m) {
-            const double l = Li[(size_t)i * k + m];
-            if (l == 0.0) continue;
-            for (int j = 0; j < k; ++j) tmp[(size_t)i * k + j] += l * A[(size_t)m * k + j];
-        }
-    for (int i = 0; i < k; ++i)          // M = tmp * Li'
-        for (int j = 0; j < k; ++j) {
-            long double s = 0.0L;
-            for (int m = 0; m <= j; ++m) s += (long double)tmp[(size_t)i * k + m] * Li[(size_t)j * k + m];
-            M[(size_t)i * k + j] = (double)s;
-        }
-    for (int i = 0; i < k; ++i)
-        for (int j = i + 1; j < k; ++j) {
-            const double v = 0.5 * (M[(size_t)i * k + j] + M[(size_t)j * k + i]);
-            M[(size_t)i * k + j] = M[(size_t)j * k + i] = v;
-        }
-    bmc_la::Mat Q;
-    bmc_la::sym_eigh(M, k, c->lam, Q);
-    c->W.assign((size_t)k * k, 0.0);
-    for (int i = 0; i < k; ++i)          // W = Li' Q
-        for (int j = 0; j < k; ++j) {
-            long double s = 0.0L;
-            for (int m = i; m < k; ++m) s += (long double)Li[(size_t)m * k + i] * Q[(size_t)m * k + j];
-            c->W[(size_t)i * k + j] = (double)s;
-        }
-    std::vector<double> Pb0(k, 0.0);
-    for (int i = 0; i < k; ++i) {
-        long double s = 0.0L;
-        for (int j = 0; j < k; ++j) s += (long double)P[(size_t)i * k + j] * b0[j];
-        Pb0[i] = (double)s;
-    }
-    c->c1.assign(k, 0.0);
-    c->c2.assign(k, 0.0);
-    for (int j = 0; j < k; ++j) {
-        long double s1 = 0.0L, s2l = 0.0L;
-        for (int i = 0; i < k; ++i) {
-            s1 += (long double)c->W[(size_t)i * k + j] * Pb0[i];
-            s2l += (long double)c->W[(size_t)i * k + j] * xty[i];
-        }
-        c->c1[j] = (double)s1;
-        c->c2[j] = (double)s2l;
-    }
+    // the basis W, lam, c1, c2 and, for rss_mode 1 (k <= 64), G = W'AW, u0 and g0
+    ChainBasis cb;
+    chain_basis(k, A, xty, pb, k <= 64, cb);
+    c->lam = std::move(cb.lam);
+    c->W = std::move(cb.W);
+    c->c1 = std::move(cb.c1);
+    c->c2 = std::move(cb.c2);
+    c->Gt = std::move(cb.G);
+    c->u0 = std::move(cb.u0);
+    c->g0 = std::move(cb.g0);
+    c->have_gram_dev = false;
     c->b0.assign(b0, b0 + k);
-    c->Pprec.assign(P.begin(), P.end());
-    c->Pb0 = Pb0;
+    c->Pprec = std::move(pb.P);
+    c->Pb0 = std::move(pb.Pb0);
     c->nu0 = nu0;
     c->s20 = sigma20;
-    // rss_mode 1 (k <= 64): G = W'AW (= diag(lam) up to rounding), the least-squares point u0 in
-    // the rotated basis and g0 = X~'(y - X~ u0) = c2 - G u0, all in extended precision
-    c->Gt.clear();
-    c->have_gram_dev = false;
-    if (k <= 64) {
-        std::vector<long double> AW((size_t)k * k, 0.0L);
-        for (int i = 0; i < k; ++i)
-            for (int m = 0; m < k; ++m) {
-                const long double aim = A[(size_t)i * k + m];
-                for (int j = 0; j < k; ++j) AW[(size_t)i * k + j] += aim * c->W[(size_t)m * k + j];
-            }
-        c->Gt.assign((size_t)k * k, 0.0);
-        std::vector<long double> Gl((size_t)k * k, 0.0L);
-        for (int i = 0; i < k; ++i)
-            for (int j = 0; j < k; ++j) {
-                long double sum = 0.0L;
-                for (int m = 0; m < k; ++m) sum += (long double)c->W[(size_t)m * k + i] * AW[(size_t)m * k + j];
-                Gl[(size_t)i * k + j] = sum;
-            }
-        for (int i = 0; i < k; ++i)
-            for (int j = 0; j < k; ++j)
-                c->Gt[(size_t)i * k + j] = (double)(0.5L * (Gl[(size_t)i * k + j] + Gl[(size_t)j * k + i]));
-        double gmax = 0.0;
-        for (int j = 0; j < k; ++j) gmax = std::max(gmax, c->Gt[(size_t)j * k + j]);
-        c->u0.assign(k, 0.0);
-        for (int j = 0; j < k; ++j) {
-            const double gj = c->Gt[(size_t)j * k + j];
-            c->u0[j] = gj > 1e-14 * gmax ? c->c2[j] / gj : 0.0;
-        }
-        c->g0.assign(k, 0.0);
-        for (int i = 0; i < k; ++i) {
-            long double sum = c->c2[i];
-            for (int j = 0; j < k; ++j) sum -= (long double)c->Gt[(size_t)i * k + j] * c->u0[j];
-            c->g0[i] = (double)sum;
-        }
-    }
     std::vector<double> WT((size_t)k * k);
     for (int i = 0; i < k; ++i)
         for (int j = 0; j < k; ++j) WT[(size_t)i * k + j] = c->W[(size_t)j * k + i];
