@@ -583,14 +583,17 @@ int bmc_cv_path(bmc_ctx* ctx, const double* A, int64_t n, int32_t k, int64_t lda
  * over the points, per draw:
  *   t_rep_out   [n_draws][8]: min, max, mean, sd, skew, kurt of y_rep[.][s] (central moments with
  *               ddof 0: sd = sqrt(m2), skew = m3 / m2^1.5, kurt = m4 / m2^2 - 3; accumulated as
- *               power sums of y_rep - center, so pass center = mean_i(y_i + offset_i)), then
- *               sum_i z[i][s]^2 and max_i |z[i][s]|
+ *               power sums of y_rep - c_s about the draw's own centre c_s = mean_i(a_i) . beta_s +
+ *               mean_i(offset_i), formed on the device; `center` is kept for the signature and no
+ *               longer read), then sum_i z[i][s]^2 and max_i |z[i][s]|
  *   t_obs2_out  [n_draws][2]: sum_i e^2 and max_i |e|, e = (y_i - a_i . beta_s) / sigma_s: the
  *               observed counterparts of the last two (those of the first six do not depend on
  *               the draw: the same functions of y + offset, left to the caller)
  * Either output may be NULL.  The Bayesian p-value of statistic j is the share of draws with
  * t_rep[s][j] >= t_obs[s][j].  One workgroup per 64 draws walks all points and nothing is
  * combined across workgroups: the results depend on the arguments alone, not on the device.
+ * Non-finite input is data: a value is NaN exactly where these definitions give NaN, and all ten
+ * values of a draw with a non-finite coefficient or without a finite sigma_s > 0 are NaN.
  * BMC_EINVAL as bmc_pointwise_loglik, and when n_points < 3 or n_points > 2^31.  Runs on the
  * context's stream and leaves the problem, the prior and the predictive draws alone.
  * bmc_ppc stages host arrays itself; the _device form reads caller-owned DEVICE memory (A, y,

@@ -922,7 +922,7 @@ class Context:
     def ppc(self, A, n, k, lda, layout, y, theta, n_draws, ldt, offset, seed, center):
         """The per-draw statistics of replicated data, t_rep (n_draws, 8), and the observed chi2
         and max_abs_z, t_obs2 (n_draws, 2), of HOST f64 arrays (bmc_ppc); A, y and theta as
-        pointwise_loglik, offset [n] or None, center = mean(y + offset)."""
+        pointwise_loglik, offset [n] or None; center is kept by the ABI and no longer read."""
         return self._ppc_call(self._lib.bmc_ppc, _dptr, A, n, k, lda, layout, y, theta, n_draws,
                               ldt, offset, seed, center)
 

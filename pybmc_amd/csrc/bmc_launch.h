@@ -368,10 +368,14 @@ hipError_t launch_loo_predict(const LooArgs& a, const LooPredictPlan& p, hipStre
 // Replicated data y_rep[i][s] = a_i . beta_s + sigma_s z[i][s] + offset_i of the model and
 // arguments of launch_score, z from the STREAM_PPC variates of `seed`, reduced over
 // the points per draw and never stored.  t_rep [S][PPC_STATS]: min, max, mean, sd, skew, kurt of
-// y_rep[.][s] (moments with ddof 0, from the power sums of y_rep - center), sum_i z^2, max_i |z|;
+// y_rep[.][s] (moments with ddof 0, from the power sums of y_rep - c_s, c_s = a_bar . beta_s +
+// mean(offset) the draw's own centre, formed on the device), sum_i z^2, max_i |z|;
 // t_obs2 [S][PPC_OBS]: sum_i ((y_i - a_i . beta_s) / sigma_s)^2 and max_i |y_i - a_i . beta_s| /
-// sigma_s.  offset may be NULL (zeros).  Work buffers (device, sized by ppc_buffers for the plan):
-// Ap, yo, Tp, sg.  No atomics, one workgroup per 64 draws: the bits depend on the arguments alone.
+// sigma_s.  offset may be NULL (zeros).  `center` is no longer read (the C ABI keeps the argument).
+// A value is NaN exactly where these definitions give NaN, and all ten of a draw with a non-finite
+// coefficient or without a finite sigma > 0 are NaN.  Work buffers (device, sized by ppc_buffers
+// for the plan): Ap, yo, Tp, sg.  No atomics, one workgroup per 64 draws: the bits depend on the
+// arguments alone.
 struct PpcArgs {
     const double* A;
     const double* y;

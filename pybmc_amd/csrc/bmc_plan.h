@@ -903,8 +903,8 @@ inline LooPredictBuffers loo_predict_buffers(const LooPredictPlan& p, int64_t n_
 // SCORE_TILE draws and walks every point tile, so the roles of plan_score are swapped and there
 // is no split: one workgroup per draw tile, whatever the CU count (fewer than 64 x CUs draws leave
 // CUs idle; the bits do not depend on the device).  Both operands are padded to whole tiles: the
-// draws [S_pad][k_pad] (with sigma_s and 1 / sigma_s per draw) and the design [n_pad][k_pad] (with
-// y and the offset per point).  Refused (ok = false): fewer than PPC_MIN_POINTS points (skew and
+// draws [S_pad][k_pad] (with sigma_s, 1 / sigma_s and the centre c_s per draw) and the design
+// [n_pad][k_pad] (with y and the offset per point, and its column means).  Refused (ok = false): fewer than PPC_MIN_POINTS points (skew and
 // kurt of fewer are constants), fewer than 2 draws, k outside 1 .. SCORE_MAX_K, more points than
 // PPC_MAX_POINTS (the noise counter carries the point pair in one 32-bit word).
 constexpr int PPC_STATS = 8;      // min, max, mean, sd, skew, kurt, chi2, max_abs_z (replicated)
@@ -942,7 +942,9 @@ struct PpcBuffers {
     size_t Ap;    // [n_pad][k_pad] f64: the design, zero in the padding
     size_t yo;    // [2][n_pad] f64: y, then the offset
     size_t Tp;    // [S_pad][k_pad] f64: the coefficients of every draw, zero in the padding
-    size_t sg;    // [2][S_pad] f64: sigma_s, then 1 / sigma_s (1 in the padding)
+    size_t sg;    // [3][S_pad] f64: sigma_s, 1 / sigma_s (1 in the padding; NaN marks a bad draw) and
+                  // the draw's centre c_s; then [k_pad + 16]: the column means of the design and,
+                  // at k_pad, the mean offset
     size_t out;   // [S][PPC_STATS] then [S][PPC_OBS] f64
     size_t total() const { return Ap + yo + Tp + sg + out; }
 };
@@ -951,7 +953,7 @@ inline PpcBuffers ppc_buffers(const PpcPlan& p, int64_t n_draws) {
     b.Ap = (size_t)p.n_pad * (size_t)p.k_pad * 8;
     b.yo = (size_t)p.n_pad * 2 * 8;
     b.Tp = (size_t)p.S_pad * (size_t)p.k_pad * 8;
-    b.sg = (size_t)p.S_pad * 2 * 8;
+    b.sg = ((size_t)p.S_pad * 3 + (size_t)p.k_pad + 16) * 8;
     b.out = (size_t)n_draws * (PPC_STATS + PPC_OBS) * 8;
     return b;
 }

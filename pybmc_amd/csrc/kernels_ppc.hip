@@ -6,15 +6,23 @@
 //
 //   ppc_pad_points  A (either layout, any lda), y, offset -> whole 64-point tiles and 16-column
 //                   slabs, zero in the padding
+//   ppc_col_mean    the column means a_bar of the padded design and the mean offset, each summed in
+//                   one fixed order (a workgroup per 16-column slab, one for the offset)
 //   ppc_pad_draws   theta (any ldt) -> the coefficients in whole 64-draw tiles and 16-column slabs,
-//                   sigma_s and 1 / sigma_s per draw (1 in the padding)
+//                   sigma_s and 1 / sigma_s per draw (1 in the padding; 1 / sigma_s is NaN for a
+//                   bad draw: a non-finite coefficient, or no finite sigma_s > 0), and the draw's
+//                   centre c_s = a_bar . beta_s + mean(offset) (0 where that is not finite)
 //   ppc_tile        workgroup = 64 draws x ALL point tiles: the tile loop of bmc_score_tile.h with
 //                   the operands swapped (the draws are the owner rows, the padded design is
 //                   walked).  A wave owns 16 draws, a lane 4 draws x 4 points of every tile; the
 //                   ten running values of each draw stay in the lane's registers over the whole
 //                   walk and meet once, at the end, in a tree over the 16 lanes that share the
 //                   draws.  The lane that ends the tree turns the power sums into the moments and
-//                   writes the draw's row.
+//                   writes the draw's row.  The power sums are of y_rep - c_s, the draw's OWN
+//                   centre: about a point all draws share, a fit whose predictions are biased by
+//                   D loses (D / sd)^4 u of kurt to m4 = a4 - 4 a1 a3 + ..., and such a fit is
+//                   what the check exists to flag.  sigma_s and c_s of the workgroup's 64 draws
+//                   wait in LDS (the lane's registers are full of running values).
 //
 // The variate of (point i, draw s): Philox4x32-10 keyed by the seed, counter (s lo, s hi,
 // STREAM_PPC, pair(i)), pair(i) = (i >> 6) 32 + (i & 31); its Box-Muller pair (bmc_math.h) gives
@@ -25,7 +33,14 @@
 // No atomics and no split over the points: every sum has one fixed order (tile by tile in the
 // lane, then the lane tree), whatever the CU count.  Padded points add nothing (their z, e and
 // centred value are replaced by 0, their y_rep by +-inf for min / max); padded draws are computed
-// and dropped.  Non-finite input propagates through the sums; min / max ignore a NaN.
+// and dropped.
+//
+// Non-finite input is data (every index comes from the shapes).  A value is NaN exactly where the
+// definitions above give NaN: a NaN among y_rep[.][s] makes min, max, mean, sd, skew and kurt NaN,
+// a NaN among e the two observed values, and nothing else (the sums propagate it; fmin / fmax would
+// drop it, so the epilogue after the walk reads it off p4 and ee, which are sums of squares and
+// NaN only if a term is).  All ten values of a bad draw are NaN.  A draw's row depends on that draw
+// alone, and a bad point on nothing but what it enters.
 #include "bmc_dev.h"
 #include "bmc_launch.h"
 #include "bmc_plan.h"
@@ -54,9 +69,53 @@ __global__ __launch_bounds__(256) void ppc_pad_points_kernel(
     }
 }
 
+// grid: k_pad / 16 workgroups of 1024 threads, one per slab of 16 columns of the padded design, and
+// one more for the offset.  Thread t of a slab's workgroup sums column t & 15 over the rows
+// (t >> 4) + 64 m, m in order, into four partial sums by m & 3 (the padded rows are zeros and add
+// nothing); the four meet as (s0 + s1) + (s2 + s3) and the 64 row groups of a column in a fixed
+// tree in LDS.  The offset is summed the same way by the threads of column 0.  cm [k_pad + 1]: the
+// column means (0 in the padded columns), then the mean offset.
+__global__ __launch_bounds__(1024) void ppc_col_mean_kernel(const double* __restrict__ Ap,
+                                                            const double* __restrict__ yo, int64_t n,
+                                                            int64_t n_pad, int32_t k_pad,
+                                                            double* __restrict__ cm) {
+    __shared__ double part[1024];
+    const int tid = threadIdx.x, c = tid & 15, g = tid >> 4;
+    const int slab = blockIdx.x;
+    const bool is_offset = slab == k_pad / 16;   // workgroup-uniform
+    const double* col = is_offset ? yo + n_pad : Ap + 16 * slab + c;
+    const int64_t step = is_offset ? 1 : k_pad;
+    const int64_t tiles = n_pad / SC_TM;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    if (!is_offset || c == 0) {
+        int64_t m = 0;
+        for (; m + 4 <= tiles; m += 4) {
+            s0 += col[(m * SC_TM + g) * step];
+            s1 += col[((m + 1) * SC_TM + g) * step];
+            s2 += col[((m + 2) * SC_TM + g) * step];
+            s3 += col[((m + 3) * SC_TM + g) * step];
+        }
+        if (m < tiles) s0 += col[(m * SC_TM + g) * step];
+        if (m + 1 < tiles) s1 += col[((m + 1) * SC_TM + g) * step];
+        if (m + 2 < tiles) s2 += col[((m + 2) * SC_TM + g) * step];
+    }
+    part[tid] = (s0 + s1) + (s2 + s3);
+    __syncthreads();
+    for (int h = 512; h >= 16; h >>= 1) {
+        if (tid < h) part[tid] += part[tid + h];
+        __syncthreads();
+    }
+    if (is_offset) {
+        if (tid == 0) cm[k_pad] = part[0] / (double)n;
+    } else if (tid < 16) {
+        cm[16 * slab + tid] = part[tid] / (double)n;
+    }
+}
+
 __global__ __launch_bounds__(256) void ppc_pad_draws_kernel(const double* __restrict__ theta,
                                                             int64_t S, int64_t ldt, int32_t k,
                                                             int64_t S_pad, int32_t k_pad,
+                                                            const double* __restrict__ cm,
                                                             double* __restrict__ Tp,
                                                             double* __restrict__ sg) {
     const int64_t total = S_pad * k_pad;
@@ -65,11 +124,24 @@ __global__ __launch_bounds__(256) void ppc_pad_draws_kernel(const double* __rest
         const int64_t s = e / k_pad;
         const int32_t j = (int32_t)(e - s * k_pad);
         Tp[e] = (s < S && j < k) ? theta[s * ldt + j] : 0.0;
-        if (j == 0) {
-            const double sigma = s < S ? theta[s * ldt + k] : 1.0;
-            sg[s] = sigma;
-            sg[S_pad + s] = 1.0 / sigma;
+    }
+    // then a thread per draw (all lanes of a wave at work, not one in k_pad): sigma_s, whether the
+    // draw is good, and its centre c_s = a_bar . beta_s + mean(offset), the columns in order
+    for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < S_pad; s += stride) {
+        const double sigma = s < S ? theta[s * ldt + k] : 1.0;
+        bool good = sigma > 0.0 && sigma < __builtin_inf();
+        double c = 0.0;
+        if (s < S) {
+            for (int32_t jj = 0; jj < k; ++jj) {
+                const double b = theta[s * ldt + jj];
+                good = good && fabs(b) < __builtin_inf();
+                c += cm[jj] * b;
+            }
         }
+        c += cm[k_pad];
+        sg[s] = sigma;
+        sg[S_pad + s] = good ? 1.0 / sigma : __builtin_nan("");
+        sg[2 * S_pad + s] = fabs(c) < __builtin_inf() ? c : 0.0;
     }
 }
 
@@ -109,10 +181,11 @@ __device__ __forceinline__ void ppc_fold(PpcRun& st, double dot, double z, doubl
 __global__ __launch_bounds__(256, 2) void ppc_tile_kernel(
     const double* __restrict__ Tp, const double* __restrict__ sg, const double* __restrict__ Ap,
     const double* __restrict__ yo, int64_t n, int64_t n_pad, int64_t S, int64_t S_pad, int32_t k,
-    int32_t k_pad, int64_t point_tiles, uint64_t seed, double center, double* __restrict__ t_rep,
+    int32_t k_pad, int64_t point_tiles, uint64_t seed, double* __restrict__ t_rep,
     double* __restrict__ t_obs2) {
     __shared__ double As[SC_LDS_DOUBLES];
     __shared__ double Bs[SC_LDS_DOUBLES];
+    __shared__ double sc[2 * SC_TM];   // (sigma_s, c_s) of the workgroup's draws
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int cl = lane & 15, kq = lane >> 4;
@@ -123,13 +196,16 @@ __global__ __launch_bounds__(256, 2) void ppc_tile_kernel(
     // (a tile starts at a multiple of 64: the high word of the draw index is the workgroup's)
     const uint32_t dlo = (uint32_t)d0 + (uint32_t)(16 * wave + kq);
     const uint32_t dhi = (uint32_t)((uint64_t)d0 >> 32);
-    double sigma[4];
     PpcRun st[4];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        sigma[r] = sg[d0 + 16 * wave + kq + 4 * r];
+    for (int r = 0; r < 4; ++r)
         st[r] = PpcRun{__builtin_inf(), -__builtin_inf(), 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (tid < SC_TM) {
+        sc[2 * tid] = sg[d0 + tid];
+        sc[2 * tid + 1] = sg[2 * S_pad + d0 + tid];
     }
+    __syncthreads();
+    const double* sc_r = sc + 2 * (16 * wave + kq);   // draw r of the lane: sc_r[8 r], sc_r[8 r + 1]
 
     // epilogue: the lane's points are i0 + cl + 16 t; points t and t + 2 (32 apart) share a
     // counter, the cosine half to t
@@ -148,19 +224,20 @@ __global__ __launch_bounds__(256, 2) void ppc_tile_kernel(
         const uint32_t pr = (uint32_t)(i0 >> 6) * 32u + (uint32_t)cl;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
+            const double sigma = sc_r[8 * r], center = sc_r[8 * r + 1];
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const u32x4 w = philox4x32_10(u32x4{dlo + 4u * r, dhi, STREAM_PPC, pr + 16u * h}, k0, k1);
                 double z0, z1;
                 box_muller_pair(u53_open0(w.x, w.y), u53_open0(w.z, w.w), z0, z1);
                 if (full) {
-                    ppc_fold<true>(st[r], acc[h][r], z0, yv[h], ov[h], sigma[r], center, true);
-                    ppc_fold<true>(st[r], acc[h + 2][r], z1, yv[h + 2], ov[h + 2], sigma[r],
-                                   center, true);
+                    ppc_fold<true>(st[r], acc[h][r], z0, yv[h], ov[h], sigma, center, true);
+                    ppc_fold<true>(st[r], acc[h + 2][r], z1, yv[h + 2], ov[h + 2], sigma, center,
+                                   true);
                 } else {
-                    ppc_fold<false>(st[r], acc[h][r], z0, yv[h], ov[h], sigma[r], center, ok[h]);
-                    ppc_fold<false>(st[r], acc[h + 2][r], z1, yv[h + 2], ov[h + 2], sigma[r],
-                                    center, ok[h + 2]);
+                    ppc_fold<false>(st[r], acc[h][r], z0, yv[h], ov[h], sigma, center, ok[h]);
+                    ppc_fold<false>(st[r], acc[h + 2][r], z1, yv[h + 2], ov[h + 2], sigma, center,
+                                    ok[h + 2]);
                 }
                 // one pair at a time: left to itself the scheduler interleaves the eight
                 // Philox / Box-Muller chains of a tile and their temporaries no longer fit beside
@@ -192,25 +269,32 @@ __global__ __launch_bounds__(256, 2) void ppc_tile_kernel(
         }
         const int64_t d = d0 + 16 * wave + kq + 4 * r;
         if (cl == 0 && d < S) {
-            // central moments (ddof 0) from the power sums about `center`
+            // central moments (ddof 0) from the power sums about the draw's centre
+            const double center = sc_r[8 * r + 1];
             const double a1 = me.p1 / nn, a2 = me.p2 / nn, a3 = me.p3 / nn, a4 = me.p4 / nn;
             const double a1s = a1 * a1;
             const double m2 = a2 - a1s;
             const double m3 = fma(2.0 * a1s, a1, fma(-3.0 * a1, a2, a3));
             const double m4 = fma(-3.0 * a1s, a1s, fma(6.0 * a1s, a2, fma(-4.0 * a1, a3, a4)));
             const double sd = sqrt(m2);
-            double* o = t_rep + d * PPC_STATS;
-            o[0] = me.mn;
-            o[1] = me.mx;
-            o[2] = center + a1;
-            o[3] = sd;
-            o[4] = m3 / (m2 * sd);
-            o[5] = m4 / (m2 * m2) - 3.0;
-            o[6] = me.zz;
-            o[7] = me.mz;
+            // fmin / fmax dropped a NaN that the definitions keep: p4 and ee are sums of squares,
+            // NaN only if a y_rep (an e) of the draw is.  A bad draw (1 / sigma_s is NaN) is NaN in
+            // all ten values.
+            const double nan = __builtin_nan("");
             const double inv_sigma = sg[S_pad + d];
-            t_obs2[d * PPC_OBS] = me.ee * inv_sigma * inv_sigma;
-            t_obs2[d * PPC_OBS + 1] = me.me * inv_sigma;
+            const bool bad = inv_sigma != inv_sigma;
+            const bool rep_nan = bad || me.p4 != me.p4, obs_nan = bad || me.ee != me.ee;
+            double* o = t_rep + d * PPC_STATS;
+            o[0] = rep_nan ? nan : me.mn;
+            o[1] = rep_nan ? nan : me.mx;
+            o[2] = rep_nan ? nan : center + a1;
+            o[3] = rep_nan ? nan : sd;
+            o[4] = rep_nan ? nan : m3 / (m2 * sd);
+            o[5] = rep_nan ? nan : m4 / (m2 * m2) - 3.0;
+            o[6] = bad ? nan : me.zz;
+            o[7] = bad ? nan : me.mz;
+            t_obs2[d * PPC_OBS] = obs_nan ? nan : me.ee * inv_sigma * inv_sigma;
+            t_obs2[d * PPC_OBS + 1] = obs_nan ? nan : me.me * inv_sigma;
         }
     }
 }
@@ -229,15 +313,18 @@ hipError_t launch_ppc(const PpcArgs& a, const PpcPlan& p, hipStream_t s) {
         hipLaunchKernelGGL(ppc_pad_points_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a.A, a.y,
                            a.offset, a.n, a.k, a.lda, a.col_major, p.n_pad, p.k_pad, a.Ap, a.yo);
     }
+    double* cm = a.sg + 3 * p.S_pad;   // the column means and the mean offset, behind the three rows
+    hipLaunchKernelGGL(ppc_col_mean_kernel, dim3((unsigned)(p.k_pad / 16 + 1)), dim3(1024), 0, s,
+                       (const double*)a.Ap, (const double*)a.yo, a.n, p.n_pad, p.k_pad, cm);
     {
         int64_t blocks = (p.S_pad * p.k_pad + 255) / 256;
         if (blocks > 8192) blocks = 8192;
         hipLaunchKernelGGL(ppc_pad_draws_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a.theta, a.S,
-                           a.ldt, a.k, p.S_pad, p.k_pad, a.Tp, a.sg);
+                           a.ldt, a.k, p.S_pad, p.k_pad, (const double*)cm, a.Tp, a.sg);
     }
     hipLaunchKernelGGL(ppc_tile_kernel, dim3((unsigned)p.grid), dim3(256), 0, s, (const double*)a.Tp,
                        (const double*)a.sg, (const double*)a.Ap, (const double*)a.yo, a.n, p.n_pad, a.S,
-                       p.S_pad, a.k, p.k_pad, p.point_tiles, a.seed, a.center, a.t_rep, a.t_obs2);
+                       p.S_pad, a.k, p.k_pad, p.point_tiles, a.seed, a.t_rep, a.t_obs2);
     return hipGetLastError();
 }
 

@@ -29,7 +29,23 @@ two equal numbers and says nothing.
 On the device (``kernels_ppc.hip``) the n x S matrix is never stored: the f64 MFMA GEMM of the
 scoring kernels with the noise made in the epilogue and the tile reduced over the points, per
 draw; one workgroup per 64 draws and no combine across workgroups, so the result does not depend
-on the device.
+on the device.  The moments come from power sums of ``y_rep[:, s] - c_s`` about the draw's own
+centre ``c_s = mean_i(a_i) . beta_s + mean(offset)``, formed on the device, so that a fit whose
+predictions are biased loses nothing of ``skew`` and ``kurt`` to cancellation.
+
+Non-finite input is data, and a value is NaN exactly where the definitions above give NaN (``min``
+and ``max`` of values with a NaN among them are NaN, as numpy's are):
+
+* A draw with a non-finite coefficient, or without a finite ``sigma_s > 0``, is NaN in all ten of
+  its values (the eight of ``t_rep`` and the observed ``chi2`` and ``max_abs_z``), as the scoring
+  and sensitivity calls treat such a draw.  Every other draw is what it is without it.
+* A NaN in ``A[i, :]`` makes ``min`` .. ``kurt`` of ``t_rep`` and the observed ``chi2`` and
+  ``max_abs_z`` NaN for every draw; the replicated ``chi2`` and ``max_abs_z`` do not read ``A``.
+* A NaN in ``y[i]`` makes ``t_obs`` NaN and leaves ``t_rep`` as it is; ``+inf`` there makes the
+  observed ``chi2`` and ``max_abs_z`` ``+inf``.
+* A NaN in ``offset[i]`` makes the six marginal columns of ``t_rep`` and ``t_obs`` NaN and nothing
+  else.
+* A NaN is never ``>=``: such a draw does not count towards a p-value.
 
 Out of scope: per-point posterior predictive p-values.  They reduce along the other axis, and they
 use every point twice (to fit and to check); ``psis_loo_predict()["loo_pit"]`` is the honest
@@ -93,12 +109,10 @@ def posterior_predictive_check(A, y, samples, burn=0, thin=1, offset=None, seed=
         raise ValueError("seed must be an integer in [0, 2^64) or None")
     seed = int(seed)
 
-    def center(A, y, off):
-        return float(np.mean(y if off is None else y + off))
-
+    # (the last scalar is the C ABI's `center`, which the device no longer reads)
     out = _pointwise_call("ppc", "ppc_device", A, y, samples, burn, thin, device,
                           min_points=MIN_POINTS, vectors=(("offset", offset),),
-                          scalars=(seed, center))
+                          scalars=(seed, 0.0))
     y = np.asarray(y)
     obs = marginal_stats(y if offset is None else y + np.asarray(offset))
     t_rep = out["t_rep"]

@@ -33,7 +33,7 @@ static int check(int64_t n, int64_t S, int k, int n_cu) {
         bad += p.rounds < 1 || p.rounds * slots < p.grid || (p.rounds - 1) * slots >= p.grid;
         const PpcBuffers b = ppc_buffers(p, S);
         bad += b.Ap != (size_t)p.n_pad * p.k_pad * 8 || b.yo != (size_t)p.n_pad * 16;
-        bad += b.Tp != (size_t)p.S_pad * p.k_pad * 8 || b.sg != (size_t)p.S_pad * 16;
+        bad += b.Tp != (size_t)p.S_pad * p.k_pad * 8 || b.sg != ((size_t)p.S_pad * 3 + p.k_pad + 16) * 8;   // sigma, 1 / sigma, centre; column means
         bad += b.out != (size_t)S * (PPC_STATS + PPC_OBS) * 8;
         bad += b.total() != b.Ap + b.yo + b.Tp + b.sg + b.out;
         // the bits may not depend on the device: everything but `rounds` is the 1-CU plan

@@ -184,6 +184,127 @@ def test_no_statistic_of_a_gpu_case_sits_on_its_comparison(case):
     assert len(cols) == 8 - len(P.DEGENERATE.get(n, ()))
 
 
+def assert_margins(cases, tag):
+    worst = np.inf
+    for n, S, A, y, th, off, seed, t_rep, t_obs in cases:
+        assert np.isfinite(np.asarray(t_rep, dtype=np.float64)).all()
+        assert np.isfinite(np.asarray(t_obs, dtype=np.float64)).all()
+        assert t_rep.shape == t_obs.shape == (S, 8) and A.shape[0] == n
+        worst = min(worst, P.margins(t_rep, t_obs)[:, P.compared(n)].min())
+    print(tag, "smallest margin", worst)
+    assert worst >= P.MARGIN_FLOOR
+    return worst
+
+
+@pytest.mark.parametrize("k", P.GRID_K)
+def test_no_statistic_of_the_shape_grid_sits_on_its_comparison(k):
+    """The same proof for the 45 (n, S) of the grid at this k (smallest margin of the whole grid:
+    1.9e-7), and the table itself: n-major case numbers, seeds with a non-zero high word, an offset
+    on every third case."""
+    shapes = P.grid_shapes(k)
+    assert len(shapes) == 45 and [c for c, _, _, _ in shapes] == list(range(45))
+    assert [(n, S) for _, n, S, _ in shapes] == [(n, S) for n in P.GRID_N for S in P.GRID_S]
+    assert all(d == 40000 + 100 * k + c for c, _, _, d in shapes)
+    cases = [P.grid_case(k, c) for c in range(45)]
+    for (c, n, S, d), got in zip(shapes, cases):
+        assert got[6] == (0x9E3779B9 << 32) | (d * 2654435761 % 2 ** 32) and got[6] >> 32 != 0
+        assert (got[5] is not None) == (c % 3 == 0)
+    assert_margins(cases, "grid k=%d" % k)
+
+
+def test_no_statistic_of_the_seed_edges_or_the_biased_fits_sits_on_its_comparison():
+    assert P.SEED_EDGES == (0, 2 ** 64 - 1) and P.BIASED == (0.3, 3.0)
+    assert_margins([P.seed_edge_case(s) for s in P.SEED_EDGES], "seed edges")
+    assert assert_margins([P.biased_case(d) for d in P.BIASED], "biased") > 2e-5
+    # the two keys are not the key of any other case, and give other variates
+    a, b = (P.seed_edge_case(s)[7] for s in P.SEED_EDGES)
+    assert not np.array_equal(a, b) and not np.array_equal(a, P.case(65, 3, 130, 11)[4])
+
+
+@pytest.mark.parametrize("delta", P.BIASED)
+def test_the_biased_fits_are_biased(delta):
+    """A condition on the INPUT of the biased cases: every draw's replicated mean lies more than 10
+    (delta = 0.3) or 150 (delta = 3) of the draw's sigma_s from mean(y), the scalar the power sums
+    were once taken about -- and 11.8 or 119 of the replicate's own sd, whose fourth power is what
+    one-pass moments about a shared centre lose of kurt."""
+    n, S, A, y, th, off, seed, t_rep, t_obs = P.biased_case(delta)
+    assert (n, S, A.shape, seed) == (200, 64, (200, 2), (7 << 32) | 5) and np.all(A[:, 0] == 1)
+    shift = np.abs(t_rep[:, 2] - y.mean())
+    in_sigma, in_sd = (shift / th[:, 2]).min(), (shift / t_rep[:, 3]).min()
+    print(delta, "shift in sigma_s", in_sigma, "in sd(y_rep)", in_sd)
+    assert in_sigma > P.BIASED_SD[delta] and P.BIASED_SD == {0.3: 10.0, 3.0: 150.0}
+    assert in_sd > (10 if delta == 0.3 else 100)
+    # the cases of CASES never see this: their draws scatter about the least-squares point
+    A0, y0, _, _, r0, _ = P.case(200, 33, 257, 17)
+    assert (np.abs(r0[:, 2] - y0.mean()) / r0[:, 3]).max() < 0.1
+
+
+# ---- the floors --------------------------------------------------------------------------------------
+@pytest.mark.parametrize("group", P.GROUPS)
+def test_floors_are_not_exceeded_when_recomputed(group):
+    """FLOORS holds, per group and per value of TEN, the larger of the float64 reference's deviation
+    from the long-double one and the effect of the generator's accuracy on the long-double one
+    (ppc_reference.measured_floors): nothing of the device.  The GPU test's bars are 64 x these."""
+    got = P.measured_floors(group)
+    print(group, " ".join("%s %.2e" % kv for kv in zip(P.TEN, got)))
+    assert len(P.TEN) == 10 and len(P.FLOORS[group]) == 10 and set(P.FLOORS) == set(P.GROUPS)
+    for name, v, floor in zip(P.TEN, got, P.FLOORS[group]):
+        assert 0 < v <= floor, (group, name, v, floor)
+        assert floor <= 1.25 * v, (group, name, "the constant is looser than its provenance says")
+
+
+def test_bars_are_64_floors_rounded_up_to_one_digit():
+    assert P.BAR_FACTOR == 64
+    assert [P.round_up_one_digit(x) for x in (9.6e-14, 1e-12, 1.01e-12, 5.2e-11, 2.3e-13)] == \
+        [1e-13, 1e-12, 2e-12, 6e-11, 3e-13]
+    for group in P.GROUPS:
+        b = P.bars(group)
+        assert tuple(b) == P.TEN
+        for name, floor in zip(P.TEN, P.FLOORS[group]):
+            assert 64 * floor <= b[name] < 128 * floor and b[name] <= P.MARGIN_FLOOR / 10
+
+
+# ---- bad input on the reference ----------------------------------------------------------------------
+def test_reference_nan_rules():
+    """What test_ppc_gpu.py asks of the device, on the reference first: a bad draw is NaN in all
+    ten values and nowhere else; a bad point spoils what the definitions say it spoils."""
+    A, y, th, seed, t_rep, t_obs = P.case(65, 3, 130, 11)
+    for bad in (np.nan, np.inf, -np.inf):
+        t = th.copy()
+        t[7, 1] = bad
+        r, o = P.reference(A, y, t, seed)
+        assert np.isnan(r[7]).all() and np.isnan(o[7, 6:]).all() and np.isfinite(o[7, :6]).all()
+        assert np.array_equal(np.delete(r, 7, 0), np.delete(t_rep, 7, 0))
+        assert np.array_equal(np.delete(o, 7, 0), np.delete(t_obs, 7, 0))
+    for bad in (np.nan, 0.0, -0.3, np.inf):
+        t = th.copy()
+        t[129, 3] = bad
+        r, o = P.reference(A, y, t, seed)
+        assert np.isnan(r[129]).all() and np.isnan(o[129, 6:]).all()
+        assert np.array_equal(r[:129], t_rep[:129]) and np.array_equal(o[:129], t_obs[:129])
+    assert list(P.bad_draws(np.array([[1.0, 1.0], [np.nan, 1.0], [1.0, 0.0], [1.0, -1.0], [1.0, np.inf]]))) == \
+        [False, True, True, True, True]
+    An = A.copy()
+    An[40, 2] = np.nan
+    r, o = P.reference(An, y, th, seed)
+    assert np.isnan(r[:, :6]).all() and np.isnan(o[:, 6:]).all() and np.isfinite(o[:, :6]).all()
+    assert np.array_equal(r[:, 6:], t_rep[:, 6:])
+    yn = y.copy()
+    yn[64] = np.nan
+    r, o = P.reference(A, yn, th, seed)
+    assert np.array_equal(r, t_rep) and np.isnan(o).all()
+    yn[64] = np.inf
+    r, o = P.reference(A, yn, th, seed)
+    assert np.array_equal(r, t_rep) and np.all(o[:, 6:] == np.inf)
+    off = np.zeros(65)
+    off[0] = np.nan
+    r, o = P.reference(A, y, th, seed, offset=off)
+    assert np.isnan(r[:, :6]).all() and np.isnan(o[:, :6]).all()
+    assert np.array_equal(r[:, 6:], t_rep[:, 6:]) and np.array_equal(o[:, 6:], t_obs[:, 6:])
+    # a NaN never counts as >=
+    assert P.p_values(r, o)["mean"] == 0.0
+
+
 def test_kurtosis_of_three_values_is_a_constant():
     """Why (3, 1, 2) leaves kurt out of the comparisons and (4, 1, 2) stands beside it."""
     assert P.DEGENERATE == {3: ("kurt",)}

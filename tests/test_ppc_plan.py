@@ -35,7 +35,8 @@ def test_smallest_accepted_shape(plan_exe):
     assert (p["point_tiles"], p["draw_tiles"], p["n_pad"], p["S_pad"], p["k_pad"]) == (1, 1, 64, 64, 16)
     assert p["grid"] == 1 and p["rounds"] == 1
     assert p["bytes_Ap"] == 64 * 16 * 8 and p["bytes_Tp"] == 64 * 16 * 8
-    assert p["bytes_yo"] == 2 * 64 * 8 and p["bytes_sg"] == 2 * 64 * 8
+    # sg: sigma_s, 1 / sigma_s and the draw's centre, then the k_pad column means and the mean offset
+    assert p["bytes_yo"] == 2 * 64 * 8 and p["bytes_sg"] == (3 * 64 + 16 + 16) * 8
     assert p["bytes_out"] == 2 * 10 * 8
     assert p["bytes_total"] == sum(p["bytes_" + key] for key in ("Ap", "yo", "Tp", "sg", "out"))
 
