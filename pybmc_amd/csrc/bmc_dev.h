@@ -58,6 +58,45 @@ __device__ __forceinline__ double wave_sum(double v) {
     return ((r0 + r1) + r2) + r3;
 }
 
+// Sum over every aligned group of W lanes (16 or 64) as an ordered butterfly: at each step the
+// lower lane's partial stands left of the +, so all W lanes end with the same bits.
+template <int W>
+__device__ __forceinline__ double lane_sum_ordered(double s, int lane) {
+#pragma unroll
+    for (int bit = 1; bit < W; bit <<= 1) {
+        const double o = __shfl_xor(s, bit);
+        s = (lane & bit) ? o + s : s + o;
+    }
+    return s;
+}
+
+// Sums and maxima over a workgroup of 256 threads in one fixed order: a tree over the thread
+// partials in red[256] (LDS); every thread returns the result, and red is free again.
+__device__ __forceinline__ double block_sum(double v, double* red) {
+    const int tid = threadIdx.x;
+    red[tid] = v;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) red[tid] += red[tid + s];
+        __syncthreads();
+    }
+    const double r = red[0];
+    __syncthreads();
+    return r;
+}
+__device__ __forceinline__ double block_max(double v, double* red) {
+    const int tid = threadIdx.x;
+    red[tid] = v;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) red[tid] = fmax(red[tid], red[tid + s]);
+        __syncthreads();
+    }
+    const double r = red[0];
+    __syncthreads();
+    return r;
+}
+
 // ---- inter-workgroup granules (cdna guide, Guideline 16 form R2) -------------
 // One naturally aligned 8-byte {tag = epoch, value = 32 data bits} written by ONE
 // agent-scope relaxed atomic store (global_store_dwordx2 sc1) and read by

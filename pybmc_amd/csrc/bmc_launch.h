@@ -340,6 +340,12 @@ inline double student_t_cnu(double nu_) {
     return (double)(lgammal(0.5L * (nu + 1.0L)) - lgammal(0.5L * nu) -
                     0.5L * logl(nu * 3.14159265358979323846264338327950288L));
 }
+// The staging of every scorer (kernels_waic.hip): A (n x k, either layout, any lda) -> Ap
+// [n_pad][k_pad] in whole 64-point tiles and 16-column slabs, y -> yo [n_pad], zero in the padding.
+// offset_row: yo has a second row, yo[n_pad + i] = offset[i] (zeros when offset is NULL).
+hipError_t launch_pad_points(const double* A, const double* y, const double* offset, bool offset_row,
+                             int64_t n, int32_t k, int64_t lda, int32_t col_major, int64_t n_pad,
+                             int32_t k_pad, double* Ap, double* yo, hipStream_t s);
 struct ScoreBuffers {
     size_t Ap, yp, ch, part;   // bytes
 };
@@ -390,10 +396,6 @@ struct PpcArgs {
 hipError_t launch_ppc(const PpcArgs& a, const PpcPlan& p, hipStream_t s);
 
 // ---- power-scaling sensitivity (kernels_sens.hip; plan_sens in bmc_sens_plan.h) -----------------
-// A (n x k, either layout) and y -> Ap [n_pad][k_pad], yo [n_pad], zero in the padding
-hipError_t launch_sens_pad_points(const double* A, const double* y, int64_t n, int32_t k, int64_t lda,
-                                  int32_t col_major, int64_t n_pad, int32_t k_pad, double* Ap, double* yo,
-                                  hipStream_t s);
 // Per draw s of theta (row s at theta + s*ldt: k coefficients, then sigma_s):
 //   lp[0][s] = -1/2 |Lp beta_s - Ly|^2   (Lp = L^-1, Ly = L^-1 b0 for C0 = L L', padded as Ap / yo)
 //   lp[1][s] = -(nu0/2 + 1) log sigma_s^2 - nu0 sigma20 / (2 sigma_s^2)
@@ -416,7 +418,11 @@ struct SensSource {
     int64_t rs0, rs1, cs1;
     int32_t n0;
 };
-// As launch_rank_gather on segments of sens_padded(S) pairs: the S draws in draw order and, when
+// The gather of launch_rank_gather from a SensSource (kernels_rank.hip: the same kernel over another
+// loader): segment jb of keys / idx starts at jb * seg_stride and takes the S draws of column col0 + jb
+hipError_t launch_key_gather(const SensSource& src, int64_t S, int64_t seg_stride, int32_t col0, int32_t Pb,
+                             uint64_t* keys, uint32_t* idx, uint64_t* or_and, uint32_t* flags, hipStream_t s);
+// That gather on segments of sens_padded(S) pairs: the S draws in draw order and, when
 // S is odd, one pad key that no real key exceeds (it stays last under the stable sort and adds no
 // live pass); or_and and flags over the real keys
 hipError_t launch_sens_gather(const SensSource& src, int64_t S, int32_t col0, int32_t Pb, uint64_t* keys,

@@ -34,6 +34,9 @@ BMC_HD double fma_c(double a, double b, double c) {
 #endif
 }
 
+// neither an infinity nor a NaN
+BMC_HD bool is_finite(double x) { return fabs(x) < __builtin_inf(); }
+
 // natural logarithm of a NORMAL double 0 < x (the generators call it with x in [2^-53, 1])
 BMC_HD double log_normal_arg(double x) {
     const double ln2_hi = 6.93147180369123816490e-01, ln2_lo = 1.90821492927058770002e-10;

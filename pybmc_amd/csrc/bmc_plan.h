@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/pybmc_amd.h"
+#include "bmc_psis_plan.h"
 
 namespace bmc {
 
@@ -778,20 +779,18 @@ constexpr int LOO_DIGIT_BITS = 8;
 constexpr int LOO_MAX_SELECT_PASSES = 64 / LOO_DIGIT_BITS;
 constexpr int64_t LOO_MIN_CAP = 64;
 constexpr int64_t LOO_MAX_CAP = 16384;   // the per-point sort is done in LDS: 128 KiB of doubles
-constexpr int LOO_MIN_TAIL = 5;
 
-// M = min(floor(S / 5), ceil(3 sqrt(S))), in integers; 0 when that is below LOO_MIN_TAIL
+// the tail of the fit (bmc_psis_plan.h); 0 when that is below the minimum: nothing is smoothed
+constexpr int LOO_MIN_TAIL = PSIS_MIN_TAIL;
 inline int64_t loo_tail(int64_t n_draws) {
-    int64_t t = 0;   // smallest t with t^2 >= 9 S
-    for (int64_t bit = (int64_t)1 << 31; bit > 0; bit >>= 1)
-        if ((t + bit - 1) * (t + bit - 1) < 9 * n_draws) t += bit;
-    int64_t M = n_draws / 5 < t ? n_draws / 5 : t;
+    const int64_t M = psis_tail_length(n_draws);
     return M < LOO_MIN_TAIL ? 0 : M;
 }
 
 struct LooPlan {
     ScorePlan score;         // tiles and draw splits of every pass over the matrix
     int64_t tail;            // M; 0: no smoothing (S < 25)
+    int32_t grid_points;     // of the generalised Pareto fit on the tail (0: no tail)
     int64_t cap;             // candidate slots per point: a power of two >= 2 (M + 1)
     int32_t select_passes;   // launches of the select kernel (0 or LOO_MAX_SELECT_PASSES)
     int32_t matrix_passes;   // all launches that walk the matrix: score, range, select, append
@@ -802,6 +801,7 @@ inline LooPlan plan_loo(int64_t n_points, int64_t n_draws, int32_t k, int n_cu) 
     LooPlan p;
     p.score = plan_score(n_points, n_draws, k, n_cu);
     p.tail = loo_tail(n_draws);
+    p.grid_points = p.tail > 0 ? psis_grid_points(p.tail) : 0;
     p.cap = LOO_MIN_CAP;
     while (p.cap < 2 * (p.tail + 1)) p.cap <<= 1;
     p.ok = p.cap <= LOO_MAX_CAP;

@@ -175,4 +175,19 @@ struct TileDrawsTV : TileDraws {
     }
 };
 
+// The other operand of the walks that own DRAWS (kernels_ppc.hip, kernels_sens.hip): theta (any ldt)
+// -> Tp [S_pad][k_pad], the k coefficients of every draw in whole tiles and slabs, zero in the
+// padding.  A grid-stride loop: every thread of the launch calls it.
+__device__ __forceinline__ void pad_rows(const double* __restrict__ theta, int64_t S, int64_t ldt,
+                                         int32_t k, int64_t S_pad, int32_t k_pad,
+                                         double* __restrict__ Tp) {
+    const int64_t total = S_pad * k_pad;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
+        const int64_t s = e / k_pad;
+        const int32_t j = (int32_t)(e - s * k_pad);
+        Tp[e] = (s < S && j < k) ? theta[s * ldt + j] : 0.0;
+    }
+}
+
 }  // namespace bmc

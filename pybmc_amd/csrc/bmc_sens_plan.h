@@ -1,13 +1,14 @@
 // Host-only plan of the power-scaling sensitivity (bmc_power_sensitivity): the
-// argument limits, the tail of the Pareto fit, the sort segment (the rank sort's geometry on a
-// segment padded to an even length), the chunks of the weight scan, the split of the columns into
-// batches that fit the device memory, and the scratch sizes.  No HIP types:
+// argument limits, the sort segment (the rank sort's geometry on a segment padded to an even
+// length), the chunks of the weight scan, the split of the columns into batches that fit the device
+// memory, and the scratch sizes; the tail of the Pareto fit is bmc_psis_plan.h's.  No HIP types:
 // tests/sens_plan_check.cpp compiles it with g++.
 #pragma once
 #include <cstddef>
 #include <cstdint>
 #include <string>
 
+#include "bmc_psis_plan.h"
 #include "bmc_rank_plan.h"
 
 namespace bmc {
@@ -21,7 +22,6 @@ constexpr int SENS_PART = 6;                             // partial sums of a (c
 constexpr int SENS_MAX_ALPHAS = 66;                        // a grid of 64 and the two of the sensitivity
 constexpr int SENS_COMPONENTS = 4;                       // prior, likelihood, prior_beta, prior_sigma2
 constexpr int SENS_LOGDENS = 3;                          // lp_beta, lp_sigma2, loglik
-constexpr int SENS_MIN_TAIL = 5;                         // no fit on a shorter tail
 constexpr int SENS_MAX_GRID = 512;                       // grid points of the fit held on chip
 constexpr int SENS_TILE = 64;                            // draws / points of an MFMA tile (SCORE_TILE)
 constexpr int32_t SENS_MAX_K = 256, SENS_MAX_MODELS = 4096;
@@ -29,29 +29,10 @@ constexpr int64_t SENS_MAX_S = RANK_MAX_S - 1;           // the padded segment s
 constexpr int32_t SENS_MAX_BATCH = 65535;               // columns of a batch: the y extent of a grid
 constexpr int64_t SENS_MAX_POINTS = (int64_t)1 << 31;
 
-// M = min(floor(S / 5), ceil(3 sqrt(S))), in integers
-inline int64_t sens_tail_length(int64_t S) {
-    if (S < 1) return 0;
-    int64_t r = 0;                       // ceil(sqrt(9 S)): the smallest r with r r >= 9 S
-    {
-        const int64_t v = 9 * S;
-        int64_t lo = 0, hi = (int64_t)1 << 18;   // (2^18)^2 > 9 * 2^31
-        while (lo < hi) {
-            const int64_t mid = lo + (hi - lo) / 2;
-            if (mid * mid >= v) hi = mid; else lo = mid + 1;
-        }
-        r = lo;
-    }
-    const int64_t fifth = S / 5;
-    return fifth < r ? fifth : r;
-}
-
-// grid points of the generalised Pareto fit on a tail of M: 30 + floor(sqrt(M))
-inline int32_t sens_grid_points(int64_t M) {
-    int64_t rt = 0;
-    while ((rt + 1) * (rt + 1) <= M) ++rt;
-    return (int32_t)(30 + rt);
-}
+// the plan's own names of the one tail rule (bmc_psis_plan.h)
+constexpr int SENS_MIN_TAIL = PSIS_MIN_TAIL;
+inline int64_t sens_tail_length(int64_t S) { return psis_tail_length(S); }
+inline int32_t sens_grid_points(int64_t M) { return psis_grid_points(M); }
 
 // the sort segment of a column: S draws and, when S is odd, one pad key that sorts last
 inline int64_t sens_padded(int64_t S) { return S + (S & 1); }

@@ -118,7 +118,7 @@ int sens_run(bmc_ctx* c, const SensIn& in, const SensOut& out) {
     const int64_t q_pad = ((int64_t)k + SENS_TILE - 1) / SENS_TILE * SENS_TILE;
     const int64_t S64 = (S + SENS_TILE - 1) / SENS_TILE * SENS_TILE;
     const int32_t k_pad = (k + 15) / 16 * 16;
-    const int64_t M = sens_tail_length(S);
+    const int64_t M = psis_tail_length(S);
 
     // small host operands in one block: Lp [q_pad][k_pad], Ly [q_pad], Vt [k][Mm], alphas [nA]
     const size_t n_lp = (size_t)q_pad * k_pad, n_vt = (size_t)k * Mm;
@@ -172,9 +172,8 @@ int sens_run(bmc_ctx* c, const SensIn& in, const SensOut& out) {
     // ---- log densities ------------------------------------------------------------------------
     HIPCHK(c, hipEventRecord(ev.e[0], c->stream));
     HIPCHK(c, hipMemcpyAsync(dptr(o_host), host.data(), host.size() * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, launch_sens_pad_points((const double*)in.A, (const double*)in.y, in.n, k, in.lda,
-                                     in.layout == BMC_COL_MAJOR, n_pad, k_pad, dptr(o_Ap), dptr(o_yo),
-                                     c->stream));
+    HIPCHK(c, launch_pad_points((const double*)in.A, (const double*)in.y, nullptr, false, in.n, k, in.lda,
+                                in.layout == BMC_COL_MAJOR, n_pad, k_pad, dptr(o_Ap), dptr(o_yo), c->stream));
     SensLogdensArgs la;
     la.theta = (const double*)in.theta;
     la.Ap = dptr(o_Ap);

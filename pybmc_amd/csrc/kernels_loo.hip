@@ -18,7 +18,8 @@
 //                  any order: they are sorted next); exp(lw) of every key above it summed per
 //                  lane, tile, lane tree and split, one fixed order
 //   loo_fit        one workgroup per point: bitonic sort of the candidates in LDS, tail and
-//                  cutoff, the Pareto fit, the smoothed tail, elpd_loo_i
+//                  cutoff, the Pareto fit (psis_fit of bmc_psis.h, shared with sens_psis_kernel; its
+//                  grid size is the plan's), the smoothed tail, elpd_loo_i
 //
 // The leave-one-out predictive moments (launch_loo_predict) run the same passes with
 // the PREDICT variants of the last two: the append also records each candidate's draw index and
@@ -39,6 +40,7 @@
 #include "bmc_dev.h"
 #include "bmc_launch.h"
 #include "bmc_plan.h"
+#include "bmc_psis.h"
 #include "bmc_score_tile.h"
 
 namespace bmc {
@@ -47,6 +49,7 @@ namespace {
 
 constexpr uint32_t LF_DONE = 1, LF_APPEND_EQ = 2, LF_NOTAIL = 4, LF_BAD = 8;
 constexpr int LOO_BINS = 1 << LOO_DIGIT_BITS;
+constexpr int LOO_MAX_GRID = 128;   // grid points of the fit held on chip (120 at LOO_MAX_CAP)
 constexpr uint64_t SIGN = 0x8000000000000000ull;
 constexpr size_t LOO_SELECT_LDS = 2 * SC_LDS_DOUBLES * 8 + (size_t)SC_TM * LOO_BINS * 4;
 
@@ -62,7 +65,6 @@ __device__ __forceinline__ double key_value(uint64_t key) {
 __device__ __forceinline__ uint64_t key_top(uint64_t key, uint32_t r) {
     return r == 0 ? 0ull : key >> (64 - r);
 }
-__device__ __forceinline__ bool not_finite(double x) { return !(fabs(x) < __builtin_inf()); }
 
 // The split and point tile of a workgroup (grid of score_tile_kernel: point tile fastest)
 struct TilePos {
@@ -113,7 +115,7 @@ __global__ __launch_bounds__(256) void loo_range_kernel(PassArgs a, uint64_t* __
                     const uint64_t key = ord_key(x);
                     kmin[r] = key < kmin[r] ? key : kmin[r];
                     kmax[r] = key > kmax[r] ? key : kmax[r];
-                    bad[r] |= not_finite(x) ? 1ull : 0ull;
+                    bad[r] |= is_finite(x) ? 0ull : 1ull;
                 }
     });
 #pragma unroll
@@ -353,22 +355,12 @@ __global__ __launch_bounds__(256) void loo_append_kernel(PassArgs a,
     // the 16 lanes that hold draws of the same point: a tree over cl, every lane the same bits
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-        double v = sum[r];
-#pragma unroll
-        for (int bit = 1; bit < 16; bit <<= 1) {
-            const double o = __shfl_xor(v, bit);
-            v = (cl & bit) ? o + v : v + o;
-        }
+        const double v = lane_sum_ordered<16>(sum[r], cl);
         if (cl == 0) body[(int64_t)pos.split * a.n_pad + pi[r]] = v;
         if constexpr (PREDICT)
 #pragma unroll
             for (int f = 0; f < 4; ++f) {
-                double u = psum[f][r];
-#pragma unroll
-                for (int bit = 1; bit < 16; bit <<= 1) {
-                    const double o = __shfl_xor(u, bit);
-                    u = (cl & bit) ? o + u : u + o;
-                }
+                const double u = lane_sum_ordered<16>(psum[f][r], cl);
                 if (cl == 0) pay[((int64_t)pos.split * a.n_pad + pi[r]) * 4 + f] = u;
             }
     }
@@ -422,40 +414,9 @@ __global__ __launch_bounds__(256) void loo_bucket_kernel(PassArgs a,
     for (int r = 0; r < 4; ++r)
 #pragma unroll
         for (int f = 0; f < 3; ++f) {
-            double u = sum[f][r];
-#pragma unroll
-            for (int bit = 1; bit < 16; bit <<= 1) {
-                const double o = __shfl_xor(u, bit);
-                u = (cl & bit) ? o + u : u + o;
-            }
+            const double u = lane_sum_ordered<16>(sum[f][r], cl);
             if (cl == 0 && live[r]) bucket[((int64_t)pos.split * a.n_pad + pi[r]) * 3 + f] = u;
         }
-}
-
-// sums and maxima over the workgroup in one fixed order: thread-strided partials, then a tree
-__device__ __forceinline__ double block_sum(double v, double* red) {
-    const int tid = threadIdx.x;
-    red[tid] = v;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
-__device__ __forceinline__ double block_max(double v, double* red) {
-    const int tid = threadIdx.x;
-    red[tid] = v;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) red[tid] = fmax(red[tid], red[tid + s]);
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
 }
 
 // What the PREDICT fit reads besides the select state: the padded operands and per-draw constants
@@ -480,7 +441,8 @@ __device__ __forceinline__ void predict_store(double* __restrict__ out, int64_t 
 }
 
 // One workgroup per point.  buf: `cap` doubles of LDS, cap >= 2 (M + 1): the sorted candidates in
-// buf[0 .. M] and, behind them, M doubles for the tail's x_j and then its smoothed lw.
+// buf[0 .. M] and, behind them, M doubles for the tail's x_j and then its smoothed lw.  mg: the
+// grid points of the fit (LooPlan::grid_points).
 // PREDICT: 16 bytes of LDS per slot: every sorted candidate stays in buf[0 .. cap), the tail's M
 // doubles are buf[cap .. cap + cap / 2), then the candidates' draw indices, sorted along as the
 // second key; out is [6][n]: elpd_loo_i, pareto_k, loo_mean, loo_sd, loo_pit, ess.
@@ -492,13 +454,13 @@ __global__ __launch_bounds__(256) void loo_fit_kernel(const uint64_t* __restrict
                                                       const double* __restrict__ cand,
                                                       const double* __restrict__ body, int64_t n,
                                                       int64_t n_pad, int64_t splits, int64_t S,
-                                                      int32_t M, int32_t cap,
+                                                      int32_t M, int32_t mg, int32_t cap,
                                                       double* __restrict__ out, FitPayload pa) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     double* buf = (double*)smem_raw;
     __shared__ double red[256];
-    __shared__ double g_theta[128], g_l[128], g_w[128];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ double g_theta[LOO_MAX_GRID], g_l[LOO_MAX_GRID], g_w[LOO_MAX_GRID];
+    const int tid = threadIdx.x;
     const int64_t i = blockIdx.x;
     const uint4 m = meta[i];
     const double inf = __builtin_inf();
@@ -586,52 +548,17 @@ __global__ __launch_bounds__(256) void loo_fit_kernel(const uint64_t* __restrict
     const double cut = llmin - buf[M];   // cutoff, as lw
     const double ecut = exp(cut);
     bool smooth = buf[0] != buf[M - 1];
-    double khat = inf, sigma = 0.0;
+    PsisFit fit{inf, 0.0, false};
     double* xs = PREDICT ? buf + cap : buf + M + 1;
     __syncthreads();   // (buf[M + 1 ..] has been read above)
 
-    // ---- generalised Pareto fit (Zhang & Stephens 2009, as loo::gpdfit) -----------------------
+    // ---- generalised Pareto fit (bmc_psis.h) on the exceedances over the cutoff, ascending ------
     if (smooth) {
-        const double dM = (double)M;
         for (int j = tid; j < M; j += 256) xs[j] = exp(llmin - buf[M - 1 - j]) - ecut;
         __syncthreads();
-        int rt = (int)sqrt(dM);
-        while ((int64_t)rt * rt > M) --rt;
-        while ((int64_t)(rt + 1) * (rt + 1) <= M) ++rt;
-        const int mg = 30 + rt;   // <= 128 for cap <= LOO_MAX_CAP
-        const double xM = xs[M - 1], xq = xs[(M + 2) / 4 - 1];
-        // a wave per grid point: lane-strided sums, then a butterfly (every lane the same bits)
-        for (int j = wave; j < mg; j += 4) {
-            const double th = 1.0 / xM + (1.0 - sqrt((double)mg / ((double)j + 0.5))) / (3.0 * xq);
-            double s = 0.0;
-            for (int e = lane; e < M; e += 64) s += log1p(-th * xs[e]);
-#pragma unroll
-            for (int bit = 1; bit < 64; bit <<= 1) {
-                const double o = __shfl_xor(s, bit);
-                s = (lane & bit) ? o + s : s + o;
-            }
-            const double kj = s / dM;
-            if (lane == 0) {
-                g_theta[j] = th;
-                g_l[j] = dM * (log(-th / kj) - kj - 1.0);
-            }
-        }
-        __syncthreads();
-        if (tid < mg) {
-            double s = 0.0;
-            for (int e = 0; e < mg; ++e) s += exp(g_l[e] - g_l[tid]);   // (+inf: weight 0)
-            g_w[tid] = 1.0 / s;
-        }
-        __syncthreads();
-        double theta = 0.0;
-        for (int e = 0; e < mg; ++e) theta += g_w[e] * g_theta[e];
-        double part = 0.0;
-        for (int e = tid; e < M; e += 256) part += log1p(-theta * xs[e]);
-        const double kraw = block_sum(part, red) / dM;
-        sigma = -kraw / theta;
-        khat = (dM * kraw + 5.0) / (dM + 10.0);
-        if (not_finite(khat)) {
-            khat = inf;
+        fit = psis_fit(xs, M, mg, red, g_theta, g_l, g_w);
+        if (!fit.finite) {
+            fit.khat = inf;
             smooth = false;
         }
     }
@@ -640,14 +567,7 @@ __global__ __launch_bounds__(256) void loo_fit_kernel(const uint64_t* __restrict
     double dpart = 0.0, mpart = -inf;
     for (int j = tid; j < M; j += 256) {
         const double llj = buf[M - 1 - j];
-        double lw;
-        if (smooth) {
-            const double l1p = log1p(-((double)j + 0.5) / (double)M);
-            const double q = fabs(khat) < 1e-30 ? -sigma * l1p : sigma * expm1(-khat * l1p) / khat;
-            lw = log(ecut + q);
-        } else {
-            lw = llmin - llj;
-        }
+        double lw = smooth ? psis_smoothed_lw(j, M, fit, ecut) : llmin - llj;
         lw = lw > 0.0 ? 0.0 : lw;
         xs[j] = lw;
         dpart += exp(lw);
@@ -661,7 +581,7 @@ __global__ __launch_bounds__(256) void loo_fit_kernel(const uint64_t* __restrict
     const double num = mx + log((double)(S - M) * exp(llmin - mx) + block_sum(npart, red));
     if (tid == 0) {
         out[i] = num - den;
-        out[n + i] = khat;
+        out[n + i] = fit.khat;
     }
 
     if constexpr (PREDICT) {
@@ -800,6 +720,7 @@ hipError_t launch_loo_passes(const LooArgs& a, const LooPlan& p, const LooPredic
     const ScorePlan& sp = p.score;
     if (!p.ok || !a.work || sa.S - p.tail < 1 || p.cap < 2 * (p.tail + 1) || p.cap > LOO_MAX_CAP ||
         (p.cap & (p.cap - 1)) != 0 || p.tail != loo_tail(sa.S) || sa.n > 0x7fffffffll ||
+        p.grid_points != (p.tail > 0 ? psis_grid_points(p.tail) : 0) || p.grid_points > LOO_MAX_GRID ||
         (pp && (sa.nu != 0.0 || sa.n_nu != 0)))
         return hipErrorInvalidValue;   // (the fit's grid is one workgroup per point)
     hipError_t e = launch_score(sa, sp, s);   // (checks the shapes and the split plan)
@@ -880,7 +801,7 @@ hipError_t launch_loo_passes(const LooArgs& a, const LooPlan& p, const LooPredic
                            (size_t)pp->fit_lds, s, (const uint64_t*)w.prefix,
                            (const uint64_t*)w.kmin, (const uint4*)w.meta, (const uint32_t*)w.count,
                            (const double*)w.cand, (const double*)w.body, sa.n, n_pad, sp.splits, sa.S,
-                           M, cap, pw.out, fp);
+                           M, p.grid_points, cap, pw.out, fp);
         return hipGetLastError();
     }
     pass(loo_append_kernel<false, TileDraws>, loo_append_kernel<false, TileDrawsT, double>,
@@ -894,7 +815,7 @@ hipError_t launch_loo_passes(const LooArgs& a, const LooPlan& p, const LooPredic
     hipLaunchKernelGGL(loo_fit_kernel<false>, dim3((unsigned)sa.n), dim3(256), fit_lds, s,
                        (const uint64_t*)w.prefix, (const uint64_t*)w.kmin, (const uint4*)w.meta,
                        (const uint32_t*)w.count, (const double*)w.cand, (const double*)w.body, sa.n,
-                       n_pad, sp.splits, sa.S, M, cap, w.out, FitPayload{});
+                       n_pad, sp.splits, sa.S, M, p.grid_points, cap, w.out, FitPayload{});
     return hipGetLastError();
 }
 

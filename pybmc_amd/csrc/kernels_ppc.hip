@@ -4,11 +4,13 @@
 // and per draw s, over the n points: min, max, mean, sd, skew, kurt of y_rep[.][s], sum_i z^2,
 // max_i |z|, and of the observed data sum_i e^2 and max_i |e|, e = (y_i - a_i . beta_s) / sigma_s.
 //
-//   ppc_pad_points  A (either layout, any lda), y, offset -> whole 64-point tiles and 16-column
-//                   slabs, zero in the padding
+//   pad_points      A (either layout, any lda), y, offset -> whole 64-point tiles and 16-column
+//                   slabs, zero in the padding (launch_pad_points of kernels_waic.hip, with the
+//                   offset row)
 //   ppc_col_mean    the column means a_bar of the padded design and the mean offset, each summed in
 //                   one fixed order (a workgroup per 16-column slab, one for the offset)
-//   ppc_pad_draws   theta (any ldt) -> the coefficients in whole 64-draw tiles and 16-column slabs,
+//   ppc_pad_draws   theta (any ldt) -> the coefficients in whole 64-draw tiles and 16-column slabs
+//                   (pad_rows of bmc_score_tile.h),
 //                   sigma_s and 1 / sigma_s per draw (1 in the padding; 1 / sigma_s is NaN for a
 //                   bad draw: a non-finite coefficient, or no finite sigma_s > 0), and the draw's
 //                   centre c_s = a_bar . beta_s + mean(offset) (0 where that is not finite)
@@ -49,25 +51,6 @@
 namespace bmc {
 
 namespace {
-
-__global__ __launch_bounds__(256) void ppc_pad_points_kernel(
-    const double* __restrict__ A, const double* __restrict__ y, const double* __restrict__ offset,
-    int64_t n, int32_t k, int64_t lda, int32_t col_major, int64_t n_pad, int32_t k_pad,
-    double* __restrict__ Ap, double* __restrict__ yo) {
-    const int64_t total = n_pad * k_pad;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
-        const int64_t i = e / k_pad;
-        const int32_t j = (int32_t)(e - i * k_pad);
-        double v = 0.0;
-        if (i < n && j < k) v = col_major ? A[(int64_t)j * lda + i] : A[i * lda + j];
-        Ap[e] = v;
-        if (j == 0) {
-            yo[i] = i < n ? y[i] : 0.0;
-            yo[n_pad + i] = (i < n && offset != nullptr) ? offset[i] : 0.0;
-        }
-    }
-}
 
 // grid: k_pad / 16 workgroups of 1024 threads, one per slab of 16 columns of the padded design, and
 // one more for the offset.  Thread t of a slab's workgroup sums column t & 15 over the rows
@@ -118,13 +101,8 @@ __global__ __launch_bounds__(256) void ppc_pad_draws_kernel(const double* __rest
                                                             const double* __restrict__ cm,
                                                             double* __restrict__ Tp,
                                                             double* __restrict__ sg) {
-    const int64_t total = S_pad * k_pad;
+    pad_rows(theta, S, ldt, k, S_pad, k_pad, Tp);
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
-        const int64_t s = e / k_pad;
-        const int32_t j = (int32_t)(e - s * k_pad);
-        Tp[e] = (s < S && j < k) ? theta[s * ldt + j] : 0.0;
-    }
     // then a thread per draw (all lanes of a wave at work, not one in k_pad): sigma_s, whether the
     // draw is good, and its centre c_s = a_bar . beta_s + mean(offset), the columns in order
     for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < S_pad; s += stride) {
@@ -134,14 +112,14 @@ __global__ __launch_bounds__(256) void ppc_pad_draws_kernel(const double* __rest
         if (s < S) {
             for (int32_t jj = 0; jj < k; ++jj) {
                 const double b = theta[s * ldt + jj];
-                good = good && fabs(b) < __builtin_inf();
+                good = good && is_finite(b);
                 c += cm[jj] * b;
             }
         }
         c += cm[k_pad];
         sg[s] = sigma;
         sg[S_pad + s] = good ? 1.0 / sigma : __builtin_nan("");
-        sg[2 * S_pad + s] = fabs(c) < __builtin_inf() ? c : 0.0;
+        sg[2 * S_pad + s] = is_finite(c) ? c : 0.0;
     }
 }
 
@@ -307,12 +285,9 @@ hipError_t launch_ppc(const PpcArgs& a, const PpcPlan& p, hipStream_t s) {
         p.point_tiles != want.point_tiles || p.draw_tiles != want.draw_tiles || p.n_pad != want.n_pad ||
         p.S_pad != want.S_pad || p.k_pad != want.k_pad || p.grid != want.grid || p.grid > 0x7fffffffll)
         return hipErrorInvalidValue;
-    {
-        int64_t blocks = (p.n_pad * p.k_pad + 255) / 256;
-        if (blocks > 8192) blocks = 8192;
-        hipLaunchKernelGGL(ppc_pad_points_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a.A, a.y,
-                           a.offset, a.n, a.k, a.lda, a.col_major, p.n_pad, p.k_pad, a.Ap, a.yo);
-    }
+    const hipError_t e = launch_pad_points(a.A, a.y, a.offset, true, a.n, a.k, a.lda, a.col_major, p.n_pad,
+                                           p.k_pad, a.Ap, a.yo, s);
+    if (e != hipSuccess) return e;
     double* cm = a.sg + 3 * p.S_pad;   // the column means and the mean offset, behind the three rows
     hipLaunchKernelGGL(ppc_col_mean_kernel, dim3((unsigned)(p.k_pad / 16 + 1)), dim3(1024), 0, s,
                        (const double*)a.Ap, (const double*)a.yo, a.n, p.n_pad, p.k_pad, cm);

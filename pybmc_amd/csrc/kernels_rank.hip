@@ -1,6 +1,8 @@
 // Rank normalisation of sampled chains: the exact rank of
 // every split draw of a column, on the raw and on the folded values, as z-scores.
-//   rank_gather       samples -> (key, index) pairs, one segment per column; non-finite flag
+//   key_gather        samples -> (key, index) pairs, one segment per column; non-finite flag.  One
+//                     template over what it reads: the split draws of a RankShape (launch_rank_gather)
+//                     or the two sources of a SensSource (launch_key_gather, for kernels_sens.hip)
 //   rank_count        per-tile digit histogram of one LSD pass
 //   rank_scan         per segment: the histograms -> the first output position of (tile, digit)
 //   rank_scatter      the stable scatter of one pass (ranks inside a tile by wave ballots)
@@ -50,7 +52,7 @@ __device__ inline void block_or_and(uint64_t o, uint64_t a, uint64_t* or_and) {
     }
 }
 
-__global__ void rank_init_kernel(int32_t Pb, uint64_t* __restrict__ or_and, uint32_t* __restrict__ flags) {
+__global__ void key_init_kernel(int32_t Pb, uint64_t* __restrict__ or_and, uint32_t* __restrict__ flags) {
     const int32_t j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j < Pb) {
         or_and[2 * j] = 0;
@@ -66,23 +68,38 @@ __device__ inline double rank_load(const RankShape& r, uint32_t e, int32_t col) 
     return r.x[row * r.ld + col];
 }
 
-// grid: gblocks * Pb, column fastest (the workgroups that read the same rows run together)
-__global__ __launch_bounds__(RANK_BLOCK) void rank_gather_kernel(
-    RankShape r, uint64_t* __restrict__ keys, uint32_t* __restrict__ idx,
-    uint64_t* __restrict__ or_and, uint32_t* __restrict__ flags) {
-    const int32_t jb = blockIdx.x % r.Pb;
-    const int64_t e0 = (int64_t)(blockIdx.x / r.Pb) * RANK_GATHER_TILE;
+// What the gather reads: element e of column col of the split draws of a RankShape, or of the two
+// sources of a SensSource
+struct RankLoad {
+    RankShape r;
+    __device__ double operator()(int64_t e, int32_t col) const { return rank_load(r, (uint32_t)e, col); }
+};
+struct SensLoad {
+    SensSource src;
+    __device__ double operator()(int64_t e, int32_t col) const {
+        return col < src.n0 ? src.p0[e * src.rs0 + col] : src.p1[e * src.rs1 + (int64_t)(col - src.n0) * src.cs1];
+    }
+};
+
+// grid: gblocks * Pb, column fastest (the workgroups that read the same rows run together).
+// Segment jb of keys / idx starts at jb * seg_stride and takes the S draws of column col0 + jb.
+template <class Load>
+__global__ __launch_bounds__(RANK_BLOCK) void key_gather_kernel(
+    Load load, int64_t S, int64_t seg_stride, int32_t col0, int32_t Pb, uint64_t* __restrict__ keys,
+    uint32_t* __restrict__ idx, uint64_t* __restrict__ or_and, uint32_t* __restrict__ flags) {
+    const int32_t jb = blockIdx.x % Pb;
+    const int64_t e0 = (int64_t)(blockIdx.x / Pb) * RANK_GATHER_TILE;
     uint64_t o = 0, a = ~0ull;
     bool bad = false;
 #pragma unroll
     for (int it = 0; it < RANK_GATHER_ITEMS; ++it) {
         const int64_t e = e0 + it * RANK_BLOCK + threadIdx.x;
-        if (e < r.S) {
-            const double x = rank_load(r, (uint32_t)e, r.col0 + jb);
+        if (e < S) {
+            const double x = load(e, col0 + jb);
             const uint64_t k = rank_key(x);
-            bad = bad || !(fabs(x) <= 1.79769313486231570815e308);
-            keys[(int64_t)jb * r.S + e] = k;
-            idx[(int64_t)jb * r.S + e] = (uint32_t)e;
+            bad = bad || !is_finite(x);
+            keys[(int64_t)jb * seg_stride + e] = k;
+            idx[(int64_t)jb * seg_stride + e] = (uint32_t)e;
             o |= k;
             a &= k;
         }
@@ -323,9 +340,19 @@ inline bool rank_shape_ok(const RankShape& r) {
 hipError_t launch_rank_gather(const RankShape& r, uint64_t* keys, uint32_t* idx, uint64_t* or_and,
                               uint32_t* flags, hipStream_t s) {
     if (!rank_shape_ok(r)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(rank_init_kernel, dim3((r.Pb + 255) / 256), dim3(256), 0, s, r.Pb, or_and, flags);
-    hipLaunchKernelGGL(rank_gather_kernel, dim3((unsigned)(gather_blocks(r) * r.Pb)), dim3(RANK_BLOCK), 0, s,
-                       r, keys, idx, or_and, flags);
+    hipLaunchKernelGGL(key_init_kernel, dim3((r.Pb + 255) / 256), dim3(256), 0, s, r.Pb, or_and, flags);
+    hipLaunchKernelGGL(key_gather_kernel<RankLoad>, dim3((unsigned)(gather_blocks(r) * r.Pb)), dim3(RANK_BLOCK),
+                       0, s, RankLoad{r}, r.S, r.S, r.col0, r.Pb, keys, idx, or_and, flags);
+    return hipGetLastError();
+}
+
+hipError_t launch_key_gather(const SensSource& src, int64_t S, int64_t seg_stride, int32_t col0, int32_t Pb,
+                             uint64_t* keys, uint32_t* idx, uint64_t* or_and, uint32_t* flags, hipStream_t s) {
+    const int64_t gblocks = (S + RANK_GATHER_TILE - 1) / RANK_GATHER_TILE;
+    if (gblocks * Pb > 0x7fffffffll) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(key_init_kernel, dim3((Pb + 255) / 256), dim3(256), 0, s, Pb, or_and, flags);
+    hipLaunchKernelGGL(key_gather_kernel<SensLoad>, dim3((unsigned)(gblocks * Pb)), dim3(RANK_BLOCK), 0, s,
+                       SensLoad{src}, S, seg_stride, col0, Pb, keys, idx, or_and, flags);
     return hipGetLastError();
 }
 
@@ -361,7 +388,7 @@ hipError_t launch_rank_pick(const RankShape& r, const uint64_t* keys, const Rank
 hipError_t launch_rank_fold(const RankShape& r, uint64_t* keys, const double* q, int32_t med_slot,
                             uint64_t* or_and, hipStream_t s) {
     if (!rank_shape_ok(r) || med_slot < 0 || med_slot >= RANK_Q_SLOTS) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(rank_init_kernel, dim3((r.Pb + 255) / 256), dim3(256), 0, s, r.Pb, or_and,
+    hipLaunchKernelGGL(key_init_kernel, dim3((r.Pb + 255) / 256), dim3(256), 0, s, r.Pb, or_and,
                        (uint32_t*)nullptr);
     hipLaunchKernelGGL(rank_fold_kernel, dim3((unsigned)(gather_blocks(r) * r.Pb)), dim3(RANK_BLOCK), 0, s, r.S,
                        gather_blocks(r), keys, q, med_slot, or_and);

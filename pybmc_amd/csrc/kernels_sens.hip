@@ -1,18 +1,23 @@
 // Power-scaling sensitivity of a sampled fit: the prior or
 // the likelihood raised to a power alpha near 1, the draws importance-reweighted with Pareto
 // smoothing, the shift of every marginal measured by the cumulative Jensen-Shannon distance.
-//   sens_pad_points   A (either layout), y -> whole 64-point tiles and 16-column slabs, zero padded
-//   sens_pad_draws    theta -> the coefficients in whole 64-draw tiles and 16-column slabs
+//   pad_points        A (either layout), y -> whole 64-point tiles and 16-column slabs, zero padded
+//                     (launch_pad_points of kernels_waic.hip, called by the entry point)
+//   sens_pad_draws    theta -> the coefficients in whole 64-draw tiles and 16-column slabs (pad_rows
+//                     of bmc_score_tile.h)
 //   sens_rss_tile     workgroup = 64 draws x ALL point tiles (the layout of ppc_tile_kernel):
 //                     sum_i (y_i - a_i . beta_s)^2 on the f64 matrix cores, one fixed order.  Run
 //                     twice: on the data (the likelihood) and on (L^-1, L^-1 b0), whose "residual
 //                     sum" is the prior's quadratic form (beta - b0)' C0^-1 (beta - b0)
 //   sens_logdens      lp_beta, lp_sigma2, loglik per draw and the component vectors
 //   sens_omega        the model-weight columns beta . Vt + 1 / M
-//   sens_gather       a column -> (key, index) pairs of an even-length segment (one pad key that
-//                     sorts last when S is odd), OR / AND masks of the real keys, non-finite flag
+//   sens_gather       a column -> (key, index) pairs of an even-length segment, OR / AND masks of
+//                     the real keys, non-finite flag (launch_key_gather: the gather of
+//                     kernels_rank.hip over a SensSource), then sens_pad_key: one pad key that
+//                     sorts last when S is odd
 //   sens_psis         workgroup = (component, alpha): tail of the sorted log density, generalised
-//                     Pareto fit, smoothed tail, normalising sum -> weights [S][W], pareto_k
+//                     Pareto fit (bmc_psis.h, shared with loo_fit_kernel), smoothed tail,
+//                     normalising sum -> weights [S][W], pareto_k
 //   sens_chunk_sum / sens_chunk_scan / sens_cjs / sens_finish
 //                     the weights gathered along a sorted column, prefix-summed (chunk sums, a
 //                     serial scan of the chunks, then the chunk again from its offset), the
@@ -23,6 +28,7 @@
 #include "bmc_dev.h"
 #include "bmc_launch.h"
 #include "bmc_plan.h"
+#include "bmc_psis.h"
 #include "bmc_score_tile.h"
 
 namespace bmc {
@@ -31,35 +37,11 @@ namespace {
 
 static_assert(SENS_TILE == SCORE_TILE, "the plan's tile is the score tile");
 constexpr double LN2 = 0.69314718055994530942;
-constexpr double DBL_BIG = 1.79769313486231570815e308;
-
-__device__ __forceinline__ bool finite_d(double x) { return fabs(x) <= DBL_BIG; }
-
-__global__ __launch_bounds__(256) void sens_pad_points_kernel(
-    const double* __restrict__ A, const double* __restrict__ y, int64_t n, int32_t k, int64_t lda,
-    int32_t col_major, int64_t n_pad, int32_t k_pad, double* __restrict__ Ap, double* __restrict__ yo) {
-    const int64_t total = n_pad * k_pad;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
-        const int64_t i = e / k_pad;
-        const int32_t j = (int32_t)(e - i * k_pad);
-        double v = 0.0;
-        if (i < n && j < k) v = col_major ? A[(int64_t)j * lda + i] : A[i * lda + j];
-        Ap[e] = v;
-        if (j == 0) yo[i] = i < n ? y[i] : 0.0;
-    }
-}
 
 __global__ __launch_bounds__(256) void sens_pad_draws_kernel(const double* __restrict__ theta, int64_t S,
                                                              int64_t ldt, int32_t k, int64_t S_pad,
                                                              int32_t k_pad, double* __restrict__ Tp) {
-    const int64_t total = S_pad * k_pad;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
-        const int64_t s = e / k_pad;
-        const int32_t j = (int32_t)(e - s * k_pad);
-        Tp[e] = (s < S && j < k) ? theta[s * ldt + j] : 0.0;
-    }
+    pad_rows(theta, S, ldt, k, S_pad, k_pad, Tp);
 }
 
 // grid: one workgroup per draw tile.  A padded point has a zero row and a zero target: it adds
@@ -108,8 +90,8 @@ __global__ __launch_bounds__(256) void sens_logdens_kernel(
     if (s >= S) return;
     const double* th = theta + s * ldt;
     const double sigma = th[k];
-    bool ok = finite_d(sigma) && sigma > 0.0;
-    for (int32_t j = 0; j < k; ++j) ok = ok && finite_d(th[j]);
+    bool ok = is_finite(sigma) && sigma > 0.0;
+    for (int32_t j = 0; j < k; ++j) ok = ok && is_finite(th[j]);
     const double nan = __builtin_nan("");
     double lb = nan, ls = nan, ll = nan;
     if (ok) {
@@ -142,61 +124,6 @@ __global__ __launch_bounds__(256) void sens_omega_kernel(const double* __restric
     omega[e] = acc + 1.0 / (double)M;
 }
 
-__global__ void sens_init_kernel(int32_t Pb, uint64_t* __restrict__ or_and, uint32_t* __restrict__ flags) {
-    const int32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < Pb) {
-        or_and[2 * j] = 0;
-        or_and[2 * j + 1] = ~0ull;
-        flags[j] = 0;
-    }
-}
-
-__device__ __forceinline__ double sens_load(const SensSource& src, int64_t e, int32_t col) {
-    return col < src.n0 ? src.p0[e * src.rs0 + col] : src.p1[e * src.rs1 + (int64_t)(col - src.n0) * src.cs1];
-}
-
-constexpr int GATHER_ITEMS = 4;
-constexpr int GATHER_TILE = 256 * GATHER_ITEMS;
-
-// grid: gblocks * Pb, column fastest
-__global__ __launch_bounds__(256) void sens_gather_kernel(SensSource src, int64_t S, int64_t S_pad, int32_t col0,
-                                                          int32_t Pb, uint64_t* __restrict__ keys,
-                                                          uint32_t* __restrict__ idx,
-                                                          uint64_t* __restrict__ or_and,
-                                                          uint32_t* __restrict__ flags) {
-    __shared__ uint64_t red[2][4];
-    const int32_t jb = blockIdx.x % Pb;
-    const int64_t e0 = (int64_t)(blockIdx.x / Pb) * GATHER_TILE;
-    uint64_t o = 0, a = ~0ull;
-    bool bad = false;
-#pragma unroll
-    for (int it = 0; it < GATHER_ITEMS; ++it) {
-        const int64_t e = e0 + it * 256 + threadIdx.x;
-        if (e < S) {
-            const double x = sens_load(src, e, col0 + jb);
-            const uint64_t key = rank_key(x);
-            bad = bad || !finite_d(x);
-            keys[(int64_t)jb * S_pad + e] = key;
-            idx[(int64_t)jb * S_pad + e] = (uint32_t)e;
-            o |= key;
-            a &= key;
-        }
-    }
-    if (__ballot(bad) != 0 && (threadIdx.x & 63) == 0) atomicOr(flags + jb, 1u);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        o |= (uint64_t)__shfl_xor((unsigned long long)o, off, 64);
-        a &= (uint64_t)__shfl_xor((unsigned long long)a, off, 64);
-    }
-    if ((threadIdx.x & 63) == 0) red[0][threadIdx.x >> 6] = o, red[1][threadIdx.x >> 6] = a;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int i = 1; i < 4; ++i) o |= red[0][i], a &= red[1][i];
-        atomicOr((unsigned long long*)or_and + 2 * jb, (unsigned long long)o);
-        atomicAnd((unsigned long long*)or_and + 2 * jb + 1, (unsigned long long)a);
-    }
-}
-
 // The pad of an odd-length segment: a key not below any real key that agrees with them on every
 // digit they share, so that it adds no live pass; it starts last and a stable sort leaves it there.
 __global__ void sens_pad_key_kernel(int32_t Pb, int64_t S, int64_t S_pad, const uint64_t* __restrict__ or_and,
@@ -210,20 +137,6 @@ __global__ void sens_pad_key_kernel(int32_t Pb, int64_t S, int64_t S_pad, const 
             pad |= (uint64_t)(RANK_DIGITS - 1) << (RANK_DIGIT_BITS * d);
     keys[(int64_t)j * S_pad + S] = pad;
     idx[(int64_t)j * S_pad + S] = (uint32_t)S;
-}
-
-// sums over the workgroup in one fixed order: a tree over the 256 thread partials
-__device__ __forceinline__ double block_sum(double v, double* red) {
-    const int tid = threadIdx.x;
-    red[tid] = v;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
 }
 
 // [lo, hi): the run of keys equal to k[p] inside k[0, n)
@@ -256,7 +169,7 @@ __global__ __launch_bounds__(256) void sens_psis_kernel(
     double* __restrict__ Wt, double* __restrict__ khat_out) {
     __shared__ double red[256];
     __shared__ double g_theta[SENS_MAX_GRID], g_l[SENS_MAX_GRID], g_w[SENS_MAX_GRID];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int32_t w = blockIdx.x, W = gridDim.x;
     const int32_t c = w / n_alphas;
     const double alpha = alphas[w - c * n_alphas];
@@ -272,50 +185,20 @@ __global__ __launch_bounds__(256) void sens_psis_kernel(
     auto lw_at = [&](int64_t p) { return am1 * rank_unkey(k[p]) - mx; };
 
     bool smooth = false;
-    double khat = inf, sigma = 0.0, ecut = 0.0;
-    if (M >= SENS_MIN_TAIL) {
+    double ecut = 0.0;
+    PsisFit fit{inf, 0.0, false};
+    if (M >= PSIS_MIN_TAIL) {
         // ascending tail: lt[j] = lw of u = M - 1 - j; the cutoff is u = M
         smooth = lw_at(pos(M - 1)) != lw_at(pos(0));
         ecut = exp(lw_at(pos(M)));
     }
     if (smooth) {
-        const double dM = (double)M;
         for (int j = tid; j < M; j += 256) xs[j] = exp(lw_at(pos(M - 1 - j))) - ecut;
         __syncthreads();
-        // mg = sens_grid_points(M) <= SENS_MAX_GRID grid points
-        const double xM = xs[M - 1], xq = xs[(M + 2) / 4 - 1];
-        // a wave per grid point: lane-strided sums, then a butterfly (every lane the same bits)
-        for (int j = wave; j < mg; j += 4) {
-            const double th = 1.0 / xM + (1.0 - sqrt((double)mg / ((double)j + 0.5))) / (3.0 * xq);
-            double s = 0.0;
-            for (int e = lane; e < M; e += 64) s += log1p(-th * xs[e]);
-#pragma unroll
-            for (int bit = 1; bit < 64; bit <<= 1) {
-                const double o = __shfl_xor(s, bit);
-                s = (lane & bit) ? o + s : s + o;
-            }
-            const double kj = s / dM;
-            if (lane == 0) {
-                g_theta[j] = th;
-                g_l[j] = dM * (log(-th / kj) - kj - 1.0);
-            }
-        }
-        __syncthreads();
-        for (int j = tid; j < mg; j += 256) {
-            double s = 0.0;
-            for (int e = 0; e < mg; ++e) s += exp(g_l[e] - g_l[j]);
-            g_w[j] = 1.0 / s;
-        }
-        __syncthreads();
-        double theta = 0.0;
-        for (int e = 0; e < mg; ++e) theta += g_w[e] * g_theta[e];
-        double part = 0.0;
-        for (int e = tid; e < M; e += 256) part += log1p(-theta * xs[e]);
-        const double kraw = block_sum(part, red) / dM;
-        sigma = -kraw / theta;
-        khat = (dM * kraw + 5.0) / (dM + 10.0);
-        if (!finite_d(khat)) {
-            khat = inf;
+        // mg = psis_grid_points(M) <= SENS_MAX_GRID grid points
+        fit = psis_fit(xs, M, mg, red, g_theta, g_l, g_w);
+        if (!fit.finite) {
+            fit.khat = inf;
             smooth = false;
         }
     }
@@ -323,9 +206,7 @@ __global__ __launch_bounds__(256) void sens_psis_kernel(
     double part = 0.0;
     if (smooth) {
         for (int j = tid; j < M; j += 256) {
-            const double l1p = log1p(-((double)j + 0.5) / (double)M);
-            const double q = fabs(khat) < 1e-30 ? -sigma * l1p : sigma * expm1(-khat * l1p) / khat;
-            double lw = log(ecut + q);
+            double lw = psis_smoothed_lw(j, M, fit, ecut);
             lw = lw > 0.0 ? 0.0 : lw;
             const double e = exp(lw);
             xs[j] = e;
@@ -353,7 +234,7 @@ __global__ __launch_bounds__(256) void sens_psis_kernel(
         }
         Wt[(int64_t)ix[p] * W + w] = e / sum;
     }
-    if (tid == 0) khat_out[w] = khat;
+    if (tid == 0) khat_out[w] = fit.khat;
 }
 
 // The weights of a thread's SENS_ITEMS consecutive sorted draws, SENS_WG vectors from w0
@@ -487,12 +368,7 @@ __global__ __launch_bounds__(SENS_BLOCK) void sens_cjs_kernel(
         for (int g = 0; g < SENS_WG; ++g)
 #pragma unroll
             for (int f = 0; f < SENS_PART; ++f) {
-                double s = acc[g][f];
-#pragma unroll
-                for (int bit = 1; bit < 64; bit <<= 1) {
-                    const double o = __shfl_xor(s, bit);
-                    s = (lane & bit) ? o + s : s + o;
-                }
+                const double s = lane_sum_ordered<64>(acc[g][f], lane);
                 if (lane == 0) red[g * SENS_PART + f][wave] = s;
             }
         __syncthreads();
@@ -533,16 +409,6 @@ inline unsigned capped_blocks(int64_t elements) {
 
 }  // namespace
 
-hipError_t launch_sens_pad_points(const double* A, const double* y, int64_t n, int32_t k, int64_t lda,
-                                  int32_t col_major, int64_t n_pad, int32_t k_pad, double* Ap, double* yo,
-                                  hipStream_t s) {
-    if (n < 1 || k < 1 || n_pad < n || n_pad % SENS_TILE || k_pad < k || k_pad % SC_KT)
-        return hipErrorInvalidValue;
-    hipLaunchKernelGGL(sens_pad_points_kernel, dim3(capped_blocks(n_pad * k_pad)), dim3(256), 0, s, A, y, n, k,
-                       lda, col_major, n_pad, k_pad, Ap, yo);
-    return hipGetLastError();
-}
-
 hipError_t launch_sens_logdens(const SensLogdensArgs& a, hipStream_t s) {
     const int64_t S64 = (a.S + SENS_TILE - 1) / SENS_TILE * SENS_TILE;
     if (a.S < 1 || a.k < 1 || a.k > SENS_MAX_K || a.ldt < (int64_t)a.k + 1 || a.k_pad < a.k || a.k_pad % SC_KT ||
@@ -570,12 +436,9 @@ hipError_t launch_sens_logdens(const SensLogdensArgs& a, hipStream_t s) {
 
 hipError_t launch_sens_gather(const SensSource& src, int64_t S, int32_t col0, int32_t Pb, uint64_t* keys,
                               uint32_t* idx, uint64_t* or_and, uint32_t* flags, hipStream_t s) {
-    const int64_t gblocks = (S + GATHER_TILE - 1) / GATHER_TILE;
-    if (S < 1 || S > SENS_MAX_S || Pb < 1 || col0 < 0 || gblocks * Pb > 0x7fffffffll)
-        return hipErrorInvalidValue;
-    hipLaunchKernelGGL(sens_init_kernel, dim3((Pb + 255) / 256), dim3(256), 0, s, Pb, or_and, flags);
-    hipLaunchKernelGGL(sens_gather_kernel, dim3((unsigned)(gblocks * Pb)), dim3(256), 0, s, src, S,
-                       sens_padded(S), col0, Pb, keys, idx, or_and, flags);
+    if (S < 1 || S > SENS_MAX_S || Pb < 1 || col0 < 0) return hipErrorInvalidValue;
+    const hipError_t e = launch_key_gather(src, S, sens_padded(S), col0, Pb, keys, idx, or_and, flags, s);
+    if (e != hipSuccess) return e;   // (more workgroups than a grid holds)
     hipLaunchKernelGGL(sens_pad_key_kernel, dim3((Pb + 255) / 256), dim3(256), 0, s, Pb, S, sens_padded(S),
                        (const uint64_t*)or_and, keys, idx);
     return hipGetLastError();
@@ -584,12 +447,12 @@ hipError_t launch_sens_gather(const SensSource& src, int64_t S, int32_t col0, in
 hipError_t launch_sens_psis(const uint64_t* keys, const uint32_t* idx, int64_t S, int32_t n_components,
                             int32_t n_alphas, const double* d_alphas, double* xs, double* Wt, double* khat,
                             hipStream_t s) {
-    const int64_t M = sens_tail_length(S);
+    const int64_t M = psis_tail_length(S);
     if (S < 2 || S > SENS_MAX_S || n_components < 1 || n_components > SENS_COMPONENTS || n_alphas < 1 ||
-        n_alphas > SENS_MAX_ALPHAS || (M >= SENS_MIN_TAIL && sens_grid_points(M) > SENS_MAX_GRID))
+        n_alphas > SENS_MAX_ALPHAS || (M >= PSIS_MIN_TAIL && psis_grid_points(M) > SENS_MAX_GRID))
         return hipErrorInvalidValue;
     hipLaunchKernelGGL(sens_psis_kernel, dim3((unsigned)(n_components * n_alphas)), dim3(256), 0, s, keys, idx,
-                       S, sens_padded(S), (int32_t)M, M >= SENS_MIN_TAIL ? sens_grid_points(M) : 0, n_alphas,
+                       S, sens_padded(S), (int32_t)M, M >= PSIS_MIN_TAIL ? psis_grid_points(M) : 0, n_alphas,
                        d_alphas, xs, Wt, khat);
     return hipGetLastError();
 }

@@ -3,8 +3,9 @@
 //   ll[i][s] = -1/2 log(2 pi) - log sigma_s - (y_i - a_i . beta_s)^2 / (2 sigma_s^2)
 // and per point i, over the S draws: logsumexp_s ll - log S, var_s ll (ddof 1), mean_s ll.
 //
-//   score_pad      A (either layout, any lda) and y -> whole 64-point tiles and 16-column slabs,
-//                  zero in the padding
+//   pad_points     A (either layout, any lda) and y -> whole 64-point tiles and 16-column slabs,
+//                  zero in the padding; with an offset row for kernels_ppc.hip (launch_pad_points:
+//                  the one staging kernel of launch_score, launch_ppc and the sensitivity)
 //   score_consts   per draw: c_s = -1/2 log(2 pi) - log sigma_s,  h_s = 1 / (2 sigma_s^2)
 //                  (score_consts_t: the constants of the Student-t density, ScoreArgs::nu > 0;
 //                  score_consts_tv: the same at a nu per draw, ScoreArgs::n_nu > 0)
@@ -50,10 +51,12 @@ __device__ __forceinline__ LlState ll_merge(const LlState& a, const LlState& b) 
     return r;
 }
 
-__global__ __launch_bounds__(256) void score_pad_kernel(
-    const double* __restrict__ A, const double* __restrict__ y, int64_t n, int32_t k, int64_t lda,
-    int32_t col_major, int64_t n_pad, int32_t k_pad, double* __restrict__ Ap,
-    double* __restrict__ yp) {
+// OFFSET_ROW: yo has a second row, the offsets (zeros without one)
+template <bool OFFSET_ROW>
+__global__ __launch_bounds__(256) void pad_points_kernel(
+    const double* __restrict__ A, const double* __restrict__ y, const double* __restrict__ offset,
+    int64_t n, int32_t k, int64_t lda, int32_t col_major, int64_t n_pad, int32_t k_pad,
+    double* __restrict__ Ap, double* __restrict__ yo) {
     const int64_t total = n_pad * k_pad;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
@@ -62,7 +65,10 @@ __global__ __launch_bounds__(256) void score_pad_kernel(
         double v = 0.0;
         if (i < n && j < k) v = col_major ? A[(int64_t)j * lda + i] : A[i * lda + j];
         Ap[e] = v;
-        if (j == 0) yp[i] = i < n ? y[i] : 0.0;
+        if (j == 0) {
+            yo[i] = i < n ? y[i] : 0.0;
+            if constexpr (OFFSET_ROW) yo[n_pad + i] = (i < n && offset != nullptr) ? offset[i] : 0.0;
+        }
     }
 }
 
@@ -255,6 +261,22 @@ ScoreBuffers score_buffers(const ScorePlan& p, int64_t n_draws) {
     return b;
 }
 
+hipError_t launch_pad_points(const double* A, const double* y, const double* offset, bool offset_row,
+                             int64_t n, int32_t k, int64_t lda, int32_t col_major, int64_t n_pad,
+                             int32_t k_pad, double* Ap, double* yo, hipStream_t s) {
+    if (n < 1 || k < 1 || n_pad < n || n_pad % SC_TM || k_pad < k || k_pad % SC_KT)
+        return hipErrorInvalidValue;
+    int64_t blocks = (n_pad * k_pad + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    if (offset_row)
+        hipLaunchKernelGGL(pad_points_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, A, y, offset, n,
+                           k, lda, col_major, n_pad, k_pad, Ap, yo);
+    else
+        hipLaunchKernelGGL(pad_points_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, A, y, offset, n,
+                           k, lda, col_major, n_pad, k_pad, Ap, yo);
+    return hipGetLastError();
+}
+
 hipError_t launch_score(const ScoreArgs& a, const ScorePlan& p, hipStream_t s) {
     if (a.n < 1 || a.S < 2 || a.k < 1 || a.k > SCORE_MAX_K || a.ldt < a.k + 1 ||
         a.lda < (a.col_major ? a.n : (int64_t)a.k) || !(a.nu >= 0.0 && a.nu < __builtin_inf()) ||
@@ -267,12 +289,9 @@ hipError_t launch_score(const ScoreArgs& a, const ScorePlan& p, hipStream_t s) {
     const uint64_t groups = (uint64_t)p.splits * (uint64_t)p.point_tiles;
     if (groups > 0x7fffffffull || p.point_tiles > 0x7fffffffll) return hipErrorInvalidValue;
     const int64_t n_pad = p.point_tiles * SC_TM;
-    {
-        int64_t blocks = (n_pad * p.k_pad + 255) / 256;
-        if (blocks > 8192) blocks = 8192;
-        hipLaunchKernelGGL(score_pad_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a.A, a.y, a.n,
-                           a.k, a.lda, a.col_major, n_pad, p.k_pad, a.Ap, a.yp);
-    }
+    const hipError_t e = launch_pad_points(a.A, a.y, nullptr, false, a.n, a.k, a.lda, a.col_major, n_pad,
+                                           p.k_pad, a.Ap, a.yp, s);
+    if (e != hipSuccess) return e;
     {
         const int64_t blocks = (a.S + 255) / 256;
         if (blocks > 0x7fffffffll) return hipErrorInvalidValue;

@@ -28,6 +28,11 @@ static int check(int64_t n, int64_t S, int k, int n_cu) {
     bad += p.tail != M;
     bad += p.tail > 0 && S < 25;
     bad += p.tail == 0 && S >= 25;
+    // the grid of the fit: 30 + floor(sqrt(M)) points, none without a tail; a plan that is ok holds
+    // them on chip (128 of each array)
+    int64_t rt = 0;
+    while ((rt + 1) * (rt + 1) <= M) ++rt;
+    bad += p.grid_points != (M > 0 ? 30 + rt : 0) || (p.ok && p.grid_points > 128);
     // the cap: a power of two, room for the tail and the cutoff (M + 1) and as much again for the
     // fit's scratch; the plan is refused, not truncated, when that exceeds the LDS sort
     bad += p.cap < p.tail + 1 || p.cap < 2 * (p.tail + 1) || (p.cap & (p.cap - 1)) != 0;
@@ -73,9 +78,10 @@ int main(int argc, char** argv) {
     if (argc == 6 && !std::strcmp(argv[1], "plan")) {
         const int64_t n = std::atoll(argv[2]);
         const LooPlan p = plan_loo(n, std::atoll(argv[3]), std::atoi(argv[4]), std::atoi(argv[5]));
-        std::printf("tail=%lld cap=%lld select_passes=%d matrix_passes=%d ok=%d splits=%lld "
+        std::printf("tail=%lld grid=%d cap=%lld select_passes=%d matrix_passes=%d ok=%d splits=%lld "
                     "workspace=%llu\n",
-                    (long long)p.tail, (long long)p.cap, p.select_passes, p.matrix_passes, (int)p.ok,
+                    (long long)p.tail, p.grid_points, (long long)p.cap, p.select_passes, p.matrix_passes,
+                    (int)p.ok,
                     (long long)p.score.splits, (unsigned long long)loo_buffers(p, n).total());
         return 0;
     }

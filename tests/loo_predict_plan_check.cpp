@@ -19,7 +19,7 @@ static int check(int64_t n, int64_t S, int k, int n_cu) {
     const LooPredictPlan p = plan_loo_predict(n, S, k, n_cu);
     const LooPlan q = plan_loo(n, S, k, n_cu);
     int bad = 0;
-    bad += p.loo.tail != q.tail || p.loo.cap != q.cap || p.loo.select_passes != q.select_passes ||
+    bad += p.loo.tail != q.tail || p.loo.grid_points != q.grid_points || p.loo.cap != q.cap || p.loo.select_passes != q.select_passes ||
            p.loo.matrix_passes != q.matrix_passes || p.loo.ok != q.ok ||
            p.loo.score.point_tiles != q.score.point_tiles ||
            p.loo.score.draw_tiles != q.score.draw_tiles ||

@@ -1,6 +1,9 @@
 // CPU check of the plan of the power-scaling sensitivity (pybmc_amd/csrc/bmc_sens_plan.h).
 //   const   the geometry constants as key=value (what the GPU tests size their cases from)
 //   tail <S>            tail length M and grid points of the fit
+//   tails               binary int64 S values on stdin -> three int32 per S on stdout: psis_tail_length(S),
+//                       psis_grid_points of it, plan_loo(...).tail (the rule of bmc_psis_plan.h as both
+//                       plans see it; tests/test_sens_plan.py holds them to integer arithmetic of its own)
 //   plan <S> <n_cols> <W> <cols_per_batch> <budget>   the plan's fields as key=value
 //   sweep   S = 1 .. a few thousand and the limits x columns x batch requests x budgets: the tail is
 //           min(S / 5, ceil(3 sqrt S)) in exact arithmetic, the grid fits on chip, the padded segment
@@ -8,6 +11,7 @@
 //           every column once, the scratch is what the kernels index, refusals exactly outside the
 //           limits; prints "sweep <plans> <failures>"
 //   check <n> <k> <S> <n_models> <n_alphas> <alpha as double> <components>   the refusal text, or "ok"
+#include "../pybmc_amd/csrc/bmc_plan.h"
 #include "../pybmc_amd/csrc/bmc_sens_plan.h"
 
 #include <cmath>
@@ -31,6 +35,7 @@ static int check_shape(int64_t S) {
     int bad = 0;
     const int64_t M = sens_tail_length(S);
     bad += M != tail_by_definition(S);
+    bad += M != psis_tail_length(S) || SENS_MIN_TAIL != PSIS_MIN_TAIL;   // the one rule under the plan's names
     bad += M < 0 || (S >= 1 && M >= S && M > 0);
     if (M >= SENS_MIN_TAIL) {
         const int32_t mg = sens_grid_points(M);
@@ -119,6 +124,21 @@ int main(int argc, char** argv) {
         printf("M=%lld grid=%d\n", (long long)M, M >= SENS_MIN_TAIL ? sens_grid_points(M) : 0);
         return 0;
     }
+    if (argc == 2 && !strcmp(argv[1], "tails")) {
+        std::vector<int64_t> in(1 << 16);
+        std::vector<int32_t> out(3 * in.size());
+        size_t got;
+        while ((got = fread(in.data(), 8, in.size(), stdin)) > 0) {
+            for (size_t i = 0; i < got; ++i) {
+                const int64_t M = psis_tail_length(in[i]);
+                out[3 * i] = (int32_t)M;
+                out[3 * i + 1] = psis_grid_points(M);
+                out[3 * i + 2] = (int32_t)plan_loo(100, in[i], 3, 256).tail;
+            }
+            if (fwrite(out.data(), 4, 3 * got, stdout) != 3 * got) return 1;
+        }
+        return 0;
+    }
     if (argc == 7 && !strcmp(argv[1], "plan")) {
         const SensPlan p = plan_sens(atoll(argv[2]), atoi(argv[3]), atoi(argv[4]), atoi(argv[5]),
                                      (size_t)strtoull(argv[6], nullptr, 10));
@@ -165,6 +185,6 @@ int main(int argc, char** argv) {
         printf("sweep %ld %ld\n", plans, failures);
         return failures != 0;
     }
-    fprintf(stderr, "usage: sens_plan_check const | tail S | plan ... | check ... | sweep\n");
+    fprintf(stderr, "usage: sens_plan_check const | tail S | tails | plan ... | check ... | sweep\n");
     return 2;
 }

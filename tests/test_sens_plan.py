@@ -58,6 +58,41 @@ def test_tail_length_is_the_reference_rule(exe):
         assert int(f["grid"]) == (30 + int(math.floor(math.sqrt(M))) if M >= 5 else 0)
 
 
+def _ceil_isqrt(v):
+    """numpy int64 ceil(sqrt(v)), v < 2^62: the float root, put right in integers"""
+    r = np.floor(np.sqrt(v.astype(np.float64))).astype(np.int64)
+    r -= r * r > v
+    r += (r + 1) * (r + 1) <= v
+    assert np.all((r * r <= v) & ((r + 1) * (r + 1) > v))
+    return r + (r * r < v)
+
+
+def test_the_one_tail_rule_in_integers(exe):
+    """psis_tail_length and psis_grid_points (bmc_psis_plan.h) against M = min(S // 5,
+    ceil_isqrt(9 S)) and grid = 30 + isqrt(M) in integers: every S up to 2^23, five values around
+    every 9 S = r^2 up to r = 139000, and the ends of the 32-bit range; and plan_loo's tail is 0
+    exactly when M < 5, M otherwise."""
+    r = np.arange(3, 139001, dtype=np.int64)
+    near = ((r * r) // 9)[:, None] + np.arange(-2, 3, dtype=np.int64)
+    S = np.concatenate([np.arange(1, 2 ** 23 + 1, dtype=np.int64), near.reshape(-1),
+                        np.array([2 ** 31 - 1, 2 ** 31, 2 ** 32 - 2], dtype=np.int64)])
+    S = S[S >= 1]
+    p = subprocess.run([exe, "tails"], input=S.tobytes(), capture_output=True)
+    assert p.returncode == 0, p.stderr[-2000:]
+    M, grid, loo_tail = np.frombuffer(p.stdout, dtype=np.int32).reshape(-1, 3).astype(np.int64).T
+    assert len(M) == len(S)
+    want = np.minimum(S // 5, _ceil_isqrt(9 * S))
+    bad = np.flatnonzero(M != want)
+    assert bad.size == 0, (S[bad[:5]], M[bad[:5]], want[bad[:5]])
+    assert np.array_equal(grid, 30 + (_ceil_isqrt(M + 1) - 1))      # floor(sqrt(M)) = ceil(sqrt(M + 1)) - 1
+    assert np.array_equal(loo_tail, np.where(M < 5, 0, M))
+    assert np.array_equal(loo_tail == 0, M < 5) and (M < 5).any() and (M >= 5).any()
+    for s in (1, 24, 25, 224, 225, 226, 2 ** 23, 139000 ** 2 // 9, 2 ** 31 - 1, 2 ** 31, 2 ** 32 - 2):
+        i = int(np.flatnonzero(S == s)[0])                          # and math.isqrt itself on a few
+        m = min(s // 5, math.isqrt(9 * s - 1) + 1)
+        assert (M[i], grid[i]) == (m, 30 + math.isqrt(m)), s
+
+
 def test_plan_of_the_benchmark_shape(exe):
     f = fields(run_plan_check(exe, "plan", 3200000, 33, 4, 0, 100 * 2 ** 30))
     assert f["ok"] == "1" and f["n_batches"] == "1" and f["cols_per_batch"] == "33"
