@@ -130,10 +130,11 @@ __device__ __forceinline__ bool granule_gather1(const gu64* gp, int n2, unsigned
     // the lanes whose tag decides: the test is the compare's own lane mask against this one
     gu64 need = __builtin_amdgcn_ballot_w64(have);
     // The loop has ONE way out, the test of a read.  An expired spin clears `need`, so the next
-    // test passes whatever it read, and the flag says that the value is not a total: as a second
-    // exit of its own it made hipcc carry "which exit" in lane-mask flags that were set, tested
-    // and branched on in front of the group sum and again behind it.
-    bool live = true;
+    // test passes whatever it read, and `need` itself says behind the loop that the value is not a
+    // total (one scalar compare): as a second exit of its own it made hipcc carry "which exit" in
+    // lane-mask flags that were set, tested and branched on in front of the group sum and again
+    // behind it, and as a flag of its own next to `need` it travelled through the loop as a
+    // per-lane value, nine VALU instructions on the way of a hit on the second read.
 #pragma unroll
     for (int d = 0; d < DEPTH - 1; ++d) {
         q[d] = granule_load(p);
@@ -148,17 +149,27 @@ __device__ __forceinline__ bool granule_gather1(const gu64* gp, int n2, unsigned
 #endif
             const gu64 w = q[d];
             const gu64 hit = __builtin_amdgcn_ballot_w64((unsigned)(w >> 32) == epoch);
-            if ((hit & need) == need) { x = have ? w : 0; return live; }
+            // One forward exit per read.  The select of the read that hit is pinned behind its own
+            // test (an empty statement hipcc may not speculate): otherwise the selects of BOTH
+            // reads are computed behind the second test and one is picked.  Only the low word is
+            // handed out: the tag has been tested and granule_sum1 reads nothing else.
+            if ((hit & need) == need) {
+                unsigned lo = have ? (unsigned)w : 0u;
+                asm volatile("" : "+v"(lo));
+                x = lo;
+                goto gathered;
+            }
         }
         if ((spins & 0x7f) == 0x7f) {
             const unsigned long long now = __builtin_amdgcn_s_memrealtime();
             if (t_start == 0) t_start = now;
             else if (now - t_start > SPIN_TIMEOUT_TICKS) {
                 need = 0;
-                live = false;
             }
         }
     }
+gathered:
+    return need != 0;
 }
 
 // Retire the reads a gather left in flight, behind the sum `tot` they no longer feed: the empty

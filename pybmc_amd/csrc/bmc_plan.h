@@ -40,12 +40,22 @@ constexpr int MAX_GROUPS = 256;   // 8 teams of <= 32 groups (exchange_sum)
 //                to land), the second ~100 cycles behind the first, so that the pair samples L2
 //                every ~half load round trip (~260 cycles) instead of twice at the same instant
 //   POLL_AGENT   first level, agent-scope store, one chain per pass: reads that arrive while the
-//                write-through is under way delay it, so the first one waits ~280 cycles
+//                write-through is under way delay it, so the first one waits ~345 cycles (80
+//                states).  It was 64 until the leader's way from the residual pass to the
+//                publication was shortened (the leader's instruction stream): the
+//                optimum is sharp and moved with it -- agent scope forced at C2, 64 / 80 / 96
+//                states: 1.110 / 0.957 / 0.962 us per iteration (parent, at 64: 0.955), 16 chains
+//                1.747 / 1.494 / 1.262 (parent 1.940); 96 lost N = 100 000 x 32 in one call
 //   POLL_PLAIN   first level of the passes that serve 4 or 8 chains (their leaders share a CU)
 //                and of the simplex sampler: back to back, as before (the spaced pair was 1.9 %
 //                slower for 32 chains at C2 and no faster for the simplex sampler)
 //   POLL_LEVEL2  team totals and relay of chains over more than 32 groups: back to back, as
 //                before (no spaced or delayed schedule was faster in the micro benchmark)
+// One POLL_LOCAL for every kernel class (one chain, 16 packed, a team's first level).  On the
+// shortened stream 40 / 16 and 32 / 16 were run on every case of the A/B protocol: neither
+// cleared the spread at C2 (0.7958 and 0.7984 against 0.7942 [0.0079]), 40 / 16 lost N = 100 000
+// x 32 (1.7888 against 1.7753 [0.0100]) and 32 / 16 lost 16 chains (0.9520 against 0.9333
+// [0.0155]), so every class keeps 32 / 24 and there is no selection by class.
 struct PollSched {
     int depth, first, gap;
 };
@@ -60,7 +70,7 @@ constexpr int poll_issue_state(PollSched s, int d) { return s.first + d * s.gap;
 #define BMC_POLL_GAP_LOCAL 24
 #endif
 #ifndef BMC_POLL_FIRST_AGENT
-#define BMC_POLL_FIRST_AGENT 64
+#define BMC_POLL_FIRST_AGENT 80
 #endif
 constexpr PollSched POLL_LOCAL{2, BMC_POLL_FIRST_LOCAL, BMC_POLL_GAP_LOCAL};
 constexpr PollSched POLL_AGENT{2, BMC_POLL_FIRST_AGENT, 0};

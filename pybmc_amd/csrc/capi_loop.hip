@@ -164,7 +164,10 @@ int run_common(bmc_ctx* c, int32_t n_chains, int64_t iters, const uint64_t* seed
     const int K = c->k;
     const size_t T = (size_t)iters, C = (size_t)n_chains;
     int rc;
-    if ((rc = ensure_all(c, {{c->xi, C * T * K * 8}, {c->gam, C * T * 8}, {c->uout, C * T * (K + 1) * 8}})))
+    // (one row more than the chains have: the loop kernel's leader prefetches row t + 1 in every
+    // iteration, the last one included, and the last chain's row T is this padding -- read, never used)
+    if ((rc = ensure_all(c, {{c->xi, (C * T + 1) * K * 8}, {c->gam, (C * T + 1) * 8},
+                             {c->uout, C * T * (K + 1) * 8}})))
         return rc;
     double* d_samples = (double*)samples_dev;
     if (!d_samples) {

@@ -86,6 +86,13 @@ __device__ __forceinline__ Sigma2 sigma2_step(double nu0_s20, double rss, double
     const bool floor_hit = scale_post < 1e-6 * gam_t;
     return Sigma2{floor_hit ? 1e-6 : scale_post, floor_hit ? 1.0 : gam_t};
 }
+// The same step with floor_t = 1e-6 * gam_t handed in: the product does not depend on the exchange,
+// so a caller with an idle slot ahead of it computes it there (same operation, same operands).
+__device__ __forceinline__ Sigma2 sigma2_step(double nu0_s20, double rss, double gam_t, double floor_t) {
+    const double scale_post = (nu0_s20 + rss) * 0.5;
+    const bool floor_hit = scale_post < floor_t;
+    return Sigma2{floor_hit ? 1e-6 : scale_post, floor_hit ? 1.0 : gam_t};
+}
 
 // PACK: the same kernel held to 128 VGPRs (4 waves per SIMD), so that two 5-wave groups of
 // different chains fit a CU side by side whatever SIMDs their waves land on -- used when more
@@ -207,10 +214,23 @@ void gibbs_loop_kernel(GibbsArgs a) {
     // takes issue slots from it whenever both are ready.  Same-box A/B, s_setprio 3 for the
     // leader: C2 0.941 -> 0.922 us per iteration, 16 chains at C2 1.056 -> 1.027.
     if (BMC_LEADER_PRIO > 0 && is_leader) __builtin_amdgcn_s_setprio(BMC_LEADER_PRIO);
-    for (int64_t t = 0; t < T_it; ++t) {
-        // (epoch0: the launch's nonce -- a granule an earlier launch left in some cache carries
-        // another base and is never taken for this launch's; 0 is never a live tag)
-        const unsigned epoch = (unsigned)(t + 1) + a.epoch0;
+    // Loop-carried scalars of the leader: the iterations left (the host admits fewer than 2^32 - 1),
+    // the next variate row and the exchange slot.  Nothing is rebuilt from t; t itself is kept for the
+    // recording wave's row addresses only.
+    unsigned left = (unsigned)T_it;
+    const double* xi_nx = xi + K;
+    const double* gam_nx = gam + 1;
+    // (the address of the (sp, g) words, kept in a register: hipcc otherwise rebuilds it, a move and
+    // an add, in front of barrier B1 in every iteration)
+    typedef __attribute__((address_space(3))) double lds_d;
+    unsigned ctl_a = (unsigned)(size_t)(lds_d*)ctl;
+    asm volatile("" : "+v"(ctl_a));
+    // (epoch0: the launch's nonce -- a granule an earlier launch left in some cache carries
+    // another base and is never taken for this launch's; 0 is never a live tag)
+    unsigned epoch = a.epoch0;           // iteration t exchanges under epoch0 + t + 1
+    size_t slot = 0;                     // words from gr: 0 and gran_stride in turn
+    for (int64_t t = 0; left != 0; ++t, --left) {
+        ++epoch;
         STAMP(7);
         if (is_leader) {
 #pragma unroll
@@ -226,7 +246,11 @@ void gibbs_loop_kernel(GibbsArgs a) {
             // behind u, rather than between the sigma2 step and the draw it feeds (both are in
             // front of barrier B1, after which the recorder reads them; tried there: slower,
             // part of the three changes that took C2 from 0.9425 to 0.9411 us)
-            if (lane == 0) { ctl[0] = sp_eff; ctl[3] = g_eff; }
+            if (lane == 0) {
+                lds_d* const cw = (lds_d*)(size_t)ctl_a;
+                cw[0] = sp_eff;
+                cw[3] = g_eff;
+            }
         }
         STAMP(0);
         __syncthreads();  // B1: u (and the previous sp, g / abort word) visible to all waves
@@ -239,14 +263,19 @@ void gibbs_loop_kernel(GibbsArgs a) {
         // prefetch next iteration's variates.  A single-workgroup chain has nothing long after
         // the residual pass to hide the loads behind, so it issues them here; chains with an
         // exchange issue them behind the pass (below).
+        // In the last iteration the row loaded is never used: it is the next chain's first row, or
+        // the row the host pads the buffers with behind the last chain (capi_loop.hip).  Lanes past
+        // K keep xi = 0: with lam = c1 = c2 = 0 such a lane draws u = xi into the padding of u_lds.
         auto prefetch = [&]() {
-            if (is_leader && t + 1 < T_it) {
+            if (is_leader) {
 #pragma unroll
                 for (int ch = 0; ch < KCH; ++ch) {
                     const int j = ch * 64 + lane;
-                    if (ch * 64 < K && j < K) xi_next[ch] = xi[(t + 1) * K + j];
+                    if (ch * 64 < K && j < K) xi_next[ch] = xi_nx[j];
                 }
-                gam_next = gam[t + 1];
+                gam_next = *gam_nx;
+                xi_nx += K;
+                ++gam_nx;
             }
         };
         if constexpr (SINGLE) prefetch();
@@ -289,9 +318,16 @@ void gibbs_loop_kernel(GibbsArgs a) {
         // of the reduction of its own.  Sharing one with simplex_loop_kernel changes the order in
         // which hipcc inlines the exchange into that kernel, and with it the register allocation
         // of its LDS-pinned, streamed and two-rows-per-lane forms.)
+        gu64* const gslot = gr + slot;
+        slot ^= (size_t)a.gran_stride;
+        // the floor of the sigma2 step, 1e-6 gam_t, in the idle slot between the publication of the
+        // group total and the first poll instead of behind the sum
+        double floor_t = 0.0;
         const double rss = group_allreduce<SINGLE, LANEWISE, (SMALLG ? 0 : -1), LOCALK, ROLE, EARLY>(
-            part, red, gr + (size_t)(t & 1) * a.gran_stride, G, g, wave, nw, lane, epoch, local,
-            got STAMP_ARGS, [] {});
+            part, red, gslot, G, g, wave, nw, lane, epoch, local, got STAMP_ARGS, [&] {
+                floor_t = 1e-6 * gam_t;
+                asm volatile("" : "+v"(floor_t));
+            });
         STAMP(8);
         if (is_rec) {
             // row t = [u_t, .]; sigma of the PREVIOUS row (its sp, g were final at B1)
@@ -303,12 +339,17 @@ void gibbs_loop_kernel(GibbsArgs a) {
             if (lane == 0 && t > 0) uout[(t - 1) * (K + 1) + K] = sqrt(sp_rec / g_rec);
         }
         if (is_leader) {
+            // The step is taken whatever the gather returned, and the flag is tested once, out of
+            // line: after an expired spin the chain is over (every wave leaves behind the next
+            // pass, the status word tells the host), so what the step makes of an undefined sum is
+            // never used -- and the straight path carries no old (sp, g) pair to fall back on.
+            // (a chain in one workgroup has no exchange and no idle slot)
+            const Sigma2 s2 = SINGLE ? sigma2_step(a.nu0_s20, rss, gam_t)
+                                     : sigma2_step(a.nu0_s20, rss, gam_t, floor_t);
+            sp_eff = s2.sp;
+            g_eff = s2.g;
             if (__builtin_expect(!got, 0)) {
                 if (lane == 0) { ctl[1] = 1.0; a.status[chain] = 1; }
-            } else {
-                const Sigma2 s2 = sigma2_step(a.nu0_s20, rss, gam_t);
-                sp_eff = s2.sp;
-                g_eff = s2.g;
             }
             STAMP(6);
         }
