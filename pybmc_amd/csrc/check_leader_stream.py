@@ -7,8 +7,9 @@ long steps -- the residual pass, the gather, the group sum, the draw -- every sc
 and every taken branch of that wave is on the serial path.  This script disassembles
 the gfx950 code object of the given host object, finds the kernel's loop copy of the leader that
 does not record and exchanges at workgroup scope, and counts instructions and taken branches on
-three stretches of the way a hit takes:
+four stretches of the way a hit takes:
 
+  draw -> B1     behind the first ``v_rsq_f64`` of the draw, up to the barrier that hands u over
   pass -> B2     behind the last ``v_fmac_f64_dpp`` of the residual pass, up to the group barrier
   hit N -> sum   behind the tag compare of read N of the gather, up to the first DPP step of the sum
   sum -> draw    behind the last add of the group sum (the one in front of the wait that retires the
@@ -21,7 +22,14 @@ not a way round the work, pass -> B2 goes through the load of the next Gamma var
 in front of the barrier) and sum -> draw through the ``v_cmp_lt_f64`` of the sigma2 step's floor.  The build fails when a count exceeds its value in LIMITS, which
 are the counts of the commit that last shortened the stream: a change that lengthens a stretch has
 to say so by raising its limit.
-Usage: check_leader_stream.py <kernels_gibbs.o>
+
+Placement.  The same loop, instruction for instruction, runs an iteration 3 % faster or slower with
+where its code lies: a sweep of 0 .. 15 ``s_nop`` in front of the loop copies (``BMC_PLACE_PAD``,
+kernels_gibbs.hip) has a period of 8, i.e. 32 bytes, best with the iteration loop's header at byte 0
+of a 32-byte window and the poll loop's at byte 28.  The script prints the two headers'
+byte addresses modulo 64 and fails when they are not at PLACE modulo PLACE_PERIOD: a change that
+moves the loop has to move it back with ``BMC_PLACE_PAD``, or measure again and say so here.
+Usage: check_leader_stream.py [--no-placement] <kernels_gibbs.o>
 """
 import heapq
 import os
@@ -36,16 +44,23 @@ KERNEL = "gibbs_loop_kernelIdLi1ELi0ELi32ELi1ELb0ELb0ELb1E"
 SUM_HEAD = "quad_perm:[1,0,3,2]"       # v_xor_b32_dpp with it: the first instruction of granule_sum1
 
 # stretch: (instructions, taken branches) at this commit
+# (sum -> draw went from 21 to 23 when pass -> B2 went from 20 to 12: the two scalar adds of the xi
+# pointer moved from in front of B2 to the loop top, where hipcc now also merges the expired flag
+# into the loop's exit condition and no longer needs the move and the branch round the exit block)
 LIMITS = {
-    "pass -> B2": (20, 0),
+    "draw -> B1": (20, 0),
+    "pass -> B2": (12, 0),
     "hit 0 -> sum": (10, 2),
     "hit 1 -> sum": (9, 2),
-    "sum -> draw": (21, 1),
+    "sum -> draw": (23, 1),
 }
+# header: byte address modulo PLACE_PERIOD the measured placement has it at
+PLACE_PERIOD = 32
+PLACE = {"loop": 0, "poll": 28}
 
 
 def parse(lines, kernel=KERNEL):
-    """The kernel's instructions as [mnemonic, text, index of the branch target or None]."""
+    """The kernel's instructions as [mnemonic, text, index of the branch target or None, byte address]."""
     ins, addr_of, on = [], [], False
     for raw in lines:
         line = raw.rstrip("\n")
@@ -61,8 +76,8 @@ def parse(lines, kernel=KERNEL):
         if not text or not m:
             continue
         t = re.search(r"<[^>]*\+0x([0-9a-fA-F]+)>", line)
-        ins.append([text.split(None, 1)[0], text, int(t.group(1), 16) if t else None])
-        addr_of.append(int(m.group(1), 16))
+        ins.append([text.split(None, 1)[0], text, int(t.group(1), 16) if t else None, int(m.group(1), 16)])
+        addr_of.append(ins[-1][3])
     if not ins:
         return ins
     index = {a - addr_of[0]: i for i, a in enumerate(addr_of)}
@@ -85,7 +100,7 @@ def stretch(ins, a, b):
             return n - 1, br
         if best.get(i, (n, br)) < (n, br) or i >= len(ins):
             continue
-        mn, _, tgt = ins[i]
+        mn, _, tgt = ins[i][:3]
         nxt = []
         if mn in ("s_endpgm", "s_barrier") and i != a:
             continue                                        # (no stretch crosses a barrier)
@@ -114,7 +129,7 @@ def leader_loop(ins):
     smallest backward-branch range with two barriers and the head of a group sum whose only global
     stores are the granule's (sc0: workgroup scope) and the status word's (a dword)."""
     found = None
-    for hi, (mn, _, lo) in enumerate(ins):
+    for hi, (mn, _, lo, *_) in enumerate(ins):
         if not is_branch(mn) or lo is None or lo > hi:
             continue
         body = ins[lo:hi + 1]
@@ -146,22 +161,56 @@ def measure(ins):
     retire = at(lambda x: x[0] == "s_waitcnt" and "vmcnt" in x[1], head)[0]
     last_add = at(lambda x: x[0].startswith("v_add_f64"), head, retire)[-1]
     gam = at(lambda x: x[0] == "global_load_dwordx2" and "sc1" not in x[1].split(), fmacs[-1], b2)[-1]
-    floor = at(lambda x: x[0].startswith("v_cmp_lt_f64"), retire)[0]
-    out = {"pass -> B2": via(ins, fmacs[-1], gam, b2)}
+    # (hipcc may rotate the loop so that the sigma2 step stands behind the back edge, at its top)
+    floor = (at(lambda x: x[0].startswith("v_cmp_lt_f64"), retire) or
+             at(lambda x: x[0].startswith("v_cmp_lt_f64"), lo, rsq))[0]
+    b1 = [i for i in at(lambda x: x[0] == "s_barrier") if i != b2][0]
+    out = {"draw -> B1": stretch(ins, rsq, b1), "pass -> B2": via(ins, fmacs[-1], gam, b2)}
     for n, t in enumerate(tags):
         out[f"hit {n} -> sum"] = stretch(ins, t, head)
     out["sum -> draw"] = via(ins, last_add, floor, rsq)
     return out
 
 
+def placement(ins):
+    """Byte addresses of the two loop headers an iteration of the leader's copy branches back to:
+    {"loop": the iteration loop's, "poll": the gather's poll loop's} (None where not found)."""
+    loop = leader_loop(ins)
+    if loop is None:
+        return {"loop": None, "poll": None}
+    lo, hi = loop
+    poll = None
+    for i in range(lo + 1, hi):
+        mn, _, tgt = ins[i][:3]
+        if not is_branch(mn) or tgt is None or not lo < tgt < i:
+            continue
+        body = ins[tgt:i + 1]
+        if any(b[0] == "s_barrier" for b in body):
+            continue
+        if any(b[0] == "global_load_dwordx2" and "sc1" in b[1].split() for b in body):
+            poll = ins[tgt][3]
+            break
+    return {"loop": ins[lo][3], "poll": poll}
+
+
 def main(argv):
+    sweep = "--no-placement" in argv        # (a placement sweep's build: print the addresses only)
+    argv = [a for a in argv if a != "--no-placement"]
     if len(argv) != 1:
         print(__doc__, file=sys.stderr)
         return 2
     with tempfile.TemporaryDirectory() as tmp:
-        got = measure(parse(device_asm(argv[0], tmp)))
+        ins = parse(device_asm(argv[0], tmp))
+    got = measure(ins)
+    # ("pass -> B2" first: the line's head is part of the gate's contract with its test)
+    order = ["pass -> B2"] + [n for n in got if n != "pass -> B2"]
     print("check_leader_stream: " + "; ".join(
-        f"{name} {c[0]} instructions {c[1]} taken" if c else f"{name} not found" for name, c in got.items()))
+        f"{name} {got[name][0]} instructions {got[name][1]} taken" if got[name] else f"{name} not found"
+        for name in order))
+    where = placement(ins)
+    print("check_leader_stream: placement " + "; ".join(
+        f"{name} header at byte {a % 64} of its 64-byte line" if a is not None else f"{name} header not found"
+        for name, a in where.items()))
     bad = []
     for name, limit in LIMITS.items():
         c = got.get(name)
@@ -171,6 +220,12 @@ def main(argv):
             bad.append(f"{name}: {c[0]} instructions, {c[1]} taken branches (limit {limit[0]}, {limit[1]})")
     extra = sorted(set(got) - set(LIMITS))
     bad += [f"{name}: a stretch without a limit" for name in extra]
+    for name, want in ({} if sweep else PLACE).items():
+        a = where.get(name)
+        if a is None or a % PLACE_PERIOD != want:
+            at = "not found" if a is None else f"at byte {a % PLACE_PERIOD}"
+            bad.append(f"{name} header {at} of its {PLACE_PERIOD}-byte window, measured placement {want}: "
+                       "adjust BMC_PLACE_PAD (kernels_gibbs.hip)")
     if bad:
         print("check_leader_stream: the leader's stream grew:", file=sys.stderr)
         for x in bad:

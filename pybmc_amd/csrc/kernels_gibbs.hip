@@ -44,6 +44,14 @@
 #ifndef BMC_LEADER_PRIO
 #define BMC_LEADER_PRIO 3      // s_setprio of the leader wave of a group (0: leave it alone)
 #endif
+// Code placement: the number of s_nop (4 bytes each, executed once per launch) in front of the
+// role-specific loop copies of the SMALLG kernels.  The headline leader's loop runs 3 % faster
+// with its header at the start of a 32-byte fetch window than 8 bytes behind it (DESIGN.md 4.1,
+// a sweep of 0 .. 15 with a period of 8); check_leader_stream.py fails the build when the header
+// is elsewhere, and this count is then what to adjust (0 .. 7 reach every position).
+#ifndef BMC_PLACE_PAD
+#define BMC_PLACE_PAD 3
+#endif
 
 namespace bmc {
 
@@ -140,7 +148,8 @@ void gibbs_loop_kernel(GibbsArgs a) {
     const LdsPlan L = lds_plan(K, (int)sizeof(T), RP, a.panels_per_group, MODE == MODE_LDS);
     double* u_lds = reinterpret_cast<double*>(smem + L.u);
     double* red = reinterpret_cast<double*>(smem + L.red);  // per-wave partials
-    double* ctl = reinterpret_cast<double*>(smem + L.ctl);  // [0] sp, [1] abort, [2] local, [3] g
+    // [0] sp, [1] abort, [2] local, [3] g, [5] [6] the last (sp, g) pair of a SMALLG chain
+    double* ctl = reinterpret_cast<double*>(smem + L.ctl);
 
     const int kpad = (K + 63) & ~63;
     for (int j = tid; j < kpad; j += blockDim.x) u_lds[j] = 0.0;
@@ -209,6 +218,19 @@ void gibbs_loop_kernel(GibbsArgs a) {
     constexpr int ROLE = decltype(role_c)::value, REC = decltype(rec_c)::value;
     const bool is_leader = ROLE < 0 ? wave == 0 : ROLE == 0;
     const bool is_rec = REC < 0 ? recorder : REC == 1;
+    // The role-specific copies keep two duties off the leader's way to the barriers.
+    // LATE_PAIR: the (sp, g) words for the recording wave are written in the idle slot of the
+    // exchange, behind barrier B2, instead of between the draw and B1; the recorder then reads
+    // them one iteration later and stores the sigma of row t - 2 in iteration t (a leader that
+    // records itself keeps the pair in registers and its rows where they were).
+    // LATE_ABORT: the leader never reads the abort word -- a failed placement check skips the
+    // loop, and its own expired spin it knows from `got` -- and the workers test it behind
+    // barrier B2, where they wait for the leader anyway, instead of in front of it.
+    // (measured one by one and together; the run-time-role loop keeps both where
+    // they were)
+    constexpr bool LATE_PAIR = SMALLG && !SINGLE && ROLE >= 0;
+    constexpr bool LATE_ABORT = SMALLG && !SINGLE && ROLE >= 0;
+    constexpr bool SELF_REC = ROLE == 0 && REC == 1;    // (a group of one wave)
     // The leader wave carries the serial chain of the iteration; the wave that shares its SIMD
     // (five waves on four SIMDs at C2; in group 0 that wave also records the draws) otherwise
     // takes issue slots from it whenever both are ready.  Same-box A/B, s_setprio 3 for the
@@ -246,17 +268,22 @@ void gibbs_loop_kernel(GibbsArgs a) {
             // behind u, rather than between the sigma2 step and the draw it feeds (both are in
             // front of barrier B1, after which the recorder reads them; tried there: slower,
             // part of the three changes that took C2 from 0.9425 to 0.9411 us)
-            if (lane == 0) {
-                lds_d* const cw = (lds_d*)(size_t)ctl_a;
-                cw[0] = sp_eff;
-                cw[3] = g_eff;
+            // (LATE_PAIR: in the idle slot of the exchange, below)
+            if constexpr (!LATE_PAIR) {
+                if (lane == 0) {
+                    lds_d* const cw = (lds_d*)(size_t)ctl_a;
+                    cw[0] = sp_eff;
+                    cw[3] = g_eff;
+                }
             }
         }
         STAMP(0);
         __syncthreads();  // B1: u (and the previous sp, g / abort word) visible to all waves
         // the abort word is read here with u but tested after the residual pass: a test here
         // would put an LDS round trip between the barrier and the first FMA of every wave
-        const double abort_w = ctl[1];
+        // (LATE_ABORT: the workers test it behind B2, the leader not at all)
+        double abort_w = 0.0;
+        if constexpr (!(LATE_ABORT && ROLE == 0)) abort_w = ctl[1];
         STAMP(1);
 
         const double gam_t = gam_next;
@@ -286,8 +313,13 @@ void gibbs_loop_kernel(GibbsArgs a) {
                 const int j = ch * 64 + lane;
                 u_rec[ch] = (ch * 64 < K && j < K) ? u_lds[j] : 0.0;
             }
-            sp_rec = ctl[0];
-            g_rec = ctl[3];
+            if constexpr (LATE_PAIR && SELF_REC) {
+                sp_rec = sp_eff;
+                g_rec = g_eff;
+            } else {   // (LATE_PAIR: the pair written behind B2 of iteration t - 1, i.e. row t - 2's)
+                sp_rec = ctl[0];
+                g_rec = ctl[3];
+            }
         }
 
         // ---- partial rss over this group's panels, then over the chain's groups ---------
@@ -303,7 +335,7 @@ void gibbs_loop_kernel(GibbsArgs a) {
         // 64.2 us: rejected)
         constexpr bool EARLY = LANEWISE && !SINGLE;
         if constexpr (EARLY) red[wave * 64 + lane] = part;
-        {   // (the empty asm ties the test to `part`, or hipcc moves it back up)
+        if constexpr (!LATE_ABORT) {   // (the empty asm ties the test to `part`, or hipcc moves it back up)
             double abort_late = abort_w;
             asm volatile("" : "+v"(abort_late) : "v"(part));
             if (__builtin_amdgcn_readfirstlane(__double2hiint(abort_late)) != 0) break;
@@ -327,8 +359,23 @@ void gibbs_loop_kernel(GibbsArgs a) {
             part, red, gslot, G, g, wave, nw, lane, epoch, local, got STAMP_ARGS, [&] {
                 floor_t = 1e-6 * gam_t;
                 asm volatile("" : "+v"(floor_t));
+                // the pair this iteration's draw used (row t - 1's sigma2), for the recording wave:
+                // written behind B2(t) and read behind B1(t + 1), so the barriers order the two
+                if constexpr (LATE_PAIR && !SELF_REC) {
+                    if (lane == 0) {
+                        lds_d* const cw = (lds_d*)(size_t)ctl_a;
+                        cw[0] = sp_eff;
+                        cw[3] = g_eff;
+                    }
+                }
             });
         STAMP(8);
+        // the workers' abort test: behind B2, where they only wait for the leader's next draw.  The
+        // word is set by the leader's expired block below, which runs the two barriers of the next
+        // iteration itself, so every wave has executed the same number of them when it leaves
+        if constexpr (LATE_ABORT && ROLE == 1) {
+            if (__builtin_amdgcn_readfirstlane(__double2hiint(abort_w)) != 0) break;
+        }
         if (is_rec) {
             // row t = [u_t, .]; sigma of the PREVIOUS row (its sp, g were final at B1)
 #pragma unroll
@@ -336,7 +383,9 @@ void gibbs_loop_kernel(GibbsArgs a) {
                 const int j = ch * 64 + lane;
                 if (ch * 64 < K && j < K) uout[t * (K + 1) + j] = u_rec[ch];
             }
-            if (lane == 0 && t > 0) uout[(t - 1) * (K + 1) + K] = sqrt(sp_rec / g_rec);
+            // (LATE_PAIR, a worker recording: the pair it read is one iteration older)
+            constexpr int BACK = (LATE_PAIR && !SELF_REC) ? 2 : 1;
+            if (lane == 0 && t >= BACK) uout[(t - BACK) * (K + 1) + K] = sqrt(sp_rec / g_rec);
         }
         if (is_leader) {
             // The step is taken whatever the gather returned, and the flag is tested once, out of
@@ -350,12 +399,27 @@ void gibbs_loop_kernel(GibbsArgs a) {
             g_eff = s2.g;
             if (__builtin_expect(!got, 0)) {
                 if (lane == 0) { ctl[1] = 1.0; a.status[chain] = 1; }
+                // LATE_ABORT: nobody tests the word in front of B2 any more.  The workers read it
+                // behind B1 of the next iteration and leave behind its B2; the leader meets them at
+                // both from here (it has nothing to draw) and leaves with them.  After the last
+                // iteration there is no next one: everybody is on the way out already.
+                if constexpr (LATE_ABORT) {
+                    if (left != 1) {
+                        __syncthreads();
+                        __syncthreads();
+                    }
+                    break;
+                }
             }
             STAMP(6);
         }
     }
-    // (the last sigma2, for the row recorded behind the loop)
-    if (is_leader && lane == 0 && ctl[1] == 0.0) { ctl[0] = sp_eff; ctl[3] = g_eff; }
+    // (the last sigma2, for the row recorded behind the loop; LATE_PAIR: in words of its own, as
+    // words 0 and 3 still hold the pair of the row before it, which the recorder has not read)
+    if (is_leader && lane == 0 && ctl[1] == 0.0) {
+        ctl[LATE_PAIR ? 5 : 0] = sp_eff;
+        ctl[LATE_PAIR ? 6 : 3] = g_eff;
+    }
     };   // run_loop
     using I0 = std::integral_constant<int, 0>;
     using I1 = std::integral_constant<int, 1>;
@@ -370,8 +434,18 @@ void gibbs_loop_kernel(GibbsArgs a) {
                 else run_loop(scope_c, I1{}, I0{});
             }
         };
-        if (local) by_role(I1{});
-        else by_role(I0{});
+        // A failed placement check is over before it starts: the word is tested once, here, behind
+        // the barrier that follows the check, by every wave alike (the role copies no longer carry
+        // the test in front of barrier B2).
+        const bool start_ok = SINGLE || __builtin_amdgcn_readfirstlane(__double2hiint(ctl[1])) == 0;
+        if (start_ok) {
+#if BMC_PLACE_PAD > 0
+            // moves the role copies by 4-byte steps (see BMC_PLACE_PAD above)
+            asm volatile(".rept %0\n\ts_nop 0\n\t.endr" ::"n"(BMC_PLACE_PAD));
+#endif
+            if (local) by_role(I1{});
+            else by_role(I0{});
+        }
     } else {
         run_loop(IR{}, IR{}, IR{});
     }
@@ -380,8 +454,16 @@ void gibbs_loop_kernel(GibbsArgs a) {
         for (int i = 0; i < 12; ++i) a.dbg[i] = (long long)acc_[i];
 #endif
     __syncthreads();
-    if (recorder && lane == 0 && T_it > 0 && ctl[1] == 0.0)
-        uout[(T_it - 1) * (K + 1) + K] = sqrt(ctl[0] / ctl[3]);
+    if (recorder && lane == 0 && T_it > 0 && ctl[1] == 0.0) {
+        if constexpr (SMALLG && !SINGLE) {
+            // two rows are owed: the loop's recorder runs one iteration behind the pair (a leader
+            // that records itself, nw == 1, has stored row T - 2 inside the loop)
+            if (T_it > 1 && nw > 1) uout[(T_it - 2) * (K + 1) + K] = sqrt(ctl[0] / ctl[3]);
+            uout[(T_it - 1) * (K + 1) + K] = sqrt(ctl[5] / ctl[6]);
+        } else {
+            uout[(T_it - 1) * (K + 1) + K] = sqrt(ctl[0] / ctl[3]);
+        }
+    }
 }
 
 // ======================================================================================
