@@ -665,7 +665,17 @@ struct PanelStore {
             // lane: all columns through DPP (C2: 1.135 vs 1.165 us per iteration).
             constexpr bool USE_DPP = KMAX >= 16;
             constexpr int JD = !USE_DPP ? KMAX : (PPW * VEC > 1 ? 4 : 0);   // first DPP column
+            // One row per lane: the LDS read of the u rows is the FIRST instruction behind barrier
+            // B1, and the fence keeps the four accumulator copies (which need nothing the barrier
+            // hands over) behind it, inside the read's latency, which every wave waits out -- in
+            // front of the read they delayed it, and the pass, by their own length (C2: 0.753 ->
+            // 0.732 us per iteration).
+            constexpr int NU = USE_DPP ? (KMAX + 15) / 16 : 1;
+            double urow[NU];
             if constexpr (JD == 0) {
+#pragma unroll
+                for (int r = 0; r < NU; ++r) urow[r] = u_lds[r * 16 + (lane & 15)];
+                __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int i = 0; i < PPW; ++i)
 #pragma unroll
@@ -689,10 +699,10 @@ struct PanelStore {
                     }
             }
             if constexpr (USE_DPP) {
-                constexpr int NU = (KMAX + 15) / 16;
-                double urow[NU];
+                if constexpr (JD != 0) {
 #pragma unroll
-                for (int r = 0; r < NU; ++r) urow[r] = u_lds[r * 16 + (lane & 15)];
+                    for (int r = 0; r < NU; ++r) urow[r] = u_lds[r * 16 + (lane & 15)];
+                }
                 if constexpr (JD == 0 && PPW * VEC == 1 && KMAX % 16 == 0 && sizeof(T) == 8) {
                     static_for<NU>([&](auto rc) {
                         constexpr int r = decltype(rc)::value;
@@ -760,6 +770,27 @@ __device__ __forceinline__ double sum_wave_rows(const double* rows, int lane) {
     const double r0 = r[0], r1 = r[64], r2 = r[128], r3 = r[192];
     const double r4 = r[256], r5 = r[320], r6 = r[384], r7 = r[448];
     return wave_sum(((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)));
+}
+
+// wave_sum for a caller whose result only lanes 0 and 1 consume (publish_pair): these lanes lie
+// in row 0 and hold its total r0 in their own register behind the four DPP steps, so they add r1,
+// r2, r3 to it in wave_sum's order, ((r0+r1)+r2)+r3 -- without the two read-lanes and the move
+// that only bring r0 back to where it is.  The other lanes get an unspecified value.
+__device__ __forceinline__ double wave_sum_row0(double v) {
+    v += dpp_mov_f64<0xB1>(v);          // quad_perm [1,0,3,2]
+    v += dpp_mov_f64<0x4E>(v);          // quad_perm [2,3,0,1]
+    v += dpp_mov_f64<0x141>(v);         // row_half_mirror
+    v += dpp_mov_f64<0x140>(v);         // row_mirror
+    const double r1 = readlane_f64(v, 16), r2 = readlane_f64(v, 32), r3 = readlane_f64(v, 48);
+    return ((v + r1) + r2) + r3;
+}
+
+// sum_wave_rows with that tail: the same tree over the rows, the same bits in lanes 0 and 1.
+__device__ __forceinline__ double sum_wave_rows_row0(const double* rows, int lane) {
+    const double* r = rows + lane;
+    const double r0 = r[0], r1 = r[64], r2 = r[128], r3 = r[192];
+    const double r4 = r[256], r5 = r[320], r6 = r[384], r7 = r[448];
+    return wave_sum_row0(((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)));
 }
 
 __device__ __forceinline__ double sum_wave_slots(const double* red, int lane) {
@@ -890,8 +921,10 @@ __device__ __forceinline__ double exchange_sum(double s, gu64* gp, int G, int g,
 // PREWRITTEN (LANEWISE only): the caller has already left its lane partials in its row of `red`
 // (right behind the residual pass, ahead of its other work in front of the barrier).
 // `idle`: work of the leader placed between publishing the group total and the first poll.
+// ROW0 (LANEWISE, not SINGLE): the group total is only published, i.e. consumed by lanes 0 and 1,
+// and the leader finishes the wave sum from those lanes' own row total (sum_wave_rows_row0).
 template <bool SINGLE = false, bool LANEWISE = false, int TEAMS = -1, int LOCAL = -1, int ROLE = -1,
-          bool PREWRITTEN = false, bool SPACED = true, typename F = NoIdleWork>
+          bool PREWRITTEN = false, bool SPACED = true, bool ROW0 = false, typename F = NoIdleWork>
 __device__ __forceinline__ double group_allreduce(double s, double* red, gu64* gp, int G, int g,
                                                   int wave, int nw, int lane, unsigned epoch,
                                                   bool local, bool& ok STAMP_PARAMS, F idle = F()) {
@@ -906,7 +939,9 @@ __device__ __forceinline__ double group_allreduce(double s, double* red, gu64* g
     __syncthreads();
     ok = true;
     if (ROLE < 0 ? wave != 0 : ROLE != 0) return 0.0;   // (ROLE: the caller knows its wave's role)
-    s = LANEWISE ? sum_wave_rows(red, lane) : sum_wave_slots(red, lane);
+    static_assert(!ROW0 || (LANEWISE && !SINGLE), "row-0 tail: lane-wise rows, total only published");
+    if constexpr (ROW0) s = sum_wave_rows_row0(red, lane);
+    else s = LANEWISE ? sum_wave_rows(red, lane) : sum_wave_slots(red, lane);
     GSTAMP(4);
     if constexpr (SINGLE) return s;
     return exchange_sum<false, TEAMS, LOCAL, SPACED>(s, gp, G, g, lane, epoch, local, ok STAMP_ARGS, idle);

@@ -7,10 +7,14 @@ long steps -- the residual pass, the gather, the group sum, the draw -- every sc
 and every taken branch of that wave is on the serial path.  This script disassembles
 the gfx950 code object of the given host object, finds the kernel's loop copy of the leader that
 does not record and exchanges at workgroup scope, and counts instructions and taken branches on
-four stretches of the way a hit takes:
+these stretches of the way a hit takes:
 
   draw -> B1     behind the first ``v_rsq_f64`` of the draw, up to the barrier that hands u over
+  B1 -> u        behind barrier B1, up to the LDS read of the u rows: nothing stands there (every
+                 wave waits out that read's latency, so whatever precedes it delays the pass)
+  B1 -> pass     behind barrier B1, up to the first ``v_fmac_f64_dpp`` of the residual pass
   pass -> B2     behind the last ``v_fmac_f64_dpp`` of the residual pass, up to the group barrier
+  B2 -> publish  behind the group barrier, up to the store of the group total's granule
   hit N -> sum   behind the tag compare of read N of the gather, up to the first DPP step of the sum
   sum -> draw    behind the last add of the group sum (the one in front of the wait that retires the
                  pending polls), over the loop's back edge, up to the first ``v_rsq_f64`` of the draw
@@ -26,7 +30,8 @@ to say so by raising its limit.
 Placement.  The same loop, instruction for instruction, runs an iteration 3 % faster or slower with
 where its code lies: a sweep of 0 .. 15 ``s_nop`` in front of the loop copies (``BMC_PLACE_PAD``,
 kernels_gibbs.hip) has a period of 8, i.e. 32 bytes, best with the iteration loop's header at byte 0
-of a 32-byte window and the poll loop's at byte 28.  The script prints the two headers'
+of a 32-byte window; the poll loop's then lies at byte 8 (at 28 before the publication lost three
+instructions; both sweeps had their best at header 0).  The script prints the two headers'
 byte addresses modulo 64 and fails when they are not at PLACE modulo PLACE_PERIOD: a change that
 moves the loop has to move it back with ``BMC_PLACE_PAD``, or measure again and say so here.
 Usage: check_leader_stream.py [--no-placement] <kernels_gibbs.o>
@@ -49,14 +54,17 @@ SUM_HEAD = "quad_perm:[1,0,3,2]"       # v_xor_b32_dpp with it: the first instru
 # into the loop's exit condition and no longer needs the move and the branch round the exit block)
 LIMITS = {
     "draw -> B1": (20, 0),
+    "B1 -> u": (0, 0),
+    "B1 -> pass": (7, 0),
     "pass -> B2": (12, 0),
+    "B2 -> publish": (53, 0),
     "hit 0 -> sum": (10, 2),
     "hit 1 -> sum": (9, 2),
     "sum -> draw": (23, 1),
 }
 # header: byte address modulo PLACE_PERIOD the measured placement has it at
 PLACE_PERIOD = 32
-PLACE = {"loop": 0, "poll": 28}
+PLACE = {"loop": 0, "poll": 8}
 
 
 def parse(lines, kernel=KERNEL):
@@ -166,6 +174,12 @@ def measure(ins):
              at(lambda x: x[0].startswith("v_cmp_lt_f64"), lo, rsq))[0]
     b1 = [i for i in at(lambda x: x[0] == "s_barrier") if i != b2][0]
     out = {"draw -> B1": stretch(ins, rsq, b1), "pass -> B2": via(ins, fmacs[-1], gam, b2)}
+    first = [i for i in fmacs if i > b1][0]
+    u_read = at(lambda x: x[0].startswith("ds_read"), b1, first)
+    if u_read:
+        out["B1 -> u"] = stretch(ins, b1, u_read[0])
+    out["B1 -> pass"] = stretch(ins, b1, first)
+    out["B2 -> publish"] = stretch(ins, b2, store)
     for n, t in enumerate(tags):
         out[f"hit {n} -> sum"] = stretch(ins, t, head)
     out["sum -> draw"] = via(ins, last_add, floor, rsq)

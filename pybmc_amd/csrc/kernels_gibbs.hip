@@ -47,10 +47,11 @@
 // Code placement: the number of s_nop (4 bytes each, executed once per launch) in front of the
 // role-specific loop copies of the SMALLG kernels.  The headline leader's loop runs 3 % faster
 // with its header at the start of a 32-byte fetch window than 8 bytes behind it (DESIGN.md 4.1,
-// a sweep of 0 .. 15 with a period of 8); check_leader_stream.py fails the build when the header
+// a sweep of 0 .. 15 with a period of 8, and again 0 .. 7 when the loop last changed: 4 % between
+// the best and the worst position); check_leader_stream.py fails the build when the header
 // is elsewhere, and this count is then what to adjust (0 .. 7 reach every position).
 #ifndef BMC_PLACE_PAD
-#define BMC_PLACE_PAD 3
+#define BMC_PLACE_PAD 0
 #endif
 
 namespace bmc {
@@ -355,7 +356,9 @@ void gibbs_loop_kernel(GibbsArgs a) {
         // the floor of the sigma2 step, 1e-6 gam_t, in the idle slot between the publication of the
         // group total and the first poll instead of behind the sum
         double floor_t = 0.0;
-        const double rss = group_allreduce<SINGLE, LANEWISE, (SMALLG ? 0 : -1), LOCALK, ROLE, EARLY>(
+        // (the role-specific leader: the group total goes to publish_pair only, lanes 0 and 1)
+        constexpr bool ROW0 = SMALLG && !SINGLE && LANEWISE && ROLE == 0;
+        const double rss = group_allreduce<SINGLE, LANEWISE, (SMALLG ? 0 : -1), LOCALK, ROLE, EARLY, true, ROW0>(
             part, red, gslot, G, g, wave, nw, lane, epoch, local, got STAMP_ARGS, [&] {
                 floor_t = 1e-6 * gam_t;
                 asm volatile("" : "+v"(floor_t));
