@@ -121,6 +121,166 @@ struct NoPollSpacing {
 // middle of the sum.  (All DEPTH registers, not the DEPTH - 1 pending ones: which register is
 // pending depends on the read that hit, and picking it would be a copy of a value that has not
 // arrived, i.e. the same wait in front of the sum.)
+// The role-specific leader of the SMALLG kernels gathers through one of the two forms below
+// (BMC_HIT_ALL, kernels_gibbs.hip).  In both a read hits when the tags of ALL 64 lanes are the
+// epoch's, i.e. when the compare's own mask is all ones, and no mask of deciding lanes is built,
+// and-ed and compared.  Lanes >= n2 read granule 0, a live granule of the same epoch: at a hit
+// their tags are the epoch's like everybody's, and their words are zeroed by the select in front
+// of the sum, whose mask is loop-invariant.  Precondition: a full EXEC and n2 >= 2 -- gibbs_kernel
+// (kernels_gibbs.hip) holds a SMALLG launch to whole waves and 2 <= G <= 32.
+//
+// granule_gather1_all: the loop of granule_gather1 in C++.  The carrier of an expired spin is
+// `dead`, or-ed into every test: 0, or all ones behind the clock test that gave up.
+template <int DEPTH = 2, int STRIDE = GRAN_PAIR_STRIDE, typename S = NoPollSpacing>
+__device__ __forceinline__ bool granule_gather1_all(const gu64* gp, int n2, unsigned epoch, int lane,
+                                                    gu64& x, gu64 (&q)[DEPTH] STAMP_PARAMS, S space = S(),
+                                                    unsigned long long t_start = 0) {
+    const bool have = lane < n2;
+    const gu64* p = gp + gran_at<STRIDE>(have ? lane : 0);
+    gu64 dead = 0;
+    asm volatile("" : "+s"(dead));
+#pragma unroll
+    for (int d = 0; d < DEPTH - 1; ++d) {
+        q[d] = granule_load(p);
+        space();
+    }
+    for (unsigned spins = 0;; ++spins) {
+#pragma unroll
+        for (int d = 0; d < DEPTH; ++d) {
+            q[(d + DEPTH - 1) % DEPTH] = granule_load(p);
+#ifdef BMC_STAMPS
+            if (stamping) acc_[9] += 1;
+#endif
+            const gu64 w = q[d];
+            const gu64 hit = __builtin_amdgcn_ballot_w64((unsigned)(w >> 32) == epoch);
+            if ((hit | dead) == ~(gu64)0) {
+                unsigned lo = have ? (unsigned)w : 0u;
+                asm volatile("" : "+v"(lo));
+                x = lo;
+                goto gathered;
+            }
+        }
+        if ((spins & 0x7f) == 0x7f) {
+            const unsigned long long now = __builtin_amdgcn_s_memrealtime();
+            if (t_start == 0) t_start = now;
+            else if (now - t_start > SPIN_TIMEOUT_TICKS) dead = ~(gu64)0;
+        }
+    }
+gathered:
+    return dead == 0;
+}
+
+// granule_gather1_asm: the poll rounds as ONE asm statement, because every C++ form of a loop with
+// two ways out comes back from hipcc as a latch with exit flags: a hit on the first
+// read falls through its test into its own select and takes one branch to the end, a hit on the
+// second takes one branch to its select and falls out of the statement.  No register copy, no
+// flag.  Two reads stay in flight, re-issued in the order of granule_gather1, with an explicit
+// s_waitcnt vmcnt(1): the variate prefetch is older in the in-order counter.
+//   The statement runs at most POLL_ROUNDS rounds (a counter register; it ends whatever memory
+// holds) and comes back with the counter at 0 when none hit.  There is no C++ loop round it -- any
+// such loop has the hit and the expiry as two exits, and with them the flags: a statement that ran
+// out hands over, out of line, to granule_gather1_all, which starts the clock there (the first
+// clock test, 128 rounds in, as in every gather), tests it every 128 rounds and expires as ever.
+//   The reads are invisible to hipcc's waitcnt pass.  They land in FIXED registers, named in the
+// statement and handed out in `q`; the caller keeps q live across granule_sum1 and retires it with
+// retire_polls_asm, and check_gather_tail.py fails the build if anything between the two touches
+// those registers (a pending read would land in a register given to something else).
+//   FIRST_PAD / GAP_A / GAP_B: the loop header lies at the start of a 32-byte fetch window: the
+// statement opens with .p2align 5 and the first read (8 bytes) and the gap's s_nop (4 bytes
+// each) are filled up to 32 bytes with FIRST_PAD s_nop 0 in front of the read.  That padding falls
+// in the idle slot in front of the first poll, whose wait states the caller shortens by it.
+constexpr unsigned POLL_ROUNDS = 128;
+// Wait states taken off the first poll's delay besides the statement's fixed padding.  Agent
+// scope: 4, the mean of its .p2align (0 .. 7 s_nop 0), so the first read stands where POLL_AGENT
+// has it.  Workgroup scope: 28, i.e. the read is issued as soon as the statement is reached -- with
+// the short poll rounds of the statement the optimum moved (C2, 4 / 8 / 12 / 16 / 20 / 28 states
+// taken off: 0.7477 / 0.7333 / 0.7343 / 0.7191 / 0.7163 / 0.7122 us per iteration against the
+// parent's 0.7311, one call).
+#ifndef BMC_POLL_ALIGN_STATES
+#define BMC_POLL_ALIGN_STATES 28
+#endif
+constexpr int POLL_ALIGN_STATES_AGENT = 4;
+#define BMC_POLL_QA "v[124:125]"
+#define BMC_POLL_QB "v[126:127]"
+#define BMC_POLL_ASM(PAD, GAP)                                                                     \
+    ".p2align 5\n\t" PAD                                                                           \
+    "global_load_dwordx2 v[124:125], %[p], off sc1\n\t" GAP                                        \
+    "0:\n\t"                                                                                       \
+    "global_load_dwordx2 v[126:127], %[p], off sc1\n\t"                                            \
+    "s_waitcnt vmcnt(1)\n\t"                                                                       \
+    "v_cmp_eq_u32_e32 vcc, %[ep], v125\n\t"                                                        \
+    "s_cmp_eq_u64 vcc, -1\n\t"                                                                     \
+    "s_cbranch_scc0 1f\n\t"                                                                        \
+    "v_cndmask_b32_e64 %[x], 0, v124, %[have]\n\t"                                                 \
+    "s_branch 3f\n\t"                                                                              \
+    "1:\n\t"                                                                                       \
+    "global_load_dwordx2 v[124:125], %[p], off sc1\n\t"                                            \
+    "s_waitcnt vmcnt(1)\n\t"                                                                       \
+    "v_cmp_eq_u32_e32 vcc, %[ep], v127\n\t"                                                        \
+    "s_cmp_eq_u64 vcc, -1\n\t"                                                                     \
+    "s_cbranch_scc1 2f\n\t"                                                                        \
+    "s_add_i32 %[cnt], %[cnt], -1\n\t"                                                             \
+    "s_cmp_lg_u32 %[cnt], 0\n\t"                                                                   \
+    "s_cbranch_scc1 0b\n\t"                                                                        \
+    "v_mov_b32_e32 %[x], 0\n\t"                                                                    \
+    "s_branch 3f\n\t"                                                                              \
+    ".p2align 5\n\t"                                                                               \
+    "2:\n\t"                                                                                       \
+    "v_cndmask_b32_e64 %[x], 0, v126, %[have]\n\t"                                                 \
+    "3:"
+// (the s_nop of the two spacings: 24 wait states in two instructions, none)
+#define BMC_NOP6 "s_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\t"
+#define BMC_NOP4 "s_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\t"
+template <int GAP>
+__device__ __forceinline__ bool granule_gather1_asm(const gu64* gp, int n2, unsigned epoch, int lane,
+                                                    gu64& x, gu64 (&q)[2]) {
+    static_assert(GAP == 0 || GAP == 24, "the spacings of POLL_AGENT and POLL_LOCAL");
+    const bool have = lane < n2;
+    const gu64* p = gp + gran_at(have ? lane : 0);
+    const gu64 have_m = __builtin_amdgcn_ballot_w64(have);
+    unsigned lo, cnt = POLL_ROUNDS;
+    if constexpr (GAP == 24)
+        asm volatile(BMC_POLL_ASM(BMC_NOP4, "s_nop 15\n\ts_nop 7\n\t")
+                     : [x] "=&v"(lo), "={" BMC_POLL_QA "}"(q[0]), "={" BMC_POLL_QB "}"(q[1]), [cnt] "+s"(cnt)
+                     : [p] "v"(p), [ep] "s"(epoch), [have] "s"(have_m)
+                     : "vcc", "scc", "memory");
+    else
+        asm volatile(BMC_POLL_ASM(BMC_NOP6, "")
+                     : [x] "=&v"(lo), "={" BMC_POLL_QA "}"(q[0]), "={" BMC_POLL_QB "}"(q[1]), [cnt] "+s"(cnt)
+                     : [p] "v"(p), [ep] "s"(epoch), [have] "s"(have_m)
+                     : "vcc", "scc", "memory");
+    x = lo;
+    // (the verdict is the counter itself, nonzero behind a hit, and opaque where the ways join: as
+    // `true` on the straight way hipcc wrote a constant flag behind every hit and carried it to
+    // the end of the iteration)
+    unsigned alive = cnt;
+    if (__builtin_expect(cnt == 0, 0)) {
+        // Ran out, out of line: the statement's last read is retired where it lands, the clock
+        // starts (the first test, 128 rounds in, as in every gather), and the polling goes on in
+        // C++ with its own reads, which are retired before the ways join: behind the join only
+        // the statement's registers are waited for.
+        asm volatile("s_waitcnt vmcnt(0)" : "+{" BMC_POLL_QA "}"(q[0]), "+{" BMC_POLL_QB "}"(q[1]));
+        gu64 q2[2];
+        const bool ok = granule_gather1_all<2>(gp, n2, epoch, lane, x, q2, NoPollSpacing(),
+                                               __builtin_amdgcn_s_memrealtime() | 1);
+        alive = (unsigned)__builtin_amdgcn_readfirstlane((int)ok);
+        asm volatile("" ::"v"(q2[0]), "v"(q2[1]));
+    }
+    asm volatile("" : "+s"(alive));
+    return alive != 0;
+}
+// what the statement's padding adds in front of the first read, in wait states (the .p2align
+// itself adds 0 .. 7 more, by where the statement lies)
+template <int GAP>
+constexpr int poll_asm_first_pad() { return GAP == 24 ? 4 : 6; }
+
+// Retire the reads of granule_gather1_asm behind the sum `tot`: the explicit wait, on the registers
+// they land in.
+__device__ __forceinline__ void retire_polls_asm(double& tot, const gu64 (&q)[2]) {
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(tot) : "{" BMC_POLL_QA "}"(q[0]), "{" BMC_POLL_QB "}"(q[1]));
+}
+
+
 template <int DEPTH = 2, int STRIDE = GRAN_PAIR_STRIDE, typename S = NoPollSpacing>
 __device__ __forceinline__ bool granule_gather1(const gu64* gp, int n2, unsigned epoch, int lane,
                                                 gu64& x, gu64 (&q)[DEPTH] STAMP_PARAMS, S space = S()) {
@@ -839,7 +999,10 @@ struct NoIdleWork {
 // RELAY passes) keep the two reads back to back.
 // When `ok` comes back false (the bounded spin expired) the return value is UNDEFINED -- the sum
 // of whatever was last read, or 0 -- and the caller must test `ok` before it uses the value.
-template <bool RELAY = false, int TEAMS = -1, int LOCAL = -1, bool SPACED = true, typename F = NoIdleWork>
+// ALLHIT: the first level's gather decides on all 64 lanes' tags (one level only): 1 =
+// granule_gather1_all, 2 = granule_gather1_asm (LOCAL known at compile time).
+template <bool RELAY = false, int TEAMS = -1, int LOCAL = -1, bool SPACED = true, int ALLHIT = 0,
+          typename F = NoIdleWork>
 __device__ __forceinline__ double exchange_sum(double s, gu64* gp, int G, int g, int lane,
                                                unsigned epoch, bool local, bool& ok STAMP_PARAMS,
                                                F idle = F()) {
@@ -865,20 +1028,39 @@ __device__ __forceinline__ double exchange_sum(double s, gu64* gp, int G, int g,
     constexpr bool PLAIN = RELAY || !SPACED;
     constexpr PollSched SL = PLAIN ? POLL_PLAIN : POLL_LOCAL, SA = PLAIN ? POLL_PLAIN : POLL_AGENT;
     static_assert(SL.depth == SA.depth, "one gather, two spacings");
-    if (local) wait_states<SL.first>();
-    else wait_states<SA.first>();
     gu64 q1[SL.depth];
-    ok = granule_gather1<SL.depth>(gp1, 2 * members, epoch, lane, x, q1 STAMP_ARGS, [&] {
+    static_assert(ALLHIT == 0 || (TEAMS == 0 && !RELAY), "all-lanes hit test: the one-level exchange");
+    // (the stamped build counts its polls in C++)
+#ifdef BMC_STAMPS
+    constexpr int HIT = ALLHIT == 2 ? 1 : ALLHIT;
+#else
+    constexpr int HIT = ALLHIT;
+#endif
+    auto gap = [&] {
         if (local) wait_states<SL.gap>();
         else wait_states<SA.gap>();
-    });
+    };
+    if constexpr (HIT == 2) {
+        // the poll rounds as one asm statement: its padding is part of the wait for the first read
+        static_assert(LOCAL >= 0 && SPACED && SL.depth == 2, "the asm gather: scope known, two reads");
+        constexpr PollSched SC = LOCAL ? SL : SA;
+        wait_states<SC.first - poll_asm_first_pad<SC.gap>() -
+                    (LOCAL ? BMC_POLL_ALIGN_STATES : POLL_ALIGN_STATES_AGENT)>();
+        ok = granule_gather1_asm<SC.gap>(gp1, 2 * members, epoch, lane, x, q1);
+    } else {
+        if (local) wait_states<SL.first>();
+        else wait_states<SA.first>();
+        if constexpr (HIT == 1) ok = granule_gather1_all<SL.depth>(gp1, 2 * members, epoch, lane, x, q1 STAMP_ARGS, gap);
+        else ok = granule_gather1<SL.depth>(gp1, 2 * members, epoch, lane, x, q1 STAMP_ARGS, gap);
+    }
     GSTAMP(5);
     // (after an expired spin the sum is taken of whatever was read and returned as it is: the
     // caller tests `ok` once, behind the sum, and the chain is over.  Leaving here put a flag
     // test and a branch in front of the sum; as `ok ? sum : 0` the flag travelled through the
     // whole serial path as set / test / branch pairs -- both tried)
     double tot = granule_sum1(x, lane);
-    retire_polls(tot, q1);
+    if constexpr (HIT == 2) retire_polls_asm(tot, q1);
+    else retire_polls(tot, q1);
     if (teams) {
         // (an expired first level must not publish its sum as a team total)
         if (__builtin_expect(!ok, 0)) return 0.0;
@@ -924,7 +1106,8 @@ __device__ __forceinline__ double exchange_sum(double s, gu64* gp, int G, int g,
 // ROW0 (LANEWISE, not SINGLE): the group total is only published, i.e. consumed by lanes 0 and 1,
 // and the leader finishes the wave sum from those lanes' own row total (sum_wave_rows_row0).
 template <bool SINGLE = false, bool LANEWISE = false, int TEAMS = -1, int LOCAL = -1, int ROLE = -1,
-          bool PREWRITTEN = false, bool SPACED = true, bool ROW0 = false, typename F = NoIdleWork>
+          bool PREWRITTEN = false, bool SPACED = true, bool ROW0 = false, int ALLHIT = 0,
+          typename F = NoIdleWork>
 __device__ __forceinline__ double group_allreduce(double s, double* red, gu64* gp, int G, int g,
                                                   int wave, int nw, int lane, unsigned epoch,
                                                   bool local, bool& ok STAMP_PARAMS, F idle = F()) {
@@ -944,7 +1127,7 @@ __device__ __forceinline__ double group_allreduce(double s, double* red, gu64* g
     else s = LANEWISE ? sum_wave_rows(red, lane) : sum_wave_slots(red, lane);
     GSTAMP(4);
     if constexpr (SINGLE) return s;
-    return exchange_sum<false, TEAMS, LOCAL, SPACED>(s, gp, G, g, lane, epoch, local, ok STAMP_ARGS, idle);
+    return exchange_sum<false, TEAMS, LOCAL, SPACED, ALLHIT>(s, gp, G, g, lane, epoch, local, ok STAMP_ARGS, idle);
 }
 
 // ---- several chains per pass (streaming / LDS residency) ---------------------------------

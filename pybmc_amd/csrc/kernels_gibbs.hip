@@ -44,14 +44,18 @@
 #ifndef BMC_LEADER_PRIO
 #define BMC_LEADER_PRIO 3      // s_setprio of the leader wave of a group (0: leave it alone)
 #endif
-// Code placement: the number of s_nop (4 bytes each, executed once per launch) in front of the
-// role-specific loop copies of the SMALLG kernels.  The headline leader's loop runs 3 % faster
-// with its header at the start of a 32-byte fetch window than 8 bytes behind it (DESIGN.md 4.1,
-// a sweep of 0 .. 15 with a period of 8, and again 0 .. 7 when the loop last changed: 4 % between
-// the best and the worst position); check_leader_stream.py fails the build when the header
-// is elsewhere, and this count is then what to adjust (0 .. 7 reach every position).
+// Code placement: the number of s_nop (4 bytes each, executed once per launch) between a 32-byte
+// boundary and the role-specific leader's loop in the SMALLG kernels (run_loop).  The headline
+// leader's loop runs 3 - 4 % faster or slower with where its header lies in its 32-byte fetch window
+// (sweeps of 0 .. 15 with a period of 8, and of 0 .. 7 whenever the loop changed);
+// check_leader_stream.py fails the build when the header is elsewhere, and this count is then what
+// to adjust (0 .. 7 reach every position).
 #ifndef BMC_PLACE_PAD
-#define BMC_PLACE_PAD 0
+#define BMC_PLACE_PAD 3
+#endif
+// A/B switch of the leader's hit path: the all-lanes hit test of its gather.
+#ifndef BMC_HIT_ALL
+#define BMC_HIT_ALL 2      // 0: the gather of every other loop, 1: all-lanes test in C++, 2: as one asm statement
 #endif
 
 namespace bmc {
@@ -252,6 +256,13 @@ void gibbs_loop_kernel(GibbsArgs a) {
     // another base and is never taken for this launch's; 0 is never a live tag)
     unsigned epoch = a.epoch0;           // iteration t exchanges under epoch0 + t + 1
     size_t slot = 0;                     // words from gr: 0 and gran_stride in turn
+    // Code placement of the role-specific leader's loop (BMC_PLACE_PAD above): a 32-byte boundary
+    // and BMC_PLACE_PAD s_nop in front of it, executed once per launch.  The boundary makes the
+    // header's place independent of the code above it.  The workgroup-scope copy only: the
+    // agent-scope copy, which lies in front of it, stays byte for byte where it was (forced agent
+    // scope lost 15 % at C2 when its loop was moved along).
+    if constexpr (SMALLG && !SINGLE && ROLE == 0 && LOCALK == 1)
+        asm volatile(".p2align 5\n\t.rept %0\n\ts_nop 0\n\t.endr" ::"n"(BMC_PLACE_PAD));
     for (int64_t t = 0; left != 0; ++t, --left) {
         ++epoch;
         STAMP(7);
@@ -358,7 +369,12 @@ void gibbs_loop_kernel(GibbsArgs a) {
         double floor_t = 0.0;
         // (the role-specific leader: the group total goes to publish_pair only, lanes 0 and 1)
         constexpr bool ROW0 = SMALLG && !SINGLE && LANEWISE && ROLE == 0;
-        const double rss = group_allreduce<SINGLE, LANEWISE, (SMALLG ? 0 : -1), LOCALK, ROLE, EARLY, true, ROW0>(
+        // (and in the workgroup-scope copy its gather decides on all 64 lanes' tags and polls through
+        // one asm statement, granule_gather1_asm.  The agent-scope copy keeps the gather it had: with
+        // the statement, agent scope forced, C2 lost 4 % and 16 chains gained 14 %, and its poll
+        // schedule, whose optimum is sharp, has not been swept again -- DESIGN.md 4.1)
+        constexpr int ALLHIT = (SMALLG && !SINGLE && ROLE == 0 && LOCALK == 1) ? BMC_HIT_ALL : 0;
+        const double rss = group_allreduce<SINGLE, LANEWISE, (SMALLG ? 0 : -1), LOCALK, ROLE, EARLY, true, ROW0, ALLHIT>(
             part, red, gslot, G, g, wave, nw, lane, epoch, local, got STAMP_ARGS, [&] {
                 floor_t = 1e-6 * gam_t;
                 asm volatile("" : "+v"(floor_t));
@@ -442,10 +458,6 @@ void gibbs_loop_kernel(GibbsArgs a) {
         // the test in front of barrier B2).
         const bool start_ok = SINGLE || __builtin_amdgcn_readfirstlane(__double2hiint(ctl[1])) == 0;
         if (start_ok) {
-#if BMC_PLACE_PAD > 0
-            // moves the role copies by 4-byte steps (see BMC_PLACE_PAD above)
-            asm volatile(".rept %0\n\ts_nop 0\n\t.endr" ::"n"(BMC_PLACE_PAD));
-#endif
             if (local) by_role(I1{});
             else by_role(I0{});
         }
@@ -1327,6 +1339,9 @@ LoopKernel gibbs_kernel(const GibbsArgs& a) {
     l.bundle_slots = a.bundle_slots;
     l.bundle_bal = a.bundle_bal;
     const KernelKey key = gibbs_kernel_key(shape_of(a.P), g, l);
+    // the SMALLG leader's gather tests the tags of all 64 lanes (granule_gather1_all): whole waves
+    // (loop_kernel) and at least one granule pair, of which the lanes past the last one read granule 0
+    if (key.family == KF_LOOP && key.smallg && (a.G < 2 || a.G > 32)) return LoopKernel{};
     const int slots = key.family == KF_WAVE ? a.n_chains
                       : key.family == KF_MULTI ? (key.slotted ? a.bundle_slots : 1)
                                                : a.nslot;
