@@ -606,6 +606,39 @@ int bmc_ppc_device(bmc_ctx* ctx, const void* dA, int64_t n_points, int32_t k, in
                    int64_t n_draws, int64_t ldt, uint64_t seed, double center, double* t_rep_out,
                    double* t_obs2_out);
 
+/* The same check of a Student-t fit (bmc_robust_run): y_rep[i][s] = a_i . beta_s + sigma_s z[i][s] +
+ * offset_i with z[i][s] a Student-t variate with nu (bmc_ppc_t) or nu_values[nu_index[s]]
+ * (bmc_ppc_tv; the table convention of bmc_pointwise_loglik_tv, at most 4096 values) degrees of
+ * freedom, made on the device: Bailey's polar form
+ *   z = sqrt(nu expm1(-(2 / nu) log u1)) cos(2 pi u2),
+ * u1 and u2 the two 53-bit uniforms in (0, 1] of ONE Philox4x32-10 call keyed by seed with counter
+ * (s lo, s hi, 0x50504354, i): the point index itself, and only the cosine half (the sine half
+ * shares the radius and is not independent of it).  z[i][s] depends on (seed, i, s, nu_s) alone,
+ * is finite for nu >= 0.06 and may be +-inf only for nu below about 0.052.  The arguments are those
+ * of bmc_ppc without `center`; t_rep_out and t_obs2_out, the sums, the moments and the NaN rules
+ * are the same: sum_i z^2 and max_i |z| are now of the t variates, and e is still
+ * (y_i - a_i . beta_s) / sigma_s.  BMC_EINVAL as bmc_ppc, and for a nu or a table entry that is not
+ * positive and finite, n_values < 1 or > 4096, or an index outside the table (host index: before
+ * anything runs; device index: after the run, the outputs are then not valid).  In the _device
+ * forms nu_values stays a HOST pointer and d_nu_index is int32 DEVICE memory.
+ * INTEGRATION.md section 12. */
+int bmc_ppc_t(bmc_ctx* ctx, const double* A, int64_t n_points, int32_t k, int64_t lda, int layout,
+              const double* y, const double* offset, const double* theta, int64_t n_draws,
+              int64_t ldt, uint64_t seed, double nu, double* t_rep_out, double* t_obs2_out);
+int bmc_ppc_t_device(bmc_ctx* ctx, const void* dA, int64_t n_points, int32_t k, int64_t lda,
+                     int layout, const void* dy, const void* doffset, const void* dtheta,
+                     int64_t n_draws, int64_t ldt, uint64_t seed, double nu, double* t_rep_out,
+                     double* t_obs2_out);
+int bmc_ppc_tv(bmc_ctx* ctx, const double* A, int64_t n_points, int32_t k, int64_t lda, int layout,
+               const double* y, const double* offset, const double* theta, int64_t n_draws,
+               int64_t ldt, uint64_t seed, const double* nu_values, int32_t n_values,
+               const int32_t* nu_index, double* t_rep_out, double* t_obs2_out);
+int bmc_ppc_tv_device(bmc_ctx* ctx, const void* dA, int64_t n_points, int32_t k, int64_t lda,
+                      int layout, const void* dy, const void* doffset, const void* dtheta,
+                      int64_t n_draws, int64_t ldt, uint64_t seed, const double* nu_values,
+                      int32_t n_values, const void* d_nu_index, double* t_rep_out,
+                      double* t_obs2_out);
+
 /* ---- power-scaling sensitivity: does the answer depend on the prior? (not in the reference) -----
  * Model and arguments A, y, theta as bmc_pointwise_loglik (n_draws >= 2 pooled draws, row s =
  * (beta_s, sigma_s)); the prior of bmc_set_prior: b0 [k], C0 [k][k] (row-major, symmetric positive

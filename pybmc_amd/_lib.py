@@ -152,6 +152,14 @@ PROTOTYPES = {
                           C.c_int64, C.c_uint64, C.c_double, _D, _D]),
     "bmc_ppc_device": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int, _P, _P, _P,
                                  C.c_int64, C.c_int64, C.c_uint64, C.c_double, _D, _D]),
+    "bmc_ppc_t": (C.c_int, [_P, _D, C.c_int64, C.c_int32, C.c_int64, C.c_int, _D, _D, _D, C.c_int64,
+                            C.c_int64, C.c_uint64, C.c_double, _D, _D]),
+    "bmc_ppc_t_device": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int, _P, _P, _P,
+                                   C.c_int64, C.c_int64, C.c_uint64, C.c_double, _D, _D]),
+    "bmc_ppc_tv": (C.c_int, [_P, _D, C.c_int64, C.c_int32, C.c_int64, C.c_int, _D, _D, _D, C.c_int64,
+                             C.c_int64, C.c_uint64, _D, C.c_int32, C.POINTER(C.c_int32), _D, _D]),
+    "bmc_ppc_tv_device": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int, _P, _P, _P,
+                                    C.c_int64, C.c_int64, C.c_uint64, _D, C.c_int32, _P, _D, _D]),
     "bmc_power_sensitivity": (C.c_int, [_P, _D, C.c_int64, C.c_int32, C.c_int64, C.c_int, _D, _D,
                                         C.c_int64, C.c_int64, _D, _D, C.c_double, C.c_double, _D,
                                         C.c_int32, _D, C.c_int32, C.c_uint32, C.c_int32, _D, _D, _D,
@@ -910,27 +918,71 @@ class Context:
                                 dA, n, k, lda, layout, dy, dtheta, n_draws, ldt)
 
     # -- posterior predictive check ---------------------------------------------------------------
-    def _ppc_call(self, fn, ptr, A, n, k, lda, layout, y, theta, n_draws, ldt, offset, seed, center):
+    def _ppc_call(self, fn, ptr, A, n, k, lda, layout, y, theta, n_draws, ldt, offset, seed, *noise):
+        """One predictive-check entry point; `noise` is what it takes between the seed and the
+        outputs: `center`, `nu`, or the table of `_nu_args`."""
         t_rep = np.empty((int(n_draws), 8))
         t_obs2 = np.empty((int(n_draws), 2))
         self._check(fn(self._h, ptr(A), int(n), int(k), int(lda), int(layout), ptr(y),
                        ptr(offset) if offset is not None else None, ptr(theta), int(n_draws),
-                       int(ldt), int(seed) & (2 ** 64 - 1), float(center), _dptr(t_rep),
-                       _dptr(t_obs2)))
+                       int(ldt), int(seed) & (2 ** 64 - 1), *noise, _dptr(t_rep), _dptr(t_obs2)))
         return {"t_rep": t_rep, "t_obs2": t_obs2}
+
+    @staticmethod
+    def _nu_args(ptr, nu_values, nu_index, n_draws):
+        """(values, count, index) as a _tv entry point takes them, and what must outlive the call:
+        `nu_values` the distinct degrees of freedom (host), `nu_index` every draw's index into
+        them, a host int32 array (ptr is _dptr) or a device address (_P)."""
+        vals = np.ascontiguousarray(nu_values, dtype=np.float64).reshape(-1)
+        if ptr is _dptr:
+            nu_index = np.ascontiguousarray(nu_index, dtype=np.int32).reshape(-1)
+            if nu_index.shape[0] != int(n_draws):
+                raise ValueError("nu_index must have one entry per draw")
+            idx = nu_index.ctypes.data_as(C.POINTER(C.c_int32))
+        else:
+            idx = _P(nu_index)
+        return (_dptr(vals), vals.shape[0], idx), (vals, nu_index)
 
     def ppc(self, A, n, k, lda, layout, y, theta, n_draws, ldt, offset, seed, center):
         """The per-draw statistics of replicated data, t_rep (n_draws, 8), and the observed chi2
         and max_abs_z, t_obs2 (n_draws, 2), of HOST f64 arrays (bmc_ppc); A, y and theta as
         pointwise_loglik, offset [n] or None; center is kept by the ABI and no longer read."""
         return self._ppc_call(self._lib.bmc_ppc, _dptr, A, n, k, lda, layout, y, theta, n_draws,
-                              ldt, offset, seed, center)
+                              ldt, offset, seed, float(center))
 
     def ppc_device(self, dA, n, k, lda, layout, dy, dtheta, n_draws, ldt, doffset, seed, center):
         """The same on DEVICE memory (bmc_ppc_device; doffset an address or None), read on the
         context's stream: the caller orders its producers before the call."""
         return self._ppc_call(self._lib.bmc_ppc_device, _P, dA, n, k, lda, layout, dy, dtheta,
-                              n_draws, ldt, doffset, seed, center)
+                              n_draws, ldt, doffset, seed, float(center))
+
+    def ppc_t(self, A, n, k, lda, layout, y, theta, n_draws, ldt, offset, seed, nu):
+        """ppc with Student-t replicated noise of `nu` degrees of freedom (bmc_ppc_t)."""
+        return self._ppc_call(self._lib.bmc_ppc_t, _dptr, A, n, k, lda, layout, y, theta, n_draws,
+                              ldt, offset, seed, float(nu))
+
+    def ppc_t_device(self, dA, n, k, lda, layout, dy, dtheta, n_draws, ldt, doffset, seed, nu):
+        """The same on DEVICE memory (bmc_ppc_t_device)."""
+        return self._ppc_call(self._lib.bmc_ppc_t_device, _P, dA, n, k, lda, layout, dy, dtheta,
+                              n_draws, ldt, doffset, seed, float(nu))
+
+    def ppc_tv(self, A, n, k, lda, layout, y, theta, n_draws, ldt, offset, seed, nu_values, nu_index):
+        """ppc with Student-t replicated noise of nu_values[nu_index[s]] degrees of freedom for draw
+        s (bmc_ppc_tv)."""
+        noise, held = self._nu_args(_dptr, nu_values, nu_index, n_draws)
+        out = self._ppc_call(self._lib.bmc_ppc_tv, _dptr, A, n, k, lda, layout, y, theta, n_draws,
+                             ldt, offset, seed, *noise)
+        del held
+        return out
+
+    def ppc_tv_device(self, dA, n, k, lda, layout, dy, dtheta, n_draws, ldt, doffset, seed, nu_values,
+                      d_nu_index):
+        """The same on DEVICE memory, the int32 index included (bmc_ppc_tv_device)."""
+        noise, held = self._nu_args(_P, nu_values, d_nu_index, n_draws)
+        out = self._ppc_call(self._lib.bmc_ppc_tv_device, _P, dA, n, k, lda, layout, dy, dtheta,
+                             n_draws, ldt, doffset, seed, *noise)
+        del held
+        return out
 
     # -- power-scaling sensitivity ----------------------------------------------------------------
     SENS_COMPONENTS = ("prior", "likelihood", "prior_beta", "prior_sigma2")   # bit order of the mask

@@ -567,6 +567,13 @@ class BayesianModelCombination:
         drawn from numpy's global stream and returned).  Returns that function's dict."""
         from .ppc import posterior_predictive_check
         self._require_gaussian("posterior_predictive_check")
+        A, y, offset = self._check_data(X)
+        return posterior_predictive_check(A, y, self._chains(), burn=burn, offset=offset, seed=seed,
+                                          device=self.device)
+
+    def _check_data(self, X):
+        """(A, y, offset) of a posterior predictive check: the training data without ``X``, else the
+        held-out frame (see ``posterior_predictive_check``)."""
         if X is None:
             if self.samples is None or self.U_hat is None:
                 raise ValueError("Must call `orthogonalize()` and `train()` before a posterior "
@@ -588,8 +595,27 @@ class BayesianModelCombination:
             A = preds @ np.asarray(self.Vt_hat, dtype=np.float64).T
             offset = preds.mean(axis=1)
             y = truth - offset
-        return posterior_predictive_check(A, y, self._chains(), burn=burn, offset=offset, seed=seed,
-                                          device=self.device)
+        return A, y, offset
+
+    def check(self, X=None, burn=0, seed=None):
+        """Posterior predictive check of the last ``train()`` under the likelihood it sampled from,
+        as ``score()`` scores it (not in the reference): for a Gaussian or simplex fit exactly
+        ``posterior_predictive_check()``; after ``{"sampler": "student_t"}`` the replicated noise
+        is Student-t with that fit's ``nu``, and after ``"nu": "estimate"`` every draw replicates
+        with its own ``nu`` -- the one predictive check that accepts a Student-t fit.  ``X``,
+        ``burn`` and ``seed`` as ``posterior_predictive_check()``.  Returns the dict of
+        ``pybmc_amd.ppc.posterior_predictive_check`` (``likelihood`` and ``nu_estimated``
+        included) and ``nu``: None for the Gaussian likelihood, the fit's value, or the mean over
+        the checked draws when it was estimated."""
+        from .ppc import posterior_predictive_check
+        nu = self._noise_df()
+        estimated = self._nu_estimated()
+        lik = {"nu_draws": self._nu_chains()} if estimated else {"nu": nu}
+        A, y, offset = self._check_data(X)
+        out = posterior_predictive_check(A, y, self._chains(), burn=burn, offset=offset, seed=seed,
+                                         device=self.device, **lik)
+        out["nu"] = float(np.mean(lik["nu_draws"][:, int(burn):])) if estimated else nu
+        return out
 
     # ----------------------------------------------------------------- predict
     def _require_trained(self):

@@ -392,6 +392,19 @@ struct PpcArgs {
     uint64_t seed;
     double center;
     double *Ap, *yo, *Tp, *sg, *t_rep, *t_obs2;
+    // The noise: nu = 0 and n_nu = 0, the standard normals above.  nu > 0 (finite): z is Student-t
+    // with nu degrees of freedom, student_t_variate (bmc_math.h) of the two uniforms of counter
+    // (s lo, s hi, STREAM_PPC_T, i).  n_nu > 0 (at most PPC_MAX_NU_VALUES; nu stays 0): a nu per
+    // draw, as ScoreArgs: all DEVICE pointers, nu_tab [2][n_nu] the distinct values and then
+    // 2 / value, nu_index [S] int32 into them (clamped into range in the kernel), nu_flag one int32
+    // word the caller has zeroed, set to 1 when an index was out of range; nus the work buffer of
+    // ppc_nu_bytes(plan) bytes.  The sums, the moments and the NaN rules do not depend on the noise.
+    double nu = 0.0;
+    int32_t n_nu = 0;
+    const double* nu_tab = nullptr;
+    const int32_t* nu_index = nullptr;
+    int32_t* nu_flag = nullptr;
+    double* nus = nullptr;
 };
 hipError_t launch_ppc(const PpcArgs& a, const PpcPlan& p, hipStream_t s);
 

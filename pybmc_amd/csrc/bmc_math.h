@@ -152,6 +152,63 @@ BMC_HD void box_muller_pair(double u1, double u2, double& z0, double& z1) {
     z1 = rad * sn;
 }
 
+// exp(x) - 1 for 0 <= x < 710 (x >= 710 gives +inf, as 710 itself does): the radius of the
+// Student-t variate below.  fdlibm's expm1 without the cases that cannot occur: x = k ln2 + r with
+// k = rint(x / ln2) in 0 .. 1024 and |r| <= ln2 / 2 (the product k ln2_hi is exact: ln2_hi ends in 32
+// zero bits), c the rounding error of r; p = expm1(r) by the rational kernel in r^2 / 2, with c
+// folded in as fdlibm folds it; then exp(x) - 1 = 2^k p + (2^k - 1), formed at half scale (2^1024 is
+// no double) by ONE fma where fdlibm branches three ways on k, since a branch per lane is what a
+// wave cannot afford.  2^(k-1) - 1/2 is exact up to k = 53 and is 2^(k-1) to well below an ulp
+// after.  Worst error found against expm1l: 1.34 ulp (tests/test_ppc_t_host.py, whose bar is 2.7).
+BMC_HD double expm1_nonneg(double x) {
+    const double ln2_hi = 6.93147180369123816490e-01, ln2_lo = 1.90821492927058770002e-10;
+    const double Q1 = -3.33333333333331316428e-02, Q2 = 1.58730158725481460165e-03,
+                 Q3 = -7.93650757867487942473e-05, Q4 = 4.00821782732936239552e-06,
+                 Q5 = -2.01099218183624371326e-07;
+    x = fmin(x, 710.0);
+    const double dk = rint(x * 1.44269504088896338700e+00);
+    const int k = (int)dk;
+    const double hi = fma(-dk, ln2_hi, x);
+    const double lo = dk * ln2_lo;
+    const double r = hi - lo;
+    const double c = (hi - r) - lo;
+    const double hfx = 0.5 * r;
+    const double hxs = r * hfx;
+    const double r1 = fma_c(hxs, fma_c(hxs, fma_c(hxs, fma_c(hxs, fma_c(hxs, Q5, Q4), Q3), Q2), Q1), 1.0);
+    const double t = fma(-r1, hfx, 3.0);
+    double e = hxs * ((r1 - t) / fma(-r, t, 6.0));
+    e = fma(r, e - c, -c) - hxs;
+    const double p = r - e;
+    const uint64_t ih = (uint64_t)(k + 1022) << 52;   // 2^(k-1); not read for k = 0
+    double h;
+    memcpy(&h, &ih, 8);
+    const double big = 2.0 * fma(h, p, h - 0.5);
+    return k == 0 ? p : big;
+}
+
+// One Student-t variate with nu > 0 degrees of freedom from two uniforms, u1 in (0, 1] and u2 in
+// [0, 1]: Bailey's polar form (R. W. Bailey, "Polar generation of random variates with the
+// t-distribution", Math. Comp. 62, 1994),
+//     t = sqrt(nu (u1^(-2/nu) - 1)) cos(2 pi u2) = sqrt(nu expm1(-(2/nu) log u1)) cos(2 pi u2),
+// exact, no rejection step, a fixed number of uniforms; as nu grows the radius tends to
+// Box-Muller's sqrt(-2 log u1).  The sine half is t_nu too, but it shares this radius: the two are
+// NOT independent (their magnitudes correlate at 0.80 for nu = 1.5), so a caller that needs
+// independent variates takes this one and draws again.  two_over_nu is 2 / nu, rounded once by the
+// caller.  u1 = 1 gives 0.  Past x = 64 the radius is sqrt(nu) exp(x / 2), which differs from
+// sqrt(nu expm1(x)) by exp(-64) / 2 of itself and is finite where exp(x) is not: the largest |t|,
+// at u1 = 2^-53, is sqrt(nu) 2^(53/nu), finite for nu >= 0.06 and +-inf only below about 0.052.
+// The logarithm, expm1 and the cosine are this file's, so the CPU build gives the device's bits.
+BMC_HD double student_t_variate(double u1, double u2, double nu, double two_over_nu) {
+    const double x = two_over_nu * -log_normal_arg(u1);
+    const bool far = x > 64.0;
+    const double em = expm1_nonneg(far ? 0.5 * x : x);
+    const double root = sqrt(nu * (far ? 1.0 : em));
+    const double rad = far ? root * (em + 1.0) : root;
+    double sn, cs;
+    sincos_2pi(u2, sn, cs);
+    return rad * cs;
+}
+
 // Inverse of the standard normal CDF for 0 < p < 1 with min(p, 1 - p) a normal double: Wichura's
 // AS 241, routine PPND16 (Applied Statistics 37(3), 1988; about 1e-16 relative).  Three rational
 // approximations of degree 7: |p - 1/2| <= 0.425 in q^2, the tails in r = sqrt(-log(min(p, 1 - p))),

@@ -967,6 +967,11 @@ inline PpcBuffers ppc_buffers(const PpcPlan& p, int64_t n_draws) {
     b.out = (size_t)n_draws * (PPC_STATS + PPC_OBS) * 8;
     return b;
 }
+// The Student-t check with a nu per draw (PpcArgs::nus) needs one buffer more, [2][S_pad] f64: nu_s,
+// then 2 / nu_s (4 and 1/2 in the padding).  A function of its own: no size above depends on the
+// noise.  At most PPC_MAX_NU_VALUES distinct values, the limit of the scorers' nu_draws.
+constexpr int32_t PPC_MAX_NU_VALUES = 4096;
+inline size_t ppc_nu_bytes(const PpcPlan& p) { return (size_t)p.S_pad * 2 * 8; }
 
 // ---- posterior predictive order statistics (kernels_predict.hip) ----------------
 // Which kernels read the requested ranks off the S draws of each of M points, and with what grid,

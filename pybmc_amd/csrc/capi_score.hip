@@ -84,7 +84,8 @@ int score_stage(bmc_ctx* c, ScoreIn& in) {
 // The _tv calls: the table of distinct nu with its constants and the zeroed flag word go to scNu; a
 // host index is checked here and staged (`in` then names the staged copy).  BMC_EINVAL for a table
 // entry that is not positive and finite, n_values < 1, a NULL pointer or a host index out of range.
-int score_nu(bmc_ctx* c, ScoreIn& in, bool on_host) {
+// for_ppc: the table of the predictive check instead, the values first and then 2 / value.
+int score_nu(bmc_ctx* c, ScoreIn& in, bool on_host, bool for_ppc = false) {
     if (in.n_nu < 1) return fail(c, BMC_EINVAL, "n_values must be >= 1");
     if (!in.nu_values || !in.nu_index) return fail(c, BMC_EINVAL, "nu_values and nu_index must not be NULL");
     const size_t V = (size_t)in.n_nu, S = (size_t)in.S;
@@ -92,8 +93,8 @@ int score_nu(bmc_ctx* c, ScoreIn& in, bool on_host) {
     for (size_t v = 0; v < V; ++v) {
         const double nu = in.nu_values[v];
         if (!(nu > 0.0 && nu < INFINITY)) return fail(c, BMC_EINVAL, "nu_values must be positive and finite");
-        tab[v] = student_t_cnu(nu);
-        tab[V + v] = nu;
+        tab[v] = for_ppc ? nu : student_t_cnu(nu);
+        tab[V + v] = for_ppc ? 2.0 / nu : nu;
     }
     if (on_host) {
         const int32_t* idx = (const int32_t*)in.nu_index;
@@ -193,11 +194,16 @@ int score_entry(bmc_ctx* c, ScoreIn in, bool on_host, ScoreFamily family,
 }
 
 // One posterior predictive check: host operands are staged first (offset may be NULL: zeros),
-// then the plan, the launch, the two result blocks to the host and one sync.
+// then the plan, the launch, the two result blocks to the host and one sync.  The noise is in.nu
+// and in.n_nu as the scoring calls carry the likelihood (a nu per draw: score_nu's table in scNu).
 int ppc_entry(bmc_ctx* c, ScoreIn in, const void* offset, bool on_host, uint64_t seed, double center,
               double* t_rep_out, double* t_obs2_out) {
-    int rc = check_score_args(c, in.A, in.n, in.k, in.lda, in.layout, in.y, in.theta, in.S, in.ldt);
+    int rc = check_score_args(c, in.A, in.n, in.k, in.lda, in.layout, in.y, in.theta, in.S, in.ldt,
+                              in.nu);
     if (rc) return rc;
+    const bool per_draw = in.nu_values || in.nu_index || in.n_nu != 0;
+    if (per_draw && in.n_nu > PPC_MAX_NU_VALUES)
+        return fail(c, BMC_EINVAL, "n_values must be at most " + std::to_string(PPC_MAX_NU_VALUES));
     const PpcPlan plan = plan_ppc(in.n, in.S, in.k, c->n_cu);
     if (!plan.ok)
         return fail(c, BMC_EINVAL, "n_points must be between " + std::to_string(PPC_MIN_POINTS) + " and " +
@@ -211,8 +217,9 @@ int ppc_entry(bmc_ctx* c, ScoreIn in, const void* offset, bool on_host, uint64_t
             offset = c->ppcOff.p;
         }
     }
+    if (per_draw && (rc = score_nu(c, in, on_host, true))) return rc;
     const PpcBuffers pb = ppc_buffers(plan, in.S);
-    if ((rc = ensure(c, c->ppcWork, pb.total()))) return rc;
+    if ((rc = ensure(c, c->ppcWork, pb.total() + (per_draw ? ppc_nu_bytes(plan) : 0)))) return rc;
     char* w = (char*)c->ppcWork.p;
     PpcArgs a;
     a.A = (const double*)in.A;
@@ -233,7 +240,18 @@ int ppc_entry(bmc_ctx* c, ScoreIn in, const void* offset, bool on_host, uint64_t
     a.sg = (double*)(w += pb.Tp);
     a.t_rep = (double*)(w += pb.sg);
     a.t_obs2 = a.t_rep + (size_t)in.S * PPC_STATS;
+    a.nu = in.nu;
+    int32_t flag = 0;
+    if (per_draw) {   // score_nu has laid scNu out: [2][n_nu] f64, [S] i32 staged index, the flag
+        a.n_nu = in.n_nu;
+        a.nu_tab = (const double*)c->scNu.p;
+        a.nu_index = (const int32_t*)in.nu_index;
+        a.nu_flag = (int32_t*)((char*)c->scNu.p + (size_t)in.n_nu * 16 + (size_t)in.S * 4);
+        a.nus = (double*)(w + pb.out);
+    }
     HIPCHK(c, launch_ppc(a, plan, c->stream));
+    if (per_draw)
+        HIPCHK(c, hipMemcpyAsync(&flag, a.nu_flag, 4, hipMemcpyDeviceToHost, c->stream));
     if (t_rep_out)
         HIPCHK(c, hipMemcpyAsync(t_rep_out, a.t_rep, (size_t)in.S * PPC_STATS * 8, hipMemcpyDeviceToHost,
                                  c->stream));
@@ -241,12 +259,17 @@ int ppc_entry(bmc_ctx* c, ScoreIn in, const void* offset, bool on_host, uint64_t
         HIPCHK(c, hipMemcpyAsync(t_obs2_out, a.t_obs2, (size_t)in.S * PPC_OBS * 8, hipMemcpyDeviceToHost,
                                  c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (flag) return fail(c, BMC_EINVAL, "nu_index must index nu_values (the results are not valid)");
     return BMC_OK;
 }
 
 // nu of a _t entry point as ScoreIn carries it: what is not positive (0 would mean Gaussian there)
 // becomes NaN, which check_score_args refuses
 double t_nu(double nu) { return nu > 0.0 ? nu : NAN; }
+
+// n_values of a bmc_ppc_tv entry point as ScoreIn carries it: 0 there would mean "no nu per draw"
+// when both pointers are NULL too, so what is not positive becomes -1, which score_nu refuses
+int32_t tv_count(int32_t n_values) { return n_values > 0 ? n_values : -1; }
 
 }  // namespace
 
@@ -379,6 +402,37 @@ int bmc_ppc_device(bmc_ctx* c, const void* dA, int64_t n_points, int32_t k, int6
                    uint64_t seed, double center, double* t_rep_out, double* t_obs2_out) {
     return ppc_entry(c, {dA, dy, dtheta, n_points, lda, n_draws, ldt, k, layout}, doffset, false, seed,
                      center, t_rep_out, t_obs2_out);
+}
+
+int bmc_ppc_t(bmc_ctx* c, const double* A, int64_t n_points, int32_t k, int64_t lda, int layout,
+              const double* y, const double* offset, const double* theta, int64_t n_draws, int64_t ldt,
+              uint64_t seed, double nu, double* t_rep_out, double* t_obs2_out) {
+    return ppc_entry(c, {A, y, theta, n_points, lda, n_draws, ldt, k, layout, t_nu(nu)}, offset, true, seed,
+                     0.0, t_rep_out, t_obs2_out);
+}
+
+int bmc_ppc_t_device(bmc_ctx* c, const void* dA, int64_t n_points, int32_t k, int64_t lda, int layout,
+                     const void* dy, const void* doffset, const void* dtheta, int64_t n_draws,
+                     int64_t ldt, uint64_t seed, double nu, double* t_rep_out, double* t_obs2_out) {
+    return ppc_entry(c, {dA, dy, dtheta, n_points, lda, n_draws, ldt, k, layout, t_nu(nu)}, doffset, false,
+                     seed, 0.0, t_rep_out, t_obs2_out);
+}
+
+int bmc_ppc_tv(bmc_ctx* c, const double* A, int64_t n_points, int32_t k, int64_t lda, int layout,
+               const double* y, const double* offset, const double* theta, int64_t n_draws, int64_t ldt,
+               uint64_t seed, const double* nu_values, int32_t n_values, const int32_t* nu_index,
+               double* t_rep_out, double* t_obs2_out) {
+    return ppc_entry(c, {A, y, theta, n_points, lda, n_draws, ldt, k, layout, 0.0, tv_count(n_values),
+                         nu_values, nu_index}, offset, true, seed, 0.0, t_rep_out, t_obs2_out);
+}
+
+int bmc_ppc_tv_device(bmc_ctx* c, const void* dA, int64_t n_points, int32_t k, int64_t lda, int layout,
+                      const void* dy, const void* doffset, const void* dtheta, int64_t n_draws,
+                      int64_t ldt, uint64_t seed, const double* nu_values, int32_t n_values,
+                      const void* d_nu_index, double* t_rep_out, double* t_obs2_out) {
+    return ppc_entry(c, {dA, dy, dtheta, n_points, lda, n_draws, ldt, k, layout, 0.0,
+                         tv_count(n_values), nu_values, d_nu_index}, doffset, false, seed, 0.0, t_rep_out,
+                     t_obs2_out);
 }
 
 }  // extern "C"

@@ -32,6 +32,9 @@
 // points of one lane (MFMA columns cl + 16 t, t and t + 2), so a Philox call serves two elements.
 // z[i][s] depends on (seed, i, s) alone.
 //
+// For a Student-t fit z is a t variate instead (PpcNoise below): one nu for all draws,
+// or nu_s per draw, staged by ppc_pad_draws beside sigma_s.  Everything after z is the same text.
+//
 // No atomics and no split over the points: every sum has one fixed order (tile by tile in the
 // lane, then the lane tree), whatever the CU count.  Padded points add nothing (their z, e and
 // centred value are replaced by 0, their y_rep by +-inf for min / max); padded draws are computed
@@ -95,12 +98,23 @@ __global__ __launch_bounds__(1024) void ppc_col_mean_kernel(const double* __rest
     }
 }
 
+// Nu... is empty (the Gaussian check and the one-nu t check) or the staging of a nu per draw (PpcNuStage,
+// the t check with nu_index): the draw's nu_s and 2 / nu_s to nus [2][S_pad], 4 and 1/2 in the padding.
+struct PpcNuStage {
+    const double* tab;      // [2][n_nu]: the distinct values, then 2 / value (formed on the host)
+    const int32_t* index;   // [S] into them; out of range: clamped, and *flag = 1
+    int32_t* flag;
+    double* nus;
+    int32_t n_nu;
+};
+
+template <typename... Nu>
 __global__ __launch_bounds__(256) void ppc_pad_draws_kernel(const double* __restrict__ theta,
                                                             int64_t S, int64_t ldt, int32_t k,
                                                             int64_t S_pad, int32_t k_pad,
                                                             const double* __restrict__ cm,
                                                             double* __restrict__ Tp,
-                                                            double* __restrict__ sg) {
+                                                            double* __restrict__ sg, Nu... nu) {
     pad_rows(theta, S, ldt, k, S_pad, k_pad, Tp);
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     // then a thread per draw (all lanes of a wave at work, not one in k_pad): sigma_s, whether the
@@ -120,6 +134,21 @@ __global__ __launch_bounds__(256) void ppc_pad_draws_kernel(const double* __rest
         sg[s] = sigma;
         sg[S_pad + s] = good ? 1.0 / sigma : __builtin_nan("");
         sg[2 * S_pad + s] = is_finite(c) ? c : 0.0;
+        if constexpr (sizeof...(Nu) > 0) {
+            const PpcNuStage st{nu...};
+            double v = 4.0, tv = 0.5;
+            if (s < S) {
+                int32_t iv = st.index[s];
+                if (iv < 0 || iv >= st.n_nu) {
+                    *st.flag = 1;
+                    iv = iv < 0 ? 0 : st.n_nu - 1;
+                }
+                v = st.tab[iv];
+                tv = st.tab[st.n_nu + iv];
+            }
+            st.nus[s] = v;
+            st.nus[S_pad + s] = tv;
+        }
     }
 }
 
@@ -154,16 +183,42 @@ __device__ __forceinline__ void ppc_fold(PpcRun& st, double dot, double z, doubl
     st.me = fmax(st.me, fabs(e));
 }
 
+// The noise of the replicated data.  PPC_GAUSS: the standard normals of the header, no further
+// argument.  PPC_T: Student-t with one nu for all draws; Lik = (double nu, double 2 / nu).
+// PPC_TV: a nu per draw; Lik = (const double* nus), [2][S_pad]: nu_s, then 2 / nu_s, which wait in
+// LDS beside sigma_s and c_s.  The t variate of (point i, draw s) is student_t_variate (bmc_math.h)
+// of the two uniforms of counter (s lo, s hi, STREAM_PPC_T, i): the point index itself, one Philox
+// call per element.  Only the cosine half of Bailey's polar pair is taken: the sine half shares
+// its radius, and handing it to point i + 32 as the Gaussian walk does would replicate data whose
+// errors depend on each other in pairs.  z[i][s] depends on (seed, i, s, nu_s) alone.
+enum PpcNoise { PPC_GAUSS = 0, PPC_T = 1, PPC_TV = 2 };
+template <typename... Lik>
+struct PpcLik {};
+template <>
+struct PpcLik<double, double> {
+    double nu, two_over_nu;
+};
+template <>
+struct PpcLik<const double*> {
+    const double* nus;
+};
+
 // grid: one workgroup per draw tile.  The workgroups that run together walk the same point tiles
 // at about the same time, so a tile of the design is fetched into each XCD's L2 once for all.
-__global__ __launch_bounds__(256, 2) void ppc_tile_kernel(
+// The t instantiations build for one workgroup per CU: the temporaries of the t variate do not fit
+// beside the running values in the 256 registers that two workgroups leave each (45 to 51 spilled);
+// with one, the overflow lives in AGPRs and nothing goes to scratch.
+template <PpcNoise NOISE, typename... Lik>
+__global__ __launch_bounds__(256, NOISE == PPC_GAUSS ? 2 : 1) void ppc_tile_kernel(
     const double* __restrict__ Tp, const double* __restrict__ sg, const double* __restrict__ Ap,
     const double* __restrict__ yo, int64_t n, int64_t n_pad, int64_t S, int64_t S_pad, int32_t k,
     int32_t k_pad, int64_t point_tiles, uint64_t seed, double* __restrict__ t_rep,
-    double* __restrict__ t_obs2) {
+    double* __restrict__ t_obs2, Lik... lik) {
+    // doubles per draw in LDS: (sigma_s, c_s), and (nu_s, 2 / nu_s) behind them for PPC_TV
+    constexpr int SCW = NOISE == PPC_TV ? 4 : 2;
     __shared__ double As[SC_LDS_DOUBLES];
     __shared__ double Bs[SC_LDS_DOUBLES];
-    __shared__ double sc[2 * SC_TM];   // (sigma_s, c_s) of the workgroup's draws
+    __shared__ double sc[SCW * SC_TM];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int cl = lane & 15, kq = lane >> 4;
@@ -178,15 +233,19 @@ __global__ __launch_bounds__(256, 2) void ppc_tile_kernel(
 #pragma unroll
     for (int r = 0; r < 4; ++r)
         st[r] = PpcRun{__builtin_inf(), -__builtin_inf(), 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    const PpcLik<Lik...> lk{lik...};
     if (tid < SC_TM) {
-        sc[2 * tid] = sg[d0 + tid];
-        sc[2 * tid + 1] = sg[2 * S_pad + d0 + tid];
+        sc[SCW * tid] = sg[d0 + tid];
+        sc[SCW * tid + 1] = sg[2 * S_pad + d0 + tid];
+        if constexpr (NOISE == PPC_TV) {
+            sc[SCW * tid + 2] = lk.nus[d0 + tid];
+            sc[SCW * tid + 3] = lk.nus[S_pad + d0 + tid];
+        }
     }
     __syncthreads();
-    const double* sc_r = sc + 2 * (16 * wave + kq);   // draw r of the lane: sc_r[8 r], sc_r[8 r + 1]
+    // draw r of the lane: sc_r[4 SCW r], sc_r[4 SCW r + 1], ..
+    const double* sc_r = sc + SCW * (16 * wave + kq);
 
-    // epilogue: the lane's points are i0 + cl + 16 t; points t and t + 2 (32 apart) share a
-    // counter, the cosine half to t
     score_tile_loop(Tp, Ap, n_pad, (int64_t)k_pad, k, k_pad, d0, 0, point_tiles, As, Bs,
                     [&](int64_t i0, const f64x4(&acc)[4]) {
         const bool full = i0 + SC_TM <= n;   // wave-uniform
@@ -199,28 +258,60 @@ __global__ __launch_bounds__(256, 2) void ppc_tile_kernel(
             ov[t] = yo[n_pad + i];
             ok[t] = i < n;
         }
-        const uint32_t pr = (uint32_t)(i0 >> 6) * 32u + (uint32_t)cl;
+        if constexpr (NOISE == PPC_GAUSS) {
+            // the lane's points are i0 + cl + 16 t; points t and t + 2 (32 apart) share a counter,
+            // the cosine half to t
+            const uint32_t pr = (uint32_t)(i0 >> 6) * 32u + (uint32_t)cl;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const double sigma = sc_r[8 * r], center = sc_r[8 * r + 1];
+            for (int r = 0; r < 4; ++r) {
+                const double sigma = sc_r[4 * SCW * r], center = sc_r[4 * SCW * r + 1];
 #pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const u32x4 w = philox4x32_10(u32x4{dlo + 4u * r, dhi, STREAM_PPC, pr + 16u * h}, k0, k1);
-                double z0, z1;
-                box_muller_pair(u53_open0(w.x, w.y), u53_open0(w.z, w.w), z0, z1);
-                if (full) {
-                    ppc_fold<true>(st[r], acc[h][r], z0, yv[h], ov[h], sigma, center, true);
-                    ppc_fold<true>(st[r], acc[h + 2][r], z1, yv[h + 2], ov[h + 2], sigma, center,
-                                   true);
-                } else {
-                    ppc_fold<false>(st[r], acc[h][r], z0, yv[h], ov[h], sigma, center, ok[h]);
-                    ppc_fold<false>(st[r], acc[h + 2][r], z1, yv[h + 2], ov[h + 2], sigma, center,
-                                    ok[h + 2]);
+                for (int h = 0; h < 2; ++h) {
+                    const u32x4 w =
+                        philox4x32_10(u32x4{dlo + 4u * r, dhi, STREAM_PPC, pr + 16u * h}, k0, k1);
+                    double z0, z1;
+                    box_muller_pair(u53_open0(w.x, w.y), u53_open0(w.z, w.w), z0, z1);
+                    if (full) {
+                        ppc_fold<true>(st[r], acc[h][r], z0, yv[h], ov[h], sigma, center, true);
+                        ppc_fold<true>(st[r], acc[h + 2][r], z1, yv[h + 2], ov[h + 2], sigma, center,
+                                       true);
+                    } else {
+                        ppc_fold<false>(st[r], acc[h][r], z0, yv[h], ov[h], sigma, center, ok[h]);
+                        ppc_fold<false>(st[r], acc[h + 2][r], z1, yv[h + 2], ov[h + 2], sigma, center,
+                                        ok[h + 2]);
+                    }
+                    // one pair at a time: left to itself the scheduler interleaves the eight
+                    // Philox / Box-Muller chains of a tile and their temporaries no longer fit
+                    // beside the 80 registers of running values
+                    __builtin_amdgcn_sched_barrier(0);
                 }
-                // one pair at a time: left to itself the scheduler interleaves the eight
-                // Philox / Box-Muller chains of a tile and their temporaries no longer fit beside
-                // the 80 registers of running values
-                __builtin_amdgcn_sched_barrier(0);
+            }
+        } else {
+            // the lane's points are i0 + cl + 16 t, each with a counter of its own (the padded
+            // index fits the word: plan_ppc refuses more than 2^31 points)
+            const uint32_t pt = (uint32_t)i0 + (uint32_t)cl;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const double sigma = sc_r[4 * SCW * r], center = sc_r[4 * SCW * r + 1];
+                double nu, two_over_nu;
+                if constexpr (NOISE == PPC_TV) {
+                    nu = sc_r[4 * SCW * r + 2];
+                    two_over_nu = sc_r[4 * SCW * r + 3];
+                } else {
+                    nu = lk.nu;
+                    two_over_nu = lk.two_over_nu;
+                }
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    const u32x4 w =
+                        philox4x32_10(u32x4{dlo + 4u * r, dhi, STREAM_PPC_T, pt + 16u * t}, k0, k1);
+                    const double z = student_t_variate(u53_open0(w.x, w.y), u53_open0(w.z, w.w), nu,
+                                                       two_over_nu);
+                    if (full) ppc_fold<true>(st[r], acc[t][r], z, yv[t], ov[t], sigma, center, true);
+                    else ppc_fold<false>(st[r], acc[t][r], z, yv[t], ov[t], sigma, center, ok[t]);
+                    // one variate at a time, as above
+                    __builtin_amdgcn_sched_barrier(0);
+                }
             }
         }
     });
@@ -248,7 +339,7 @@ __global__ __launch_bounds__(256, 2) void ppc_tile_kernel(
         const int64_t d = d0 + 16 * wave + kq + 4 * r;
         if (cl == 0 && d < S) {
             // central moments (ddof 0) from the power sums about the draw's centre
-            const double center = sc_r[8 * r + 1];
+            const double center = sc_r[4 * SCW * r + 1];
             const double a1 = me.p1 / nn, a2 = me.p2 / nn, a3 = me.p3 / nn, a4 = me.p4 / nn;
             const double a1s = a1 * a1;
             const double m2 = a2 - a1s;
@@ -283,7 +374,9 @@ hipError_t launch_ppc(const PpcArgs& a, const PpcPlan& p, hipStream_t s) {
     const PpcPlan want = plan_ppc(a.n, a.S, a.k, 1);
     if (!p.ok || !want.ok || a.ldt < (int64_t)a.k + 1 || a.lda < (a.col_major ? a.n : (int64_t)a.k) ||
         p.point_tiles != want.point_tiles || p.draw_tiles != want.draw_tiles || p.n_pad != want.n_pad ||
-        p.S_pad != want.S_pad || p.k_pad != want.k_pad || p.grid != want.grid || p.grid > 0x7fffffffll)
+        p.S_pad != want.S_pad || p.k_pad != want.k_pad || p.grid != want.grid || p.grid > 0x7fffffffll ||
+        !(a.nu >= 0.0 && a.nu < __builtin_inf()) || a.n_nu < 0 || a.n_nu > PPC_MAX_NU_VALUES ||
+        (a.n_nu > 0 && (a.nu != 0.0 || !a.nu_tab || !a.nu_index || !a.nu_flag || !a.nus)))
         return hipErrorInvalidValue;
     const hipError_t e = launch_pad_points(a.A, a.y, a.offset, true, a.n, a.k, a.lda, a.col_major, p.n_pad,
                                            p.k_pad, a.Ap, a.yo, s);
@@ -291,15 +384,30 @@ hipError_t launch_ppc(const PpcArgs& a, const PpcPlan& p, hipStream_t s) {
     double* cm = a.sg + 3 * p.S_pad;   // the column means and the mean offset, behind the three rows
     hipLaunchKernelGGL(ppc_col_mean_kernel, dim3((unsigned)(p.k_pad / 16 + 1)), dim3(1024), 0, s,
                        (const double*)a.Ap, (const double*)a.yo, a.n, p.n_pad, p.k_pad, cm);
-    {
-        int64_t blocks = (p.S_pad * p.k_pad + 255) / 256;
-        if (blocks > 8192) blocks = 8192;
-        hipLaunchKernelGGL(ppc_pad_draws_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a.theta, a.S,
+    int64_t blocks = (p.S_pad * p.k_pad + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    if (a.n_nu > 0)
+        hipLaunchKernelGGL(ppc_pad_draws_kernel<PpcNuStage>, dim3((unsigned)blocks), dim3(256), 0, s,
+                           a.theta, a.S, a.ldt, a.k, p.S_pad, p.k_pad, (const double*)cm, a.Tp, a.sg,
+                           PpcNuStage{a.nu_tab, a.nu_index, a.nu_flag, a.nus, a.n_nu});
+    else
+        hipLaunchKernelGGL(ppc_pad_draws_kernel<>, dim3((unsigned)blocks), dim3(256), 0, s, a.theta, a.S,
                            a.ldt, a.k, p.S_pad, p.k_pad, (const double*)cm, a.Tp, a.sg);
-    }
-    hipLaunchKernelGGL(ppc_tile_kernel, dim3((unsigned)p.grid), dim3(256), 0, s, (const double*)a.Tp,
-                       (const double*)a.sg, (const double*)a.Ap, (const double*)a.yo, a.n, p.n_pad, a.S,
-                       p.S_pad, a.k, p.k_pad, p.point_tiles, a.seed, a.t_rep, a.t_obs2);
+    if (a.n_nu > 0)
+        hipLaunchKernelGGL((ppc_tile_kernel<PPC_TV, const double*>), dim3((unsigned)p.grid), dim3(256), 0,
+                           s, (const double*)a.Tp, (const double*)a.sg, (const double*)a.Ap,
+                           (const double*)a.yo, a.n, p.n_pad, a.S, p.S_pad, a.k, p.k_pad, p.point_tiles,
+                           a.seed, a.t_rep, a.t_obs2, (const double*)a.nus);
+    else if (a.nu > 0.0)
+        hipLaunchKernelGGL((ppc_tile_kernel<PPC_T, double, double>), dim3((unsigned)p.grid), dim3(256), 0,
+                           s, (const double*)a.Tp, (const double*)a.sg, (const double*)a.Ap,
+                           (const double*)a.yo, a.n, p.n_pad, a.S, p.S_pad, a.k, p.k_pad, p.point_tiles,
+                           a.seed, a.t_rep, a.t_obs2, a.nu, 2.0 / a.nu);
+    else
+        hipLaunchKernelGGL(ppc_tile_kernel<PPC_GAUSS>, dim3((unsigned)p.grid), dim3(256), 0, s,
+                           (const double*)a.Tp, (const double*)a.sg, (const double*)a.Ap,
+                           (const double*)a.yo, a.n, p.n_pad, a.S, p.S_pad, a.k, p.k_pad, p.point_tiles,
+                           a.seed, a.t_rep, a.t_obs2);
     return hipGetLastError();
 }
 
