@@ -752,7 +752,8 @@ int bmc_robust_run_device(bmc_ctx* ctx, double nu, int32_t n_chains, int64_t ite
  *   variates of those shapes.  The index the kernel would have picked from u_t is still computed and
  *   written to nu_idx_out; the chain continues on the forced path.
  * nu_idx_out [n_chains][iters] (rows a stopped chain never reached hold -1); tstat_out
- * [n_chains][iters] or NULL.  BMC_EINVAL (nothing is launched) for whatever bmc_robust_run refuses,
+ * [n_chains][iters] (rows a stopped chain never reached hold NaN, in d_tstat_out of the _device form
+ * too) or NULL.  BMC_EINVAL (nothing is launched) for whatever bmc_robust_run refuses,
  * n_grid outside 1 .. 64, a grid that is not strictly increasing, positive and finite, weights that
  * are negative, not finite or all zero, nu_init out of range or of weight zero, a nu_path entry out of
  * range.  Everything else -- statuses, stats, launches of at most 1024 chains, chain c bit for bit its

@@ -97,6 +97,7 @@ int robust_common(bmc_ctx* c, double nu, const NuSpec* ns, int32_t n_chains, int
         HIPCHK(c, hipMemcpyAsync(d_tab, tab.data(), 4 * G * 8, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (T > 0) HIPCHK(c, hipMemsetAsync(d_idx, 0xff, C * T * 4, c->stream));   // -1: never drawn
+        if (T > 0 && d_tstat) HIPCHK(c, hipMemsetAsync(d_tstat, 0xff, C * T * 8, c->stream));   // NaN: likewise
         if (replay_nu && Tt > 0) {
             HIPCHK(c, hipMemcpyAsync(d_unu, ns->u_nu, C * Tt * 8, hipMemcpyHostToDevice, c->stream));
             HIPCHK(c, hipMemcpyAsync(d_path, ns->nu_path, C * Tt * 4, hipMemcpyHostToDevice, c->stream));
