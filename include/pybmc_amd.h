@@ -692,6 +692,61 @@ int bmc_power_sensitivity_device(bmc_ctx* ctx, const void* dA, int64_t n_points,
                                  double* weights_out, uint32_t* flags_out);
 int bmc_sens_last_timing(bmc_ctx* ctx, double ms_out[4]);
 
+/* The same under the Student-t likelihood of bmc_robust_run (a fit of the robust sampler): the
+ * arguments of bmc_power_sensitivity and, behind cols_per_batch, the degrees of freedom.  _t: one
+ * `nu` (positive, finite) for every draw.  _tv (a fit that estimated nu): nu_values [n_values]
+ * (1 .. 4096 distinct values, positive and finite; host), nu_index [n_draws] int32 into them (host;
+ * DEVICE memory in the _device form) and nu_log_prior [n_values] (host; may be NULL: nu has no
+ * prior), the log of the normalised prior weight of every value.  With r_is = y_i - a_i . beta_s,
+ *   loglik = n (C(nu_s) - log sigma_s) - (nu_s + 1)/2 sum_i log1p(r_is^2 / (nu_s sigma_s^2)),
+ *   C(nu)  = lgamma((nu + 1)/2) - lgamma(nu/2) - 1/2 log(nu pi)   (long double, once per value),
+ *   lp_nu  = nu_log_prior[nu_index[s]]   (0 without a prior),
+ * lp_beta and lp_sigma2 as above, bit for bit; all four NaN for a draw with a non-finite coefficient
+ * or without a finite sigma > 0.  `components` has a fifth bit: bit 0 prior = lp_beta + lp_sigma2 +
+ * lp_nu, bits 1 .. 3 as above, bit 4 prior_nu = lp_nu (only with nu_log_prior).  logdens_out is
+ * [4][n_draws]: lp_beta, lp_sigma2, loglik, lp_nu.  The _tv forms have one more quantity column,
+ * the LAST: q = k + 1 + n_models is nu_s, so Q = k + 2 + n_models; the other columns keep their
+ * places.  A _tv call whose index holds one value returns the bits of the _t call.  BMC_EINVAL
+ * also for a nu, a table entry or n_values outside these limits, a non-finite nu_log_prior, bit 4
+ * without a prior and an index outside the table: a host index before any launch, a device index
+ * clamped where it is read and reported after the run (the outputs are then not valid).  The
+ * context stays usable.  bmc_sens_last_timing counts the Student-t pass under the log densities. */
+int bmc_power_sensitivity_t(bmc_ctx* ctx, const double* A, int64_t n_points, int32_t k, int64_t lda,
+                            int layout, const double* y, const double* theta, int64_t n_draws,
+                            int64_t ldt, const double* b0, const double* C0, double nu0,
+                            double sigma20, const double* Vt, int32_t n_models, const double* alphas,
+                            int32_t n_alphas, uint32_t components, int32_t cols_per_batch, double nu,
+                            double* logdens_out, double* pareto_k_out, double* mean_out,
+                            double* sd_out, double* cjs_out, double* weights_out,
+                            uint32_t* flags_out);
+int bmc_power_sensitivity_t_device(bmc_ctx* ctx, const void* dA, int64_t n_points, int32_t k,
+                                   int64_t lda, int layout, const void* dy, const void* dtheta,
+                                   int64_t n_draws, int64_t ldt, const double* b0, const double* C0,
+                                   double nu0, double sigma20, const double* Vt, int32_t n_models,
+                                   const double* alphas, int32_t n_alphas, uint32_t components,
+                                   int32_t cols_per_batch, double nu, double* logdens_out,
+                                   double* pareto_k_out, double* mean_out, double* sd_out,
+                                   double* cjs_out, double* weights_out, uint32_t* flags_out);
+int bmc_power_sensitivity_tv(bmc_ctx* ctx, const double* A, int64_t n_points, int32_t k, int64_t lda,
+                             int layout, const double* y, const double* theta, int64_t n_draws,
+                             int64_t ldt, const double* b0, const double* C0, double nu0,
+                             double sigma20, const double* Vt, int32_t n_models, const double* alphas,
+                             int32_t n_alphas, uint32_t components, int32_t cols_per_batch,
+                             const double* nu_values, int32_t n_values, const int32_t* nu_index,
+                             const double* nu_log_prior, double* logdens_out, double* pareto_k_out,
+                             double* mean_out, double* sd_out, double* cjs_out, double* weights_out,
+                             uint32_t* flags_out);
+int bmc_power_sensitivity_tv_device(bmc_ctx* ctx, const void* dA, int64_t n_points, int32_t k,
+                                    int64_t lda, int layout, const void* dy, const void* dtheta,
+                                    int64_t n_draws, int64_t ldt, const double* b0, const double* C0,
+                                    double nu0, double sigma20, const double* Vt, int32_t n_models,
+                                    const double* alphas, int32_t n_alphas, uint32_t components,
+                                    int32_t cols_per_batch, const double* nu_values, int32_t n_values,
+                                    const void* d_nu_index, const double* nu_log_prior,
+                                    double* logdens_out, double* pareto_k_out, double* mean_out,
+                                    double* sd_out, double* cjs_out, double* weights_out,
+                                    uint32_t* flags_out);
+
 /* ---- Student-t (outlier-robust) Gibbs sampler, many chains per launch (not in the reference) ----
  * The resident problem of bmc_set_problem (f64 storage, either layout, 1 <= k <= 32, n < 2^32) and
  * the prior of bmc_set_prior, with the likelihood y_n | beta, sigma2, lambda_n ~ N(x_n . beta,

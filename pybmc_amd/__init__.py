@@ -13,7 +13,8 @@ from .ppc import PPC_STATS, posterior_predictive_check, ppc_summary
 from .rankdiag import rank_diagnostics, rank_normalize
 from .sampling_utils import coverage, rndm_m_random_calculator
 from .scoring import compare_elpd, pointwise_log_likelihood, psis_loo, psis_loo_predict, waic
-from .sensitivity import power_scale_sensitivity, power_scale_weights, sensitivity_summary
+from .sensitivity import (T_COMPONENTS, power_scale_sensitivity, power_scale_weights,
+                          sensitivity_summary)
 
 __all__ = [
     "Dataset",
@@ -43,4 +44,5 @@ __all__ = [
     "power_scale_sensitivity",
     "power_scale_weights",
     "sensitivity_summary",
+    "T_COMPONENTS",
 ]

@@ -169,6 +169,25 @@ PROTOTYPES = {
                                                C.c_double, _D, C.c_int32, _D, C.c_int32, C.c_uint32,
                                                C.c_int32, _D, _D, _D, _D, _D, _D,
                                                C.POINTER(C.c_uint32)]),
+    "bmc_power_sensitivity_t": (C.c_int, [_P, _D, C.c_int64, C.c_int32, C.c_int64, C.c_int, _D, _D,
+                                          C.c_int64, C.c_int64, _D, _D, C.c_double, C.c_double, _D,
+                                          C.c_int32, _D, C.c_int32, C.c_uint32, C.c_int32, C.c_double,
+                                          _D, _D, _D, _D, _D, _D, C.POINTER(C.c_uint32)]),
+    "bmc_power_sensitivity_t_device": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int, _P,
+                                                 _P, C.c_int64, C.c_int64, _D, _D, C.c_double,
+                                                 C.c_double, _D, C.c_int32, _D, C.c_int32, C.c_uint32,
+                                                 C.c_int32, C.c_double, _D, _D, _D, _D, _D, _D,
+                                                 C.POINTER(C.c_uint32)]),
+    "bmc_power_sensitivity_tv": (C.c_int, [_P, _D, C.c_int64, C.c_int32, C.c_int64, C.c_int, _D, _D,
+                                           C.c_int64, C.c_int64, _D, _D, C.c_double, C.c_double, _D,
+                                           C.c_int32, _D, C.c_int32, C.c_uint32, C.c_int32, _D,
+                                           C.c_int32, C.POINTER(C.c_int32), _D, _D, _D, _D, _D, _D, _D,
+                                           C.POINTER(C.c_uint32)]),
+    "bmc_power_sensitivity_tv_device": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int, _P,
+                                                  _P, C.c_int64, C.c_int64, _D, _D, C.c_double,
+                                                  C.c_double, _D, C.c_int32, _D, C.c_int32, C.c_uint32,
+                                                  C.c_int32, _D, C.c_int32, _P, _D, _D, _D, _D, _D, _D,
+                                                  _D, C.POINTER(C.c_uint32)]),
     "bmc_sens_last_timing": (C.c_int, [_P, _D]),
     "bmc_robust_run": (C.c_int, [_P, C.c_double, C.c_int32, C.c_int64, C.c_int64, C.c_int,
                                  C.POINTER(C.c_uint64), _D, _D, _D, _D, _D, C.POINTER(Stats)]),
@@ -987,8 +1006,13 @@ class Context:
     # -- power-scaling sensitivity ----------------------------------------------------------------
     SENS_COMPONENTS = ("prior", "likelihood", "prior_beta", "prior_sigma2")   # bit order of the mask
 
+    SENS_T_COMPONENTS = SENS_COMPONENTS + ("prior_nu",)   # the mask of the Student-t forms
+
     def _sens_call(self, fn, ptr, A, n, k, lda, layout, y, theta, n_draws, ldt, prior, Vt, alphas,
-                   components, cols_per_batch, want_weights):
+                   components, cols_per_batch, want_weights, likelihood=(), logdens_rows=3,
+                   nu_column=False):
+        """One sensitivity entry point; `likelihood` is what a Student-t form takes between
+        cols_per_batch and the outputs (`nu`, or the table of `_nu_args` and the log prior)."""
         b0, C0, nu0, sigma20 = prior
         b0 = np.ascontiguousarray(b0, dtype=np.float64).reshape(-1)
         C0 = np.ascontiguousarray(C0, dtype=np.float64)
@@ -1003,15 +1027,16 @@ class Context:
             n_models = int(Vt.shape[1])
         S, mask = int(n_draws), int(components)
         n_comp = bin(mask).count("1")
-        W, Q = n_comp * len(alphas), int(k) + 1 + n_models
-        out = {"logdens": np.empty((3, S)), "pareto_k": np.empty((n_comp, len(alphas))),
+        W, Q = n_comp * len(alphas), int(k) + 1 + n_models + (1 if nu_column else 0)
+        out = {"logdens": np.empty((logdens_rows, S)), "pareto_k": np.empty((n_comp, len(alphas))),
                "mean": np.empty((n_comp, len(alphas), Q)), "sd": np.empty((n_comp, len(alphas), Q)),
                "cjs": np.empty((n_comp, len(alphas), Q)),
                "weights": np.empty((S, W)) if want_weights else None}
         flags = np.zeros(n_comp + Q, dtype=np.uint32)
         self._check(fn(self._h, ptr(A), int(n), int(k), int(lda), int(layout), ptr(y), ptr(theta), S,
                        int(ldt), _dptr(b0), _dptr(C0), float(nu0), float(sigma20), _dptr(Vt), n_models,
-                       _dptr(alphas), len(alphas), mask, int(cols_per_batch), _dptr(out["logdens"]),
+                       _dptr(alphas), len(alphas), mask, int(cols_per_batch), *likelihood,
+                       _dptr(out["logdens"]),
                        _dptr(out["pareto_k"]), _dptr(out["mean"]), _dptr(out["sd"]), _dptr(out["cjs"]),
                        _dptr(out["weights"]), flags.ctypes.data_as(C.POINTER(C.c_uint32))))
         out["component_flags"] = flags[:n_comp].astype(bool)
@@ -1035,6 +1060,54 @@ class Context:
         return self._sens_call(self._lib.bmc_power_sensitivity_device, _P, dA, n, k, lda, layout, dy,
                                dtheta, n_draws, ldt, prior, Vt, alphas, components, cols_per_batch,
                                want_weights)
+
+    def power_sensitivity_t(self, A, n, k, lda, layout, y, theta, n_draws, ldt, prior, Vt, alphas,
+                            components, cols_per_batch, want_weights, nu):
+        """power_sensitivity under the Student-t likelihood with `nu` degrees of freedom
+        (bmc_power_sensitivity_t): components a mask in the order of SENS_T_COMPONENTS (prior_nu is
+        not valid here), ``logdens`` (4, S) with a last row of zeros, the log prior of nu."""
+        return self._sens_call(self._lib.bmc_power_sensitivity_t, _dptr, A, n, k, lda, layout, y, theta,
+                               n_draws, ldt, prior, Vt, alphas, components, cols_per_batch, want_weights,
+                               likelihood=(float(nu),), logdens_rows=4)
+
+    def power_sensitivity_t_device(self, dA, n, k, lda, layout, dy, dtheta, n_draws, ldt, prior, Vt,
+                                   alphas, components, cols_per_batch, want_weights, nu):
+        """The same on DEVICE memory (bmc_power_sensitivity_t_device)."""
+        return self._sens_call(self._lib.bmc_power_sensitivity_t_device, _P, dA, n, k, lda, layout, dy,
+                               dtheta, n_draws, ldt, prior, Vt, alphas, components, cols_per_batch,
+                               want_weights, likelihood=(float(nu),), logdens_rows=4)
+
+    def _sens_call_tv(self, fn, ptr, args, nu_values, nu_index, nu_log_prior):
+        table, held = self._nu_args(ptr, nu_values, nu_index, args[7])   # (args[7]: n_draws)
+        if nu_log_prior is not None:
+            nu_log_prior = np.ascontiguousarray(nu_log_prior, dtype=np.float64).reshape(-1)
+            if nu_log_prior.shape[0] != table[1]:
+                raise ValueError("nu_log_prior must have one entry per value of nu_values")
+        out = self._sens_call(fn, ptr, *args, likelihood=(*table, _dptr(nu_log_prior)), logdens_rows=4,
+                              nu_column=True)
+        del held
+        return out
+
+    def power_sensitivity_tv(self, A, n, k, lda, layout, y, theta, n_draws, ldt, prior, Vt, alphas,
+                             components, cols_per_batch, want_weights, nu_values, nu_index,
+                             nu_log_prior=None):
+        """power_sensitivity under the Student-t likelihood with nu_values[nu_index[s]] degrees of
+        freedom for draw s (bmc_power_sensitivity_tv); nu_log_prior, one entry per value or None,
+        is the log of the normalised prior weight of every value (with it, prior_nu is a
+        component).  ``logdens`` is (4, S); the quantity columns end in one more, nu."""
+        return self._sens_call_tv(self._lib.bmc_power_sensitivity_tv, _dptr,
+                                  (A, n, k, lda, layout, y, theta, n_draws, ldt, prior, Vt, alphas,
+                                   components, cols_per_batch, want_weights),
+                                  nu_values, nu_index, nu_log_prior)
+
+    def power_sensitivity_tv_device(self, dA, n, k, lda, layout, dy, dtheta, n_draws, ldt, prior, Vt,
+                                    alphas, components, cols_per_batch, want_weights, nu_values,
+                                    d_nu_index, nu_log_prior=None):
+        """The same on DEVICE memory, the int32 index included (bmc_power_sensitivity_tv_device)."""
+        return self._sens_call_tv(self._lib.bmc_power_sensitivity_tv_device, _P,
+                                  (dA, n, k, lda, layout, dy, dtheta, n_draws, ldt, prior, Vt, alphas,
+                                   components, cols_per_batch, want_weights),
+                                  nu_values, d_nu_index, nu_log_prior)
 
     def sens_last_timing(self):
         """Device milliseconds of the last power_sensitivity* call: log densities, sorts, Pareto

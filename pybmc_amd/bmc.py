@@ -12,7 +12,7 @@ import pandas as pd
 
 from .data import apply_domain_filters
 from .inference_utils import (USVt_hat_extraction, gibbs_sampler, gibbs_sampler_robust,
-                              gibbs_sampler_simplex)
+                              gibbs_sampler_simplex, robust_nu_prior)
 from .sampling_utils import predictive_coverage, rndm_m_random_calculator
 
 
@@ -52,6 +52,7 @@ class BayesianModelCombination:
         self._trained_with = None   # (sampler, [b0, C0, nu0, sigma20][, nu]) of the last train()
         self.row_weights = None     # (N,) mean latent weight per training row ("student_t" only)
         self.nu_samples = None      # draws of nu, one per row of samples ("nu": "estimate" only)
+        self._nu_prior = None       # (grid, weights) of the prior nu had ("nu": "estimate" only)
 
     # ------------------------------------------------------------------ set-up
     def orthogonalize(self, property, train_df, components_kept, method="auto"):
@@ -153,6 +154,7 @@ class BayesianModelCombination:
                               [b_mean_prior, b_mean_cov, nu0, sigma20])
         self.row_weights = None
         self.nu_samples = None
+        self._nu_prior = None
         if sampler == "student_t":
             devices = opts.get("devices")
             if devices is not None and list(devices) != [self.device]:
@@ -174,6 +176,7 @@ class BayesianModelCombination:
             res, w, stats = got[0], got[1], got[-1]
             if estimate:
                 self.nu_samples = np.ascontiguousarray(got[2]).reshape(-1)   # pooled in chain order
+                self._nu_prior = robust_nu_prior(extra.get("nu_grid"), extra.get("nu_prior"))[:2]
             self.last_stats = stats
             self.samples = res if res.ndim == 2 else res.reshape(-1, res.shape[-1])
             self.row_weights = w if w.ndim == 1 else w.mean(axis=0)
@@ -420,6 +423,37 @@ class BayesianModelCombination:
             self.U_hat, np.asarray(self.centered_experiment_train, dtype=np.float64), self._chains(),
             prior, Vt_hat=self.Vt_hat, burn=burn, alphas=alphas, device=self.device,
             models=self.models)
+
+    def sensitivity(self, burn=0, alphas=None, training_options=None):
+        """``prior_sensitivity`` under the likelihood the last ``train()`` sampled from, as
+        ``score()`` and ``check()`` read a fit: the plain call after a Gaussian fit, the Student-t
+        likelihood with that fit's ``nu`` after ``{"sampler": "student_t"}`` and, after
+        ``"nu": "estimate"``, every draw with its own ``nu`` and the prior that fit gave ``nu``: the
+        columns then end in ``nu``, and ``prior_nu`` is a third component beside ``prior`` and
+        ``likelihood`` -- does the posterior of ``nu`` only restate its prior?  Arguments and result as
+        ``prior_sensitivity`` (the result's ``likelihood`` and ``nu`` say which call it was); after
+        ``sampler == "simplex"`` it raises ``ValueError``."""
+        if self.samples is None or self.U_hat is None or self._trained_with is None:
+            raise ValueError("Must call `orthogonalize()` and `train()` before the prior sensitivity.")
+        sampler, prior = self._trained_with[:2]
+        opts = training_options if training_options is not None else {}
+        if sampler == "simplex" or opts.get("sampler", "gibbs_sampling") == "simplex":
+            raise ValueError('sensitivity supports the Gibbs samplers only (sampler == "simplex")')
+        prior = [opts.get("b_mean_prior", prior[0]), opts.get("b_mean_cov", prior[1]),
+                 opts.get("nu0_chosen", prior[2]), opts.get("sigma20_chosen", prior[3])]
+        lik, components = {}, ("prior", "likelihood")
+        if self._nu_estimated():
+            lik = {"nu_draws": self._nu_chains()}
+            if self._nu_prior is not None:
+                lik.update(nu_grid=self._nu_prior[0], nu_prior=self._nu_prior[1])
+                components += ("prior_nu",)
+        elif sampler == "student_t":
+            lik = {"nu": self._trained_with[2]}
+        from .sensitivity import power_scale_sensitivity
+        return power_scale_sensitivity(
+            self.U_hat, np.asarray(self.centered_experiment_train, dtype=np.float64), self._chains(),
+            prior, Vt_hat=self.Vt_hat, burn=burn, alphas=alphas, components=components,
+            device=self.device, models=self.models, **lik)
 
     def _cv_arguments(self, what, n_folds, groups, training_options, seed):
         """(options, y, fold labels, group values or None, prior) of ``cross_validate`` and

@@ -423,13 +423,30 @@ struct SensLogdensArgs {
     uint32_t components;
     double nu0, sigma20;
     double *Tp, *rss, *lp, *comps, *omega;
+    // host-only: n_nu > 0 selects the Student-t likelihood (the Gaussian kernels are not launched):
+    //   lp[2][s] = n (C(nu_s) - log sigma_s) - (nu_s + 1)/2 sum_i log1p((y_i - a_i . beta_s)^2 / (nu_s sigma_s^2))
+    //   lp[3][s] = the log prior of nu_s (a fourth row), comps of the bits (lp0 + lp1 + lp3, lp2, lp0, lp1, lp3)
+    // with nu_s = the nu_index[s]-th value of the table (nu_index NULL: the first value for every
+    // draw, a fixed nu).  All DEVICE pointers: nu_tab [3][n_nu] = student_t_cnu of every value, the
+    // values, their log prior (zeros when there is none); nu_index [S] int32 (clamped into range in
+    // the kernel); nu_flag one int32 word the caller has zeroed, set to 1 when an index was out of
+    // range; tc [SENS_T_STAGED][S] work: g, hn, c, nu and lp_nu per draw (tc + 3 S is the nu column).
+    int32_t n_nu = 0;
+    const double* nu_tab = nullptr;
+    const int32_t* nu_index = nullptr;
+    int32_t* nu_flag = nullptr;
+    double* tc = nullptr;
 };
+constexpr int SENS_T_STAGED = 5;
 hipError_t launch_sens_logdens(const SensLogdensArgs& a, hipStream_t s);
-// Column j of a batch is p0[e * rs0 + j] for j < n0, else p1[e * rs1 + (j - n0) * cs1], e < S
+// Column j of a batch is p0[e * rs0 + j] for j < n0, else p1[e * rs1 + (j - n0) * cs1], e < S; from
+// column n1 on it is p2[e] (one more column behind the two sources: the nu of every draw)
 struct SensSource {
     const double *p0, *p1;
     int64_t rs0, rs1, cs1;
     int32_t n0;
+    const double* p2 = nullptr;
+    int32_t n1 = 0x7fffffff;
 };
 // The gather of launch_rank_gather from a SensSource (kernels_rank.hip: the same kernel over another
 // loader): segment jb of keys / idx starts at jb * seg_stride and takes the S draws of column col0 + jb

@@ -1,8 +1,9 @@
 // Host-only plan of the power-scaling sensitivity (bmc_power_sensitivity): the
 // argument limits, the sort segment (the rank sort's geometry on a segment padded to an even
 // length), the chunks of the weight scan, the split of the columns into batches that fit the device
-// memory, and the scratch sizes; the tail of the Pareto fit is bmc_psis_plan.h's.  No HIP types:
-// tests/sens_plan_check.cpp compiles it with g++.
+// memory, and the scratch sizes; the tail of the Pareto fit is bmc_psis_plan.h's.  Below them the
+// validator and the plan of the Student-t forms (bmc_power_sensitivity_t / _tv).  No HIP types:
+// tests/sens_plan_check.cpp and tests/sens_t_plan_check.cpp compile it with g++.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -108,6 +109,83 @@ inline SensPlan plan_sens(int64_t S, int32_t n_cols, int32_t W, int32_t cols_per
     p.chunks = sens_chunks(S);
     p.M = sens_tail_length(S);
     p.grid_points = p.M >= SENS_MIN_TAIL ? sens_grid_points(p.M) : 0;
+    p.W = W;
+    int64_t launch_cap = RANK_MAX_BLOCKS / (p.tiles * RANK_ITEMS);
+    if (launch_cap > SENS_MAX_BATCH) launch_cap = SENS_MAX_BATCH;
+    int64_t Pb = cols_per_batch;
+    if (Pb == 0) {
+        sens_scratch(p, 1);
+        if (p.bytes_total > budget) {
+            p.why = "one column needs " + std::to_string(p.bytes_total) + " bytes of device memory; " +
+                    std::to_string(budget) + " are free";
+            return p;
+        }
+        Pb = (int64_t)(budget / p.bytes_total);
+    }
+    if (Pb > n_cols) Pb = n_cols;
+    if (Pb > launch_cap) Pb = launch_cap;
+    if (Pb < 1) Pb = 1;
+    p.cols_per_batch = (int32_t)Pb;
+    p.n_batches = (int32_t)((n_cols + Pb - 1) / Pb);
+    sens_scratch(p, Pb);
+    p.ok = true;
+    return p;
+}
+
+// ---- the Student-t forms (bmc_power_sensitivity_t / _tv) -----------------------
+// A fifth component, the prior of nu, and a fourth log density, lp_nu: only a _tv call that was
+// given nu_log_prior has them.  The table of distinct nu has the limits of bmc_pointwise_loglik_tv.
+constexpr int SENS_T_COMPONENTS = 5;                     // SENS_COMPONENTS' four, then prior_nu
+constexpr int SENS_T_LOGDENS = 4;                        // SENS_LOGDENS' three, then lp_nu
+constexpr int32_t SENS_MAX_NU_VALUES = 4096;             // distinct nu of a call (PPC_MAX_NU_VALUES)
+constexpr int32_t SENS_T_MAX_W = SENS_T_COMPONENTS * (SENS_MAX_ALPHAS + 2);
+
+inline bool sens_positive_finite(double v) { return v > 0.0 && v <= 1.79769313486231570815e308; }
+
+inline int32_t sens_t_count_components(uint32_t components) {
+    int32_t n = 0;
+    for (int b = 0; b < SENS_T_COMPONENTS; ++b) n += (components >> b) & 1;
+    return n;
+}
+
+// "" when the arguments are inside the limits of the Student-t forms, else the reason.  A fixed nu
+// is a table of one value without an index (per_draw false); nu_log_prior may be NULL.
+inline std::string sens_t_check(int64_t n_points, int32_t k, int64_t S, int32_t n_models,
+                                const double* alphas, int32_t n_alphas, uint32_t components, bool per_draw,
+                                const double* nu_values, int32_t n_values, const double* nu_log_prior) {
+    // (the shape and the alphas by the Gaussian form's rules; the mask has its own below)
+    const std::string base = sens_check(n_points, k, S, n_models, alphas, n_alphas, 1u);
+    if (!base.empty()) return base;
+    const bool wide = components >= (1u << SENS_COMPONENTS);
+    if (components == 0 || components >= (1u << SENS_T_COMPONENTS))
+        return "components must be a non-empty mask of prior (1), likelihood (2), prior_beta (4), "
+               "prior_sigma2 (8), prior_nu (16)";
+    if (!nu_values) return per_draw ? "nu_values and nu_index must not be NULL" : "nu must be positive and finite";
+    if (n_values < 1 || n_values > SENS_MAX_NU_VALUES) return "n_values must be between 1 and 4096";
+    for (int32_t v = 0; v < n_values; ++v)
+        if (!sens_positive_finite(nu_values[v]))
+            return per_draw ? "nu_values must be positive and finite" : "nu must be positive and finite";
+    if (nu_log_prior)
+        for (int32_t v = 0; v < n_values; ++v)
+            if (!(nu_log_prior[v] >= -1.79769313486231570815e308 && nu_log_prior[v] <= 1.79769313486231570815e308))
+                return "nu_log_prior must be finite";
+    if (wide && !(per_draw && nu_log_prior)) return "the component prior_nu (16) needs nu_log_prior";
+    if (sens_t_count_components(components) * n_alphas > SENS_T_MAX_W)
+        return "need between 1 and 340 weight vectors";
+    return "";
+}
+
+// plan_sens at the weight-vector bound of the Student-t forms
+inline SensPlan plan_sens_t(int64_t S, int32_t n_cols, int32_t W, int32_t cols_per_batch, size_t budget) {
+    if (W <= SENS_COMPONENTS * SENS_MAX_ALPHAS) return plan_sens(S, n_cols, W, cols_per_batch, budget);
+    // the checks and the segment of plan_sens with one vector, then the batch at the real W
+    SensPlan p = plan_sens(S, n_cols, 1, cols_per_batch, budget);
+    if (!p.ok) return p;
+    p.ok = false;
+    if (W > SENS_T_MAX_W) {
+        p.why = "need between 1 and 340 weight vectors";
+        return p;
+    }
     p.W = W;
     int64_t launch_cap = RANK_MAX_BLOCKS / (p.tiles * RANK_ITEMS);
     if (launch_cap > SENS_MAX_BATCH) launch_cap = SENS_MAX_BATCH;

@@ -1,7 +1,8 @@
 // C ABI, power-scaling sensitivity of a sampled fit to its prior and its likelihood (Kallioinen,
 // Paananen, Buerkner & Vehtari 2023).  The log densities, the
 // Pareto-smoothed weights and the distances are made on the device (kernels_sens.hip); every
-// vector is sorted once, by the passes of the rank diagnostics (kernels_rank.hip).
+// vector is sorted once, by the passes of the rank diagnostics (kernels_rank.hip).  The Student-t
+// forms (_t, _tv) are the same driver with the likelihood as data in SensIn.
 #include <algorithm>
 #include <cmath>
 
@@ -26,6 +27,14 @@ struct SensIn {
     double nu0, sigma20;
     int32_t n_models, n_alphas, cols_per_batch;
     uint32_t components;
+    // the likelihood as data: Gaussian, or (student) Student-t with nu_values[nu_index[s]] degrees of
+    // freedom for draw s; per_draw false: nu_values[0] for every draw and no index (the _t entry
+    // points).  nu_values and nu_log_prior (NULL: no prior of nu) are host, nu_index int32 where A is
+    bool student = false, per_draw = false;
+    int32_t n_nu = 0;
+    const double* nu_values = nullptr;
+    const void* nu_index = nullptr;
+    const double* nu_log_prior = nullptr;
 };
 
 struct SensOut {
@@ -99,8 +108,10 @@ inline size_t up256(size_t bytes) { return (bytes + 255) / 256 * 256; }
 int sens_run(bmc_ctx* c, const SensIn& in, const SensOut& out) {
     const int32_t k = in.k, Mm = in.n_models, nA = in.n_alphas;
     const int64_t S = in.S;
-    const int32_t n_comp = sens_count_components(in.components);
-    const int32_t W = n_comp * nA, Qn = k + 1 + Mm;
+    const bool student = in.student;
+    const int32_t n_comp = student ? sens_t_count_components(in.components) : sens_count_components(in.components);
+    const int32_t W = n_comp * nA, Qn = k + 1 + Mm + (in.per_draw ? 1 : 0);
+    const int32_t lp_rows = student ? SENS_T_LOGDENS : SENS_LOGDENS;
     const double nan = std::nan("");
 
     // C0 = L L' on the host; the quadratic form is |L^-1 beta - L^-1 b0|^2
@@ -120,9 +131,16 @@ int sens_run(bmc_ctx* c, const SensIn& in, const SensOut& out) {
     const int32_t k_pad = (k + 15) / 16 * 16;
     const int64_t M = psis_tail_length(S);
 
-    // small host operands in one block: Lp [q_pad][k_pad], Ly [q_pad], Vt [k][Mm], alphas [nA]
-    const size_t n_lp = (size_t)q_pad * k_pad, n_vt = (size_t)k * Mm;
-    std::vector<double> host(n_lp + q_pad + n_vt + nA, 0.0);
+    // small host operands in one block: Lp [q_pad][k_pad], Ly [q_pad], Vt [k][Mm], alphas [nA] and, for
+    // the Student-t likelihood, the table of nu [3][V]: C(nu), nu, its log prior (zeros without one)
+    const size_t n_lp = (size_t)q_pad * k_pad, n_vt = (size_t)k * Mm, V = (size_t)in.n_nu;
+    const size_t h_tab = n_lp + q_pad + n_vt + nA;
+    std::vector<double> host(h_tab + 3 * V, 0.0);
+    for (size_t v = 0; v < V; ++v) {
+        host[h_tab + v] = student_t_cnu(in.nu_values[v]);
+        host[h_tab + V + v] = in.nu_values[v];
+        host[h_tab + 2 * V + v] = in.nu_log_prior ? in.nu_log_prior[v] : 0.0;
+    }
     for (int32_t i = 0; i < k; ++i) {
         long double s = 0.0L;
         for (int32_t j = 0; j <= i; ++j) {
@@ -142,9 +160,11 @@ int sens_run(bmc_ctx* c, const SensIn& in, const SensOut& out) {
         return o;
     };
     const size_t o_host = take(host.size()), o_Ap = take((size_t)n_pad * k_pad), o_yo = take(n_pad),
-                 o_Tp = take((size_t)S64 * k_pad), o_rss = take(2 * (size_t)S), o_lp = take(SENS_LOGDENS * (size_t)S),
+                 o_Tp = take((size_t)S64 * k_pad), o_rss = take(2 * (size_t)S), o_lp = take(lp_rows * (size_t)S),
                  o_comps = take((size_t)n_comp * S), o_omega = take((size_t)S * Mm),
-                 o_Wt = take((size_t)S * W), o_xs = take((size_t)W * (M > 0 ? M : 1)), o_khat = take(W);
+                 o_Wt = take((size_t)S * W), o_xs = take((size_t)W * (M > 0 ? M : 1)), o_khat = take(W),
+                 o_tc = take(student ? SENS_T_STAGED * (size_t)S : 0),
+                 o_flag = take(student ? 1 : 0);   // one int32 word: an index was out of range
     const size_t fixed = at;
 
     size_t free_b = 0, total_b = 0;
@@ -155,7 +175,8 @@ int sens_run(bmc_ctx* c, const SensIn& in, const SensOut& out) {
     if (avail <= fixed)
         return fail(c, BMC_ENOMEM, "the log densities and weights need " + std::to_string(fixed) +
                                        " bytes of device memory; " + std::to_string(avail) + " are free");
-    const SensPlan p = plan_sens(S, Qn, W, in.cols_per_batch, avail - fixed);
+    const SensPlan p = student ? plan_sens_t(S, Qn, W, in.cols_per_batch, avail - fixed)
+                               : plan_sens(S, Qn, W, in.cols_per_batch, avail - fixed);
     if (!p.ok) return fail(c, p.S == 0 ? BMC_EINVAL : BMC_ENOMEM, p.why);
     const int32_t Pb_max = std::max(p.cols_per_batch, n_comp);
     const size_t o_out = take((size_t)Pb_max * W * 3);
@@ -198,6 +219,14 @@ int sens_run(bmc_ctx* c, const SensIn& in, const SensOut& out) {
     la.lp = dptr(o_lp);
     la.comps = dptr(o_comps);
     la.omega = dptr(o_omega);
+    if (student) {
+        la.n_nu = in.n_nu;
+        la.nu_tab = dptr(o_host) + h_tab;
+        la.nu_index = in.per_draw ? (const int32_t*)in.nu_index : nullptr;
+        la.nu_flag = (int32_t*)dptr(o_flag);
+        HIPCHK(c, hipMemsetAsync(la.nu_flag, 0, 4, c->stream));
+        la.tc = dptr(o_tc);
+    }
     HIPCHK(c, launch_sens_logdens(la, c->stream));
     HIPCHK(c, hipEventRecord(ev.e[1], c->stream));
 
@@ -215,12 +244,15 @@ int sens_run(bmc_ctx* c, const SensIn& in, const SensOut& out) {
     HIPCHK(c, hipEventRecord(ev.e[3], c->stream));
     std::vector<double> khat(W);
     HIPCHK(c, hipMemcpyAsync(khat.data(), dptr(o_khat), (size_t)W * 8, hipMemcpyDeviceToHost, c->stream));
+    int32_t bad_index = 0;
+    if (student) HIPCHK(c, hipMemcpyAsync(&bad_index, la.nu_flag, 4, hipMemcpyDeviceToHost, c->stream));
     if (out.logdens)
-        HIPCHK(c, hipMemcpyAsync(out.logdens, dptr(o_lp), (size_t)SENS_LOGDENS * S * 8, hipMemcpyDeviceToHost,
+        HIPCHK(c, hipMemcpyAsync(out.logdens, dptr(o_lp), (size_t)lp_rows * S * 8, hipMemcpyDeviceToHost,
                                  c->stream));
     if (out.weights)
         HIPCHK(c, hipMemcpyAsync(out.weights, dptr(o_Wt), (size_t)S * W * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (bad_index) return fail(c, BMC_EINVAL, "nu_index must index nu_values (the results are not valid)");
     const int span0[3] = {0, 1, 2};
     for (int i = 0; i < 3; ++i) {
         HIPCHK(c, hipEventElapsedTime(&ms, ev.e[i], ev.e[i + 1]));
@@ -237,7 +269,11 @@ int sens_run(bmc_ctx* c, const SensIn& in, const SensOut& out) {
     }
 
     // ---- the quantity columns, batch by batch -------------------------------------------------------
-    const SensSource col_src{(const double*)in.theta, dptr(o_omega), in.ldt, (int64_t)Mm, 1, k + 1};
+    SensSource col_src{(const double*)in.theta, dptr(o_omega), in.ldt, (int64_t)Mm, 1, k + 1};
+    if (in.per_draw) {   // the nu of every draw, staged for the pass: the last column
+        col_src.p2 = dptr(o_tc) + 3 * (size_t)S;
+        col_src.n1 = k + 1 + Mm;
+    }
     std::vector<double> res;
     for (int32_t bi = 0; bi < p.n_batches; ++bi) {
         int32_t col0, Pb;
@@ -279,8 +315,16 @@ int sens_entry(bmc_ctx* c, SensIn in, bool on_host, const SensOut& out) {
     if (!in.b0 || !in.C0) return fail(c, BMC_EINVAL, "b0 and C0 must not be NULL");
     if (in.n_models > 0 && !in.Vt) return fail(c, BMC_EINVAL, "Vt must not be NULL when n_models > 0");
     const std::string why =
-        sens_check(in.n, in.k, in.S, in.n_models, in.alphas, in.n_alphas, in.components);
+        in.student ? sens_t_check(in.n, in.k, in.S, in.n_models, in.alphas, in.n_alphas, in.components,
+                                  in.per_draw, in.nu_values, in.n_nu, in.nu_log_prior)
+                   : sens_check(in.n, in.k, in.S, in.n_models, in.alphas, in.n_alphas, in.components);
     if (!why.empty()) return fail(c, BMC_EINVAL, why);
+    if (in.per_draw && !in.nu_index) return fail(c, BMC_EINVAL, "nu_values and nu_index must not be NULL");
+    if (in.per_draw && on_host) {   // a host index is checked before any launch
+        const int32_t* idx = (const int32_t*)in.nu_index;
+        for (int64_t s = 0; s < in.S; ++s)
+            if (idx[s] < 0 || idx[s] >= in.n_nu) return fail(c, BMC_EINVAL, "nu_index must index nu_values");
+    }
     if (in.layout != BMC_ROW_MAJOR && in.layout != BMC_COL_MAJOR)
         return fail(c, BMC_EINVAL, "layout must be BMC_ROW_MAJOR or BMC_COL_MAJOR");
     if (in.lda < (in.layout == BMC_COL_MAJOR ? in.n : (int64_t)in.k))
@@ -294,8 +338,14 @@ int sens_entry(bmc_ctx* c, SensIn in, bool on_host, const SensOut& out) {
         const size_t abytes = up256(strided_bytes(in.n, in.k, in.lda, in.layout, 8));
         const size_t ybytes = up256((size_t)in.n * 8);
         const size_t tbytes = strided_bytes(in.S, in.k + 1, in.ldt, BMC_ROW_MAJOR, 8);
-        if (int rc = ensure(c, c->snStage, abytes + ybytes + tbytes)) return rc;
+        const size_t ibytes = in.per_draw ? (size_t)in.S * 4 : 0;
+        if (int rc = ensure(c, c->snStage, abytes + ybytes + up256(tbytes) + ibytes)) return rc;
         char* s = (char*)c->snStage.p;
+        if (in.per_draw) {
+            char* si = s + abytes + ybytes + up256(tbytes);
+            HIPCHK(c, hipMemcpyAsync(si, in.nu_index, ibytes, hipMemcpyHostToDevice, c->stream));
+            in.nu_index = si;
+        }
         HIPCHK(c, hipMemcpyAsync(s, in.A, strided_bytes(in.n, in.k, in.lda, in.layout, 8), hipMemcpyHostToDevice,
                                  c->stream));
         HIPCHK(c, hipMemcpyAsync(s + abytes, in.y, (size_t)in.n * 8, hipMemcpyHostToDevice, c->stream));
@@ -333,6 +383,68 @@ int bmc_power_sensitivity_device(bmc_ctx* c, const void* dA, int64_t n_points, i
                           sigma20, n_models, n_alphas, cols_per_batch, components},
                       false, {logdens_out, pareto_k_out, mean_out, sd_out, cjs_out, weights_out, flags_out});
 }
+
+// The Student-t forms: the Gaussian call's SensIn with the likelihood filled in.  A fixed nu is a
+// table of one value without an index; what is not positive and finite is refused by sens_t_check.
+#define SENS_T_IN(A, y, theta)                                                                        \
+    SensIn in{A, y, theta, n_points, lda, n_draws, ldt, k, layout, b0, C0, Vt, alphas, nu0, sigma20,  \
+              n_models, n_alphas, cols_per_batch, components};                                        \
+    in.student = true
+
+int bmc_power_sensitivity_t(bmc_ctx* c, const double* A, int64_t n_points, int32_t k, int64_t lda, int layout,
+                            const double* y, const double* theta, int64_t n_draws, int64_t ldt,
+                            const double* b0, const double* C0, double nu0, double sigma20, const double* Vt,
+                            int32_t n_models, const double* alphas, int32_t n_alphas, uint32_t components,
+                            int32_t cols_per_batch, double nu, double* logdens_out, double* pareto_k_out,
+                            double* mean_out, double* sd_out, double* cjs_out, double* weights_out,
+                            uint32_t* flags_out) {
+    SENS_T_IN(A, y, theta);
+    in.nu_values = &nu, in.n_nu = 1;
+    return sens_entry(c, in, true, {logdens_out, pareto_k_out, mean_out, sd_out, cjs_out, weights_out, flags_out});
+}
+
+int bmc_power_sensitivity_t_device(bmc_ctx* c, const void* dA, int64_t n_points, int32_t k, int64_t lda,
+                                   int layout, const void* dy, const void* dtheta, int64_t n_draws,
+                                   int64_t ldt, const double* b0, const double* C0, double nu0,
+                                   double sigma20, const double* Vt, int32_t n_models, const double* alphas,
+                                   int32_t n_alphas, uint32_t components, int32_t cols_per_batch, double nu,
+                                   double* logdens_out, double* pareto_k_out, double* mean_out,
+                                   double* sd_out, double* cjs_out, double* weights_out,
+                                   uint32_t* flags_out) {
+    SENS_T_IN(dA, dy, dtheta);
+    in.nu_values = &nu, in.n_nu = 1;
+    return sens_entry(c, in, false, {logdens_out, pareto_k_out, mean_out, sd_out, cjs_out, weights_out, flags_out});
+}
+
+int bmc_power_sensitivity_tv(bmc_ctx* c, const double* A, int64_t n_points, int32_t k, int64_t lda, int layout,
+                             const double* y, const double* theta, int64_t n_draws, int64_t ldt,
+                             const double* b0, const double* C0, double nu0, double sigma20, const double* Vt,
+                             int32_t n_models, const double* alphas, int32_t n_alphas, uint32_t components,
+                             int32_t cols_per_batch, const double* nu_values, int32_t n_values,
+                             const int32_t* nu_index, const double* nu_log_prior, double* logdens_out,
+                             double* pareto_k_out, double* mean_out, double* sd_out, double* cjs_out,
+                             double* weights_out, uint32_t* flags_out) {
+    SENS_T_IN(A, y, theta);
+    in.per_draw = true;
+    in.nu_values = nu_values, in.n_nu = n_values, in.nu_index = nu_index, in.nu_log_prior = nu_log_prior;
+    return sens_entry(c, in, true, {logdens_out, pareto_k_out, mean_out, sd_out, cjs_out, weights_out, flags_out});
+}
+
+int bmc_power_sensitivity_tv_device(bmc_ctx* c, const void* dA, int64_t n_points, int32_t k, int64_t lda,
+                                    int layout, const void* dy, const void* dtheta, int64_t n_draws,
+                                    int64_t ldt, const double* b0, const double* C0, double nu0,
+                                    double sigma20, const double* Vt, int32_t n_models, const double* alphas,
+                                    int32_t n_alphas, uint32_t components, int32_t cols_per_batch,
+                                    const double* nu_values, int32_t n_values, const void* d_nu_index,
+                                    const double* nu_log_prior, double* logdens_out, double* pareto_k_out,
+                                    double* mean_out, double* sd_out, double* cjs_out, double* weights_out,
+                                    uint32_t* flags_out) {
+    SENS_T_IN(dA, dy, dtheta);
+    in.per_draw = true;
+    in.nu_values = nu_values, in.n_nu = n_values, in.nu_index = d_nu_index, in.nu_log_prior = nu_log_prior;
+    return sens_entry(c, in, false, {logdens_out, pareto_k_out, mean_out, sd_out, cjs_out, weights_out, flags_out});
+}
+#undef SENS_T_IN
 
 int bmc_sens_last_timing(bmc_ctx* c, double ms_out[4]) {
     if (!c || !ms_out) return BMC_EINVAL;

@@ -77,6 +77,7 @@ struct RankLoad {
 struct SensLoad {
     SensSource src;
     __device__ double operator()(int64_t e, int32_t col) const {
+        if (col >= src.n1) return src.p2[e];
         return col < src.n0 ? src.p0[e * src.rs0 + col] : src.p1[e * src.rs1 + (int64_t)(col - src.n0) * src.cs1];
     }
 };

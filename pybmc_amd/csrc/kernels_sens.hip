@@ -10,6 +10,10 @@
 //                     twice: on the data (the likelihood) and on (L^-1, L^-1 b0), whose "residual
 //                     sum" is the prior's quadratic form (beta - b0)' C0^-1 (beta - b0)
 //   sens_logdens      lp_beta, lp_sigma2, loglik per draw and the component vectors
+//   sens_consts_t / sens_tsum_tile / sens_logdens_t
+//                     the same three under the Student-t likelihood, nu fixed or one per draw:
+//                     the walk of sens_rss_tile with sum_i log1p(g_s r_is^2) in place of the
+//                     squares, and a fourth log density, the prior of nu
 //   sens_omega        the model-weight columns beta . Vt + 1 / M
 //   sens_gather       a column -> (key, index) pairs of an even-length segment, OR / AND masks of
 //                     the real keys, non-finite flag (launch_key_gather: the gather of
@@ -107,6 +111,108 @@ __global__ __launch_bounds__(256) void sens_logdens_kernel(
     int c = 0;
 #pragma unroll
     for (int b = 0; b < SENS_COMPONENTS; ++b)
+        if ((components >> b) & 1) comps[(int64_t)(c++) * S + s] = v[b];
+}
+
+// ---- the Student-t likelihood (SensLogdensArgs::n_nu > 0) -----------------------
+// one thread per draw: tc[0] = g = 1 / (nu sigma^2), tc[1] = hn = (nu + 1)/2, tc[2] = c = C(nu) -
+// log sigma (the constants of score_consts_tv_kernel), tc[3] = nu, tc[4] = the log prior of nu, at
+// the draw's own nu from tab [3][n_nu] = (C(nu), nu, log prior).  index NULL: entry 0 for every
+// draw (a fixed nu is a table of one value); an index out of range is clamped and reported.
+__global__ __launch_bounds__(256) void sens_consts_t_kernel(const double* __restrict__ theta, int64_t S,
+                                                            int64_t ldt, int32_t k,
+                                                            const double* __restrict__ tab, int32_t n_nu,
+                                                            const int32_t* __restrict__ index,
+                                                            int32_t* __restrict__ flag,
+                                                            double* __restrict__ tc) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= S) return;
+    int32_t iv = index ? index[s] : 0;
+    if (iv < 0 || iv >= n_nu) {
+        *flag = 1;
+        iv = iv < 0 ? 0 : n_nu - 1;
+    }
+    const double cnu = tab[iv], nu = tab[n_nu + iv];
+    const double sg = theta[s * ldt + k];
+    tc[s] = 1.0 / (nu * sg * sg);
+    tc[S + s] = 0.5 * (nu + 1.0);
+    tc[2 * S + s] = cnu - log(sg);
+    tc[3 * S + s] = nu;
+    tc[4 * S + s] = tab[2 * n_nu + iv];
+}
+
+// sens_rss_tile_kernel's walk with the Student-t term in place of the square: tsum[d] = sum_i
+// log1p(g_d (y_i - a_i . beta_d)^2), g [S] = 1 / (nu_d sigma_d^2).  A padded point has e = 0 and
+// adds log1p_nonneg(0 g) = 0 exactly for a finite g (tests/sens_t_plan_check.cpp); a draw with a NaN
+// or infinite g has no log density anyway (sens_logdens_t_kernel).  One order of summation per
+// (n, S), no atomics; the same code for a fixed nu and a nu per draw.
+__global__ __launch_bounds__(256, 2) void sens_tsum_tile_kernel(
+    const double* __restrict__ Tp, const double* __restrict__ Ap, const double* __restrict__ yo,
+    int64_t n_pad, int32_t k, int32_t k_pad, int64_t point_tiles, int64_t S, const double* __restrict__ g,
+    double* __restrict__ tsum) {
+    __shared__ double As[SC_LDS_DOUBLES];
+    __shared__ double Bs[SC_LDS_DOUBLES];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int cl = lane & 15, kq = lane >> 4;
+    const int64_t d0 = (int64_t)blockIdx.x * SC_TM;
+    double gr[4], tt[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int64_t d = d0 + 16 * wave + kq + 4 * r;
+        gr[r] = g[d < S ? d : S - 1];   // (a draw past S: its sum is dropped below)
+    }
+    score_tile_loop(Tp, Ap, n_pad, (int64_t)k_pad, k, k_pad, d0, 0, point_tiles, As, Bs,
+                    [&](int64_t i0, const f64x4(&acc)[4]) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const double yv = yo[i0 + cl + 16 * t];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const double e = yv - acc[t][r];
+                tt[r] += log1p_nonneg((e * e) * gr[r]);
+            }
+        }
+    });
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        double v = tt[r];
+#pragma unroll
+        for (int bit = 1; bit < 16; bit <<= 1) v += __shfl_xor(v, bit);
+        const int64_t d = d0 + 16 * wave + kq + 4 * r;
+        if (cl == 0 && d < S) tsum[d] = v;
+    }
+}
+
+// sens_logdens_kernel under the Student-t likelihood: lp_beta and lp_sigma2 by its own expressions
+// (the same bits), loglik = n c - hn tsum, lp_nu from the staged row; the same NaN rule, for all four.
+__global__ __launch_bounds__(256) void sens_logdens_t_kernel(
+    const double* __restrict__ theta, int64_t S, int64_t ldt, int32_t k, const double* __restrict__ tsum,
+    const double* __restrict__ rss_q, const double* __restrict__ tc, double n_points, double nu0,
+    double sigma20, uint32_t components, double* __restrict__ lp, double* __restrict__ comps) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= S) return;
+    const double* th = theta + s * ldt;
+    const double sigma = th[k];
+    bool ok = is_finite(sigma) && sigma > 0.0;
+    for (int32_t j = 0; j < k; ++j) ok = ok && is_finite(th[j]);
+    const double nan = __builtin_nan("");
+    double lb = nan, ls = nan, ll = nan, ln = nan;
+    if (ok) {
+        const double s2 = sigma * sigma;
+        lb = -0.5 * rss_q[s];
+        ls = -(nu0 / 2.0 + 1.0) * log(s2) - nu0 * sigma20 / (2.0 * s2);
+        ll = n_points * tc[2 * S + s] - tc[S + s] * tsum[s];
+        ln = tc[4 * S + s];
+    }
+    lp[s] = lb;
+    lp[S + s] = ls;
+    lp[2 * S + s] = ll;
+    lp[3 * S + s] = ln;
+    const double v[SENS_T_COMPONENTS] = {(lb + ls) + ln, ll, lb, ls, ln};
+    int c = 0;
+#pragma unroll
+    for (int b = 0; b < SENS_T_COMPONENTS; ++b)
         if ((components >> b) & 1) comps[(int64_t)(c++) * S + s] = v[b];
 }
 
@@ -413,18 +519,32 @@ hipError_t launch_sens_logdens(const SensLogdensArgs& a, hipStream_t s) {
     const int64_t S64 = (a.S + SENS_TILE - 1) / SENS_TILE * SENS_TILE;
     if (a.S < 1 || a.k < 1 || a.k > SENS_MAX_K || a.ldt < (int64_t)a.k + 1 || a.k_pad < a.k || a.k_pad % SC_KT ||
         a.n_pad < 1 || a.n_pad % SENS_TILE || a.q_pad < a.k || a.q_pad % SENS_TILE || a.S_pad != S64 ||
-        S64 / SENS_TILE > 0x7fffffffll || a.components == 0 || a.components >= (1u << SENS_COMPONENTS))
+        S64 / SENS_TILE > 0x7fffffffll || a.components == 0 ||
+        a.components >= (1u << (a.n_nu > 0 ? SENS_T_COMPONENTS : SENS_COMPONENTS)) || a.n_nu < 0 ||
+        a.n_nu > SENS_MAX_NU_VALUES || (a.n_nu > 0 && (!a.nu_tab || !a.nu_flag || !a.tc)))
         return hipErrorInvalidValue;
     hipLaunchKernelGGL(sens_pad_draws_kernel, dim3(capped_blocks(S64 * a.k_pad)), dim3(256), 0, s, a.theta, a.S,
                        a.ldt, a.k, S64, a.k_pad, a.Tp);
-    const dim3 grid((unsigned)(S64 / SENS_TILE));
-    hipLaunchKernelGGL(sens_rss_tile_kernel, grid, dim3(256), 0, s, (const double*)a.Tp, a.Ap, a.yo, a.n_pad,
-                       a.k, a.k_pad, a.n_pad / SENS_TILE, a.S, a.rss);
+    const dim3 grid((unsigned)(S64 / SENS_TILE)), per_draw((unsigned)((a.S + 255) / 256));
+    if (a.n_nu > 0) {
+        hipLaunchKernelGGL(sens_consts_t_kernel, per_draw, dim3(256), 0, s, a.theta, a.S, a.ldt, a.k, a.nu_tab,
+                           a.n_nu, a.nu_index, a.nu_flag, a.tc);
+        hipLaunchKernelGGL(sens_tsum_tile_kernel, grid, dim3(256), 0, s, (const double*)a.Tp, a.Ap, a.yo, a.n_pad,
+                           a.k, a.k_pad, a.n_pad / SENS_TILE, a.S, (const double*)a.tc, a.rss);
+    } else {
+        hipLaunchKernelGGL(sens_rss_tile_kernel, grid, dim3(256), 0, s, (const double*)a.Tp, a.Ap, a.yo, a.n_pad,
+                           a.k, a.k_pad, a.n_pad / SENS_TILE, a.S, a.rss);
+    }
     hipLaunchKernelGGL(sens_rss_tile_kernel, grid, dim3(256), 0, s, (const double*)a.Tp, a.Lp, a.Ly, a.q_pad,
                        a.k, a.k_pad, a.q_pad / SENS_TILE, a.S, a.rss + a.S);
-    hipLaunchKernelGGL(sens_logdens_kernel, dim3((unsigned)((a.S + 255) / 256)), dim3(256), 0, s, a.theta, a.S,
-                       a.ldt, a.k, (const double*)a.rss, (const double*)(a.rss + a.S), (double)a.n, a.nu0,
-                       a.sigma20, a.components, a.lp, a.comps);
+    if (a.n_nu > 0)
+        hipLaunchKernelGGL(sens_logdens_t_kernel, per_draw, dim3(256), 0, s, a.theta, a.S, a.ldt, a.k,
+                           (const double*)a.rss, (const double*)(a.rss + a.S), (const double*)a.tc, (double)a.n,
+                           a.nu0, a.sigma20, a.components, a.lp, a.comps);
+    else
+        hipLaunchKernelGGL(sens_logdens_kernel, per_draw, dim3(256), 0, s, a.theta, a.S, a.ldt, a.k,
+                           (const double*)a.rss, (const double*)(a.rss + a.S), (double)a.n, a.nu0, a.sigma20,
+                           a.components, a.lp, a.comps);
     if (a.n_models > 0) {
         const int64_t total = a.S * a.n_models;
         if ((total + 255) / 256 > 0x7fffffffll) return hipErrorInvalidValue;
@@ -448,7 +568,7 @@ hipError_t launch_sens_psis(const uint64_t* keys, const uint32_t* idx, int64_t S
                             int32_t n_alphas, const double* d_alphas, double* xs, double* Wt, double* khat,
                             hipStream_t s) {
     const int64_t M = psis_tail_length(S);
-    if (S < 2 || S > SENS_MAX_S || n_components < 1 || n_components > SENS_COMPONENTS || n_alphas < 1 ||
+    if (S < 2 || S > SENS_MAX_S || n_components < 1 || n_components > SENS_T_COMPONENTS || n_alphas < 1 ||
         n_alphas > SENS_MAX_ALPHAS || (M >= PSIS_MIN_TAIL && psis_grid_points(M) > SENS_MAX_GRID))
         return hipErrorInvalidValue;
     hipLaunchKernelGGL(sens_psis_kernel, dim3((unsigned)(n_components * n_alphas)), dim3(256), 0, s, keys, idx,

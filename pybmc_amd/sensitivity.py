@@ -41,6 +41,25 @@ and the weighted mean and sd.  The sensitivity is
 likelihood both at or above it read ``"prior-data conflict"``, the prior alone
 ``"strong prior / weak likelihood"``, anything else ``"-"``.
 
+With ``nu=`` the model is the one the robust sampler draws from (``gibbs_sampler_robust``,
+``train({"sampler": "student_t"})``): ``y_i ~ a_i . beta + sigma t_nu``, the latent row weights
+integrated out as ``scoring`` integrates them.  The priors and ``lp_beta``, ``lp_sigma2`` are the
+same; with ``r_i = y_i - a_i . beta``
+
+* ``loglik = N (C(nu) - log sigma) - (nu + 1)/2 sum_i log1p(r_i^2 / (nu sigma^2))``,
+  ``C(nu) = lgamma((nu + 1)/2) - lgamma(nu/2) - 1/2 log(nu pi)``.
+
+With ``nu_draws=`` (a fit that estimated ``nu``: ``gibbs_sampler_robust(nu="estimate")``) draw s has
+its own ``nu_s`` in place of ``nu``, and ``nu`` is one more quantity column, the last.  That fit has
+a prior the others lack, the discrete prior of ``nu``: with ``nu_grid`` / ``nu_prior`` (the
+sampler's arguments, through ``robust_nu_prior``)
+
+* ``lp_nu = log(w_g / sum w)`` for ``nu_s = nu_grid[g]``
+
+joins the prior, ``prior = lp_beta + lp_sigma2 + lp_nu``, and is a component of its own,
+``prior_nu`` (``T_COMPONENTS``): whether the posterior of ``nu``, and the ``sigma`` and weights that
+move with it, only restates that prior.  Without them ``lp_nu = 0``.
+
 Out of scope: moment matching when ``pareto_k`` is high (k is reported), ``r_eff != 1``, the
 simplex sampler (its target is not this posterior), power-scaling parts of the likelihood, plots.
 """
@@ -48,9 +67,10 @@ from __future__ import annotations
 
 import numpy as np
 
-from .scoring import _pointwise_call
+from .scoring import _check_nu, _is_torch, _nu_table, _pointwise_call
 
 COMPONENTS = ("prior", "likelihood", "prior_beta", "prior_sigma2")   # the bit order of the C ABI
+T_COMPONENTS = COMPONENTS + ("prior_nu",)   # of the Student-t forms; prior_nu only with a nu prior
 DEFAULT_COMPONENTS = ("prior", "likelihood")
 MAX_ALPHAS = 64
 THRESHOLD = 0.05
@@ -69,19 +89,21 @@ def _check_alpha(name, a):
     return a
 
 
-def _check_components(components):
+def _check_components(components, known=COMPONENTS):
     if isinstance(components, str):
         components = (components,)
     components = tuple(components)
     if not components:
-        raise ValueError("components must name at least one of " + ", ".join(COMPONENTS))
+        raise ValueError("components must name at least one of " + ", ".join(known))
     for c in components:
-        if c not in COMPONENTS:
-            raise ValueError(f"unknown component {c!r}; known: " + ", ".join(COMPONENTS))
+        if c not in known:
+            if c in T_COMPONENTS:
+                raise ValueError(f"the component {c!r} needs nu_draws and a nu prior (nu_grid, nu_prior)")
+            raise ValueError(f"unknown component {c!r}; known: " + ", ".join(known))
     if len(set(components)) != len(components):
         raise ValueError("components must not repeat")
     # the C ABI returns the components in bit order
-    return tuple(c for c in COMPONENTS if c in components)
+    return tuple(c for c in known if c in components)
 
 
 def _check_prior(prior_info, k):
@@ -101,8 +123,46 @@ def _check_prior(prior_info, k):
     return b0, C0, nu0, sigma20
 
 
+def _likelihood(nu, nu_draws, nu_grid, nu_prior, samples, burn, thin):
+    """What a call needs of the likelihood: a dict with ``host`` / ``device`` (the context methods),
+    ``scalars`` (what they take behind ``want_weights``), ``held`` (kept alive during the call),
+    ``known`` (the components it has), ``name`` and ``nu`` (the result's ``likelihood`` and ``nu``)
+    and ``nu_column``.  ValueError for what the module docstring rules out (no GPU needed)."""
+    if nu_draws is None and (nu_grid is not None or nu_prior is not None):
+        raise ValueError("nu_grid and nu_prior describe the prior of nu_draws; give nu_draws")
+    name = "power_sensitivity"
+    lik = {"host": name, "device": name + "_device", "scalars": (), "held": None, "known": COMPONENTS,
+           "name": "gaussian", "nu": None, "nu_column": False}
+    if nu_draws is None:
+        nu = _check_nu(nu)
+        if nu is not None:
+            lik.update(host=name + "_t", device=name + "_t_device", scalars=(nu,), name="student_t", nu=nu)
+        return lik
+    if nu is not None:
+        raise ValueError("give nu (one value for all draws) or nu_draws (one per draw), not both")
+    values, index = _nu_table(nu_draws, samples, burn, thin)
+    held = index
+    if _is_torch(samples) and samples.is_cuda:   # the index goes where the draws are
+        import torch
+        held = torch.as_tensor(index, device=samples.device)
+    log_prior = None
+    if nu_grid is not None or nu_prior is not None:
+        from .inference_utils import robust_nu_prior
+        grid, weight, _ = robust_nu_prior(nu_grid, nu_prior)
+        at = np.searchsorted(grid, values)
+        at[at == grid.shape[0]] = 0
+        if not (np.all(grid[at] == values) and np.all(weight[at] > 0)):
+            raise ValueError("every value of nu_draws must be a value of nu_grid with a positive prior weight")
+        log_prior = np.log(weight[at] / weight.sum())
+        lik["known"] = T_COMPONENTS
+    lik.update(host=name + "_tv", device=name + "_tv_device", held=held, name="student_t",
+               scalars=(values, index if held is index else held.data_ptr(), log_prior),
+               nu=float(np.mean(values[index])), nu_column=True)
+    return lik
+
+
 def _run(A, y, samples, prior_info, Vt_hat, burn, thin, alphas, components, device, cols_per_batch,
-         want_weights):
+         want_weights, lik=None):
     a_shape = tuple(np.shape(A))
     if len(a_shape) != 2:
         raise ValueError(f"A must be (n_points, k); got {len(a_shape)} dimensions")
@@ -112,22 +172,24 @@ def _run(A, y, samples, prior_info, Vt_hat, burn, thin, alphas, components, devi
         Vt_hat = np.asarray(Vt_hat, dtype=np.float64)
         if Vt_hat.ndim != 2 or Vt_hat.shape[0] != k or Vt_hat.shape[1] < 1:
             raise ValueError(f"Vt_hat must be ({k}, n_models); got {Vt_hat.shape}")
-    mask = sum(1 << COMPONENTS.index(c) for c in components)
-    return _pointwise_call("power_sensitivity", "power_sensitivity_device", A, y, samples, burn, thin,
+    mask = sum(1 << T_COMPONENTS.index(c) for c in components)
+    host, dev, tail = (("power_sensitivity", "power_sensitivity_device", ()) if lik is None else
+                       (lik["host"], lik["device"], lik["scalars"]))
+    return _pointwise_call(host, dev, A, y, samples, burn, thin,
                            device, scalars=(prior, Vt_hat, np.asarray(alphas, dtype=np.float64), mask,
-                                            int(cols_per_batch), bool(want_weights)))
+                                            int(cols_per_batch), bool(want_weights), *tail))
 
 
-def column_names(k, n_models=0, models=None):
+def column_names(k, n_models=0, models=None, nu=False):
     """Names of the quantity columns: ``beta_0 .. beta_{k-1}``, ``sigma`` and the model weights
-    (``models`` or ``omega_0 ..``)."""
+    (``models`` or ``omega_0 ..``); with ``nu`` one more, ``nu``, the last."""
     if models is not None:
         models = [str(m) for m in models]
         if len(models) != n_models:
             raise ValueError(f"models must name the {n_models} columns of Vt_hat; got {len(models)}")
     else:
         models = [f"omega_{m}" for m in range(n_models)]
-    return [f"beta_{j}" for j in range(k)] + ["sigma"] + models
+    return [f"beta_{j}" for j in range(k)] + ["sigma"] + models + (["nu"] if nu else [])
 
 
 def diagnose(psens_prior, psens_likelihood, threshold=THRESHOLD):
@@ -141,7 +203,8 @@ def diagnose(psens_prior, psens_likelihood, threshold=THRESHOLD):
 
 def power_scale_sensitivity(A, y, samples, prior_info, Vt_hat=None, burn=0, thin=1, alphas=None,
                             components=DEFAULT_COMPONENTS, device=0, alpha_lo=0.99, alpha_hi=1.01,
-                            models=None, cols_per_batch=0):
+                            models=None, cols_per_batch=0, nu=None, nu_draws=None, nu_grid=None,
+                            nu_prior=None):
     """Prior and likelihood sensitivity of every coefficient, of sigma and of every model weight
     (module docstring), from draws already taken.
 
@@ -159,8 +222,20 @@ def power_scale_sensitivity(A, y, samples, prior_info, Vt_hat=None, burn=0, thin
     unless both ``prior`` and ``likelihood`` were asked for), per component and alpha ``mean``,
     ``sd``, ``cjs`` ``[component] (n_alphas, Q)`` and ``pareto_k[component] (n_alphas,)``, the per-draw
     ``log_prior``, ``log_lik``, ``log_prior_beta``, ``log_prior_sigma2`` ``(S,)``, the boolean
-    ``component_flags`` / ``column_flags`` of non-finite input, ``threshold`` and ``n_draws``."""
-    components = _check_components(components)
+    ``component_flags`` / ``column_flags`` of non-finite input, ``threshold`` and ``n_draws``.
+
+    ``nu=None`` is the Gaussian likelihood; a positive finite number the Student-t one with that
+    many degrees of freedom.  ``nu_draws`` (instead of ``nu``) is the Student-t likelihood with a
+    ``nu`` per draw, as ``pointwise_log_likelihood`` takes it; the columns then end in ``nu``.
+    ``nu_grid`` and ``nu_prior`` (only with ``nu_draws``; the arguments of
+    ``gibbs_sampler_robust(nu="estimate")``, defaults included when one of the two is given) are
+    the prior that fit gave ``nu``: it joins ``prior``, and ``prior_nu`` becomes a component
+    (``T_COMPONENTS``); every drawn value must be a grid value of positive weight.  The result
+    also carries ``likelihood`` (``"gaussian"`` or ``"student_t"``), ``nu`` (None, the value, or
+    the mean over the pooled draws) and ``log_prior_nu`` ``(S,)`` (None for the Gaussian
+    likelihood, zeros without a prior of ``nu``)."""
+    lik = _likelihood(nu, nu_draws, nu_grid, nu_prior, samples, burn, thin)
+    components = _check_components(components, lik["known"])
     lo, hi = _check_alpha("alpha_lo", alpha_lo), _check_alpha("alpha_hi", alpha_hi)
     if not lo < 1.0 < hi:
         raise ValueError("need alpha_lo < 1 < alpha_hi")
@@ -169,10 +244,10 @@ def power_scale_sensitivity(A, y, samples, prior_info, Vt_hat=None, burn=0, thin
         raise ValueError(f"at most {MAX_ALPHAS} alphas; got {len(grid)}")
     all_alphas = np.array([lo, hi] + grid, dtype=np.float64)
     out = _run(A, y, samples, prior_info, Vt_hat, burn, thin, all_alphas, components, device,
-               cols_per_batch, False)
+               cols_per_batch, False, lik)
     k = np.shape(A)[1]
     n_models = 0 if Vt_hat is None else np.shape(Vt_hat)[1]
-    res = {"columns": column_names(k, n_models, models), "components": components,
+    res = {"columns": column_names(k, n_models, models, lik["nu_column"]), "components": components,
            "alphas": all_alphas, "threshold": THRESHOLD, "n_draws": int(out["logdens"].shape[1]),
            "psens": {}, "mean": {}, "sd": {}, "cjs": {}, "pareto_k": {}}
     for ci, c in enumerate(components):
@@ -184,23 +259,28 @@ def power_scale_sensitivity(A, y, samples, prior_info, Vt_hat=None, burn=0, thin
                                                            res["psens"]["likelihood"])]
     else:
         res["diagnosis"] = [NO_FINDING] * len(res["columns"])
-    lb, ls, ll = out["logdens"]
-    res.update(log_prior=lb + ls, log_lik=ll, log_prior_beta=lb, log_prior_sigma2=ls,
+    lb, ls, ll = out["logdens"][:3]
+    ln = out["logdens"][3] if lik["name"] == "student_t" else None
+    res.update(log_prior=lb + ls if ln is None else (lb + ls) + ln, log_lik=ll, log_prior_beta=lb,
+               log_prior_sigma2=ls, log_prior_nu=ln, likelihood=lik["name"], nu=lik["nu"],
                component_flags=dict(zip(components, out["component_flags"].tolist())),
                column_flags=out["column_flags"])
     return res
 
 
 def power_scale_weights(A, y, samples, prior_info, component="prior", alpha=1.01, burn=0, thin=1,
-                        device=0):
+                        device=0, nu=None, nu_draws=None, nu_grid=None, nu_prior=None):
     """The Pareto-smoothed, normalised importance weights of the pooled draws under one component
     raised to the power ``alpha`` (module docstring): what reweights any other function of the
-    draws.  Arguments as ``power_scale_sensitivity``.  Returns ``(weights (S,), pareto_k)``;
+    draws.  Arguments as ``power_scale_sensitivity``, the likelihood (``nu``, ``nu_draws``,
+    ``nu_grid``, ``nu_prior``) included.  Returns ``(weights (S,), pareto_k)``;
     ``pareto_k`` is inf where nothing was smoothed, the weights NaN when the component has a
     non-finite log density."""
-    (component,) = _check_components((component,) if isinstance(component, str) else component)
+    lik = _likelihood(nu, nu_draws, nu_grid, nu_prior, samples, burn, thin)
+    (component,) = _check_components((component,) if isinstance(component, str) else component,
+                                     lik["known"])
     alpha = _check_alpha("alpha", alpha)
-    out = _run(A, y, samples, prior_info, None, burn, thin, [alpha], (component,), device, 0, True)
+    out = _run(A, y, samples, prior_info, None, burn, thin, [alpha], (component,), device, 0, True, lik)
     return out["weights"][:, 0].copy(), float(out["pareto_k"][0, 0])
 
 
