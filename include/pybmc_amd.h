@@ -262,6 +262,28 @@ int bmc_predict(bmc_ctx* ctx, const double* preds, int64_t n_points, int32_t n_m
                 const double* truth, const int32_t* cov_lo, const int32_t* cov_hi,
                 int32_t n_cov, double* rndm_m_out, double* bands_out, int64_t* cov_hits_out);
 
+/* bmc_predict with Student-t noise made on the device (after a Student-t fit): rndm_m[s][p] =
+ * preds[p] . w_s + sigma_s t[p][s], t with nu (bmc_predict_t) or nu_draws[s] (bmc_predict_tv,
+ * [n_draws]) degrees of freedom.  Device generator only: t[p][s] is Bailey's polar variate of the
+ * two uniforms of Philox counter (e lo, e hi, "PRET", 0), e = p * n_draws + s, under key = seed;
+ * it depends on (seed, p, s, nu_s) alone.  Every other argument, the outputs and the refusals
+ * are bmc_predict's; bmc_predict_draws and bmc_predict_timing follow as after bmc_predict.
+ * BMC_EINVAL for nu_draws == NULL and for a nu that is not finite or below 0.06: the largest
+ * |t| = sqrt(nu) 2^(53/nu) leaves the doubles below about 0.052 (replay host-made noise through
+ * bmc_predict for such nu). */
+int bmc_predict_t(bmc_ctx* ctx, const double* preds, int64_t n_points, int32_t n_models,
+                  const double* theta, int32_t n_draws, int32_t k, const double* Vt_hat,
+                  uint64_t seed, const int32_t* q_index, const double* q_gamma, int32_t n_q,
+                  const double* truth, const int32_t* cov_lo, const int32_t* cov_hi,
+                  int32_t n_cov, double* rndm_m_out, double* bands_out, int64_t* cov_hits_out,
+                  double nu);
+int bmc_predict_tv(bmc_ctx* ctx, const double* preds, int64_t n_points, int32_t n_models,
+                   const double* theta, int32_t n_draws, int32_t k, const double* Vt_hat,
+                   uint64_t seed, const int32_t* q_index, const double* q_gamma, int32_t n_q,
+                   const double* truth, const int32_t* cov_lo, const int32_t* cov_hi,
+                   int32_t n_cov, double* rndm_m_out, double* bands_out, int64_t* cov_hits_out,
+                   const double* nu_draws);
+
 /* The draws of the LAST bmc_predict on this context, in the layout the caller wants (they stay
  * on the device until the next bmc_predict or bmc_destroy, so a caller that asked bmc_predict for
  * bands / coverage only can still fetch them afterwards):

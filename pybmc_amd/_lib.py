@@ -21,6 +21,9 @@ BMC_OK, BMC_EINVAL, BMC_ESINGULAR, BMC_EHIP, BMC_ENOMEM, BMC_ETIMEOUT, BMC_ESTAT
 BMC_F64, BMC_F32 = 0, 1
 BMC_ROW_MAJOR, BMC_COL_MAJOR = 0, 1
 BMC_RNG_DEVICE, BMC_RNG_REPLAY = 0, 1
+# smallest nu of device-made predictive t noise (bmc_predict_t): below about 0.052 the largest
+# |t| = sqrt(nu) 2^(53/nu) is no double
+MIN_PREDICT_NU = 0.06
 
 
 class Tuning(C.Structure):
@@ -89,6 +92,14 @@ PROTOTYPES = {
                               C.c_uint64, _D, C.POINTER(C.c_int32), _D, C.c_int32, _D,
                               C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, _D, _D,
                               C.POINTER(C.c_int64)]),
+    "bmc_predict_t": (C.c_int, [_P, _D, C.c_int64, C.c_int32, _D, C.c_int32, C.c_int32, _D,
+                                C.c_uint64, C.POINTER(C.c_int32), _D, C.c_int32, _D,
+                                C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, _D, _D,
+                                C.POINTER(C.c_int64), C.c_double]),
+    "bmc_predict_tv": (C.c_int, [_P, _D, C.c_int64, C.c_int32, _D, C.c_int32, C.c_int32, _D,
+                                 C.c_uint64, C.POINTER(C.c_int32), _D, C.c_int32, _D,
+                                 C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, _D, _D,
+                                 C.POINTER(C.c_int64), _D]),
     "bmc_chain_diagnostics": (C.c_int, [_P, _D, C.c_int32, C.c_int64, C.c_int32, C.c_int64,
                                         C.c_int64, _D, _D, _D, _D, _D, C.POINTER(C.c_int64)]),
     "bmc_chain_diagnostics_device": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int64,
@@ -681,11 +692,16 @@ class Context:
         return out.T
 
     def predict(self, preds, theta, Vt_hat, seed=0, noise=None, q=(2.5, 50, 97.5), truth=None,
-                cov_percentiles=None, want_draws=True, draws_order="C"):
+                cov_percentiles=None, want_draws=True, draws_order="C", nu=None, nu_draws=None):
         """preds (M, Km), theta (S, k+1) selected posterior rows, Vt_hat (k, Km).
         Returns (rndm_m (S, M) or None, bands (len(q), M), coverage or None).  rndm_m is
         C-ordered like the reference's (draws_order="C", default) or Fortran-ordered
-        (draws_order="F": the device layout, a point's draws contiguous)."""
+        (draws_order="F": the device layout, a point's draws contiguous).
+
+        The noise: standard normals made on the device from ``seed`` (default); ``noise`` (S, M),
+        replayed; Student-t variates made on the device from ``seed`` with ``nu`` degrees of freedom
+        (bmc_predict_t) or ``nu_draws`` (S,) or (S, 1), one value per draw (bmc_predict_tv), every
+        value finite and at least ``MIN_PREDICT_NU``.  At most one of the three may be given."""
         preds = np.ascontiguousarray(preds, dtype=np.float64)
         theta = np.ascontiguousarray(theta, dtype=np.float64)
         Vt_hat = np.ascontiguousarray(Vt_hat, dtype=np.float64)
@@ -693,6 +709,21 @@ class Context:
         S, k1 = theta.shape
         if Vt_hat.shape != (k1 - 1, Km):
             raise ValueError("Vt_hat must be (k, n_models) with k = theta.shape[1] - 1")
+        if sum(x is not None for x in (noise, nu, nu_draws)) > 1:
+            raise ValueError("at most one of noise, nu and nu_draws may be given")
+        if nu is not None:
+            if np.ndim(nu) != 0:
+                raise ValueError("nu must be one number (nu_draws takes one per draw)")
+            nu = float(nu)
+            if not (np.isfinite(nu) and nu >= MIN_PREDICT_NU):
+                raise ValueError(f"nu must be finite and at least {MIN_PREDICT_NU}")
+        if nu_draws is not None:
+            nu_draws = np.asarray(nu_draws, dtype=np.float64)
+            if nu_draws.shape not in ((S,), (S, 1)):
+                raise ValueError("nu_draws must be (n_draws,) or (n_draws, 1)")
+            nu_draws = np.ascontiguousarray(nu_draws.reshape(S))
+            if not (np.isfinite(nu_draws).all() and (nu_draws >= MIN_PREDICT_NU).all()):
+                raise ValueError(f"every nu_draws must be finite and at least {MIN_PREDICT_NU}")
         qi, qg = order_stat_plan(S, q)
         bands = np.empty((len(q), M))
         lo = hi = hits = None
@@ -709,13 +740,20 @@ class Context:
             if nz.shape != (S, M):
                 raise ValueError("noise must be (n_draws, n_points)")
         i32p = C.POINTER(C.c_int32)
-        self._check(self._lib.bmc_predict(
-            self._h, _dptr(preds), M, Km, _dptr(theta), S, k1 - 1, _dptr(Vt_hat),
-            BMC_RNG_REPLAY if nz is not None else BMC_RNG_DEVICE, int(seed) & (2 ** 64 - 1),
-            _dptr(nz), qi.ctypes.data_as(i32p), _dptr(qg), len(q), _dptr(tr),
-            lo.ctypes.data_as(i32p) if lo is not None else None,
-            hi.ctypes.data_as(i32p) if hi is not None else None, n_cov, None,
-            _dptr(bands), hits.ctypes.data_as(C.POINTER(C.c_int64)) if hits is not None else None))
+        problem = (self._h, _dptr(preds), M, Km, _dptr(theta), S, k1 - 1, _dptr(Vt_hat))
+        seed = int(seed) & (2 ** 64 - 1)
+        asked = (qi.ctypes.data_as(i32p), _dptr(qg), len(q), _dptr(tr),
+                 lo.ctypes.data_as(i32p) if lo is not None else None,
+                 hi.ctypes.data_as(i32p) if hi is not None else None, n_cov, None,
+                 _dptr(bands), hits.ctypes.data_as(C.POINTER(C.c_int64)) if hits is not None else None)
+        if nu is not None:
+            self._check(self._lib.bmc_predict_t(*problem, seed, *asked, nu))
+        elif nu_draws is not None:
+            self._check(self._lib.bmc_predict_tv(*problem, seed, *asked, _dptr(nu_draws)))
+        else:
+            self._check(self._lib.bmc_predict(
+                *problem, BMC_RNG_REPLAY if nz is not None else BMC_RNG_DEVICE, seed, _dptr(nz),
+                *asked))
         self._last_predict = (M, S)
         cov = None if hits is None else [int(h) / M * 100 for h in hits]
         return (self.predict_draws(draws_order) if want_draws else None), bands, cov

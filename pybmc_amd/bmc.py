@@ -666,9 +666,10 @@ class BayesianModelCombination:
             frames.append(f)
         return frames
 
-    def predict(self, X):
+    def predict(self, X, noise_source="host"):
         """Posterior predictive for a DataFrame of model predictions
-        (reference bmc.py:195-242)."""
+        (reference bmc.py:195-242).  ``noise_source``: where the t noise of a Student-t fit is made,
+        ``"host"`` or ``"device"`` (``rndm_m_random_calculator``); a Gaussian fit ignores it."""
         self._require_trained()
         if not isinstance(X, pd.DataFrame):
             raise ValueError(
@@ -676,14 +677,15 @@ class BayesianModelCombination:
         domain_keys = [c for c in X.columns if c not in self.models]
         rndm_m, (lo, med, up) = rndm_m_random_calculator(
             X[self.models].values, self.samples, self.Vt_hat, device=self.device,
-            noise_df=self._noise_df())
+            noise_df=self._noise_df(), noise_source=noise_source)
         lo_df, med_df, up_df = self._band_frames(X[domain_keys].reset_index(drop=True),
                                                  lo, med, up)
         return rndm_m, lo_df, med_df, up_df
 
-    def predict2(self, property):
+    def predict2(self, property, noise_source="host"):
         """Posterior predictive for a property of ``data_dict``
-        (reference bmc.py:244-337), including its model-set checks and prints."""
+        (reference bmc.py:244-337), including its model-set checks and prints.  ``noise_source``
+        as in ``predict``."""
         self._require_trained()
         if property not in self.data_dict:
             raise KeyError(f"Property '{property}' not found in data_dict.")
@@ -710,22 +712,23 @@ class BayesianModelCombination:
         idx = [self.models.index(m) for m in available]
         rndm_m, (lo, med, up) = rndm_m_random_calculator(
             df[available].values, self.samples, self.Vt_hat[:, idx], device=self.device,
-            noise_df=self._noise_df())
+            noise_df=self._noise_df(), noise_source=noise_source)
         lo_df, med_df, up_df = self._band_frames(df[domain_keys].reset_index(drop=True),
                                                  lo, med, up)
         return rndm_m, lo_df, med_df, up_df
 
     # ---------------------------------------------------------------- evaluate
-    def evaluate(self, domain_filter=None):
+    def evaluate(self, domain_filter=None, noise_source="host"):
         """Coverage of the credible intervals at 0,5,...,100 %
-        (reference bmc.py:339-376; same filter semantics)."""
+        (reference bmc.py:339-376; same filter semantics).  ``noise_source`` as in ``predict``."""
         self._require_trained()
         # tuple ranges use Series.between in the reference (bmc.py:360): inclusive, like the
         # explicit comparisons of the shared helper
         df = apply_domain_filters(self.data_dict[self.current_property], domain_filter)
         return predictive_coverage(np.arange(0, 101, 5), df[self.models].to_numpy(), self.samples,
                                    self.Vt_hat, df[self.truth_column_name].to_numpy(),
-                                   device=self.device, noise_df=self._noise_df())
+                                   device=self.device, noise_df=self._noise_df(),
+                                   noise_source=noise_source)
 
 
 def _series_tensor(samples, Vt_hat, device, nu=None):

@@ -141,6 +141,6 @@ __host__ __device__ inline double u53_open0(uint32_t hi, uint32_t lo) {
 enum : uint32_t { STREAM_NORMAL = 0x4e4f524du, STREAM_GAMMA = 0x47414d4du,
                   STREAM_PRED_NORMAL = 0x50524544u, STREAM_UNIFORM = 0x554e4946u,
                   STREAM_PPC = 0x50504353u, STREAM_PPC_T = 0x50504354u, STREAM_ROBUST = 0x524f4253u,
-                  STREAM_NU = 0x4e554446u };
+                  STREAM_NU = 0x4e554446u, STREAM_PRED_T = 0x50524554u };
 
 }  // namespace bmc

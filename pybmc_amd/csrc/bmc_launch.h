@@ -108,6 +108,12 @@ struct PredictArgs {
     double* sig;           // [S_pad] scratch
     uint64_t seed;
     const double* noise_replay;  // [S][M] or NULL (device generator)
+    // Student-t noise, device generator only (both unset: standard normals).  nu > 0: t noise with
+    // nu degrees of freedom for every draw.  nus (nu stays 0): [2][S_pad], nu_s then 2 / nu_s, the
+    // padded draws holding 4 and 1/2; z[p][s] = student_t_variate (bmc_math.h) of the two uniforms
+    // of counter (e lo, e hi, STREAM_PRED_T, 0), e = p S + s.
+    double nu = 0.0;
+    const double* nus = nullptr;
     double* R;             // [M_pad][S_pad]
     const int32_t* q_index;
     const double* q_gamma;

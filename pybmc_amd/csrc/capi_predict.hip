@@ -1,11 +1,24 @@
 // C ABI, posterior predictive: bmc_predict, its draws and its timing (kernels_predict.hip)
 #include "bmc_ctx.h"
 
-extern "C" {
+#include <cmath>
+#include <vector>
 
-int bmc_predict(bmc_ctx* c, const double* preds, int64_t M, int32_t Km, const double* theta,
+namespace {
+
+// which noise a predictive call asks for: bmc_predict (normals: generated or replayed),
+// bmc_predict_t (one nu), bmc_predict_tv (a nu per draw)
+enum PredictNoise { NOISE_NORMAL, NOISE_T, NOISE_TV };
+
+// below 0.06 the largest |t| = sqrt(nu) 2^(53/nu) nears the end of the doubles (+-inf below about
+// 0.052) and the order statistics would interpolate inf - inf
+bool nu_ok(double nu) { return std::isfinite(nu) && nu >= 0.06; }
+
+// the one driver of bmc_predict, bmc_predict_t and bmc_predict_tv
+int predict_run(bmc_ctx* c, const double* preds, int64_t M, int32_t Km, const double* theta,
                 int32_t S, int32_t k, const double* Vt_hat, int rng_mode, uint64_t seed,
-                const double* noise, const int32_t* q_index, const double* q_gamma, int32_t n_q,
+                const double* noise, PredictNoise kind, double nu, const double* nu_draws,
+                const int32_t* q_index, const double* q_gamma, int32_t n_q,
                 const double* truth, const int32_t* cov_lo, const int32_t* cov_hi, int32_t n_cov,
                 double* rndm_m_out, double* bands_out, int64_t* cov_hits_out) {
     if (!c) return BMC_EINVAL;
@@ -23,6 +36,14 @@ int bmc_predict(bmc_ctx* c, const double* preds, int64_t M, int32_t Km, const do
         return fail(c, BMC_EINVAL, "noise must be given exactly in replay mode");
     if (rng_mode != BMC_RNG_REPLAY && rng_mode != BMC_RNG_DEVICE)
         return fail(c, BMC_EINVAL, "rng_mode must be 0 or 1");
+    if (kind == NOISE_T && !nu_ok(nu))
+        return fail(c, BMC_EINVAL, "nu must be finite and at least 0.06");
+    if (kind == NOISE_TV) {
+        if (!nu_draws) return fail(c, BMC_EINVAL, "nu_draws must not be NULL");
+        for (int32_t s = 0; s < S; ++s)
+            if (!nu_ok(nu_draws[s]))
+                return fail(c, BMC_EINVAL, "every nu_draws[s] must be finite and at least 0.06");
+    }
     for (int i = 0; i < n_q; ++i)
         if (q_index[i] < 0 || q_index[i] >= S) return fail(c, BMC_EINVAL, "q_index out of range");
     for (int i = 0; i < n_cov; ++i)
@@ -42,7 +63,7 @@ int bmc_predict(bmc_ctx* c, const double* preds, int64_t M, int32_t Km, const do
     if ((rc = ensure_all(c, {{c->pPreds, szP}, {c->pTheta, szT}, {c->pVt, szV},
                              {c->pWt, ((size_t)a.S_pad * a.Km_pad + 16) * 8},
                              {c->pPad, ((size_t)a.M_pad * a.Km_pad + 16) * 8},
-                             {c->pSig, (size_t)a.S_pad * 8},
+                             {c->pSig, (size_t)3 * a.S_pad * 8},   // sig | nu_s | 2 / nu_s
                              {c->pR, (size_t)a.M_pad * a.S_pad * 8},
                              {c->pBands, (size_t)(n_q > 0 ? n_q : 1) * M * 8}})))
         return rc;
@@ -71,6 +92,20 @@ int bmc_predict(bmc_ctx* c, const double* preds, int64_t M, int32_t Km, const do
         if ((rc = ensure(c, c->pNoise, (size_t)S * M * 8))) return rc;
         HIPCHK(c, hipMemcpyAsync(c->pNoise.p, noise, (size_t)S * M * 8, hipMemcpyHostToDevice, c->stream));
         a.noise_replay = (const double*)c->pNoise.p;
+    }
+    // nu_s and 2 / nu_s behind sig, 2 / nu_s rounded here, once per value (one value per draw
+    // then gives the bits of the one-nu call); the padded draws: 4 and 1/2
+    std::vector<double> nus;   // (lives until the stream is synchronised)
+    if (kind == NOISE_T) a.nu = nu;
+    if (kind == NOISE_TV) {
+        nus.resize((size_t)2 * a.S_pad);
+        for (int32_t s = 0; s < a.S_pad; ++s) {
+            nus[s] = s < S ? nu_draws[s] : 4.0;
+            nus[(size_t)a.S_pad + s] = 2.0 / nus[s];
+        }
+        double* d_nus = (double*)c->pSig.p + a.S_pad;
+        HIPCHK(c, hipMemcpyAsync(d_nus, nus.data(), nus.size() * 8, hipMemcpyHostToDevice, c->stream));
+        a.nus = d_nus;
     }
     a.preds = (const double*)c->pPreds.p;
     a.theta = (const double*)c->pTheta.p;
@@ -109,6 +144,40 @@ int bmc_predict(bmc_ctx* c, const double* preds, int64_t M, int32_t Km, const do
     c->pS = S;
     c->pS_pad = a.S_pad;
     return BMC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bmc_predict(bmc_ctx* c, const double* preds, int64_t M, int32_t Km, const double* theta,
+                int32_t S, int32_t k, const double* Vt_hat, int rng_mode, uint64_t seed,
+                const double* noise, const int32_t* q_index, const double* q_gamma, int32_t n_q,
+                const double* truth, const int32_t* cov_lo, const int32_t* cov_hi, int32_t n_cov,
+                double* rndm_m_out, double* bands_out, int64_t* cov_hits_out) {
+    return predict_run(c, preds, M, Km, theta, S, k, Vt_hat, rng_mode, seed, noise, NOISE_NORMAL, 0.0,
+                       nullptr, q_index, q_gamma, n_q, truth, cov_lo, cov_hi, n_cov, rndm_m_out,
+                       bands_out, cov_hits_out);
+}
+
+int bmc_predict_t(bmc_ctx* c, const double* preds, int64_t M, int32_t Km, const double* theta,
+                  int32_t S, int32_t k, const double* Vt_hat, uint64_t seed, const int32_t* q_index,
+                  const double* q_gamma, int32_t n_q, const double* truth, const int32_t* cov_lo,
+                  const int32_t* cov_hi, int32_t n_cov, double* rndm_m_out, double* bands_out,
+                  int64_t* cov_hits_out, double nu) {
+    return predict_run(c, preds, M, Km, theta, S, k, Vt_hat, BMC_RNG_DEVICE, seed, nullptr, NOISE_T,
+                       nu, nullptr, q_index, q_gamma, n_q, truth, cov_lo, cov_hi, n_cov, rndm_m_out,
+                       bands_out, cov_hits_out);
+}
+
+int bmc_predict_tv(bmc_ctx* c, const double* preds, int64_t M, int32_t Km, const double* theta,
+                   int32_t S, int32_t k, const double* Vt_hat, uint64_t seed, const int32_t* q_index,
+                   const double* q_gamma, int32_t n_q, const double* truth, const int32_t* cov_lo,
+                   const int32_t* cov_hi, int32_t n_cov, double* rndm_m_out, double* bands_out,
+                   int64_t* cov_hits_out, const double* nu_draws) {
+    return predict_run(c, preds, M, Km, theta, S, k, Vt_hat, BMC_RNG_DEVICE, seed, nullptr, NOISE_TV,
+                       0.0, nu_draws, q_index, q_gamma, n_q, truth, cov_lo, cov_hi, n_cov, rndm_m_out,
+                       bands_out, cov_hits_out);
 }
 
 int bmc_predict_draws(bmc_ctx* c, double* out, int layout) {

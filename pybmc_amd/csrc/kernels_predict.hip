@@ -2,7 +2,8 @@
 //
 //   predict_weights   Wt[s][m] = sum_i theta[s][i] Vt_hat[i][m] + 1/Km,  sig[s] = theta[s][k]   (:60-67)
 //   predict_gemm      R[p][s]  = sum_m preds[p][m] Wt[s][m] + z[p][s] sig[s]                    (:70-77)
-//                     v_mfma_f64_16x16x4_f64, noise fused into the epilogue
+//                     v_mfma_f64_16x16x4_f64, noise fused into the epilogue: standard normals, or
+//                     Student-t variates after a Student-t fit (PgNoise below)
 //   predict_orderstat per point p: sort the S draws (bitonic, LDS), interpolate the requested
 //                     order statistics like numpy's linear method (:80-82), count coverage
 //                     hits sorted[lo] <= truth <= sorted[hi]                                   (:24-34)
@@ -118,11 +119,34 @@ __global__ __launch_bounds__(256) void predict_pad_kernel(const double* __restri
     }
 }
 
+// The noise of the epilogue.  PG_GAUSS: the standard normals of pg_noise (or the caller's array,
+// replay mode), no further argument.  PG_T: Student-t with one nu for all draws; Lik = (double nu,
+// double 2 / nu).  PG_TV: a nu per draw; Lik = (const double* nus), [2][S_pad]: nu_s, then 2 / nu_s,
+// read beside sig (the padded draws hold nu = 4, so that their 0 * t stays finite).  The t variate of
+// (point p, draw s) is student_t_variate (bmc_math.h) of the two uniforms of counter
+// (e lo, e hi, STREAM_PRED_T, 0), e = p S + s: one Philox call per element and the cosine half
+// alone -- the sine half shares its radius, and handing it to point p + 4 as the Gaussian walk does
+// would tie the magnitudes of the two points' noise together.  Nothing of the tiling
+// enters the counter: z[p][s] depends on (seed, p, s, nu_s) alone.  The t instantiations have no
+// replay mode and ignore noise_replay.
+enum PgNoise { PG_GAUSS = 0, PG_T = 1, PG_TV = 2 };
+template <typename... Lik>
+struct PgLik {};
+template <>
+struct PgLik<double, double> {
+    double nu, two_over_nu;
+};
+template <>
+struct PgLik<const double*> {
+    const double* nus;
+};
+
+template <PgNoise NOISE, typename... Lik>
 __global__ __launch_bounds__(256) void predict_gemm_kernel(
     const double* __restrict__ P, const double* __restrict__ Wt, const double* __restrict__ sig,
     int64_t M, int32_t S, int32_t S_pad, int32_t Km_pad, uint64_t seed,
     const double* __restrict__ noise_replay, double* __restrict__ R, uint32_t ntx, uint32_t nty,
-    uint32_t nsx) {
+    uint32_t nsx, Lik... lik) {
     __shared__ double As[2 * PG_TM * PG_LD];
     __shared__ double Bs[2 * PG_TM * PG_LD];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -228,6 +252,37 @@ __global__ __launch_bounds__(256) void predict_gemm_kernel(
     const int32_t sl0 = s0 + cl;
     double* r0 = R + pe0 * S_pad + sl0;
     const uint64_t e0 = (uint64_t)pe0 * (uint64_t)S + (uint64_t)sl0;
+    if constexpr (NOISE != PG_GAUSS) {
+        // every one of the 16 entries draws for itself: entry (t, j) is point pe0 + 4 j, draw
+        // sl0 + 16 t
+        const PgLik<Lik...> lk{lik...};
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const double sg = sig[sl0 + 16 * t];
+            double nu, two_over_nu;
+            if constexpr (NOISE == PG_TV) {
+                nu = lk.nus[sl0 + 16 * t];
+                two_over_nu = lk.nus[S_pad + sl0 + 16 * t];
+            } else {
+                nu = lk.nu;
+                two_over_nu = lk.two_over_nu;
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint64_t e = e0 + (uint64_t)(4 * j) * (uint64_t)S + (uint64_t)(16 * t);
+                const u32x4 w = philox4x32_10(
+                    u32x4{(uint32_t)e, (uint32_t)(e >> 32), STREAM_PRED_T, 0u}, k0, k1);
+                const double z = student_t_variate(u53_open0(w.x, w.y), u53_open0(w.z, w.w), nu,
+                                                   two_over_nu);
+                __builtin_nontemporal_store(fma(z, sg, acc[t][j]),
+                                            r0 + (int64_t)(4 * j) * S_pad + 16 * t);
+                // one variate at a time: the temporaries of the logarithm, expm1 and the cosine
+                // of several chains do not fit beside the accumulators
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        return;
+    }
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
         const double sg = sig[sl0 + 16 * t];
@@ -573,9 +628,23 @@ hipError_t launch_predict(const PredictArgs& a, hipStream_t s) {
         const uint64_t nsuper8 = ((uint64_t)nsx * nsy + 7) / 8 * 8;
         const uint64_t nblocks = nsuper8 * PG_ST * PG_ST;
         if (nblocks > 0x7fffffffull) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(predict_gemm_kernel, dim3((unsigned)nblocks), dim3(256), 0, s, (const double*)a.P,
-                           (const double*)a.Wt, (const double*)a.sig, a.M, a.S, a.S_pad, a.Km_pad, a.seed,
-                           a.noise_replay, a.R, ntx, nty, nsx);
+        // (the t noise is the device generator's alone)
+        if ((a.nus || a.nu != 0.0) && (a.noise_replay || (a.nus && a.nu != 0.0) || !(a.nu >= 0.0)))
+            return hipErrorInvalidValue;
+        const dim3 grid((unsigned)nblocks);
+        if (a.nus)
+            hipLaunchKernelGGL((predict_gemm_kernel<PG_TV, const double*>), grid, dim3(256), 0, s,
+                               (const double*)a.P, (const double*)a.Wt, (const double*)a.sig, a.M, a.S,
+                               a.S_pad, a.Km_pad, a.seed, a.noise_replay, a.R, ntx, nty, nsx, a.nus);
+        else if (a.nu != 0.0)
+            hipLaunchKernelGGL((predict_gemm_kernel<PG_T, double, double>), grid, dim3(256), 0, s,
+                               (const double*)a.P, (const double*)a.Wt, (const double*)a.sig, a.M, a.S,
+                               a.S_pad, a.Km_pad, a.seed, a.noise_replay, a.R, ntx, nty, nsx, a.nu,
+                               2.0 / a.nu);
+        else
+            hipLaunchKernelGGL(predict_gemm_kernel<PG_GAUSS>, grid, dim3(256), 0, s, (const double*)a.P,
+                               (const double*)a.Wt, (const double*)a.sig, a.M, a.S, a.S_pad, a.Km_pad,
+                               a.seed, a.noise_replay, a.R, ntx, nty, nsx);
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;

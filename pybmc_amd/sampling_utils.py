@@ -23,9 +23,9 @@ def _choose(rng, samples, noise_df):
 
 def _t_noise(rng, noise_df, n_points):
     """Student-t predictive noise for the replay ``noise=`` argument of ``Context.predict``, drawn on
-    the host from the generator that made the ``choice``, right after it.  This path is
-    host-bound: 80 kB of variates per point are generated and uploaded (on-device t noise in the
-    predictive kernels is a follow-up)."""
+    the host from the generator that made the ``choice``, right after it (``noise_source="host"``).
+    This path is host-bound: 80 kB of variates per point are generated and uploaded;
+    ``noise_source="device"`` makes the noise in the predictive kernel instead."""
     if np.ndim(noise_df) == 0:
         noise_df = float(noise_df)
     if not np.all(np.asarray(noise_df) > 0):
@@ -33,8 +33,26 @@ def _t_noise(rng, noise_df, n_points):
     return rng.standard_t(noise_df, (N_PREDICTIVE_DRAWS, n_points))
 
 
+def _noise_args(rng, noise_df, noise_source, n_points):
+    """What ``Context.predict`` gets for the noise, as keywords: nothing (normal noise), the host's
+    ``standard_t`` array as ``noise=``, or, for the device's own t variates, ``nu=`` / ``nu_draws=``
+    (the chosen rows' values)."""
+    if noise_df is None:
+        return {}
+    if noise_source == "host":
+        return {"noise": _t_noise(rng, noise_df, n_points)}
+    if np.ndim(noise_df) == 0:
+        return {"nu": float(noise_df)}
+    return {"nu_draws": np.ascontiguousarray(noise_df, dtype=np.float64).reshape(-1)}
+
+
+def _check_noise_source(noise_source):
+    if noise_source not in ("host", "device"):
+        raise ValueError(f'noise_source must be "host" or "device"; got {noise_source!r}')
+
+
 def rndm_m_random_calculator(filtered_model_predictions, samples, Vt_hat, *, seed=None,
-                             device=0, noise_df=None):
+                             device=0, noise_df=None, noise_source="host"):
     """Posterior-predictive draws and 2.5/50/97.5 % bands on the GPU
     (reference sampling_utils.py:40-84).
 
@@ -44,13 +62,20 @@ def rndm_m_random_calculator(filtered_model_predictions, samples, Vt_hat, *, see
     re-seeding numpy's global stream (:54, quirk Q2) is not reproduced.
 
     ``noise_df`` (after a Student-t fit, ``gibbs_sampler_robust``): the predictive noise is
-    ``sigma_s * t_nu`` instead of ``sigma_s * z``, with
-    ``Generator(PCG64(seed)).standard_t(noise_df, (10000, n_points))`` taken from the generator
-    that made the ``choice``, right after it, and replayed through the predictive kernels.  That
-    path is host-bound (80 kB of variates per point).  ``noise_df`` may also hold one value per row
+    ``sigma_s * t_nu`` instead of ``sigma_s * z``.  ``noise_df`` may also hold one value per row
     of ``samples`` (a fit with nu estimated): the rows are then chosen from ``samples`` with that
     column appended, and draw s gets ``t`` noise of its own degrees of freedom.
+
+    ``noise_source`` says where the t noise is made (ignored when ``noise_df`` is None):
+    ``"host"`` (default) takes ``Generator(PCG64(seed)).standard_t(noise_df, (10000, n_points))``
+    from the generator that made the ``choice``, right after it, and replays it through the
+    predictive kernels: 80 kB of variates per point, generated and uploaded.  ``"device"`` makes
+    the same ``choice`` and hands the chosen rows' degrees of freedom to the predictive kernel, which
+    draws the variates itself from ``seed`` (``Context.predict(nu=)`` / ``nu_draws=``; every value
+    finite and at least 0.06): nothing but the inputs is uploaded.  The two are different variates
+    of the same distribution.
     """
+    _check_noise_source(noise_source)
     preds = np.ascontiguousarray(filtered_model_predictions, dtype=np.float64)
     samples = np.ascontiguousarray(samples, dtype=np.float64)
     Vt_hat = np.ascontiguousarray(Vt_hat, dtype=np.float64)
@@ -62,18 +87,20 @@ def rndm_m_random_calculator(filtered_model_predictions, samples, Vt_hat, *, see
     ctx = _lib.default_context(device)
     rng = np.random.Generator(np.random.PCG64(seed))
     theta, noise_df = _choose(rng, samples, noise_df)
-    noise = None if noise_df is None else _t_noise(rng, noise_df, preds.shape[0])
+    noise = _noise_args(rng, noise_df, noise_source, preds.shape[0])
     with ctx.lock:
-        rndm_m, bands, _ = ctx.predict(preds, theta, Vt_hat, seed=seed, noise=noise)
+        rndm_m, bands, _ = ctx.predict(preds, theta, Vt_hat, seed=seed, **noise)
     return rndm_m, [bands[0], bands[1], bands[2]]
 
 
 def predictive_coverage(percentiles, filtered_model_predictions, samples, Vt_hat, truth, *,
-                        seed=None, device=0, noise_df=None):
+                        seed=None, device=0, noise_df=None, noise_source="host"):
     """``coverage(percentiles, rndm_m_random_calculator(...)[0], ...)`` fused on the GPU:
     the draws are sorted where they were produced and only the hit counts come back
-    (what ``BayesianModelCombination.evaluate`` needs, reference bmc.py:366-376).  ``noise_df``:
-    Student-t noise as in ``rndm_m_random_calculator`` (host-bound)."""
+    (what ``BayesianModelCombination.evaluate`` needs, reference bmc.py:366-376).  ``noise_df`` and
+    ``noise_source``: Student-t noise as in ``rndm_m_random_calculator``, replayed from the host
+    or made on the device."""
+    _check_noise_source(noise_source)
     preds = np.ascontiguousarray(filtered_model_predictions, dtype=np.float64)
     samples = np.ascontiguousarray(samples, dtype=np.float64)
     if samples.shape[0] < N_PREDICTIVE_DRAWS:
@@ -83,11 +110,11 @@ def predictive_coverage(percentiles, filtered_model_predictions, samples, Vt_hat
             np.random.randint(0, 2 ** 32, dtype=np.uint64))
     rng = np.random.Generator(np.random.PCG64(seed))
     theta, noise_df = _choose(rng, samples, noise_df)
-    noise = None if noise_df is None else _t_noise(rng, noise_df, preds.shape[0])
+    noise = _noise_args(rng, noise_df, noise_source, preds.shape[0])
     ctx = _lib.default_context(device)
     with ctx.lock:
-        _, _, cov = ctx.predict(preds, theta, Vt_hat, seed=seed, noise=noise, q=(), truth=truth,
-                                cov_percentiles=list(percentiles), want_draws=False)
+        _, _, cov = ctx.predict(preds, theta, Vt_hat, seed=seed, q=(), truth=truth,
+                                cov_percentiles=list(percentiles), want_draws=False, **noise)
     return cov
 
 
