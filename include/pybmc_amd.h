@@ -596,6 +596,43 @@ int bmc_cv_path(bmc_ctx* ctx, const double* A, int64_t n, int32_t k, int64_t lda
                 int64_t burn, int64_t thin, const uint64_t* seeds, const int32_t* comps,
                 int32_t n_comps, double* elpd_out, double* mean_out, double* draws_out);
 
+/* ---- exact K-fold cross-validation under the Student-t likelihood, all folds in one launch -----
+ * Arguments and results as bmc_kfold_cv, with k <= 32 and these differences.
+ *   The chains.  Chain (f, c) is a chain of bmc_robust_run (bmc_robust_run_nu for the _tv call) on
+ *   the training rows of fold f, in the caller's row order, under seeds[f * n_chains + c]: `iters`
+ *   sweeps from lambda = 1 and the OLS sigma2 of THOSE rows, the gamma shape (nu0 + n_train) / 2,
+ *   the weight variates counted by the row's position within the training rows.  The kept draws
+ *   (the first `burn` dropped, every `thin`-th of the rest) equal, bit for bit, rows burn, burn +
+ *   thin, ... of what bmc_robust_run(nu, 1 chain, iters, burn 0) draws after bmc_set_problem and
+ *   bmc_set_prior on those rows alone; likewise the nu indices of bmc_robust_run_nu.
+ *   The scores.  elpd_out[i] is the lppd of bmc_pointwise_loglik_t (bmc_pointwise_loglik_tv with the
+ *   draws' own nu) on the rows of fold f and its pooled kept draws.
+ *   weight_out   [n_folds][n_chains][n], may be NULL: the mean of lambda_i over the sweeps after
+ *                `burn` (thinning does not apply to it) at the caller's row index i, NaN at the
+ *                fold's own held-out rows.
+ *   nu_idx_out   (_tv) [n_folds][n_chains][kept] indices into nu_grid of the kept sweeps; may be NULL.
+ * nu_grid, nu_weight, n_grid, nu_init as bmc_robust_run_nu; every fold has its own table of the
+ * grid's constants, which depend on n_train.  Every fold's training rows are packed on the device
+ * (n_folds copies of about n - n_f rows) and all n_folds * n_chains chains run one workgroup each,
+ * in launches of at most 1024, in as many batches of whole folds as the free device memory asks
+ * for.  The resident problem and prior of the context are not touched (the set-up scratch of
+ * bmc_set_problem and the run buffers are used).  Deterministic.
+ * BMC_EINVAL for bad arguments, BMC_ESINGULAR when C0 or X'X of a fold's training rows is singular
+ * (the message names the fold) or a Cholesky pivot of a chain is not positive and finite (the
+ * message names the fold and the chain), BMC_ENOMEM when not one fold fits the device.  The context
+ * stays usable after an error.  INTEGRATION.md section 11.2. */
+int bmc_kfold_cv_t(bmc_ctx* ctx, const double* A, int64_t n, int32_t k, int64_t lda, int layout,
+                   const double* y, const int64_t* fold, int32_t n_folds, const double* b0,
+                   const double* C0, double nu0, double sigma20, int32_t n_chains, int64_t iters,
+                   int64_t burn, int64_t thin, const uint64_t* seeds, double nu, double* elpd_out,
+                   double* mean_out, double* draws_out, double* weight_out);
+int bmc_kfold_cv_tv(bmc_ctx* ctx, const double* A, int64_t n, int32_t k, int64_t lda, int layout,
+                    const double* y, const int64_t* fold, int32_t n_folds, const double* b0,
+                    const double* C0, double nu0, double sigma20, int32_t n_chains, int64_t iters,
+                    int64_t burn, int64_t thin, const uint64_t* seeds, const double* nu_grid,
+                    const double* nu_weight, int32_t n_grid, int32_t nu_init, double* elpd_out,
+                    double* mean_out, double* draws_out, double* weight_out, int32_t* nu_idx_out);
+
 /* ---- posterior predictive check: do data replicated from the fit look like the data? ----------
  * Model and arguments A, y, theta as bmc_pointwise_loglik; offset [n_points] or NULL (zeros).
  * Replicated data y_rep[i][s] = a_i . beta_s + sigma_s z[i][s] + offset_i, z[i][s] the standard

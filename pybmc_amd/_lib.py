@@ -155,6 +155,14 @@ PROTOTYPES = {
                                C.POINTER(C.c_int64), C.c_int32, _D, _D, C.c_double, C.c_double,
                                C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_uint64), _D,
                                _D, _D]),
+    "bmc_kfold_cv_t": (C.c_int, [_P, _D, C.c_int64, C.c_int32, C.c_int64, C.c_int, _D,
+                                 C.POINTER(C.c_int64), C.c_int32, _D, _D, C.c_double, C.c_double,
+                                 C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_uint64),
+                                 C.c_double, _D, _D, _D, _D]),
+    "bmc_kfold_cv_tv": (C.c_int, [_P, _D, C.c_int64, C.c_int32, C.c_int64, C.c_int, _D,
+                                  C.POINTER(C.c_int64), C.c_int32, _D, _D, C.c_double, C.c_double,
+                                  C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_uint64),
+                                  _D, _D, C.c_int32, C.c_int32, _D, _D, _D, _D, C.POINTER(C.c_int32)]),
     "bmc_cv_path": (C.c_int, [_P, _D, C.c_int64, C.c_int32, C.c_int64, C.c_int, _D,
                               C.POINTER(C.c_int64), C.c_int32, _D, _D, C.c_double, C.c_double,
                               C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_uint64),
@@ -1177,6 +1185,44 @@ class Context:
                 (self._lib.bmc_last_error(self._h) or b"").decode("utf-8", "replace"))
         self._check(rc)
         return elpd, mean, draws
+
+    def kfold_cv_t(self, A, n, k, lda, layout, y, fold, n_folds, b0, C0, nu0, sigma20, n_chains, iters,
+                   burn, thin, seeds, nu=None, nu_grid=None, nu_weight=None, nu_init=None,
+                   return_draws=False, return_row_weights=False):
+        """bmc_kfold_cv_t (``nu`` a number) or bmc_kfold_cv_tv (``nu_grid``, ``nu_weight`` and the
+        index ``nu_init``) of HOST arrays, the arguments of ``kfold_cv``.  Returns (elpd_cv_i [n],
+        cv_mean_i [n], draws (n_folds, n_chains, kept, k+1) or None, row weights (n_folds, n_chains,
+        n) or None, grid indices (n_folds, n_chains, kept) int32 or None).  A singular fold or a
+        failed Cholesky pivot raises SingularFoldError."""
+        kept = max(0, -(-(int(iters) - int(burn)) // int(thin)))
+        elpd, mean = np.empty(n), np.empty(n)
+        draws = np.empty((n_folds, n_chains, kept, k + 1)) if return_draws else None
+        w = np.empty((n_folds, n_chains, n)) if return_row_weights else None
+        b0 = np.ascontiguousarray(b0, dtype=np.float64)
+        C0 = np.ascontiguousarray(C0, dtype=np.float64)
+        fold = np.ascontiguousarray(fold, dtype=np.int64)
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+        head = (self._h, _dptr(A), int(n), int(k), int(lda), int(layout), _dptr(y),
+                fold.ctypes.data_as(C.POINTER(C.c_int64)), int(n_folds), _dptr(b0), _dptr(C0),
+                float(nu0), float(sigma20), int(n_chains), int(iters), int(burn), int(thin),
+                seeds.ctypes.data_as(C.POINTER(C.c_uint64)))
+        idx = None
+        if nu_grid is None:
+            rc = self._lib.bmc_kfold_cv_t(*head, float(nu), _dptr(elpd), _dptr(mean), _dptr(draws), _dptr(w))
+        else:
+            grid = np.ascontiguousarray(nu_grid, dtype=np.float64).reshape(-1)
+            wt = np.ascontiguousarray(nu_weight, dtype=np.float64).reshape(-1)
+            if wt.shape != grid.shape:
+                raise ValueError("nu_weight must have one entry per grid value")
+            idx = np.empty((n_folds, n_chains, kept), dtype=np.int32)
+            rc = self._lib.bmc_kfold_cv_tv(*head, _dptr(grid), _dptr(wt), grid.shape[0], int(nu_init),
+                                           _dptr(elpd), _dptr(mean), _dptr(draws), _dptr(w),
+                                           idx.ctypes.data_as(C.POINTER(C.c_int32)))
+        if rc == BMC_ESINGULAR:
+            raise SingularFoldError(
+                (self._lib.bmc_last_error(self._h) or b"").decode("utf-8", "replace"))
+        self._check(rc)
+        return elpd, mean, draws, w, idx
 
     def cv_path(self, A, n, k, lda, layout, y, fold, n_folds, b0, C0, nu0, sigma20, n_chains, iters,
                 burn, thin, seeds, comps, return_draws=False):

@@ -455,13 +455,14 @@ class BayesianModelCombination:
             prior, Vt_hat=self.Vt_hat, burn=burn, alphas=alphas, components=components,
             device=self.device, models=self.models, **lik)
 
-    def _cv_arguments(self, what, n_folds, groups, training_options, seed):
-        """(options, y, fold labels, group values or None, prior) of ``cross_validate`` and
-        ``component_path``; ValueError for what neither accepts."""
+    def _cv_arguments(self, what, n_folds, groups, training_options, seed, gaussian_only=True):
+        """(options, y, fold labels, group values or None, prior) of ``cross_validate``,
+        ``component_path`` and ``validate``; ValueError for what they do not accept."""
         if self.U_hat is None:
             raise ValueError("Must call `orthogonalize()` before cross-validating.")
         opts = training_options if training_options is not None else {}
-        self._require_gaussian(what, training_options)
+        if gaussian_only:
+            self._require_gaussian(what, training_options)
         if opts.get("sampler", "gibbs_sampling") == "simplex":
             raise ValueError(f'{what} supports the Gibbs sampler only (sampler == "simplex")')
         from .cv import fold_labels, group_labels
@@ -515,6 +516,10 @@ class BayesianModelCombination:
                        opts.get("iterations", 50000), burn=opts.get("burn", 10000),
                        thin=opts.get("thin", 1), n_chains=int(opts.get("n_chains", 1)), seed=seed,
                        device=self.device)
+        return self._cv_extras(out, y, folds, values)
+
+    def _cv_extras(self, out, y, folds, values):
+        """The extras of ``cross_validate()`` on a ``kfold_cv`` result."""
         mu = np.asarray(self._predictions_mean_train, dtype=np.float64)
         out["folds"] = folds
         if values is not None:
@@ -523,6 +528,39 @@ class BayesianModelCombination:
         out["truth"] = y + mu
         out["residual"] = y - out["cv_mean_i"]
         return out
+
+    def validate(self, n_folds=10, groups=None, training_options=None, seed=None):
+        """``cross_validate()`` under the likelihood the options name: the plain call for the
+        Gaussian Gibbs sampler, and for ``{"sampler": "student_t", "nu": ...}`` exact
+        cross-validation of the Student-t fit (``pybmc_amd.cv.kfold_cv(nu=...)``: every fold's
+        chains are ``gibbs_sampler_robust``'s on its training rows, all in one launch, the held-out
+        rows scored under the t density).  Options that name no sampler take the likelihood of the
+        last ``train()``, as ``score()``, ``check()`` and ``sensitivity()`` read a fit: its ``nu``, or
+        ``"estimate"`` with that fit's grid and prior.  ``"nu": "estimate"`` takes the optional
+        ``nu_grid``, ``nu_prior`` and ``nu_init`` of ``train()``.  Arguments, defaults and the returned
+        extras (``folds``, ``groups``, ``predicted``, ``truth``, ``residual``) are
+        ``cross_validate()``'s; a Student-t result also carries ``likelihood`` and ``nu``.
+        ``sampler == "simplex"`` raises ``ValueError``."""
+        opts = training_options if training_options is not None else {}
+        trained = self._trained_with
+        sampler = opts.get("sampler", trained[0] if trained is not None else None)
+        if sampler != "student_t":
+            return self.cross_validate(n_folds, groups, training_options, seed)
+        opts, y, folds, values, prior = self._cv_arguments("validate", n_folds, groups, training_options,
+                                                          seed, gaussian_only=False)
+        extra = {key: opts[key] for key in ("nu_grid", "nu_prior", "nu_init") if key in opts}
+        if "nu" in opts or opts.get("sampler") == "student_t":
+            nu = opts.get("nu", 4.0)
+        else:                               # the last train()'s own likelihood
+            nu = trained[2]
+            if isinstance(nu, str) and self._nu_prior is not None and not extra:
+                extra = {"nu_grid": self._nu_prior[0], "nu_prior": self._nu_prior[1]}
+        from .cv import kfold_cv
+        out = kfold_cv(np.asarray(self.U_hat, dtype=np.float64), y, prior, folds,
+                       opts.get("iterations", 50000), burn=opts.get("burn", 10000),
+                       thin=opts.get("thin", 1), n_chains=int(opts.get("n_chains", 1)), seed=seed,
+                       device=self.device, nu=nu if isinstance(nu, str) else float(nu), **extra)
+        return self._cv_extras(out, y, folds, values)
 
     def component_path(self, n_folds=10, groups=None, components=None, training_options=None, seed=None):
         """Choose ``components_kept`` by cross-validation (not in the reference;

@@ -38,6 +38,49 @@ struct RobustArgs {
     double* tstat;        // [C][iters]: T_t = sum_n (log lambda_n - lambda_n), or NULL
 };
 
+// The folded form (bmc_kfold_cv_t): chains of DIFFERENT problems in one launch.
+// One entry per fold of the batch, device memory:
+struct RobustFold {
+    const double* Z;       // [robust_rows_padded(n)][ldz]: the fold's training rows, packed as above
+    const double* yv;      // [robust_rows_padded(n)]
+    const double* nu_tab;  // [4][n_grid]: robust_nu_table at THIS n (nu on a grid only)
+    int64_t n;             // training rows
+    int64_t rows_per_wave; // robust_rows_per_wave(n)
+    double sigma2_init;    // the OLS start value of the training rows
+};
+// Launch-wide: k, the prior, nu, the sweeps.  Per chain of the launch: its fold, the first row of its
+// block of ws ([n][2]) and wsum ([n]) -- n differs between folds -- and, at the chain's index as in
+// RobustArgs, seeds, xi, gam, samples, status, nu_idx and tstat.  Device RNG only.
+struct RobustFoldedArgs {
+    const RobustFold* fold;        // [folds of the batch]
+    const int32_t* fold_of_chain;  // [C]: index into fold
+    const int64_t* row0;           // [C]: rows, from ws / wsum
+    int32_t k;
+    const double* P;
+    const double* Pb0;
+    double nu, shape_l;
+    double nu0_s20;
+    int64_t iters, burn;
+    int32_t n_chains;
+    const uint64_t* seeds;
+    const double* xi;      // [C][burn + iters][k]
+    const double* gam;     // [C][burn + iters]: shape (nu0 + n of the chain's fold) / 2
+    double* ws;
+    double* samples;       // [C][iters][k + 1]
+    double* wsum;
+    int32_t* status;
+    int32_t n_grid, nu_init;   // n_grid = 0: nu fixed
+    int32_t* nu_idx;       // [C][iters]
+    double* tstat;         // [C][iters] or NULL
+};
+// one workgroup per chain, a.n_chains <= ROBUST_MAX_CHAINS_PER_LAUNCH; a.n_grid > 0 draws nu
+hipError_t launch_robust_folded(const RobustFoldedArgs& a, hipStream_t s);
+// out[ch][s][0 .. width) = in[ch][s * thin][0 .. width), s < kept, of chains that hold rows_in rows
+hipError_t launch_robust_thin(const double* in, int64_t chains, int64_t rows_in, int64_t thin, int64_t kept,
+                              int32_t width, double* out, hipStream_t s);
+hipError_t launch_robust_thin_idx(const int32_t* in, int64_t chains, int64_t rows_in, int64_t thin, int64_t kept,
+                                  int32_t* out, hipStream_t s);
+
 // panels (f64) -> Z, yv
 hipError_t launch_robust_pack(const Panels& P, double* Z, double* yv, hipStream_t s);
 // one workgroup per chain, a.n_chains <= ROBUST_MAX_CHAINS_PER_LAUNCH

@@ -7,7 +7,10 @@
 // bmc_cv_path (the plan in bmc_cvpath_plan.h) does the same for every candidate
 // component count at once: model k is the leading k columns, so one gather and one Gram pass at
 // the widest candidate serve all of them, and the m x F x C chains share the device.
-// Both entry points are the same stages around their own chain stage (the variates, the chain
+// bmc_kfold_cv_t / bmc_kfold_cv_tv (the plan in bmc_cvt_plan.h) are the Student-t
+// form: X'LX changes every sweep, so every fold's training rows are packed for the robust sampler's
+// kernel and all F x C chains run in its folded form, one workgroup each.
+// All entry points are the same stages around their own chain stage (the variates, the chain
 // kernel and its batching): cv_check_args, cv_front, training_stats, cv_rss, score_fold, cv_scatter.
 #include <algorithm>
 #include <atomic>
@@ -18,6 +21,9 @@
 #include "bmc_basis.h"
 #include "bmc_ctx.h"
 #include "bmc_cv.h"
+#include "bmc_cvt_plan.h"
+#include "bmc_robust.h"
+#include "host_linalg.hpp"
 
 namespace {
 
@@ -202,9 +208,18 @@ int cv_rss(bmc_ctx* c, CvFront& fr, const std::vector<double>& beta, int nb, int
 }
 
 // held-out scores of fold f (nf rows): the score kernels on the fold's row segment against its S
-// pooled draws theta [S][kj + 1], the log predictive densities into the fold's segment of elpd_row
+// pooled draws theta [S][kj + 1], the log predictive densities into the fold's segment of elpd_row.
+// The likelihood as ScoreArgs names it: Gaussian, Student-t with one nu, or (n_nu > 0) a nu per draw
+// from the device table nu_tab through nu_index, with the zeroed flag word nu_flag.
+struct FoldLikelihood {
+    double nu = 0.0;
+    int32_t n_nu = 0;
+    const double* nu_tab = nullptr;
+    const int32_t* nu_index = nullptr;
+    int32_t* nu_flag = nullptr;
+};
 int score_fold(bmc_ctx* c, const CvFront& fr, int f, int64_t nf, int64_t S, int kj, const double* theta,
-               double* elpd_row) {
+               double* elpd_row, const FoldLikelihood& lik = FoldLikelihood()) {
     const ScorePlan plan = plan_score(nf, S, kj, c->n_cu);
     const ScoreBuffers sb = score_buffers(plan, S);
     if (int rc = ensure_all(c, {{c->scAp, sb.Ap}, {c->scYp, sb.yp}, {c->scCh, sb.ch}, {c->scPart, sb.part},
@@ -217,6 +232,7 @@ int score_fold(bmc_ctx* c, const CvFront& fr, int f, int64_t nf, int64_t S, int 
     sa.n = nf; sa.lda = fr.ldz; sa.S = S; sa.ldt = (int64_t)kj + 1; sa.k = kj; sa.col_major = 0;
     sa.Ap = (double*)c->scAp.p; sa.yp = (double*)c->scYp.p; sa.ch = (double*)c->scCh.p;
     sa.part = (double*)c->scPart.p; sa.out = (double*)c->scOut.p;
+    sa.nu = lik.nu; sa.n_nu = lik.n_nu; sa.nu_tab = lik.nu_tab; sa.nu_index = lik.nu_index; sa.nu_flag = lik.nu_flag;
     HIPCHK(c, launch_score(sa, plan, c->stream));
     HIPCHK(c, hipMemcpyAsync(elpd_row + fr.seg.offset[f], sa.out, (size_t)nf * 8, hipMemcpyDeviceToDevice,
                              c->stream));
@@ -246,6 +262,288 @@ int cv_scatter(bmc_ctx* c, const CvFront& fr, int m, int64_t n, const DevBuf& dE
 int fail_prior(bmc_ctx* c, BasisStatus st, const std::string& who) {
     if (st == BASIS_C0_SINGULAR) return fail(c, BMC_ESINGULAR, who + "Singular matrix (b_mean_cov)");
     return fail(c, BMC_EINVAL, who + "prior precision inv(b_mean_cov) + 1e-6 I is not positive definite");
+}
+
+// ---- Student-t folds (bmc_kfold_cv_t, bmc_kfold_cv_tv) ------------------------------
+
+// nu on a grid: the prior and where the kept indices go (host, [F][C][kept], or NULL)
+struct CvtNu {
+    const double *grid, *weight;
+    int32_t n_grid, nu_init;
+    int32_t* idx_out;
+};
+
+// device blocks of the per-fold set-up, reused from fold to fold
+struct CvtSetup {
+    DevBuf dTr, dG, dGy, dXp, dYp;
+};
+
+// The set-up of one fold's training rows tr [nt] (caller's row indices, ascending), the steps of
+// bmc_set_problem, bmc_set_prior and bmc_robust_run on those rows alone: gather, panelise, the Gram
+// of the panels, the host solve, rss at the least-squares point on the panels, sigma2_init =
+// max(rss / nt, 1e-6), and the pack into Z / yv.  *singular: X'X of the rows has no solve.
+int cvt_fold_setup(bmc_ctx* c, const CvFront& fr, int64_t lda, int layout, int k, const std::vector<int64_t>& tr,
+                   CvtSetup& st, double* Z, double* yv, double* sigma2_init, bool* singular) {
+    const int64_t nt = (int64_t)tr.size();
+    const int ldg = cv_ldz(k), ka = k + 1;
+    Panels P;
+    P.n = nt;
+    P.k = k;
+    P.f32 = 0;
+    P.vec = choose_vec(nt, k, 0);
+    const int RP = 64 * P.vec;
+    P.npanels = (int32_t)((nt + RP - 1) / RP);
+    P.stream_keep = 1 << 30;
+    int rc;
+    if ((rc = upload(c, st.dTr, tr.data(), (size_t)nt * 8)) ||
+        (rc = ensure_all(c, {{st.dG, (size_t)nt * ldg * 8}, {st.dGy, (size_t)nt * 8},
+                             {st.dXp, (size_t)P.npanels * k * RP * 8}, {st.dYp, (size_t)P.npanels * RP * 8}})))
+        return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // tr may be a temporary of the caller
+    P.X = st.dXp.p;
+    P.y = st.dYp.p;
+    HIPCHK(c, launch_cv_gather((const double*)fr.dA.p, (const double*)fr.dY.p, lda, layout == BMC_COL_MAJOR, k,
+                               (const int64_t*)st.dTr.p, nt, (double*)st.dG.p, (double*)st.dGy.p, c->stream));
+    HIPCHK(c, launch_panelize(st.dG.p, st.dGy.p, nt, k, ldg, 0, 0, P.vec, st.dXp.p, st.dYp.p, P.npanels, c->stream));
+    const size_t gsz = (size_t)ka * ka;
+    if ((rc = ensure_all(c, {{c->gramScratch, gram_scratch_bytes(P)}, {c->gramOut, gsz * 8}}))) return rc;
+    HIPCHK(c, launch_gram(P, c->gramScratch.p, (double*)c->gramOut.p, c->stream));
+    std::vector<double> gram(gsz);
+    HIPCHK(c, hipMemcpyAsync(gram.data(), c->gramOut.p, gsz * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    bmc_la::Mat At((size_t)k * k);
+    std::vector<double> xty(k), bols;
+    for (int i = 0; i < k; ++i) {
+        for (int j = 0; j < k; ++j) At[(size_t)i * k + j] = gram[(size_t)i * ka + j];
+        xty[i] = gram[(size_t)i * ka + k];
+    }
+    *singular = !bmc_la::solve(At, xty, k, bols);
+    if (*singular) return BMC_OK;
+    if ((rc = ensure_rss(c, P, 8)) || (rc = ensure(c, c->coef, (size_t)8 * k * 8))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->coef.p, bols.data(), (size_t)k * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, launch_residual_rss(P, (const double*)c->coef.p, 1, (double*)c->rssPartial.p, (unsigned*)c->ticket.p,
+                                  (double*)c->rssOut.p, c->stream));
+    double rss0 = 0.0;
+    HIPCHK(c, hipMemcpyAsync(&rss0, c->rssOut.p, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, launch_robust_pack(P, Z, yv, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    double s2 = rss0 / (double)nt;
+    if (!(s2 >= 1e-6)) s2 = s2 != s2 ? s2 : 1e-6;   // max(s2, 1e-6); NaN propagates
+    *sigma2_init = s2;
+    return BMC_OK;
+}
+
+int kfold_cv_t(bmc_ctx* c, const std::string& name, const double* A, int64_t n, int32_t k, int64_t lda, int layout,
+               const double* y, const int64_t* fold, int32_t F, const double* b0, const double* C0, double nu0,
+               double sigma20, int32_t C, int64_t iters, int64_t burn, int64_t thin, const uint64_t* seeds,
+               double nu, const CvtNu* ns, double* elpd_out, double* mean_out, double* draws_out,
+               double* weight_out) {
+    if (!A || !y || !fold || !b0 || !C0 || !seeds || !elpd_out || !mean_out)
+        return fail(c, BMC_EINVAL, name + "A, y, fold, b0, C0, seeds, elpd_out and mean_out must not be NULL");
+    if (layout != BMC_ROW_MAJOR && layout != BMC_COL_MAJOR)
+        return fail(c, BMC_EINVAL, name + "layout must be BMC_ROW_MAJOR or BMC_COL_MAJOR");
+    std::vector<int64_t> count;
+    const std::string bad = cvt_check(n, k, F, fold, C, iters, burn, thin, nu, ns ? ns->grid : nullptr,
+                                      ns ? ns->weight : nullptr, ns ? ns->n_grid : 0, ns ? ns->nu_init : 0, &count);
+    if (!bad.empty()) return fail(c, BMC_EINVAL, name + bad);
+    if (ns && (!ns->grid || !ns->weight)) return fail(c, BMC_EINVAL, name + "nu_grid and nu_weight must not be NULL");
+    if (lda < (layout == BMC_COL_MAJOR ? n : (int64_t)k))
+        return fail(c, BMC_EINVAL, name + "lda is smaller than the leading dimension of A");
+    const int G = ns ? ns->n_grid : 0;
+    if (ns) nu = ns->grid[ns->nu_init];
+    const int64_t T = iters, Ta = T - burn, kept = cv_kept_draws(iters, burn, thin), S = (int64_t)C * kept;
+    const size_t K = (size_t)k, K1 = K + 1;
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc;
+
+    PriorBasis pb;
+    if (const BasisStatus st = prior_basis(k, C0, k, b0, pb)) return fail_prior(c, st, name);
+
+    // ---- rows into fold order (the held-out segments of the score and the mean), A and y on the device ----
+    CvFront fr;
+    if ((rc = cv_front(c, A, n, k, lda, layout, y, fold, F, k, fr))) return rc;
+    const CvSegments& seg = fr.seg;
+
+    DevBuf dPrior, dBbar, dElpd, dMean, dZt, dWs, dWsum, dDesc, dFoldOf, dRow0, dNuTab, dIdxA, dIdxK, dScNu;
+    std::vector<double> prior(K * K + K);
+    std::copy(pb.P.begin(), pb.P.end(), prior.begin());
+    std::copy(pb.Pb0.begin(), pb.Pb0.end(), prior.begin() + K * K);
+    if ((rc = upload(c, dPrior, prior.data(), prior.size() * 8)) ||
+        (rc = upload(c, c->seeds, seeds, (size_t)F * C * sizeof(uint64_t))) ||
+        (rc = ensure_all(c, {{dBbar, (size_t)F * K * 8}, {dElpd, (size_t)seg.n_pad * 8},
+                             {dMean, (size_t)seg.n_pad * 8}})))
+        return rc;
+    HIPCHK(c, hipMemsetAsync(dElpd.p, 0, (size_t)seg.n_pad * 8, c->stream));
+    // the score's table of a nu per draw: student_t_cnu of every grid value, the values, the flag word
+    if (ns) {
+        std::vector<double> tab(2 * (size_t)G);
+        for (int g = 0; g < G; ++g) {
+            tab[g] = student_t_cnu(ns->grid[g]);
+            tab[(size_t)G + g] = ns->grid[g];
+        }
+        if ((rc = ensure(c, dScNu, (size_t)G * 16 + 4))) return rc;
+        HIPCHK(c, hipMemcpyAsync(dScNu.p, tab.data(), (size_t)G * 16, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemsetAsync((char*)dScNu.p + (size_t)G * 16, 0, 4, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));   // tab is a local
+    }
+    if (weight_out) {
+        const double nan = std::nan("");
+        std::fill(weight_out, weight_out + (size_t)F * C * (size_t)n, nan);
+    }
+
+    // ---- batches of whole folds that fit the device ----
+    size_t budget = 0;
+    if ((rc = chain_budget(c, &budget))) return rc;
+    std::vector<CvtBatch> batches;
+    {
+        int32_t too_big = 0;
+        size_t need = 0;
+        if (!plan_cvt(F, C, k, count.data(), n, T, burn, kept, G, budget, batches, &too_big, &need))
+            return fail(c, BMC_ENOMEM, name + "fold " + std::to_string(too_big) + " with its " + std::to_string(C) +
+                                           " chains needs " + std::to_string(need) + " bytes of device memory; " +
+                                           std::to_string(budget) + " are free");
+    }
+    CvtSetup setup;
+    std::vector<std::vector<int64_t>> tr;
+    for (const CvtBatch& b : batches) {
+        const int nf = b.f1 - b.f0;
+        const size_t nch = (size_t)nf * C;
+        if ((rc = ensure_all(c, {{dZt, (size_t)(b.z_len + b.yv_len) * 8}, {dWs, (size_t)b.rows * 16},
+                                 {dWsum, (size_t)b.rows * 8}, {c->xi, nch * T * K * 8}, {c->gam, nch * T * 8},
+                                 {c->uout, nch * Ta * K1 * 8}, {c->samples, nch * kept * K1 * 8},
+                                 {c->status, nch * sizeof(int32_t)}, {dDesc, (size_t)nf * sizeof(RobustFold)},
+                                 {dFoldOf, nch * 4}, {dRow0, nch * 8}})))
+            return rc;
+        if (ns && (rc = ensure_all(c, {{dNuTab, (size_t)nf * 4 * G * 8}, {dIdxA, nch * Ta * 4}, {dIdxK, nch * kept * 4}})))
+            return rc;
+        double* Zb = (double*)dZt.p;
+        double* yvb = Zb + b.z_len;
+        // ---- every fold's own rows, start value and nu table ----
+        std::vector<RobustFold> desc(nf);
+        std::vector<int32_t> fold_of(nch);
+        std::vector<int64_t> row0(nch);
+        std::vector<double> nutab(ns ? (size_t)nf * 4 * G : 0);
+        tr.assign(nf, {});
+        for (int q = 0; q < nf; ++q) {
+            const CvtFold& d = b.folds[q];
+            tr[q].reserve((size_t)d.n_train);
+            for (int64_t i = 0; i < n; ++i)
+                if (fold[i] != d.fold) tr[q].push_back(i);
+            bool singular = false;
+            double s2 = 0.0;
+            if ((rc = cvt_fold_setup(c, fr, lda, layout, k, tr[q], setup, Zb + d.z_off, yvb + d.yv_off, &s2, &singular)))
+                return rc;
+            if (singular)
+                return fail(c, BMC_ESINGULAR, name + "fold " + std::to_string(d.fold) +
+                                                  ": Singular matrix (X'X of its training rows)");
+            desc[q].Z = Zb + d.z_off;
+            desc[q].yv = yvb + d.yv_off;
+            desc[q].nu_tab = ns ? (const double*)dNuTab.p + (size_t)q * 4 * G : nullptr;
+            desc[q].n = d.n_train;
+            desc[q].rows_per_wave = d.rows_per_wave;
+            desc[q].sigma2_init = s2;
+            if (ns) robust_nu_table(ns->grid, ns->weight, G, d.n_train, &nutab[(size_t)q * 4 * G]);
+            for (int cc = 0; cc < C; ++cc) {
+                fold_of[(size_t)q * C + cc] = q;
+                row0[(size_t)q * C + cc] = d.row0 + (int64_t)cc * d.n_train;
+            }
+        }
+        HIPCHK(c, hipMemcpyAsync(dDesc.p, desc.data(), (size_t)nf * sizeof(RobustFold), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(dFoldOf.p, fold_of.data(), nch * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(dRow0.p, row0.data(), nch * 8, hipMemcpyHostToDevice, c->stream));
+        if (ns) {
+            HIPCHK(c, hipMemcpyAsync(dNuTab.p, nutab.data(), nutab.size() * 8, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemsetAsync(dIdxA.p, 0xff, nch * Ta * 4, c->stream));   // -1: never drawn
+        }
+        HIPCHK(c, hipMemsetAsync(c->status.p, 0, nch * sizeof(int32_t), c->stream));
+        // ---- the variates of chain (f, c) under its own seed; the gamma shape is the fold's ----
+        for (int q = 0; q < nf; ++q) {
+            const CvtFold& d = b.folds[q];
+            const size_t l0 = (size_t)q * C;
+            const double shape = (nu0 + (double)d.n_train) / 2.0;
+            HIPCHK(c, launch_rng_fill((const uint64_t*)c->seeds.p + (size_t)d.fold * C, C, (int64_t)(T * K),
+                                      (double*)c->xi.p + l0 * T * K, shape, T, (double*)c->gam.p + l0 * T, c->stream));
+        }
+        // ---- all chains of the batch, one workgroup each ----
+        RobustFoldedArgs a;
+        a.fold = (const RobustFold*)dDesc.p;
+        a.k = k;
+        a.P = (const double*)dPrior.p;
+        a.Pb0 = (const double*)dPrior.p + K * K;
+        a.nu = nu;
+        a.shape_l = (nu + 1.0) / 2.0;
+        a.nu0_s20 = nu0 * sigma20;
+        a.iters = Ta;
+        a.burn = burn;
+        a.ws = (double*)dWs.p;
+        a.wsum = (double*)dWsum.p;
+        a.n_grid = G;
+        a.nu_init = ns ? ns->nu_init : 0;
+        a.tstat = nullptr;
+        for (const CvtLaunch& l : b.launches) {
+            const size_t c0 = (size_t)l.chain0;
+            a.n_chains = l.n_chains;
+            a.fold_of_chain = (const int32_t*)dFoldOf.p + c0;
+            a.row0 = (const int64_t*)dRow0.p + c0;
+            a.seeds = (const uint64_t*)c->seeds.p + (size_t)b.f0 * C + c0;
+            a.xi = (const double*)c->xi.p + c0 * T * K;
+            a.gam = (const double*)c->gam.p + c0 * T;
+            a.samples = (double*)c->uout.p + c0 * Ta * K1;
+            a.status = (int32_t*)c->status.p + c0;
+            a.nu_idx = ns ? (int32_t*)dIdxA.p + c0 * Ta : nullptr;
+            HIPCHK(c, launch_robust_folded(a, c->stream));
+        }
+        std::vector<int32_t> st(nch, 0);
+        HIPCHK(c, hipMemcpyAsync(st.data(), c->status.p, nch * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));   // also: desc, fold_of, row0 and nutab are locals
+        for (size_t i = 0; i < nch; ++i)
+            if (st[i] != 0)
+                return fail(c, BMC_ESINGULAR, name + "fold " + std::to_string(b.f0 + (int)(i / C)) + ", chain " +
+                                                  std::to_string(i % C) + ": a Cholesky pivot of X'LX / sigma2 + "
+                                                  "inv(C0) + 1e-6 I was not positive and finite");
+        // ---- every thin-th draw after burn, the fold means, the held-out scores ----
+        HIPCHK(c, launch_robust_thin((const double*)c->uout.p, (int64_t)nch, Ta, thin, kept, (int32_t)K1,
+                                     (double*)c->samples.p, c->stream));
+        if (ns)
+            HIPCHK(c, launch_robust_thin_idx((const int32_t*)dIdxA.p, (int64_t)nch, Ta, thin, kept, (int32_t*)dIdxK.p,
+                                             c->stream));
+        HIPCHK(c, launch_cv_colmean((const double*)c->samples.p, k, S, nf, b.f0, (double*)dBbar.p, c->stream));
+        for (int q = 0; q < nf; ++q) {
+            const int f = b.f0 + q;
+            FoldLikelihood lik;
+            if (ns) {
+                lik.n_nu = G;
+                lik.nu_tab = (const double*)dScNu.p;
+                lik.nu_index = (const int32_t*)dIdxK.p + (size_t)q * S;
+                lik.nu_flag = (int32_t*)((char*)dScNu.p + (size_t)G * 16);
+            } else {
+                lik.nu = nu;
+            }
+            if ((rc = score_fold(c, fr, f, count[f], S, k, (const double*)c->samples.p + (size_t)q * S * K1,
+                                 (double*)dElpd.p, lik)))
+                return rc;
+        }
+        if (draws_out)
+            if ((rc = copy_to_host(c, draws_out + (size_t)b.f0 * C * kept * K1, c->samples.p, nch * kept * K1 * 8,
+                                   nch * kept * K1 * 8, 1)))
+                return rc;
+        if (ns && ns->idx_out)
+            if ((rc = copy_to_host(c, ns->idx_out + (size_t)b.f0 * C * kept, dIdxK.p, nch * kept * 4, nch * kept * 4, 1)))
+                return rc;
+        if (weight_out) {
+            std::vector<double> w((size_t)b.rows);
+            if ((rc = copy_to_host(c, w.data(), dWsum.p, (size_t)b.rows * 8, (size_t)b.rows * 8, 1))) return rc;
+            for (int q = 0; q < nf; ++q)
+                for (int cc = 0; cc < C; ++cc) {
+                    const double* src = &w[(size_t)row0[(size_t)q * C + cc]];
+                    double* dst = weight_out + ((size_t)(b.f0 + q) * C + cc) * (size_t)n;
+                    for (size_t r = 0; r < tr[q].size(); ++r) dst[tr[q][r]] = src[r];
+                }
+        }
+    }
+    HIPCHK(c, launch_cv_mean((const double*)fr.dZ.p, fr.ldz, k, (const int32_t*)fr.dRowFold.p, (const double*)dBbar.p,
+                             seg.n_pad, (double*)dMean.p, c->stream));
+    return cv_scatter(c, fr, 1, n, dElpd, dMean, elpd_out, mean_out);
 }
 
 }  // namespace
@@ -535,6 +833,29 @@ int bmc_cv_path(bmc_ctx* c, const double* A, int64_t n, int32_t k, int64_t lda, 
                                  (const double*)dBbar.p + voff[j], seg.n_pad, (double*)dMean.p + (size_t)j * npad,
                                  c->stream));
     return cv_scatter(c, fr, m, n, dElpd, dMean, elpd_out, mean_out);
+}
+
+int bmc_kfold_cv_t(bmc_ctx* c, const double* A, int64_t n, int32_t k, int64_t lda, int layout,
+                   const double* y, const int64_t* fold, int32_t n_folds, const double* b0,
+                   const double* C0, double nu0, double sigma20, int32_t n_chains, int64_t iters,
+                   int64_t burn, int64_t thin, const uint64_t* seeds, double nu, double* elpd_out,
+                   double* mean_out, double* draws_out, double* weight_out) {
+    if (!c) return BMC_EINVAL;
+    return kfold_cv_t(c, "bmc_kfold_cv_t: ", A, n, k, lda, layout, y, fold, n_folds, b0, C0, nu0, sigma20,
+                      n_chains, iters, burn, thin, seeds, nu, nullptr, elpd_out, mean_out, draws_out, weight_out);
+}
+
+int bmc_kfold_cv_tv(bmc_ctx* c, const double* A, int64_t n, int32_t k, int64_t lda, int layout,
+                    const double* y, const int64_t* fold, int32_t n_folds, const double* b0,
+                    const double* C0, double nu0, double sigma20, int32_t n_chains, int64_t iters,
+                    int64_t burn, int64_t thin, const uint64_t* seeds, const double* nu_grid,
+                    const double* nu_weight, int32_t n_grid, int32_t nu_init, double* elpd_out,
+                    double* mean_out, double* draws_out, double* weight_out, int32_t* nu_idx_out) {
+    if (!c) return BMC_EINVAL;
+    if (n_grid < 1) return fail(c, BMC_EINVAL, "bmc_kfold_cv_tv: " + robust_nu_check(nu_grid, nu_weight, n_grid, nu_init));
+    const CvtNu ns{nu_grid, nu_weight, n_grid, nu_init, nu_idx_out};
+    return kfold_cv_t(c, "bmc_kfold_cv_tv: ", A, n, k, lda, layout, y, fold, n_folds, b0, C0, nu0, sigma20,
+                      n_chains, iters, burn, thin, seeds, 0.0, &ns, elpd_out, mean_out, draws_out, weight_out);
 }
 
 }  // extern "C"

@@ -31,6 +31,12 @@
 //      of the next sweep reads nu and (nu + 1) / 2 from the grid's LDS table, three barriers later.
 // Every sum's order is fixed by (N, k): a chain's bits do not depend on its index, its launch, its
 // neighbours or the device.
+//   * robust_chain_kernel<KC, NU_FREE, true>   the folded form (bmc_kfold_cv_t): chains
+//                           of DIFFERENT problems in one launch, each workgroup finding its rows, row
+//                           count, slab size, start value and nu table through a descriptor;
+//   * robust_thin_kernel    every thin-th row of a chain's draws or nu indices.
+#include <type_traits>
+
 #include "bmc_dev.h"
 #include "bmc_rng.h"
 #include "bmc_robust.h"
@@ -74,8 +80,14 @@ __device__ __forceinline__ double wave_max(double v) {   // the data movement of
 
 // NU_FREE = false: nu is a.nu in every sweep.  NU_FREE = true: nu is a value of the grid a.nu_tab,
 // drawn anew at the end of every sweep (steps 5 and 6 of bmc_robust_run_nu).
-template <int KC, bool NU_FREE>
-__global__ __launch_bounds__(ROBUST_THREADS) void robust_chain_kernel(const RobustArgs a) {
+// FOLDED = true (bmc_kfold_cv_t): every workgroup finds its own problem through a
+// descriptor -- chain c of the launch works on the packed rows, the row count, the slab size, the
+// start value and (NU_FREE) the nu table of fold a.fold_of_chain[c], and on rows a.row0[c] .. of ws and
+// wsum.  Device RNG only.  Everything after these reads is the code of the unfolded form: the chain
+// is the one a launch on that fold's rows alone draws.
+template <int KC, bool NU_FREE, bool FOLDED>
+__global__ __launch_bounds__(ROBUST_THREADS) void robust_chain_kernel(
+    const typename std::conditional<FOLDED, RobustFoldedArgs, RobustArgs>::type a) {
     constexpr int NT = KC > 16 ? 2 : 1, NP = NT * (NT + 1) / 2, LDZ = 16 * NT, LDL = KC + 1;
     __shared__ double s_part[ROBUST_WAVES][NP][256];
     __shared__ double s_xty[ROBUST_WAVES][4][LDZ];
@@ -89,15 +101,29 @@ __global__ __launch_bounds__(ROBUST_THREADS) void robust_chain_kernel(const Robu
     __shared__ int s_idx;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, kq = lane >> 4, cl = lane & 15;
-    const int64_t c = blockIdx.x, N = a.n, Tt = a.burn + a.iters;
+    // the chain's problem: the launch's own, or (FOLDED) what its fold's descriptor names
+    const RobustFold* fd = nullptr;
+    if constexpr (FOLDED) fd = a.fold + a.fold_of_chain[blockIdx.x];
+    int64_t N_;
+    if constexpr (FOLDED) N_ = fd->n; else N_ = a.n;
+    const int64_t c = blockIdx.x, N = N_, Tt = a.burn + a.iters;
     const int k = a.k;
-    const double* __restrict__ Z = a.Z;
-    const double* __restrict__ yv = a.yv;
+    const double *Z_, *yv_;
+    if constexpr (FOLDED) { Z_ = fd->Z; yv_ = fd->yv; } else { Z_ = a.Z; yv_ = a.yv; }
+    const double* __restrict__ Z = Z_;
+    const double* __restrict__ yv = yv_;
     const double* xi = a.xi + (size_t)c * Tt * k;
     const double* gam = a.gam + (size_t)c * Tt;
-    const double* gl = a.gl ? a.gl + (size_t)c * Tt * N : nullptr;
-    double* ws = a.ws + (size_t)c * N * 2;
-    double* wsum = a.wsum + (size_t)c * N;
+    const double* gl = nullptr;      // replay mode: the unfolded form only
+    double *ws, *wsum;
+    if constexpr (FOLDED) {
+        ws = a.ws + 2 * a.row0[c];
+        wsum = a.wsum + a.row0[c];
+    } else {
+        gl = a.gl ? a.gl + (size_t)c * Tt * N : nullptr;
+        ws = a.ws + (size_t)c * N * 2;
+        wsum = a.wsum + (size_t)c * N;
+    }
     double* out = a.samples + (size_t)c * a.iters * (k + 1);
     uint32_t k0 = 0, k1 = 0;
     if (a.seeds) {
@@ -106,8 +132,10 @@ __global__ __launch_bounds__(ROBUST_THREADS) void robust_chain_kernel(const Robu
         k1 = (uint32_t)(seed >> 32);
     }
     // this wave's slab; phases B and L give row slab0 + lane + 64 i to the lane, every sweep
-    const int64_t slab0 = wave * a.rows_per_wave;
-    const int64_t slab1 = slab0 + a.rows_per_wave < N ? slab0 + a.rows_per_wave : N;
+    int64_t rpw;
+    if constexpr (FOLDED) rpw = fd->rows_per_wave; else rpw = a.rows_per_wave;
+    const int64_t slab0 = wave * rpw;
+    const int64_t slab1 = slab0 + rpw < N ? slab0 + rpw : N;
     const int64_t gsteps = slab1 > slab0 ? (slab1 - slab0 + 3) / 4 * 4 : 0;   // rows of phase G
 
     for (int64_t row = slab0 + lane; row < slab1; row += 64) {
@@ -117,10 +145,15 @@ __global__ __launch_bounds__(ROBUST_THREADS) void robust_chain_kernel(const Robu
     }
     if (tid == 0) s_fail = 0;
     if constexpr (NU_FREE) {
-        if (tid < 4 * a.n_grid) s_nu[tid] = a.nu_tab[tid];
+        if constexpr (FOLDED) {
+            if (tid < 4 * a.n_grid) s_nu[tid] = fd->nu_tab[tid];
+        } else {
+            if (tid < 4 * a.n_grid) s_nu[tid] = a.nu_tab[tid];
+        }
         if (tid == 0) s_idx = a.nu_init;
     }
-    double sigma2 = a.sigma2_init;
+    double sigma2;
+    if constexpr (FOLDED) sigma2 = fd->sigma2_init; else sigma2 = a.sigma2_init;
     int64_t t_fail = -1;
     __syncthreads();
 
@@ -311,8 +344,10 @@ __global__ __launch_bounds__(ROBUST_THREADS) void robust_chain_kernel(const Robu
                         }
                     }
                     double u;
-                    if (a.u_nu) {
-                        u = a.u_nu[(size_t)c * Tt + t];
+                    const double* u_nu = nullptr;    // replay mode: the unfolded form only
+                    if constexpr (!FOLDED) u_nu = a.u_nu;
+                    if (u_nu) {
+                        u = u_nu[(size_t)c * Tt + t];
                     } else {
                         const u32x4 w = philox4x32_10(
                             u32x4{(uint32_t)t, (uint32_t)((uint64_t)t >> 32), STREAM_NU, 0u}, k0, k1);
@@ -325,7 +360,8 @@ __global__ __launch_bounds__(ROBUST_THREADS) void robust_chain_kernel(const Robu
                         a.nu_idx[(size_t)c * a.iters + (t - a.burn)] = pick;
                         if (a.tstat) a.tstat[(size_t)c * a.iters + (t - a.burn)] = T;
                     }
-                    s_idx = a.nu_path ? a.nu_path[(size_t)c * Tt + t] : pick;
+                    if constexpr (FOLDED) s_idx = pick;
+                    else s_idx = a.nu_path ? a.nu_path[(size_t)c * Tt + t] : pick;
                 }
             }
         }
@@ -344,7 +380,47 @@ __global__ __launch_bounds__(ROBUST_THREADS) void robust_chain_kernel(const Robu
 
 template <int KC, bool NU_FREE>
 hipError_t launch_kc(const RobustArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL((robust_chain_kernel<KC, NU_FREE>), dim3((unsigned)a.n_chains), dim3(ROBUST_THREADS), 0, s, a);
+    hipLaunchKernelGGL((robust_chain_kernel<KC, NU_FREE, false>), dim3((unsigned)a.n_chains), dim3(ROBUST_THREADS), 0, s, a);
+    return hipGetLastError();
+}
+template <int KC, bool NU_FREE>
+hipError_t launch_kc(const RobustFoldedArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL((robust_chain_kernel<KC, NU_FREE, true>), dim3((unsigned)a.n_chains), dim3(ROBUST_THREADS), 0, s, a);
+    return hipGetLastError();
+}
+template <bool NU_FREE>
+hipError_t launch_folded_kc(const RobustFoldedArgs& a, hipStream_t s) {
+    switch (robust_kc(a.k)) {
+        case 4: return launch_kc<4, NU_FREE>(a, s);
+        case 8: return launch_kc<8, NU_FREE>(a, s);
+        case 16: return launch_kc<16, NU_FREE>(a, s);
+        default: return launch_kc<32, NU_FREE>(a, s);
+    }
+}
+
+// out[ch][s][.] = in[ch][s * thin][.], s < kept, rows of `width` elements: every thin-th of the
+// `rows_in` rows a chain holds
+template <class T>
+__global__ __launch_bounds__(256) void robust_thin_kernel(const T* __restrict__ in, int64_t chains,
+                                                          int64_t rows_in, int64_t thin, int64_t kept,
+                                                          int32_t width, T* __restrict__ out) {
+    const int64_t total = chains * kept * width;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
+        const int64_t row = e / width;
+        const int32_t j = (int32_t)(e - row * width);
+        const int64_t ch = row / kept, sdraw = row - ch * kept;
+        out[e] = in[(ch * rows_in + sdraw * thin) * width + j];
+    }
+}
+template <class T>
+hipError_t launch_thin(const T* in, int64_t chains, int64_t rows_in, int64_t thin, int64_t kept, int32_t width,
+                       T* out, hipStream_t s) {
+    if (chains < 1 || kept < 1 || thin < 1 || width < 1 || (kept - 1) * thin >= rows_in) return hipErrorInvalidValue;
+    int64_t blocks = (chains * kept * width + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(robust_thin_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, s, in, chains, rows_in, thin,
+                       kept, width, out);
     return hipGetLastError();
 }
 
@@ -382,6 +458,25 @@ hipError_t launch_robust_nu(const RobustArgs& a, hipStream_t s) {
         case 16: return launch_kc<16, true>(a, s);
         default: return launch_kc<32, true>(a, s);
     }
+}
+
+hipError_t launch_robust_folded(const RobustFoldedArgs& a, hipStream_t s) {
+    if (a.n_chains < 1 || a.n_chains > ROBUST_MAX_CHAINS_PER_LAUNCH || a.k < 1 || a.k > ROBUST_MAX_K ||
+        !a.fold || !a.fold_of_chain || !a.row0 || !a.seeds)
+        return hipErrorInvalidValue;
+    if (a.n_grid == 0) return launch_folded_kc<false>(a, s);
+    if (a.n_grid < 1 || a.n_grid > ROBUST_MAX_NU_GRID || a.nu_init < 0 || a.nu_init >= a.n_grid || !a.nu_idx)
+        return hipErrorInvalidValue;
+    return launch_folded_kc<true>(a, s);
+}
+
+hipError_t launch_robust_thin(const double* in, int64_t chains, int64_t rows_in, int64_t thin, int64_t kept,
+                              int32_t width, double* out, hipStream_t s) {
+    return launch_thin(in, chains, rows_in, thin, kept, width, out, s);
+}
+hipError_t launch_robust_thin_idx(const int32_t* in, int64_t chains, int64_t rows_in, int64_t thin, int64_t kept,
+                                  int32_t* out, hipStream_t s) {
+    return launch_thin(in, chains, rows_in, thin, kept, 1, out, s);
 }
 
 }  // namespace bmc

@@ -109,7 +109,8 @@ def cv_summary(y, folds, n_folds, elpd_i, mean_i, n_draws):
 
 
 def kfold_cv(A, y, prior_info, folds, iterations, burn=0, thin=1, n_chains=1, seed=None, seeds=None,
-             return_draws=False, device=0):
+             return_draws=False, device=0, nu=None, nu_grid=None, nu_prior=None, nu_init=None,
+             return_row_weights=False):
     """Exact cross-validation over the folds named by ``folds`` (module docstring).
 
     ``A`` is ``(n, k)`` float64 with k <= 64 (either memory order), ``y`` ``(n,)``, ``prior_info =
@@ -122,7 +123,21 @@ def kfold_cv(A, y, prior_info, folds, iterations, burn=0, thin=1, n_chains=1, se
     ``n_folds``, ``n_draws`` (pooled kept draws per fold), the pointwise ``elpd_cv_i`` and
     ``cv_mean_i``, ``seeds``, and with ``return_draws`` the ``draws`` ``(F, n_chains, kept, k+1)``.
     Argument errors are ``ValueError`` before any GPU work; a fold whose training Gram is
-    numerically singular raises ``_lib.SingularFoldError`` naming it."""
+    numerically singular raises ``_lib.SingularFoldError`` naming it.
+
+    ``nu`` selects the Student-t likelihood of ``gibbs_sampler_robust`` (``None``: the Gaussian call
+    above, unchanged): a positive number, or ``"estimate"`` with ``nu_grid``, ``nu_prior`` and
+    ``nu_init`` as that sampler takes them.  Then k <= 32, and chain (f, c) IS the chain
+    ``gibbs_sampler_robust(y[train], A[train], iterations, prior_info, nu, seeds=[seeds[f, c]])``
+    draws, bit for bit -- start value, gamma shape and the grid's constants are the training set's
+    own -- of which rows ``burn::thin`` are kept; the held-out rows are scored under the t density
+    (``scoring.pointwise_log_likelihood(nu=...)``, or ``nu_draws=`` the fold's own draws of nu).
+    All F x n_chains chains share one launch, a workgroup each.  The result also carries
+    ``likelihood="student_t"`` and ``nu`` (the value, or the pooled mean of the kept draws of nu);
+    with ``"estimate"`` and ``return_draws`` the ``nu_draws`` ``(F, n_chains, kept)``; with
+    ``return_row_weights`` the ``row_weights`` ``(F, n_chains, n)``: the mean weight of every
+    training row over the sweeps after ``burn``, NaN at the fold's own held-out rows.  A chain whose
+    conditional precision stops being positive definite raises ``_lib.SingularFoldError`` too."""
     from . import _lib
 
     A = np.asarray(A)
@@ -134,6 +149,24 @@ def kfold_cv(A, y, prior_info, folds, iterations, burn=0, thin=1, n_chains=1, se
     # (the draws this call will make, as the shape of samples scoring checks)
     k1 = (A.shape[1] if A.ndim == 2 else 0) + 1
     n, k, C, T, kept = _check_shapes(A.shape, y.shape, (n_chains, iterations, k1), burn, thin)
+    grid = weight = init = None
+    if nu is None:
+        if nu_grid is not None or nu_prior is not None or nu_init is not None or return_row_weights:
+            raise ValueError('nu_grid, nu_prior, nu_init and return_row_weights need nu (a number or "estimate")')
+    else:
+        from .inference_utils import ROBUST_MAX_K, robust_nu_prior
+        if isinstance(nu, str):
+            if nu != "estimate":
+                raise ValueError('nu must be a positive number or "estimate"')
+            grid, weight, init = robust_nu_prior(nu_grid, nu_prior, nu_init)
+        else:
+            if nu_grid is not None or nu_prior is not None or nu_init is not None:
+                raise ValueError('nu_grid, nu_prior and nu_init need nu="estimate"')
+            nu = float(nu)
+            if not nu > 0 or not np.isfinite(nu):
+                raise ValueError("nu must be positive and finite")
+        if k > ROBUST_MAX_K:
+            raise ValueError(f"the Student-t cross-validation supports at most {ROBUST_MAX_K} columns; got {k}")
     if k > MAX_K:
         raise ValueError(f"k must be at most {MAX_K} (one lane per coefficient); got {k}")
     if burn >= iterations:
@@ -147,6 +180,23 @@ def kfold_cv(A, y, prior_info, folds, iterations, burn=0, thin=1, n_chains=1, se
     seeds = _check_seeds(seed, seeds, F, C)
     Ah, lda, layout = _host_matrix(A)
     ctx = _lib.default_context(device)
+    if nu is not None:
+        want_idx = grid is not None
+        with ctx.lock:
+            elpd_i, mean_i, draws, w, idx = ctx.kfold_cv_t(
+                Ah, n, k, lda, layout, np.ascontiguousarray(y), f, F, b0, C0, nu0, s20, C, T, int(burn),
+                int(thin), seeds.reshape(-1), nu=None if want_idx else nu, nu_grid=grid, nu_weight=weight,
+                nu_init=init, return_draws=return_draws, return_row_weights=return_row_weights)
+        out = cv_summary(y, f, F, elpd_i, mean_i, C * kept)
+        out.update(elpd_cv_i=elpd_i, cv_mean_i=mean_i, seeds=seeds, likelihood="student_t",
+                   nu=float(np.mean(grid[idx])) if want_idx else nu)
+        if return_draws:
+            out["draws"] = draws
+            if want_idx:
+                out["nu_draws"] = grid[idx]
+        if return_row_weights:
+            out["row_weights"] = w
+        return out
     with ctx.lock:
         elpd_i, mean_i, draws = ctx.kfold_cv(Ah, n, k, lda, layout, np.ascontiguousarray(y), f, F, b0,
                                              C0, nu0, s20, C, T, int(burn), int(thin), seeds.reshape(-1),
