@@ -931,20 +931,12 @@ class Context:
 
     def _score_call_tv(self, fn, keys, ptr, A, n, k, lda, layout, y, theta, n_draws, ldt, nu_values,
                        nu_index):
-        """A _tv entry point: `nu_values` the distinct degrees of freedom (host), `nu_index` every
-        draw's index into them, a host int32 array (ptr is _dptr) or a device address (_P)."""
+        """A _tv entry point: `nu_values` and `nu_index` as `_nu_args` takes them."""
         out = {key: np.empty(n) for key in keys}
-        vals = np.ascontiguousarray(nu_values, dtype=np.float64).reshape(-1)
-        if ptr is _dptr:
-            nu_index = np.ascontiguousarray(nu_index, dtype=np.int32).reshape(-1)
-            if nu_index.shape[0] != int(n_draws):
-                raise ValueError("nu_index must have one entry per draw")
-            idx = nu_index.ctypes.data_as(C.POINTER(C.c_int32))
-        else:
-            idx = _P(nu_index)
+        table, held = self._nu_args(ptr, nu_values, nu_index, n_draws)
         self._check(fn(self._h, ptr(A), int(n), int(k), int(lda), int(layout), ptr(y), ptr(theta),
-                       int(n_draws), int(ldt), _dptr(vals), vals.shape[0], idx,
-                       *(_dptr(out[key]) for key in keys)))
+                       int(n_draws), int(ldt), *table, *(_dptr(out[key]) for key in keys)))
+        del held
         return out
 
     def pointwise_loglik_tv(self, A, n, k, lda, layout, y, theta, n_draws, ldt, nu_values, nu_index):

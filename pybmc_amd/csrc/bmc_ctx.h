@@ -145,7 +145,51 @@ int ensure_rss(bmc_ctx* c, const Panels& P, size_t n_out);
 int copy_to_host(bmc_ctx* c, void* dst, const void* src_dev, size_t row_bytes, size_t src_pitch,
                  size_t rows);
 
+// The panels of an n x k problem stored at X and y (f32: as floats): rows per lane by choose_vec
+Panels make_panels(int64_t n, int32_t k, int32_t f32, const void* X, const void* y);
+// those of the resident problem, with its columns at X
 Panels panels_of(const bmc_ctx* c, const void* X);
+
+// The least-squares start of a row set from its panels (the resident problem's, and every fold's
+// training rows in bmc_kfold_cv_t).  gram_to_host: the Gram of [X y], (k+1) x (k+1); one sync.
+// ols_start: A = X'X and xty = X'y out of it, the least-squares point (singular: A has no solve, and
+// nothing further is computed), rss there by one launch_residual_rss, sigma2_init = sigma2_floor(rss / n)
+int gram_to_host(bmc_ctx* c, const Panels& P, std::vector<double>& gram);
+struct OlsStart {
+    std::vector<double> A, xty, bols;
+    bool singular = false;
+    double rss = 0.0, sigma2_init = 0.0;
+};
+int ols_start(bmc_ctx* c, const Panels& P, const std::vector<double>& gram, OlsStart& o);
+// max(s2, 1e-6); NaN propagates
+inline double sigma2_floor(double s2) { return !(s2 >= 1e-6) && s2 == s2 ? 1e-6 : s2; }
+
+// The host side of a NuPerDraw (bmc_launch.h).  stage_nu lays b out as [rows][V] f64 table of `shape`,
+// [S] int32 staged index, one int32 flag word: the table up (one sync: it is a local), the flag
+// zeroed, a host index copied behind the table; v names them (the index: the staged copy, else as
+// given, a device pointer or NULL where the caller sets it later).
+int stage_nu(bmc_ctx* c, DevBuf& b, NuTable shape, const double* values, int32_t V, int64_t S,
+             const void* index, bool index_on_host, NuPerDraw& v);
+// BMC_EINVAL unless every entry of a host index lies in [0, V)
+int check_nu_index(bmc_ctx* c, const void* index, int64_t S, int32_t V);
+// The flag word back: fetch queues the copy (nothing for an unset v); after the caller's next sync,
+// result is BMC_EINVAL with the one message when an index was out of range
+struct NuFlagRead {
+    int32_t word = 0;
+    int fetch(bmc_ctx* c, const NuPerDraw& v);
+    int result(bmc_ctx* c) const;
+};
+
+// BMC_ESINGULAR for the first chain of the robust kernels whose status is not 0;
+// say(i, what) is the message: how the caller names chain i around what happened
+template <class Say>
+int robust_status_check(bmc_ctx* c, const std::vector<int32_t>& st, Say say) {
+    const std::string what = "a Cholesky pivot of X'LX / sigma2 + inv(C0) + 1e-6 I was not positive and finite";
+    for (size_t i = 0; i < st.size(); ++i)
+        if (st[i] != 0) return fail(c, BMC_ESINGULAR, say(i, what));
+    return BMC_OK;
+}
+
 Shape shape_of(const bmc_ctx* c);
 Chip chip_of(const bmc_ctx* c);
 uint32_t launch_nonce(bmc_ctx* c, uint64_t n_tags);

@@ -143,4 +143,39 @@ enum : uint32_t { STREAM_NORMAL = 0x4e4f524du, STREAM_GAMMA = 0x47414d4du,
                   STREAM_PPC = 0x50504353u, STREAM_PPC_T = 0x50504354u, STREAM_ROBUST = 0x524f4253u,
                   STREAM_NU = 0x4e554446u, STREAM_PRED_T = 0x50524554u };
 
+// ---- a nu per draw (NuPerDraw, bmc_launch.h) ------------------------------------------------------
+// A draw's index into the n_nu distinct values, as loaded: one out of range is clamped into
+// [0, n_nu) and reported through the flag word
+__device__ __forceinline__ int32_t nu_index_clamped(int32_t iv, int32_t n_nu, int32_t* flag) {
+    if (iv < 0 || iv >= n_nu) {
+        *flag = 1;
+        iv = iv < 0 ? 0 : n_nu - 1;
+    }
+    return iv;
+}
+
+// The Student-t noise of a kernel as its trailing arguments Lik...: (double nu, double 2 / nu), one
+// nu for all draws, or (const double* nus), [2][S_pad]: nu_s, then 2 / nu_s
+template <typename... Lik>
+struct TNoise {};
+struct NuPair {
+    double nu, two_over_nu;
+};
+template <>
+struct TNoise<double, double> {
+    double nu, two_over_nu;
+    __device__ __forceinline__ NuPair pair(int, int) const { return NuPair{nu, two_over_nu}; }
+};
+template <>
+struct TNoise<const double*> {
+    const double* nus;
+    // draw s of two rows that lie `stride` doubles apart
+    __device__ __forceinline__ NuPair pair(int s, int stride) const { return NuPair{nus[s], nus[stride + s]}; }
+};
+// student_t_variate (bmc_math.h) of the two uniforms of Philox counter c under key (k0, k1)
+__device__ __forceinline__ double student_t_at(u32x4 c, uint32_t k0, uint32_t k1, NuPair p) {
+    const u32x4 w = philox4x32_10(c, k0, k1);
+    return student_t_variate(u53_open0(w.x, w.y), u53_open0(w.z, w.w), p.nu, p.two_over_nu);
+}
+
 }  // namespace bmc

@@ -321,6 +321,26 @@ hipError_t launch_rank_indicators(const RankShape& r, const double* q, int32_t s
 // nu > 0 selects the Student-t density with nu degrees of freedom (bmc_score_tile.h, TileDrawsT):
 // ll[i][s] = lgamma((nu + 1)/2) - lgamma(nu/2) - 1/2 log(nu pi) - log sigma_s
 //            - (nu + 1)/2 log1p((y_i - a_i . beta_s)^2 / (nu sigma_s^2));  nu = 0 is the Gaussian one.
+// A Student-t likelihood (or noise) with a nu of its own for every draw: n_nu > 0 distinct values and
+// every draw's index into them (a scalar nu beside it stays 0).  Host-only: the kernels take the
+// members as scalars and pointers.  All DEVICE pointers.  The host side of it is stage_nu (bmc_ctx.h).
+enum NuTable { NU_SCORE = 0, NU_PPC = 1, NU_SENS = 2 };
+struct NuPerDraw {
+    int32_t n_nu = 0;
+    // [rows][n_nu], a row per quantity of the distinct values (nu_table below): NU_SCORE [cnu, nu]
+    // (cnu = student_t_cnu), NU_PPC [nu, 2 / nu], NU_SENS [cnu, nu, log prior of nu]
+    const double* tab = nullptr;
+    // [S] int32 into the values, clamped into range in the kernel (nu_index_clamped, bmc_dev.h).
+    // NU_SENS only: NULL is entry 0 for every draw (a fixed nu is a table of one value)
+    const int32_t* index = nullptr;
+    int32_t* flag = nullptr;   // one int32 word the caller has zeroed; 1: an index was out of range
+    // what every launcher asks: unset, or 1 .. max_values values with their table and flag word, an
+    // index (unless NULL is allowed) and no scalar nu beside them
+    bool valid(double nu, int32_t max_values, bool null_index_ok = false) const {
+        return n_nu == 0 || (n_nu > 0 && n_nu <= max_values && nu == 0.0 && tab && flag && (index || null_index_ok));
+    }
+};
+
 struct ScorePlan;
 struct ScoreArgs {
     const double* A;
@@ -330,14 +350,7 @@ struct ScoreArgs {
     int32_t k, col_major;
     double *Ap, *yp, *ch, *part, *out;
     double nu = 0.0;   // host-only: the likelihood (0: Gaussian; else positive and finite)
-    // host-only: n_nu > 0 selects the Student-t density with a nu per draw (TileDrawsTV; nu stays 0).
-    // All three are DEVICE pointers: nu_tab [2][n_nu] = cnu of every distinct value (student_t_cnu),
-    // then the values; nu_index [S] int32 into them (clamped into range in the kernel); nu_flag one
-    // int32 word the caller has zeroed, set to 1 when an index was out of range.
-    int32_t n_nu = 0;
-    const double* nu_tab = nullptr;
-    const int32_t* nu_index = nullptr;
-    int32_t* nu_flag = nullptr;
+    NuPerDraw per_draw;   // host-only: set, the Student-t density with a nu per draw (TileDrawsTV; NU_SCORE)
 };
 // lgamma((nu + 1)/2) - lgamma(nu/2) - 1/2 log(nu pi), the constant of the t_nu density, in long
 // double: the difference of the two lgamma loses digits as nu grows
@@ -345,6 +358,17 @@ inline double student_t_cnu(double nu_) {
     const long double nu = (long double)nu_;
     return (double)(lgammal(0.5L * (nu + 1.0L)) - lgammal(0.5L * nu) -
                     0.5L * logl(nu * 3.14159265358979323846264338327950288L));
+}
+// The table of a NuPerDraw of `shape` for V values: tab [nu_table_rows(shape)][V].  2 / nu is rounded
+// here, once per value; log_prior is read for NU_SENS alone (NULL: zeros)
+inline int nu_table_rows(NuTable shape) { return shape == NU_SENS ? 3 : 2; }
+inline void nu_table(NuTable shape, const double* values, const double* log_prior, size_t V, double* tab) {
+    for (size_t v = 0; v < V; ++v) {
+        const double nu = values[v];
+        tab[v] = shape == NU_PPC ? nu : student_t_cnu(nu);
+        tab[V + v] = shape == NU_PPC ? 2.0 / nu : nu;
+        if (shape == NU_SENS) tab[2 * V + v] = log_prior ? log_prior[v] : 0.0;
+    }
 }
 // The staging of every scorer (kernels_waic.hip): A (n x k, either layout, any lda) -> Ap
 // [n_pad][k_pad] in whole 64-point tiles and 16-column slabs, y -> yo [n_pad], zero in the padding.
@@ -398,18 +422,13 @@ struct PpcArgs {
     uint64_t seed;
     double center;
     double *Ap, *yo, *Tp, *sg, *t_rep, *t_obs2;
-    // The noise: nu = 0 and n_nu = 0, the standard normals above.  nu > 0 (finite): z is Student-t
-    // with nu degrees of freedom, student_t_variate (bmc_math.h) of the two uniforms of counter
-    // (s lo, s hi, STREAM_PPC_T, i).  n_nu > 0 (at most PPC_MAX_NU_VALUES; nu stays 0): a nu per
-    // draw, as ScoreArgs: all DEVICE pointers, nu_tab [2][n_nu] the distinct values and then
-    // 2 / value, nu_index [S] int32 into them (clamped into range in the kernel), nu_flag one int32
-    // word the caller has zeroed, set to 1 when an index was out of range; nus the work buffer of
-    // ppc_nu_bytes(plan) bytes.  The sums, the moments and the NaN rules do not depend on the noise.
+    // The noise: nu = 0 and per_draw unset, the standard normals above.  nu > 0 (finite): z is
+    // Student-t with nu degrees of freedom, student_t_variate (bmc_math.h) of the two uniforms of
+    // counter (s lo, s hi, STREAM_PPC_T, i).  per_draw set (NuPerDraw, NU_PPC, at most
+    // PPC_MAX_NU_VALUES values): a nu per draw, and nus the work buffer of ppc_nu_bytes(plan) bytes.
+    // The sums, the moments and the NaN rules do not depend on the noise.
     double nu = 0.0;
-    int32_t n_nu = 0;
-    const double* nu_tab = nullptr;
-    const int32_t* nu_index = nullptr;
-    int32_t* nu_flag = nullptr;
+    NuPerDraw per_draw;
     double* nus = nullptr;
 };
 hipError_t launch_ppc(const PpcArgs& a, const PpcPlan& p, hipStream_t s);
@@ -429,18 +448,12 @@ struct SensLogdensArgs {
     uint32_t components;
     double nu0, sigma20;
     double *Tp, *rss, *lp, *comps, *omega;
-    // host-only: n_nu > 0 selects the Student-t likelihood (the Gaussian kernels are not launched):
+    // host-only: per_draw set (NuPerDraw, NU_SENS, at most SENS_MAX_NU_VALUES values; its index may
+    // be NULL) selects the Student-t likelihood (the Gaussian kernels are not launched):
     //   lp[2][s] = n (C(nu_s) - log sigma_s) - (nu_s + 1)/2 sum_i log1p((y_i - a_i . beta_s)^2 / (nu_s sigma_s^2))
     //   lp[3][s] = the log prior of nu_s (a fourth row), comps of the bits (lp0 + lp1 + lp3, lp2, lp0, lp1, lp3)
-    // with nu_s = the nu_index[s]-th value of the table (nu_index NULL: the first value for every
-    // draw, a fixed nu).  All DEVICE pointers: nu_tab [3][n_nu] = student_t_cnu of every value, the
-    // values, their log prior (zeros when there is none); nu_index [S] int32 (clamped into range in
-    // the kernel); nu_flag one int32 word the caller has zeroed, set to 1 when an index was out of
-    // range; tc [SENS_T_STAGED][S] work: g, hn, c, nu and lp_nu per draw (tc + 3 S is the nu column).
-    int32_t n_nu = 0;
-    const double* nu_tab = nullptr;
-    const int32_t* nu_index = nullptr;
-    int32_t* nu_flag = nullptr;
+    // tc [SENS_T_STAGED][S] work: g, hn, c, nu and lp_nu per draw (tc + 3 S is the nu column).
+    NuPerDraw per_draw;
     double* tc = nullptr;
 };
 constexpr int SENS_T_STAGED = 5;

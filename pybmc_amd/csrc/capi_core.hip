@@ -140,18 +140,20 @@ int copy_to_host(bmc_ctx* c, void* dst, const void* src_dev, size_t row_bytes, s
     return BMC_OK;
 }
 
-Panels panels_of(const bmc_ctx* c, const void* X) {
+Panels make_panels(int64_t n, int32_t k, int32_t f32, const void* X, const void* y) {
     Panels P;
     P.X = X;
-    P.y = c->Yp.p;
-    P.n = c->n;
-    P.k = c->k;
-    P.vec = c->vec;
-    P.npanels = c->npanels;
-    P.f32 = c->f32;
+    P.y = y;
+    P.n = n;
+    P.k = k;
+    P.vec = choose_vec(n, k, f32);
+    P.npanels = (int32_t)((n + 64 * P.vec - 1) / (64 * P.vec));
+    P.f32 = f32;
     P.stream_keep = 1 << 30;
     return P;
 }
+
+Panels panels_of(const bmc_ctx* c, const void* X) { return make_panels(c->n, c->k, c->f32, X, c->Yp.p); }
 
 int ensure_rss(bmc_ctx* c, const Panels& P, size_t n_out) {
     if (int rc = ensure_all(c, {{c->rssPartial, (size_t)rss_groups(P) * 8 * sizeof(double)},
@@ -163,19 +165,19 @@ int ensure_rss(bmc_ctx* c, const Panels& P, size_t n_out) {
     return BMC_OK;
 }
 
-int rss_on_raw(bmc_ctx* c, const double* coef_host, int32_t nb, double* out_host) {
-    const Panels P = panels_of(c, c->Xraw.p);
+// rss of nb host coefficient vectors on panels P -> out_host
+static int rss_on_panels(bmc_ctx* c, const Panels& P, const double* coef_host, int32_t nb, double* out_host) {
     // all coefficient vectors up in one copy, one launch per 8 of them back to back on the
     // stream (the kernel re-zeroes its ticket), all results down in one copy, one sync
     const int32_t nb8 = (nb + 7) / 8 * 8;
     int rc;
-    if ((rc = ensure_rss(c, P, nb8)) || (rc = ensure(c, c->coef, (size_t)nb8 * c->k * sizeof(double))))
+    if ((rc = ensure_rss(c, P, nb8)) || (rc = ensure(c, c->coef, (size_t)nb8 * P.k * sizeof(double))))
         return rc;
-    HIPCHK(c, hipMemcpyAsync(c->coef.p, coef_host, (size_t)nb * c->k * sizeof(double),
+    HIPCHK(c, hipMemcpyAsync(c->coef.p, coef_host, (size_t)nb * P.k * sizeof(double),
                              hipMemcpyHostToDevice, c->stream));
     for (int32_t b0 = 0; b0 < nb; b0 += 8) {
         const int32_t m = nb - b0 < 8 ? nb - b0 : 8;
-        HIPCHK(c, launch_residual_rss(P, (const double*)c->coef.p + (size_t)b0 * c->k, m,
+        HIPCHK(c, launch_residual_rss(P, (const double*)c->coef.p + (size_t)b0 * P.k, m,
                                       (double*)c->rssPartial.p, (unsigned*)c->ticket.p,
                                       (double*)c->rssOut.p + b0, c->stream));
     }
@@ -183,6 +185,72 @@ int rss_on_raw(bmc_ctx* c, const double* coef_host, int32_t nb, double* out_host
                              c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return BMC_OK;
+}
+
+int rss_on_raw(bmc_ctx* c, const double* coef_host, int32_t nb, double* out_host) {
+    return rss_on_panels(c, panels_of(c, c->Xraw.p), coef_host, nb, out_host);
+}
+
+int gram_to_host(bmc_ctx* c, const Panels& P, std::vector<double>& gram) {
+    const size_t gsz = (size_t)(P.k + 1) * (P.k + 1);
+    if (int rc = ensure_all(c, {{c->gramScratch, gram_scratch_bytes(P)}, {c->gramOut, gsz * 8}}))
+        return rc;
+    HIPCHK(c, launch_gram(P, c->gramScratch.p, (double*)c->gramOut.p, c->stream));
+    gram.assign(gsz, 0.0);
+    HIPCHK(c, hipMemcpyAsync(gram.data(), c->gramOut.p, gsz * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return BMC_OK;
+}
+
+int ols_start(bmc_ctx* c, const Panels& P, const std::vector<double>& gram, OlsStart& o) {
+    const int k = P.k, ka = k + 1;
+    o.A.resize((size_t)k * k);   // OLS start value            (inference_utils.py:26-37)
+    o.xty.resize(k);
+    for (int i = 0; i < k; ++i) {
+        for (int j = 0; j < k; ++j) o.A[(size_t)i * k + j] = gram[(size_t)i * ka + j];
+        o.xty[i] = gram[(size_t)i * ka + k];
+    }
+    o.singular = !bmc_la::solve(o.A, o.xty, k, o.bols);
+    if (o.singular) return BMC_OK;
+    if (int rc = rss_on_panels(c, P, o.bols.data(), 1, &o.rss)) return rc;
+    o.sigma2_init = sigma2_floor(o.rss / (double)P.n);
+    return BMC_OK;
+}
+
+int stage_nu(bmc_ctx* c, DevBuf& b, NuTable shape, const double* values, int32_t n_values, int64_t n_draws,
+             const void* index, bool index_on_host, NuPerDraw& v) {
+    const size_t V = (size_t)n_values, S = (size_t)n_draws, tbytes = nu_table_rows(shape) * V * 8;
+    std::vector<double> tab(tbytes / 8);
+    nu_table(shape, values, nullptr, V, tab.data());
+    if (int rc = ensure(c, b, tbytes + S * 4 + 4)) return rc;
+    char* base = (char*)b.p;
+    HIPCHK(c, hipMemcpyAsync(base, tab.data(), tbytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // tab is a local
+    HIPCHK(c, hipMemsetAsync(base + tbytes + S * 4, 0, 4, c->stream));
+    if (index_on_host) {
+        HIPCHK(c, hipMemcpyAsync(base + tbytes, index, S * 4, hipMemcpyHostToDevice, c->stream));
+        index = base + tbytes;
+    }
+    v.n_nu = n_values;
+    v.tab = (const double*)base;
+    v.index = (const int32_t*)index;
+    v.flag = (int32_t*)(base + tbytes + S * 4);
+    return BMC_OK;
+}
+
+int check_nu_index(bmc_ctx* c, const void* index, int64_t S, int32_t V) {
+    const int32_t* idx = (const int32_t*)index;
+    for (int64_t s = 0; s < S; ++s)
+        if (idx[s] < 0 || idx[s] >= V) return fail(c, BMC_EINVAL, "nu_index must index nu_values");
+    return BMC_OK;
+}
+
+int NuFlagRead::fetch(bmc_ctx* c, const NuPerDraw& v) {
+    if (v.n_nu > 0) HIPCHK(c, hipMemcpyAsync(&word, v.flag, 4, hipMemcpyDeviceToHost, c->stream));
+    return BMC_OK;
+}
+int NuFlagRead::result(bmc_ctx* c) const {
+    return word ? fail(c, BMC_EINVAL, "nu_index must index nu_values (the results are not valid)") : BMC_OK;
 }
 
 Shape shape_of(const bmc_ctx* c) { return Shape{c->n, c->k, c->f32, c->vec, c->npanels}; }
@@ -205,30 +273,27 @@ namespace {
 
 // Gram of the panelised problem -> host copy; marks the problem as set.
 int finish_problem(bmc_ctx* c) {
-    const int32_t k = c->k;
-    const Panels P = panels_of(c, c->Xraw.p);
-    const size_t gsz = (size_t)(k + 1) * (k + 1);
-    if (int rc = ensure_all(c, {{c->gramScratch, gram_scratch_bytes(P)}, {c->gramOut, gsz * 8}}))
-        return rc;
-    HIPCHK(c, launch_gram(P, c->gramScratch.p, (double*)c->gramOut.p, c->stream));
-    c->gram.assign(gsz, 0.0);
-    HIPCHK(c, hipMemcpyAsync(c->gram.data(), c->gramOut.p, gsz * 8, hipMemcpyDeviceToHost,
-                             c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (int rc = gram_to_host(c, panels_of(c, c->Xraw.p), c->gram)) return rc;
     c->have_problem = true;
     return BMC_OK;
+}
+
+// the context's shape fields of an n x k problem; its panels, their storage still to come
+Panels set_shape(bmc_ctx* c, int64_t n, int32_t k, int32_t f32) {
+    const Panels P = make_panels(n, k, f32, nullptr, nullptr);
+    c->n = n;
+    c->k = k;
+    c->f32 = f32;
+    c->vec = P.vec;
+    c->npanels = P.npanels;
+    return P;
 }
 
 int set_problem_common(bmc_ctx* c, const void* dX, const void* dy, int64_t n, int32_t k,
                        int64_t ldx, int layout, int dtype) {
     c->have_problem = c->have_prior = false;
-    c->n = n;
-    c->k = k;
-    c->f32 = dtype == BMC_F32;
-    c->vec = choose_vec(n, k, c->f32);
-    const int RP = 64 * c->vec;
-    c->npanels = (int32_t)((n + RP - 1) / RP);
-    const size_t es = c->f32 ? 4 : 8;
+    const Panels P = set_shape(c, n, k, dtype == BMC_F32);
+    const size_t RP = 64 * P.vec, es = c->f32 ? 4 : 8;
     if (int rc = ensure_all(c, {{c->Xraw, (size_t)c->npanels * k * RP * es},
                                 {c->Xrot, (size_t)c->npanels * k * RP * es},
                                 {c->Yp, (size_t)c->npanels * RP * es}}))
@@ -382,31 +447,21 @@ int bmc_set_prior(bmc_ctx* c, const double* b0, const double* C0, double nu0, do
     if (!b0 || !C0) return fail(c, BMC_EINVAL, "b0 and C0 must not be NULL");
     HIPCHK(c, hipSetDevice(c->device));
     c->have_prior = false;
-    const int k = c->k, ka = k + 1;
+    const int k = c->k;
     // P = inv(C0) and the prior's part of the basis        (inference_utils.py:22; bmc_basis.h)
     PriorBasis pb;
     const BasisStatus st = prior_basis(k, C0, k, b0, pb);
     if (st == BASIS_C0_SINGULAR) return fail(c, BMC_ESINGULAR, "Singular matrix (b_mean_cov)");
-    // OLS start value                                      (inference_utils.py:26-37)
-    bmc_la::Mat A((size_t)k * k);
-    std::vector<double> xty(k);
-    for (int i = 0; i < k; ++i) {
-        for (int j = 0; j < k; ++j) A[(size_t)i * k + j] = c->gram[(size_t)i * ka + j];
-        xty[i] = c->gram[(size_t)i * ka + k];
-    }
-    std::vector<double> bols;
-    if (!bmc_la::solve(A, xty, k, bols)) return fail(c, BMC_ESINGULAR, "Singular matrix (X'X)");
-    double rss0 = 0.0;
-    int rc = rss_on_raw(c, bols.data(), 1, &rss0);
+    OlsStart ols;
+    int rc = ols_start(c, panels_of(c, c->Xraw.p), c->gram, ols);
     if (rc) return rc;
-    double s2 = rss0 / (double)c->n;
-    if (!(s2 >= 1e-6)) s2 = s2 != s2 ? s2 : 1e-6;  // max(s2, 1e-6); NaN propagates
-    c->sigma2_init = s2;
+    if (ols.singular) return fail(c, BMC_ESINGULAR, "Singular matrix (X'X)");
+    c->sigma2_init = ols.sigma2_init;
     if (st == BASIS_NOT_PD)
         return fail(c, BMC_EINVAL, "prior precision inv(b_mean_cov) + 1e-6 I is not positive definite");
     // the basis W, lam, c1, c2 and, for rss_mode 1 (k <= 64), G = W'AW, u0 and g0
     ChainBasis cb;
-    chain_basis(k, A, xty, pb, k <= 64, cb);
+    chain_basis(k, ols.A, ols.xty, pb, k <= 64, cb);
     c->lam = std::move(cb.lam);
     c->W = std::move(cb.W);
     c->c1 = std::move(cb.c1);
@@ -451,9 +506,9 @@ int bmc_orthogonalize(bmc_ctx* c, const double* F, int64_t n, int32_t km, int64_
     HIPCHK(c, hipSetDevice(c->device));
     c->have_problem = c->have_prior = false;
     // panels of the centred matrix use the row-per-lane choice of the FINAL (n x k) problem
-    const int vec = choose_vec(n, k, 0);
-    const int RP = 64 * vec;
-    const int32_t npanels = (int32_t)((n + RP - 1) / RP);
+    Panels P = make_panels(n, k, 0, nullptr, nullptr);
+    const int vec = P.vec, RP = 64 * vec;
+    const int32_t npanels = P.npanels;
     int rc;
     const size_t fbytes = (size_t)((size_t)ldf * (n - 1) + km) * 8;
     const size_t toff = (fbytes + 255) & ~(size_t)255;
@@ -469,14 +524,9 @@ int bmc_orthogonalize(bmc_ctx* c, const double* F, int64_t n, int32_t km, int64_
                             (const double*)((char*)c->stage.p + toff), vec, npanels,
                             (double*)c->oFc.p, (double*)c->Yp.p, (double*)c->oMu.p, c->stream));
     // Gram of the centred matrix: Fc'Fc = V S^2 V'  (the SVD of bmc.py:119 through its Gram)
-    Panels P;
-    P.X = c->oFc.p; P.y = c->Yp.p; P.n = n; P.k = km; P.vec = vec; P.npanels = npanels; P.f32 = 0;
-    const size_t gsz = (size_t)(km + 1) * (km + 1);
-    if ((rc = ensure_all(c, {{c->gramScratch, gram_scratch_bytes(P)}, {c->gramOut, gsz * 8}}))) return rc;
-    HIPCHK(c, launch_gram(P, c->gramScratch.p, (double*)c->gramOut.p, c->stream));
-    std::vector<double> ga(gsz);
-    HIPCHK(c, hipMemcpyAsync(ga.data(), c->gramOut.p, gsz * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    P.X = c->oFc.p, P.y = c->Yp.p, P.k = km;
+    std::vector<double> ga;
+    if ((rc = gram_to_host(c, P, ga))) return rc;
     bmc_la::Mat Gm((size_t)km * km), Q;
     for (int i = 0; i < km; ++i)
         for (int j = 0; j < km; ++j) Gm[(size_t)i * km + j] = ga[(size_t)i * (km + 1) + j];
@@ -508,11 +558,7 @@ int bmc_orthogonalize(bmc_ctx* c, const double* F, int64_t n, int32_t km, int64_
         }
     }
     // the sampler's problem: X = U_hat (n x k panels), y = centred truth
-    c->n = n;
-    c->k = k;
-    c->f32 = 0;
-    c->vec = vec;
-    c->npanels = npanels;
+    set_shape(c, n, k, 0);
     if ((rc = ensure_all(c, {{c->Xraw, (size_t)npanels * k * RP * 8},
                              {c->Xrot, (size_t)npanels * k * RP * 8},
                              {c->oW, W.size() * 8}})))

@@ -198,10 +198,8 @@ int cv_rss(bmc_ctx* c, CvFront& fr, const std::vector<double>& beta, int nb, int
             at_ols += r0;
             at_u0 += r1;
         }
-        double s2 = (double)at_ols / (double)(n - count[s.fold]);
-        if (!(s2 >= 1e-6)) s2 = s2 != s2 ? s2 : 1e-6;   // max(s2, 1e-6); NaN propagates
         s.scal[0] = (double)at_u0;
-        s.scal[1] = s2;
+        s.scal[1] = sigma2_floor((double)at_ols / (double)(n - count[s.fold]));
         s.scal[2] = nu0_sigma20;
     }
     return BMC_OK;
@@ -209,17 +207,9 @@ int cv_rss(bmc_ctx* c, CvFront& fr, const std::vector<double>& beta, int nb, int
 
 // held-out scores of fold f (nf rows): the score kernels on the fold's row segment against its S
 // pooled draws theta [S][kj + 1], the log predictive densities into the fold's segment of elpd_row.
-// The likelihood as ScoreArgs names it: Gaussian, Student-t with one nu, or (n_nu > 0) a nu per draw
-// from the device table nu_tab through nu_index, with the zeroed flag word nu_flag.
-struct FoldLikelihood {
-    double nu = 0.0;
-    int32_t n_nu = 0;
-    const double* nu_tab = nullptr;
-    const int32_t* nu_index = nullptr;
-    int32_t* nu_flag = nullptr;
-};
+// The likelihood as ScoreArgs names it: Gaussian, Student-t with one nu, or a nu per draw.
 int score_fold(bmc_ctx* c, const CvFront& fr, int f, int64_t nf, int64_t S, int kj, const double* theta,
-               double* elpd_row, const FoldLikelihood& lik = FoldLikelihood()) {
+               double* elpd_row, double nu = 0.0, const NuPerDraw& per_draw = NuPerDraw()) {
     const ScorePlan plan = plan_score(nf, S, kj, c->n_cu);
     const ScoreBuffers sb = score_buffers(plan, S);
     if (int rc = ensure_all(c, {{c->scAp, sb.Ap}, {c->scYp, sb.yp}, {c->scCh, sb.ch}, {c->scPart, sb.part},
@@ -232,7 +222,7 @@ int score_fold(bmc_ctx* c, const CvFront& fr, int f, int64_t nf, int64_t S, int 
     sa.n = nf; sa.lda = fr.ldz; sa.S = S; sa.ldt = (int64_t)kj + 1; sa.k = kj; sa.col_major = 0;
     sa.Ap = (double*)c->scAp.p; sa.yp = (double*)c->scYp.p; sa.ch = (double*)c->scCh.p;
     sa.part = (double*)c->scPart.p; sa.out = (double*)c->scOut.p;
-    sa.nu = lik.nu; sa.n_nu = lik.n_nu; sa.nu_tab = lik.nu_tab; sa.nu_index = lik.nu_index; sa.nu_flag = lik.nu_flag;
+    sa.nu = nu; sa.per_draw = per_draw;
     HIPCHK(c, launch_score(sa, plan, c->stream));
     HIPCHK(c, hipMemcpyAsync(elpd_row + fr.seg.offset[f], sa.out, (size_t)nf * 8, hipMemcpyDeviceToDevice,
                              c->stream));
@@ -279,21 +269,15 @@ struct CvtSetup {
 };
 
 // The set-up of one fold's training rows tr [nt] (caller's row indices, ascending), the steps of
-// bmc_set_problem, bmc_set_prior and bmc_robust_run on those rows alone: gather, panelise, the Gram
-// of the panels, the host solve, rss at the least-squares point on the panels, sigma2_init =
-// max(rss / nt, 1e-6), and the pack into Z / yv.  *singular: X'X of the rows has no solve.
+// bmc_set_problem, bmc_set_prior and bmc_robust_run on those rows alone: gather, panelise, the
+// least-squares start of the panels (gram_to_host, ols_start: the routines of the resident problem),
+// and the pack into Z / yv.  *singular: X'X of the rows has no solve.
 int cvt_fold_setup(bmc_ctx* c, const CvFront& fr, int64_t lda, int layout, int k, const std::vector<int64_t>& tr,
                    CvtSetup& st, double* Z, double* yv, double* sigma2_init, bool* singular) {
     const int64_t nt = (int64_t)tr.size();
-    const int ldg = cv_ldz(k), ka = k + 1;
-    Panels P;
-    P.n = nt;
-    P.k = k;
-    P.f32 = 0;
-    P.vec = choose_vec(nt, k, 0);
+    const int ldg = cv_ldz(k);
+    Panels P = make_panels(nt, k, 0, nullptr, nullptr);
     const int RP = 64 * P.vec;
-    P.npanels = (int32_t)((nt + RP - 1) / RP);
-    P.stream_keep = 1 << 30;
     int rc;
     if ((rc = upload(c, st.dTr, tr.data(), (size_t)nt * 8)) ||
         (rc = ensure_all(c, {{st.dG, (size_t)nt * ldg * 8}, {st.dGy, (size_t)nt * 8},
@@ -305,31 +289,12 @@ int cvt_fold_setup(bmc_ctx* c, const CvFront& fr, int64_t lda, int layout, int k
     HIPCHK(c, launch_cv_gather((const double*)fr.dA.p, (const double*)fr.dY.p, lda, layout == BMC_COL_MAJOR, k,
                                (const int64_t*)st.dTr.p, nt, (double*)st.dG.p, (double*)st.dGy.p, c->stream));
     HIPCHK(c, launch_panelize(st.dG.p, st.dGy.p, nt, k, ldg, 0, 0, P.vec, st.dXp.p, st.dYp.p, P.npanels, c->stream));
-    const size_t gsz = (size_t)ka * ka;
-    if ((rc = ensure_all(c, {{c->gramScratch, gram_scratch_bytes(P)}, {c->gramOut, gsz * 8}}))) return rc;
-    HIPCHK(c, launch_gram(P, c->gramScratch.p, (double*)c->gramOut.p, c->stream));
-    std::vector<double> gram(gsz);
-    HIPCHK(c, hipMemcpyAsync(gram.data(), c->gramOut.p, gsz * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    bmc_la::Mat At((size_t)k * k);
-    std::vector<double> xty(k), bols;
-    for (int i = 0; i < k; ++i) {
-        for (int j = 0; j < k; ++j) At[(size_t)i * k + j] = gram[(size_t)i * ka + j];
-        xty[i] = gram[(size_t)i * ka + k];
-    }
-    *singular = !bmc_la::solve(At, xty, k, bols);
-    if (*singular) return BMC_OK;
-    if ((rc = ensure_rss(c, P, 8)) || (rc = ensure(c, c->coef, (size_t)8 * k * 8))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->coef.p, bols.data(), (size_t)k * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, launch_residual_rss(P, (const double*)c->coef.p, 1, (double*)c->rssPartial.p, (unsigned*)c->ticket.p,
-                                  (double*)c->rssOut.p, c->stream));
-    double rss0 = 0.0;
-    HIPCHK(c, hipMemcpyAsync(&rss0, c->rssOut.p, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, launch_robust_pack(P, Z, yv, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    double s2 = rss0 / (double)nt;
-    if (!(s2 >= 1e-6)) s2 = s2 != s2 ? s2 : 1e-6;   // max(s2, 1e-6); NaN propagates
-    *sigma2_init = s2;
+    std::vector<double> gram;
+    OlsStart ols;
+    if ((rc = gram_to_host(c, P, gram)) || (rc = ols_start(c, P, gram, ols))) return rc;
+    *singular = ols.singular;
+    *sigma2_init = ols.sigma2_init;
+    if (!ols.singular) HIPCHK(c, launch_robust_pack(P, Z, yv, c->stream));
     return BMC_OK;
 }
 
@@ -374,18 +339,9 @@ int kfold_cv_t(bmc_ctx* c, const std::string& name, const double* A, int64_t n, 
                              {dMean, (size_t)seg.n_pad * 8}})))
         return rc;
     HIPCHK(c, hipMemsetAsync(dElpd.p, 0, (size_t)seg.n_pad * 8, c->stream));
-    // the score's table of a nu per draw: student_t_cnu of every grid value, the values, the flag word
-    if (ns) {
-        std::vector<double> tab(2 * (size_t)G);
-        for (int g = 0; g < G; ++g) {
-            tab[g] = student_t_cnu(ns->grid[g]);
-            tab[(size_t)G + g] = ns->grid[g];
-        }
-        if ((rc = ensure(c, dScNu, (size_t)G * 16 + 4))) return rc;
-        HIPCHK(c, hipMemcpyAsync(dScNu.p, tab.data(), (size_t)G * 16, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemsetAsync((char*)dScNu.p + (size_t)G * 16, 0, 4, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));   // tab is a local
-    }
+    // the score's table of a nu per draw over the grid; every fold's index is set where it is scored
+    NuPerDraw score_nu;
+    if (ns && (rc = stage_nu(c, dScNu, NU_SCORE, ns->grid, G, 0, nullptr, false, score_nu))) return rc;
     if (weight_out) {
         const double nan = std::nan("");
         std::fill(weight_out, weight_out + (size_t)F * C * (size_t)n, nan);
@@ -496,11 +452,10 @@ int kfold_cv_t(bmc_ctx* c, const std::string& name, const double* A, int64_t n, 
         std::vector<int32_t> st(nch, 0);
         HIPCHK(c, hipMemcpyAsync(st.data(), c->status.p, nch * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));   // also: desc, fold_of, row0 and nutab are locals
-        for (size_t i = 0; i < nch; ++i)
-            if (st[i] != 0)
-                return fail(c, BMC_ESINGULAR, name + "fold " + std::to_string(b.f0 + (int)(i / C)) + ", chain " +
-                                                  std::to_string(i % C) + ": a Cholesky pivot of X'LX / sigma2 + "
-                                                  "inv(C0) + 1e-6 I was not positive and finite");
+        if ((rc = robust_status_check(c, st, [&](size_t i, const std::string& what) {
+                return name + "fold " + std::to_string(b.f0 + (int)(i / C)) + ", chain " + std::to_string(i % C) + ": " + what;
+            })))
+            return rc;
         // ---- every thin-th draw after burn, the fold means, the held-out scores ----
         HIPCHK(c, launch_robust_thin((const double*)c->uout.p, (int64_t)nch, Ta, thin, kept, (int32_t)K1,
                                      (double*)c->samples.p, c->stream));
@@ -510,17 +465,9 @@ int kfold_cv_t(bmc_ctx* c, const std::string& name, const double* A, int64_t n, 
         HIPCHK(c, launch_cv_colmean((const double*)c->samples.p, k, S, nf, b.f0, (double*)dBbar.p, c->stream));
         for (int q = 0; q < nf; ++q) {
             const int f = b.f0 + q;
-            FoldLikelihood lik;
-            if (ns) {
-                lik.n_nu = G;
-                lik.nu_tab = (const double*)dScNu.p;
-                lik.nu_index = (const int32_t*)dIdxK.p + (size_t)q * S;
-                lik.nu_flag = (int32_t*)((char*)dScNu.p + (size_t)G * 16);
-            } else {
-                lik.nu = nu;
-            }
+            if (ns) score_nu.index = (const int32_t*)dIdxK.p + (size_t)q * S;
             if ((rc = score_fold(c, fr, f, count[f], S, k, (const double*)c->samples.p + (size_t)q * S * K1,
-                                 (double*)dElpd.p, lik)))
+                                 (double*)dElpd.p, ns ? 0.0 : nu, score_nu)))
                 return rc;
         }
         if (draws_out)

@@ -191,12 +191,9 @@ int robust_common(bmc_ctx* c, double nu, const NuSpec* ns, int32_t n_chains, int
         stats->bytes_per_pass = (N * K + N) * 8;
         stats->passes = 2 * (burn + iters) * (int64_t)n_chains;
     }
-    for (size_t i = 0; i < C; ++i)
-        if (st[i] != 0)
-            return fail(c, BMC_ESINGULAR,
-                        "bmc_robust_run: a Cholesky pivot of X'LX / sigma2 + inv(C0) + 1e-6 I was not "
-                        "positive and finite (chain " + std::to_string(i) + ")");
-    return BMC_OK;
+    return robust_status_check(c, st, [](size_t i, const std::string& what) {
+        return "bmc_robust_run: " + what + " (chain " + std::to_string(i) + ")";
+    });
 }
 
 }  // namespace

@@ -18,6 +18,7 @@ struct ScoreIn {
     int32_t n_nu = 0;
     const double* nu_values = nullptr;
     const void* nu_index = nullptr;
+    NuPerDraw staged;   // what score_nu has made of the three
 };
 
 int check_score_args(bmc_ctx* c, const void* A, int64_t n, int32_t k, int64_t lda, int layout,
@@ -54,12 +55,7 @@ int score_args(bmc_ctx* c, const ScorePlan& plan, const ScoreIn& in, ScoreArgs& 
     a.k = in.k;
     a.col_major = in.layout == BMC_COL_MAJOR;
     a.nu = in.nu;
-    if (in.n_nu > 0) {   // score_nu has laid scNu out: [2][n_nu] f64, [S] i32 staged index, the flag
-        a.n_nu = in.n_nu;
-        a.nu_tab = (const double*)c->scNu.p;
-        a.nu_index = (const int32_t*)in.nu_index;
-        a.nu_flag = (int32_t*)((char*)c->scNu.p + (size_t)in.n_nu * 16 + (size_t)in.S * 4);
-    }
+    a.per_draw = in.staged;
     a.Ap = (double*)c->scAp.p;
     a.yp = (double*)c->scYp.p;
     a.ch = (double*)c->scCh.p;
@@ -81,36 +77,18 @@ int score_stage(bmc_ctx* c, ScoreIn& in) {
     return BMC_OK;
 }
 
-// The _tv calls: the table of distinct nu with its constants and the zeroed flag word go to scNu; a
-// host index is checked here and staged (`in` then names the staged copy).  BMC_EINVAL for a table
-// entry that is not positive and finite, n_values < 1, a NULL pointer or a host index out of range.
-// for_ppc: the table of the predictive check instead, the values first and then 2 / value.
-int score_nu(bmc_ctx* c, ScoreIn& in, bool on_host, bool for_ppc = false) {
+// The _tv calls: the table of distinct nu (of `shape`), a host index and the zeroed flag word go to
+// scNu (stage_nu), and in.staged names them.  BMC_EINVAL for a table entry that is not positive and
+// finite, n_values < 1, a NULL pointer or a host index out of range.
+int score_nu(bmc_ctx* c, ScoreIn& in, bool on_host, NuTable shape) {
     if (in.n_nu < 1) return fail(c, BMC_EINVAL, "n_values must be >= 1");
     if (!in.nu_values || !in.nu_index) return fail(c, BMC_EINVAL, "nu_values and nu_index must not be NULL");
-    const size_t V = (size_t)in.n_nu, S = (size_t)in.S;
-    std::vector<double> tab(2 * V);
-    for (size_t v = 0; v < V; ++v) {
-        const double nu = in.nu_values[v];
-        if (!(nu > 0.0 && nu < INFINITY)) return fail(c, BMC_EINVAL, "nu_values must be positive and finite");
-        tab[v] = for_ppc ? nu : student_t_cnu(nu);
-        tab[V + v] = for_ppc ? 2.0 / nu : nu;
-    }
-    if (on_host) {
-        const int32_t* idx = (const int32_t*)in.nu_index;
-        for (size_t s = 0; s < S; ++s)
-            if (idx[s] < 0 || idx[s] >= in.n_nu) return fail(c, BMC_EINVAL, "nu_index must index nu_values");
-    }
-    if (int rc = ensure(c, c->scNu, V * 16 + S * 4 + 4)) return rc;
-    char* base = (char*)c->scNu.p;
-    HIPCHK(c, hipMemcpyAsync(base, tab.data(), V * 16, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));   // tab is a local
-    HIPCHK(c, hipMemsetAsync(base + V * 16 + S * 4, 0, 4, c->stream));
-    if (on_host) {
-        HIPCHK(c, hipMemcpyAsync(base + V * 16, in.nu_index, S * 4, hipMemcpyHostToDevice, c->stream));
-        in.nu_index = base + V * 16;
-    }
-    return BMC_OK;
+    for (int32_t v = 0; v < in.n_nu; ++v)
+        if (!(in.nu_values[v] > 0.0 && in.nu_values[v] < INFINITY))
+            return fail(c, BMC_EINVAL, "nu_values must be positive and finite");
+    if (on_host)
+        if (int rc = check_nu_index(c, in.nu_index, in.S, in.n_nu)) return rc;
+    return stage_nu(c, c->scNu, shape, in.nu_values, in.n_nu, in.S, in.nu_index, on_host, in.staged);
 }
 
 // A family plans and launches on device operands and says where result f lies: src[f], [n] each
@@ -175,13 +153,11 @@ int score_entry(bmc_ctx* c, ScoreIn in, bool on_host, ScoreFamily family,
     HIPCHK(c, hipSetDevice(c->device));
     if (on_host && (rc = score_stage(c, in))) return rc;
     const bool per_draw = in.nu_values || in.nu_index || in.n_nu != 0;
-    if (per_draw && (rc = score_nu(c, in, on_host))) return rc;
+    if (per_draw && (rc = score_nu(c, in, on_host, NU_SCORE))) return rc;
     const double* src[7] = {};
     if ((rc = family(c, in, src))) return rc;
-    int32_t flag = 0;
-    if (per_draw)
-        HIPCHK(c, hipMemcpyAsync(&flag, (char*)c->scNu.p + (size_t)in.n_nu * 16 + (size_t)in.S * 4, 4,
-                                 hipMemcpyDeviceToHost, c->stream));
+    NuFlagRead flag;
+    if ((rc = flag.fetch(c, in.staged))) return rc;
     int f = 0;
     for (double* out : dst) {
         if (out)
@@ -189,8 +165,7 @@ int score_entry(bmc_ctx* c, ScoreIn in, bool on_host, ScoreFamily family,
         ++f;
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (flag) return fail(c, BMC_EINVAL, "nu_index must index nu_values (the results are not valid)");
-    return BMC_OK;
+    return flag.result(c);
 }
 
 // One posterior predictive check: host operands are staged first (offset may be NULL: zeros),
@@ -217,7 +192,7 @@ int ppc_entry(bmc_ctx* c, ScoreIn in, const void* offset, bool on_host, uint64_t
             offset = c->ppcOff.p;
         }
     }
-    if (per_draw && (rc = score_nu(c, in, on_host, true))) return rc;
+    if (per_draw && (rc = score_nu(c, in, on_host, NU_PPC))) return rc;
     const PpcBuffers pb = ppc_buffers(plan, in.S);
     if ((rc = ensure(c, c->ppcWork, pb.total() + (per_draw ? ppc_nu_bytes(plan) : 0)))) return rc;
     char* w = (char*)c->ppcWork.p;
@@ -241,17 +216,11 @@ int ppc_entry(bmc_ctx* c, ScoreIn in, const void* offset, bool on_host, uint64_t
     a.t_rep = (double*)(w += pb.sg);
     a.t_obs2 = a.t_rep + (size_t)in.S * PPC_STATS;
     a.nu = in.nu;
-    int32_t flag = 0;
-    if (per_draw) {   // score_nu has laid scNu out: [2][n_nu] f64, [S] i32 staged index, the flag
-        a.n_nu = in.n_nu;
-        a.nu_tab = (const double*)c->scNu.p;
-        a.nu_index = (const int32_t*)in.nu_index;
-        a.nu_flag = (int32_t*)((char*)c->scNu.p + (size_t)in.n_nu * 16 + (size_t)in.S * 4);
-        a.nus = (double*)(w + pb.out);
-    }
+    a.per_draw = in.staged;
+    if (per_draw) a.nus = (double*)(w + pb.out);
     HIPCHK(c, launch_ppc(a, plan, c->stream));
-    if (per_draw)
-        HIPCHK(c, hipMemcpyAsync(&flag, a.nu_flag, 4, hipMemcpyDeviceToHost, c->stream));
+    NuFlagRead flag;
+    if ((rc = flag.fetch(c, in.staged))) return rc;
     if (t_rep_out)
         HIPCHK(c, hipMemcpyAsync(t_rep_out, a.t_rep, (size_t)in.S * PPC_STATS * 8, hipMemcpyDeviceToHost,
                                  c->stream));
@@ -259,8 +228,7 @@ int ppc_entry(bmc_ctx* c, ScoreIn in, const void* offset, bool on_host, uint64_t
         HIPCHK(c, hipMemcpyAsync(t_obs2_out, a.t_obs2, (size_t)in.S * PPC_OBS * 8, hipMemcpyDeviceToHost,
                                  c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (flag) return fail(c, BMC_EINVAL, "nu_index must index nu_values (the results are not valid)");
-    return BMC_OK;
+    return flag.result(c);
 }
 
 // nu of a _t entry point as ScoreIn carries it: what is not positive (0 would mean Gaussian there)

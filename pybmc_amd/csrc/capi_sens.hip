@@ -136,11 +136,7 @@ int sens_run(bmc_ctx* c, const SensIn& in, const SensOut& out) {
     const size_t n_lp = (size_t)q_pad * k_pad, n_vt = (size_t)k * Mm, V = (size_t)in.n_nu;
     const size_t h_tab = n_lp + q_pad + n_vt + nA;
     std::vector<double> host(h_tab + 3 * V, 0.0);
-    for (size_t v = 0; v < V; ++v) {
-        host[h_tab + v] = student_t_cnu(in.nu_values[v]);
-        host[h_tab + V + v] = in.nu_values[v];
-        host[h_tab + 2 * V + v] = in.nu_log_prior ? in.nu_log_prior[v] : 0.0;
-    }
+    nu_table(NU_SENS, in.nu_values, in.nu_log_prior, V, host.data() + h_tab);
     for (int32_t i = 0; i < k; ++i) {
         long double s = 0.0L;
         for (int32_t j = 0; j <= i; ++j) {
@@ -219,12 +215,12 @@ int sens_run(bmc_ctx* c, const SensIn& in, const SensOut& out) {
     la.lp = dptr(o_lp);
     la.comps = dptr(o_comps);
     la.omega = dptr(o_omega);
-    if (student) {
-        la.n_nu = in.n_nu;
-        la.nu_tab = dptr(o_host) + h_tab;
-        la.nu_index = in.per_draw ? (const int32_t*)in.nu_index : nullptr;
-        la.nu_flag = (int32_t*)dptr(o_flag);
-        HIPCHK(c, hipMemsetAsync(la.nu_flag, 0, 4, c->stream));
+    if (student) {   // the NuPerDraw in this call's own work block
+        la.per_draw.n_nu = in.n_nu;
+        la.per_draw.tab = dptr(o_host) + h_tab;
+        la.per_draw.index = in.per_draw ? (const int32_t*)in.nu_index : nullptr;
+        la.per_draw.flag = (int32_t*)dptr(o_flag);
+        HIPCHK(c, hipMemsetAsync(la.per_draw.flag, 0, 4, c->stream));
         la.tc = dptr(o_tc);
     }
     HIPCHK(c, launch_sens_logdens(la, c->stream));
@@ -244,15 +240,15 @@ int sens_run(bmc_ctx* c, const SensIn& in, const SensOut& out) {
     HIPCHK(c, hipEventRecord(ev.e[3], c->stream));
     std::vector<double> khat(W);
     HIPCHK(c, hipMemcpyAsync(khat.data(), dptr(o_khat), (size_t)W * 8, hipMemcpyDeviceToHost, c->stream));
-    int32_t bad_index = 0;
-    if (student) HIPCHK(c, hipMemcpyAsync(&bad_index, la.nu_flag, 4, hipMemcpyDeviceToHost, c->stream));
+    NuFlagRead flag;
+    if ((rc = flag.fetch(c, la.per_draw))) return rc;
     if (out.logdens)
         HIPCHK(c, hipMemcpyAsync(out.logdens, dptr(o_lp), (size_t)lp_rows * S * 8, hipMemcpyDeviceToHost,
                                  c->stream));
     if (out.weights)
         HIPCHK(c, hipMemcpyAsync(out.weights, dptr(o_Wt), (size_t)S * W * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (bad_index) return fail(c, BMC_EINVAL, "nu_index must index nu_values (the results are not valid)");
+    if ((rc = flag.result(c))) return rc;
     const int span0[3] = {0, 1, 2};
     for (int i = 0; i < 3; ++i) {
         HIPCHK(c, hipEventElapsedTime(&ms, ev.e[i], ev.e[i + 1]));
@@ -320,11 +316,8 @@ int sens_entry(bmc_ctx* c, SensIn in, bool on_host, const SensOut& out) {
                    : sens_check(in.n, in.k, in.S, in.n_models, in.alphas, in.n_alphas, in.components);
     if (!why.empty()) return fail(c, BMC_EINVAL, why);
     if (in.per_draw && !in.nu_index) return fail(c, BMC_EINVAL, "nu_values and nu_index must not be NULL");
-    if (in.per_draw && on_host) {   // a host index is checked before any launch
-        const int32_t* idx = (const int32_t*)in.nu_index;
-        for (int64_t s = 0; s < in.S; ++s)
-            if (idx[s] < 0 || idx[s] >= in.n_nu) return fail(c, BMC_EINVAL, "nu_index must index nu_values");
-    }
+    if (in.per_draw && on_host)   // a host index is checked before any launch
+        if (int rc = check_nu_index(c, in.nu_index, in.S, in.n_nu)) return rc;
     if (in.layout != BMC_ROW_MAJOR && in.layout != BMC_COL_MAJOR)
         return fail(c, BMC_EINVAL, "layout must be BMC_ROW_MAJOR or BMC_COL_MAJOR");
     if (in.lda < (in.layout == BMC_COL_MAJOR ? in.n : (int64_t)in.k))

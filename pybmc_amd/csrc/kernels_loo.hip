@@ -35,7 +35,7 @@
 // The likelihood enters through the draws type alone (bmc_score_tile.h): the passes that compute ll
 // (range, select, the non-PREDICT append) are templates <D, L...> on it, TileDraws for the Gaussian
 // density, TileDrawsT with its scalar for the Student-t one (ScoreArgs::nu > 0) and TileDrawsTV for
-// the Student-t one with a nu per draw (ScoreArgs::n_nu > 0); init, scan and
+// the Student-t one with a nu per draw (ScoreArgs::per_draw); init, scan and
 // fit see values of ll only.  The PREDICT variants and loo_bucket are Gaussian only.
 #include "bmc_dev.h"
 #include "bmc_launch.h"
@@ -721,7 +721,7 @@ hipError_t launch_loo_passes(const LooArgs& a, const LooPlan& p, const LooPredic
     if (!p.ok || !a.work || sa.S - p.tail < 1 || p.cap < 2 * (p.tail + 1) || p.cap > LOO_MAX_CAP ||
         (p.cap & (p.cap - 1)) != 0 || p.tail != loo_tail(sa.S) || sa.n > 0x7fffffffll ||
         p.grid_points != (p.tail > 0 ? psis_grid_points(p.tail) : 0) || p.grid_points > LOO_MAX_GRID ||
-        (pp && (sa.nu != 0.0 || sa.n_nu != 0)))
+        (pp && (sa.nu != 0.0 || sa.per_draw.n_nu != 0)))
         return hipErrorInvalidValue;   // (the fit's grid is one workgroup per point)
     hipError_t e = launch_score(sa, sp, s);   // (checks the shapes and the split plan)
     if (e != hipSuccess) return e;
@@ -746,7 +746,7 @@ hipError_t launch_loo_passes(const LooArgs& a, const LooPlan& p, const LooPredic
     pa.point_tiles = (uint32_t)sp.point_tiles;
 
     // a pass over the matrix under the call's likelihood (launch_score has checked sa.nu)
-    const bool student = sa.nu > 0.0, per_draw = sa.n_nu > 0;
+    const bool student = sa.nu > 0.0, per_draw = sa.per_draw.n_nu > 0;
     const double hn = 0.5 * (sa.nu + 1.0);
     auto pass = [&](auto gauss, auto student_t, auto student_tv, size_t lds, auto... args) {
         if (per_draw) hipLaunchKernelGGL(student_tv, dim3(groups), dim3(256), lds, s, pa, args...);

@@ -138,11 +138,7 @@ __global__ __launch_bounds__(256) void ppc_pad_draws_kernel(const double* __rest
             const PpcNuStage st{nu...};
             double v = 4.0, tv = 0.5;
             if (s < S) {
-                int32_t iv = st.index[s];
-                if (iv < 0 || iv >= st.n_nu) {
-                    *st.flag = 1;
-                    iv = iv < 0 ? 0 : st.n_nu - 1;
-                }
+                const int32_t iv = nu_index_clamped(st.index[s], st.n_nu, st.flag);
                 v = st.tab[iv];
                 tv = st.tab[st.n_nu + iv];
             }
@@ -184,24 +180,13 @@ __device__ __forceinline__ void ppc_fold(PpcRun& st, double dot, double z, doubl
 }
 
 // The noise of the replicated data.  PPC_GAUSS: the standard normals of the header, no further
-// argument.  PPC_T: Student-t with one nu for all draws; Lik = (double nu, double 2 / nu).
-// PPC_TV: a nu per draw; Lik = (const double* nus), [2][S_pad]: nu_s, then 2 / nu_s, which wait in
-// LDS beside sigma_s and c_s.  The t variate of (point i, draw s) is student_t_variate (bmc_math.h)
+// argument.  PPC_T and PPC_TV: Student-t with one nu for all draws or a nu per draw, Lik as TNoise
+// (bmc_dev.h) names it; the pairs of PPC_TV wait in LDS beside sigma_s and c_s.  The t variate of (point i, draw s) is student_t_variate (bmc_math.h)
 // of the two uniforms of counter (s lo, s hi, STREAM_PPC_T, i): the point index itself, one Philox
 // call per element.  Only the cosine half of Bailey's polar pair is taken: the sine half shares
 // its radius, and handing it to point i + 32 as the Gaussian walk does would replicate data whose
 // errors depend on each other in pairs.  z[i][s] depends on (seed, i, s, nu_s) alone.
 enum PpcNoise { PPC_GAUSS = 0, PPC_T = 1, PPC_TV = 2 };
-template <typename... Lik>
-struct PpcLik {};
-template <>
-struct PpcLik<double, double> {
-    double nu, two_over_nu;
-};
-template <>
-struct PpcLik<const double*> {
-    const double* nus;
-};
 
 // grid: one workgroup per draw tile.  The workgroups that run together walk the same point tiles
 // at about the same time, so a tile of the design is fetched into each XCD's L2 once for all.
@@ -233,7 +218,7 @@ __global__ __launch_bounds__(256, NOISE == PPC_GAUSS ? 2 : 1) void ppc_tile_kern
 #pragma unroll
     for (int r = 0; r < 4; ++r)
         st[r] = PpcRun{__builtin_inf(), -__builtin_inf(), 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    const PpcLik<Lik...> lk{lik...};
+    const TNoise<Lik...> lk{lik...};
     if (tid < SC_TM) {
         sc[SCW * tid] = sg[d0 + tid];
         sc[SCW * tid + 1] = sg[2 * S_pad + d0 + tid];
@@ -245,6 +230,11 @@ __global__ __launch_bounds__(256, NOISE == PPC_GAUSS ? 2 : 1) void ppc_tile_kern
     __syncthreads();
     // draw r of the lane: sc_r[4 SCW r], sc_r[4 SCW r + 1], ..
     const double* sc_r = sc + SCW * (16 * wave + kq);
+    // where the walk finds (nu, 2 / nu): the pairs of PPC_TV in LDS, behind (sigma_s, c_s)
+    const auto noise = [&] {
+        if constexpr (NOISE == PPC_TV) return TNoise<const double*>{sc_r + 2};
+        else return lk;
+    }();
 
     score_tile_loop(Tp, Ap, n_pad, (int64_t)k_pad, k, k_pad, d0, 0, point_tiles, As, Bs,
                     [&](int64_t i0, const f64x4(&acc)[4]) {
@@ -293,20 +283,11 @@ __global__ __launch_bounds__(256, NOISE == PPC_GAUSS ? 2 : 1) void ppc_tile_kern
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const double sigma = sc_r[4 * SCW * r], center = sc_r[4 * SCW * r + 1];
-                double nu, two_over_nu;
-                if constexpr (NOISE == PPC_TV) {
-                    nu = sc_r[4 * SCW * r + 2];
-                    two_over_nu = sc_r[4 * SCW * r + 3];
-                } else {
-                    nu = lk.nu;
-                    two_over_nu = lk.two_over_nu;
-                }
+                const NuPair nt = noise.pair(4 * SCW * r, 1);
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
-                    const u32x4 w =
-                        philox4x32_10(u32x4{dlo + 4u * r, dhi, STREAM_PPC_T, pt + 16u * t}, k0, k1);
-                    const double z = student_t_variate(u53_open0(w.x, w.y), u53_open0(w.z, w.w), nu,
-                                                       two_over_nu);
+                    const double z =
+                        student_t_at(u32x4{dlo + 4u * r, dhi, STREAM_PPC_T, pt + 16u * t}, k0, k1, nt);
                     if (full) ppc_fold<true>(st[r], acc[t][r], z, yv[t], ov[t], sigma, center, true);
                     else ppc_fold<false>(st[r], acc[t][r], z, yv[t], ov[t], sigma, center, ok[t]);
                     // one variate at a time, as above
@@ -372,11 +353,11 @@ __global__ __launch_bounds__(256, NOISE == PPC_GAUSS ? 2 : 1) void ppc_tile_kern
 
 hipError_t launch_ppc(const PpcArgs& a, const PpcPlan& p, hipStream_t s) {
     const PpcPlan want = plan_ppc(a.n, a.S, a.k, 1);
+    const NuPerDraw& v = a.per_draw;
     if (!p.ok || !want.ok || a.ldt < (int64_t)a.k + 1 || a.lda < (a.col_major ? a.n : (int64_t)a.k) ||
         p.point_tiles != want.point_tiles || p.draw_tiles != want.draw_tiles || p.n_pad != want.n_pad ||
         p.S_pad != want.S_pad || p.k_pad != want.k_pad || p.grid != want.grid || p.grid > 0x7fffffffll ||
-        !(a.nu >= 0.0 && a.nu < __builtin_inf()) || a.n_nu < 0 || a.n_nu > PPC_MAX_NU_VALUES ||
-        (a.n_nu > 0 && (a.nu != 0.0 || !a.nu_tab || !a.nu_index || !a.nu_flag || !a.nus)))
+        !(a.nu >= 0.0 && a.nu < __builtin_inf()) || !v.valid(a.nu, PPC_MAX_NU_VALUES) || (v.n_nu > 0 && !a.nus))
         return hipErrorInvalidValue;
     const hipError_t e = launch_pad_points(a.A, a.y, a.offset, true, a.n, a.k, a.lda, a.col_major, p.n_pad,
                                            p.k_pad, a.Ap, a.yo, s);
@@ -386,14 +367,14 @@ hipError_t launch_ppc(const PpcArgs& a, const PpcPlan& p, hipStream_t s) {
                        (const double*)a.Ap, (const double*)a.yo, a.n, p.n_pad, p.k_pad, cm);
     int64_t blocks = (p.S_pad * p.k_pad + 255) / 256;
     if (blocks > 8192) blocks = 8192;
-    if (a.n_nu > 0)
+    if (v.n_nu > 0)
         hipLaunchKernelGGL(ppc_pad_draws_kernel<PpcNuStage>, dim3((unsigned)blocks), dim3(256), 0, s,
                            a.theta, a.S, a.ldt, a.k, p.S_pad, p.k_pad, (const double*)cm, a.Tp, a.sg,
-                           PpcNuStage{a.nu_tab, a.nu_index, a.nu_flag, a.nus, a.n_nu});
+                           PpcNuStage{v.tab, v.index, v.flag, a.nus, v.n_nu});
     else
         hipLaunchKernelGGL(ppc_pad_draws_kernel<>, dim3((unsigned)blocks), dim3(256), 0, s, a.theta, a.S,
                            a.ldt, a.k, p.S_pad, p.k_pad, (const double*)cm, a.Tp, a.sg);
-    if (a.n_nu > 0)
+    if (v.n_nu > 0)
         hipLaunchKernelGGL((ppc_tile_kernel<PPC_TV, const double*>), dim3((unsigned)p.grid), dim3(256), 0,
                            s, (const double*)a.Tp, (const double*)a.sg, (const double*)a.Ap,
                            (const double*)a.yo, a.n, p.n_pad, a.S, p.S_pad, a.k, p.k_pad, p.point_tiles,

@@ -120,9 +120,9 @@ __global__ __launch_bounds__(256) void predict_pad_kernel(const double* __restri
 }
 
 // The noise of the epilogue.  PG_GAUSS: the standard normals of pg_noise (or the caller's array,
-// replay mode), no further argument.  PG_T: Student-t with one nu for all draws; Lik = (double nu,
-// double 2 / nu).  PG_TV: a nu per draw; Lik = (const double* nus), [2][S_pad]: nu_s, then 2 / nu_s,
-// read beside sig (the padded draws hold nu = 4, so that their 0 * t stays finite).  The t variate of
+// replay mode), no further argument.  PG_T and PG_TV: Student-t with one nu for all draws or a nu
+// per draw, Lik as TNoise (bmc_dev.h) names it; the pairs of PG_TV are read beside sig (the padded
+// draws hold nu = 4, so that their 0 * t stays finite).  The t variate of
 // (point p, draw s) is student_t_variate (bmc_math.h) of the two uniforms of counter
 // (e lo, e hi, STREAM_PRED_T, 0), e = p S + s: one Philox call per element and the cosine half
 // alone -- the sine half shares its radius, and handing it to point p + 4 as the Gaussian walk does
@@ -130,16 +130,6 @@ __global__ __launch_bounds__(256) void predict_pad_kernel(const double* __restri
 // enters the counter: z[p][s] depends on (seed, p, s, nu_s) alone.  The t instantiations have no
 // replay mode and ignore noise_replay.
 enum PgNoise { PG_GAUSS = 0, PG_T = 1, PG_TV = 2 };
-template <typename... Lik>
-struct PgLik {};
-template <>
-struct PgLik<double, double> {
-    double nu, two_over_nu;
-};
-template <>
-struct PgLik<const double*> {
-    const double* nus;
-};
 
 template <PgNoise NOISE, typename... Lik>
 __global__ __launch_bounds__(256) void predict_gemm_kernel(
@@ -255,25 +245,16 @@ __global__ __launch_bounds__(256) void predict_gemm_kernel(
     if constexpr (NOISE != PG_GAUSS) {
         // every one of the 16 entries draws for itself: entry (t, j) is point pe0 + 4 j, draw
         // sl0 + 16 t
-        const PgLik<Lik...> lk{lik...};
+        const TNoise<Lik...> lk{lik...};
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             const double sg = sig[sl0 + 16 * t];
-            double nu, two_over_nu;
-            if constexpr (NOISE == PG_TV) {
-                nu = lk.nus[sl0 + 16 * t];
-                two_over_nu = lk.nus[S_pad + sl0 + 16 * t];
-            } else {
-                nu = lk.nu;
-                two_over_nu = lk.two_over_nu;
-            }
+            const NuPair nt = lk.pair(sl0 + 16 * t, S_pad);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const uint64_t e = e0 + (uint64_t)(4 * j) * (uint64_t)S + (uint64_t)(16 * t);
-                const u32x4 w = philox4x32_10(
-                    u32x4{(uint32_t)e, (uint32_t)(e >> 32), STREAM_PRED_T, 0u}, k0, k1);
-                const double z = student_t_variate(u53_open0(w.x, w.y), u53_open0(w.z, w.w), nu,
-                                                   two_over_nu);
+                const double z =
+                    student_t_at(u32x4{(uint32_t)e, (uint32_t)(e >> 32), STREAM_PRED_T, 0u}, k0, k1, nt);
                 __builtin_nontemporal_store(fma(z, sg, acc[t][j]),
                                             r0 + (int64_t)(4 * j) * S_pad + 16 * t);
                 // one variate at a time: the temporaries of the logarithm, expm1 and the cosine

@@ -114,7 +114,7 @@ __global__ __launch_bounds__(256) void sens_logdens_kernel(
         if ((components >> b) & 1) comps[(int64_t)(c++) * S + s] = v[b];
 }
 
-// ---- the Student-t likelihood (SensLogdensArgs::n_nu > 0) -----------------------
+// ---- the Student-t likelihood (SensLogdensArgs::per_draw) ----------------------
 // one thread per draw: tc[0] = g = 1 / (nu sigma^2), tc[1] = hn = (nu + 1)/2, tc[2] = c = C(nu) -
 // log sigma (the constants of score_consts_tv_kernel), tc[3] = nu, tc[4] = the log prior of nu, at
 // the draw's own nu from tab [3][n_nu] = (C(nu), nu, log prior).  index NULL: entry 0 for every
@@ -127,11 +127,7 @@ __global__ __launch_bounds__(256) void sens_consts_t_kernel(const double* __rest
                                                             double* __restrict__ tc) {
     const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= S) return;
-    int32_t iv = index ? index[s] : 0;
-    if (iv < 0 || iv >= n_nu) {
-        *flag = 1;
-        iv = iv < 0 ? 0 : n_nu - 1;
-    }
+    const int32_t iv = nu_index_clamped(index ? index[s] : 0, n_nu, flag);
     const double cnu = tab[iv], nu = tab[n_nu + iv];
     const double sg = theta[s * ldt + k];
     tc[s] = 1.0 / (nu * sg * sg);
@@ -517,18 +513,19 @@ inline unsigned capped_blocks(int64_t elements) {
 
 hipError_t launch_sens_logdens(const SensLogdensArgs& a, hipStream_t s) {
     const int64_t S64 = (a.S + SENS_TILE - 1) / SENS_TILE * SENS_TILE;
+    const NuPerDraw& v = a.per_draw;
     if (a.S < 1 || a.k < 1 || a.k > SENS_MAX_K || a.ldt < (int64_t)a.k + 1 || a.k_pad < a.k || a.k_pad % SC_KT ||
         a.n_pad < 1 || a.n_pad % SENS_TILE || a.q_pad < a.k || a.q_pad % SENS_TILE || a.S_pad != S64 ||
         S64 / SENS_TILE > 0x7fffffffll || a.components == 0 ||
-        a.components >= (1u << (a.n_nu > 0 ? SENS_T_COMPONENTS : SENS_COMPONENTS)) || a.n_nu < 0 ||
-        a.n_nu > SENS_MAX_NU_VALUES || (a.n_nu > 0 && (!a.nu_tab || !a.nu_flag || !a.tc)))
+        a.components >= (1u << (v.n_nu > 0 ? SENS_T_COMPONENTS : SENS_COMPONENTS)) ||
+        !v.valid(0.0, SENS_MAX_NU_VALUES, true) || (v.n_nu > 0 && !a.tc))
         return hipErrorInvalidValue;
     hipLaunchKernelGGL(sens_pad_draws_kernel, dim3(capped_blocks(S64 * a.k_pad)), dim3(256), 0, s, a.theta, a.S,
                        a.ldt, a.k, S64, a.k_pad, a.Tp);
     const dim3 grid((unsigned)(S64 / SENS_TILE)), per_draw((unsigned)((a.S + 255) / 256));
-    if (a.n_nu > 0) {
-        hipLaunchKernelGGL(sens_consts_t_kernel, per_draw, dim3(256), 0, s, a.theta, a.S, a.ldt, a.k, a.nu_tab,
-                           a.n_nu, a.nu_index, a.nu_flag, a.tc);
+    if (v.n_nu > 0) {
+        hipLaunchKernelGGL(sens_consts_t_kernel, per_draw, dim3(256), 0, s, a.theta, a.S, a.ldt, a.k, v.tab,
+                           v.n_nu, v.index, v.flag, a.tc);
         hipLaunchKernelGGL(sens_tsum_tile_kernel, grid, dim3(256), 0, s, (const double*)a.Tp, a.Ap, a.yo, a.n_pad,
                            a.k, a.k_pad, a.n_pad / SENS_TILE, a.S, (const double*)a.tc, a.rss);
     } else {
@@ -537,7 +534,7 @@ hipError_t launch_sens_logdens(const SensLogdensArgs& a, hipStream_t s) {
     }
     hipLaunchKernelGGL(sens_rss_tile_kernel, grid, dim3(256), 0, s, (const double*)a.Tp, a.Lp, a.Ly, a.q_pad,
                        a.k, a.k_pad, a.q_pad / SENS_TILE, a.S, a.rss + a.S);
-    if (a.n_nu > 0)
+    if (v.n_nu > 0)
         hipLaunchKernelGGL(sens_logdens_t_kernel, per_draw, dim3(256), 0, s, a.theta, a.S, a.ldt, a.k,
                            (const double*)a.rss, (const double*)(a.rss + a.S), (const double*)a.tc, (double)a.n,
                            a.nu0, a.sigma20, a.components, a.lp, a.comps);

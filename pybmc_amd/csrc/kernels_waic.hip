@@ -8,7 +8,7 @@
 //                  the one staging kernel of launch_score, launch_ppc and the sensitivity)
 //   score_consts   per draw: c_s = -1/2 log(2 pi) - log sigma_s,  h_s = 1 / (2 sigma_s^2)
 //                  (score_consts_t: the constants of the Student-t density, ScoreArgs::nu > 0;
-//                  score_consts_tv: the same at a nu per draw, ScoreArgs::n_nu > 0)
+//                  score_consts_tv: the same at a nu per draw, ScoreArgs::per_draw)
 //   score_tile     workgroup = 64 points x the draw tiles of one split.  a_i . beta_s on
 //                  v_mfma_f64_16x16x4_f64 (the tile loop of bmc_score_tile.h, shared with
 //                  kernels_loo.hip); the tile is reduced in the epilogue
@@ -105,11 +105,7 @@ __global__ __launch_bounds__(256) void score_consts_tv_kernel(const double* __re
                                                               double* __restrict__ ch) {
     const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= S) return;
-    int32_t iv = index[s];
-    if (iv < 0 || iv >= n_nu) {
-        *flag = 1;
-        iv = iv < 0 ? 0 : n_nu - 1;
-    }
+    const int32_t iv = nu_index_clamped(index[s], n_nu, flag);
     const double cnu = tab[iv], nu = tab[n_nu + iv];
     const double sg = theta[s * ldt + k];
     ch[s] = cnu - log(sg);
@@ -280,8 +276,7 @@ hipError_t launch_pad_points(const double* A, const double* y, const double* off
 hipError_t launch_score(const ScoreArgs& a, const ScorePlan& p, hipStream_t s) {
     if (a.n < 1 || a.S < 2 || a.k < 1 || a.k > SCORE_MAX_K || a.ldt < a.k + 1 ||
         a.lda < (a.col_major ? a.n : (int64_t)a.k) || !(a.nu >= 0.0 && a.nu < __builtin_inf()) ||
-        a.n_nu < 0 || (a.n_nu > 0 && (a.nu != 0.0 || !a.nu_tab || !a.nu_index || !a.nu_flag)) ||
-        p.k_pad < a.k || p.k_pad % SC_KT != 0 ||
+        !a.per_draw.valid(a.nu, INT32_MAX) || p.k_pad < a.k || p.k_pad % SC_KT != 0 ||
         p.point_tiles != (a.n + SC_TM - 1) / SC_TM || p.draw_tiles != (a.S + SC_TM - 1) / SC_TM ||
         p.splits < 1 || p.tiles_per_split < 1 || p.splits * p.tiles_per_split < p.draw_tiles ||
         (p.splits - 1) * p.tiles_per_split >= p.draw_tiles)
@@ -295,9 +290,10 @@ hipError_t launch_score(const ScoreArgs& a, const ScorePlan& p, hipStream_t s) {
     {
         const int64_t blocks = (a.S + 255) / 256;
         if (blocks > 0x7fffffffll) return hipErrorInvalidValue;
-        if (a.n_nu > 0) {
+        if (a.per_draw.n_nu > 0) {
+            const NuPerDraw& v = a.per_draw;
             hipLaunchKernelGGL(score_consts_tv_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a.theta,
-                               a.S, a.ldt, a.k, a.nu_tab, a.n_nu, a.nu_index, a.nu_flag, a.ch);
+                               a.S, a.ldt, a.k, v.tab, v.n_nu, v.index, v.flag, a.ch);
         } else if (a.nu > 0.0) {
             hipLaunchKernelGGL(score_consts_t_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a.theta,
                                a.S, a.ldt, a.k, student_t_cnu(a.nu), a.nu, a.ch);
@@ -306,7 +302,7 @@ hipError_t launch_score(const ScoreArgs& a, const ScorePlan& p, hipStream_t s) {
                                a.S, a.ldt, a.k, a.ch);
         }
     }
-    if (a.n_nu > 0)
+    if (a.per_draw.n_nu > 0)
         hipLaunchKernelGGL(score_tile_kernel<TileDrawsTV>, dim3((unsigned)groups), dim3(256), 0, s,
                            (const double*)a.Ap, (const double*)a.yp, a.theta, (const double*)a.ch, a.S,
                            a.ldt, a.k, p.k_pad, (uint32_t)p.point_tiles, p.tiles_per_split,

@@ -268,3 +268,43 @@ def test_score_on_the_standin_dataset():
     assert sorted(out["names"]) == ["gaussian", "student_t"] and np.isfinite(out["se_diff"]).all()
     with pytest.raises(ValueError, match="supports the Gaussian Gibbs sampler only"):
         b.waic()
+
+
+# ---- 8. a nu per draw: the index out of range ------------------------------------------------------------------
+def test_tv_refuses_an_index_out_of_range_and_rezeroes_its_flag():
+    """n = 65, S = 66, k = 3, two nu values: one full and one partly filled tile on both axes.  A host
+    index holding -1 or V is refused before any launch; the same index on the device is clamped in
+    the kernel and reported after it; and the valid call that follows on the same context returns
+    the bits of a fresh context, so the flag word is zeroed by every call."""
+    import torch
+    from pybmc_amd import _lib
+    n, S, k = 65, 66, 3
+    A, y, th = T.shape_case(k, n, S)
+    vals = np.array([3.0, 7.5])
+    good = (np.arange(S) % 2).astype(np.int32)
+    dev = torch.device("cuda", 0)
+    Ad, yd, thd = (torch.as_tensor(v, device=dev) for v in (A, y, th))
+    good_d = torch.as_tensor(good, device=dev)
+    torch.cuda.synchronize()
+    ctx, fresh = _lib.Context(0), _lib.Context(0)
+    host = lambda c, name, idx: getattr(c, name)(A, n, k, k, 0, y, th, S, k + 1, vals, idx)
+    device = lambda c, name, idx_d: getattr(c, name + "_device")(
+        Ad.data_ptr(), n, k, k, 0, yd.data_ptr(), thd.data_ptr(), S, k + 1, vals, idx_d.data_ptr())
+    for name in ("pointwise_loglik_tv", "psis_loo_tv"):
+        want = host(fresh, name, good)
+        want_d = device(fresh, name, good_d)
+        for key in want:
+            assert np.isfinite(want[key]).all() and np.array_equal(want[key], want_d[key]), (name, key)
+        for at, bad_value in ((0, -1), (S - 1, len(vals)), (64, -1), (17, len(vals))):
+            bad = good.copy()
+            bad[at] = bad_value
+            with pytest.raises(ValueError, match="nu_index must index nu_values"):
+                host(ctx, name, bad)
+            for key, v in host(ctx, name, good).items():
+                assert np.array_equal(v, want[key]), (name, key, at, bad_value, "host")
+            bad_d = torch.as_tensor(bad, device=dev)
+            torch.cuda.synchronize()
+            with pytest.raises(ValueError, match=r"nu_index must index nu_values \(the results are not valid\)"):
+                device(ctx, name, bad_d)
+            for key, v in device(ctx, name, good_d).items():
+                assert np.array_equal(v, want[key]), (name, key, at, bad_value, "device")
