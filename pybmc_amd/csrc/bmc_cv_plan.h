@@ -16,6 +16,10 @@ constexpr int CV_MAX_CHAINS_PER_LAUNCH = 2048;    // the bound of the other one-
 constexpr int CV_ROW_PAD = 4;                     // rows per v_mfma_f64_16x16x4_f64 k-step
 constexpr int CV_GRAM_CHUNK = 512;                // rows per Gram partial (a multiple of CV_ROW_PAD)
 constexpr int CV_RSS_CHUNK = 64;                  // rows per block-rss partial
+// cv_gather_kernel and cv_unrotate_kernel are grid-stride loops: at most CV_STRIDE_BLOCKS blocks of
+// CV_STRIDE_THREADS threads, so a launch of more elements than their product makes a second trip
+constexpr int CV_STRIDE_THREADS = 256;
+constexpr int CV_STRIDE_BLOCKS = 8192;
 
 // columns of the gathered matrix [A | y | 0-pad]: whole 16-column MFMA tiles
 inline int cv_ldz(int k) { return (k + 1 + 15) / 16 * 16; }

@@ -333,8 +333,8 @@ hipError_t launch_cv_gather(const double* A, const double* y, int64_t lda, int c
                             const int64_t* src, int64_t n_pad, double* Z, double* ys, hipStream_t s) {
     if (k < 1 || k > CV_MAX_K || n_pad < 1) return hipErrorInvalidValue;
     const int32_t ldz = cv_ldz(k);
-    hipLaunchKernelGGL(cv_gather_kernel, dim3(blocks_for(n_pad * ldz, 256, 8192)), dim3(256), 0, s, A, y,
-                       lda, col_major, k, src, n_pad, ldz, Z, ys);
+    hipLaunchKernelGGL(cv_gather_kernel, dim3(blocks_for(n_pad * ldz, CV_STRIDE_THREADS, CV_STRIDE_BLOCKS)),
+                       dim3(256), 0, s, A, y, lda, col_major, k, src, n_pad, ldz, Z, ys);
     return hipGetLastError();
 }
 
@@ -391,7 +391,8 @@ hipError_t launch_cv_unrotate(const double* u, const double* WT, int32_t k, int3
                               int32_t fold0, int64_t chains, int64_t T, int64_t burn, int64_t thin,
                               int64_t kept, double* out, hipStream_t s) {
     if (chains < 1 || kept < 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(cv_unrotate_kernel, dim3(blocks_for(chains * kept * (k + 1), 256, 8192)), dim3(256),
+    hipLaunchKernelGGL(cv_unrotate_kernel,
+                       dim3(blocks_for(chains * kept * (k + 1), CV_STRIDE_THREADS, CV_STRIDE_BLOCKS)), dim3(256),
                        0, s, u, WT, k, chains_per_fold, fold0, chains, T, burn, thin, kept, out);
     return hipGetLastError();
 }

@@ -3,6 +3,8 @@
 //   cv_plan_check segments F label...           -> offsets | counts | src | gram chunks | rss chunks
 //   cv_plan_check batches F C K T burn thin budget -> kept bytes | f0-f1:chain0+n,chain0+n;...
 //   cv_plan_check sweep                         -> random labels: every row once, stable, padded
+//   cv_plan_check widths                        -> "k cv_ldz cv_tiles cv_kmax" per line, k = 1 .. CV_MAX_K
+//   cv_plan_check chunks F label...             -> n_pad | gram chunks | rss chunks (segments without src)
 #include "../pybmc_amd/csrc/bmc_cv_plan.h"
 
 #include <cstdio>
@@ -83,6 +85,22 @@ int main(int argc, char** argv) {
         const std::vector<int64_t> l = labels_from(argc, argv, 4);
         const std::string r = cv_check((int64_t)l.size(), k, F, l.data());
         std::printf("%s\n", r.empty() ? "ok" : r.c_str());
+        return 0;
+    }
+    if (!std::strcmp(argv[1], "widths")) {
+        for (int k = 1; k <= CV_MAX_K; ++k) std::printf("%d %d %d %d\n", k, cv_ldz(k), cv_tiles(k), cv_kmax(k));
+        return 0;
+    }
+    if (!std::strcmp(argv[1], "chunks") && argc >= 3) {
+        const int F = std::atoi(argv[2]);
+        const std::vector<int64_t> l = labels_from(argc, argv, 3);
+        if (!cv_check((int64_t)l.size(), 1, F, l.data()).empty()) return 3;
+        const CvSegments s = cv_segments((int64_t)l.size(), F, l.data());
+        std::printf("%lld | ", (long long)s.n_pad);
+        print_chunks(s.gram);
+        std::printf(" | ");
+        print_chunks(s.rss);
+        std::printf("\n");
         return 0;
     }
     if (!std::strcmp(argv[1], "segments") && argc >= 3) {
