@@ -546,6 +546,45 @@ int bmc_psis_loo_predict_device(bmc_ctx* ctx, const void* dA, int64_t n_points, 
                                 double* pareto_k_out, double* lppd_out, double* loo_mean_out,
                                 double* loo_sd_out, double* loo_pit_out, double* ess_out);
 
+/* ---- the same under a Student-t likelihood (not in the reference) ------------------------------
+ * The _t forms take the arguments of bmc_psis_loo_t, the _tv forms those of bmc_psis_loo_tv, each
+ * followed by the four further outputs of bmc_psis_loo_predict.  Weights, tie sharing, ess, NaN
+ * rules and the draw limit as bmc_psis_loo_predict; ll[i][s], elpd_loo_out, pareto_k_out and
+ * lppd_out as (and bit-equal to) bmc_psis_loo_t / _tv.  With nu_s the draw's degrees of freedom (nu
+ * in the _t forms) and F_nu the Student-t distribution function:
+ *   loo_mean_out  y_i - sum_s w_s r_s      (the location of the predictive distribution; its mean
+ *                                           where every nu_s > 1)
+ *   loo_sd_out    sqrt(sum_s w_s (sigma_s^2 nu_s / (nu_s - 2) + r_s^2) - (sum_s w_s r_s)^2) when
+ *                 every nu of the call (nu; every entry of nu_values) exceeds 2, else +inf at every
+ *                 point that is not NaN (decided before the launch: no infinity is summed)
+ *   loo_pit_out   sum_s w_s F_{nu_s}(r_s / sigma_s)
+ * Two more passes over the matrix than bmc_psis_loo_t at most (the sums run in two phases).
+ * BMC_EINVAL as bmc_psis_loo_t / _tv and bmc_psis_loo_predict, and when nu, or an entry of
+ * nu_values, lies outside 0.06 .. 1000 (the range over which F_nu is held to its accuracy bar), or
+ * n_values < 1.  INTEGRATION.md section 10. */
+int bmc_psis_loo_predict_t(bmc_ctx* ctx, const double* A, int64_t n_points, int32_t k, int64_t lda,
+                           int layout, const double* y, const double* theta, int64_t n_draws,
+                           int64_t ldt, double nu, double* elpd_loo_out, double* pareto_k_out,
+                           double* lppd_out, double* loo_mean_out, double* loo_sd_out,
+                           double* loo_pit_out, double* ess_out);
+int bmc_psis_loo_predict_t_device(bmc_ctx* ctx, const void* dA, int64_t n_points, int32_t k,
+                                  int64_t lda, int layout, const void* dy, const void* dtheta,
+                                  int64_t n_draws, int64_t ldt, double nu, double* elpd_loo_out,
+                                  double* pareto_k_out, double* lppd_out, double* loo_mean_out,
+                                  double* loo_sd_out, double* loo_pit_out, double* ess_out);
+int bmc_psis_loo_predict_tv(bmc_ctx* ctx, const double* A, int64_t n_points, int32_t k, int64_t lda,
+                            int layout, const double* y, const double* theta, int64_t n_draws,
+                            int64_t ldt, const double* nu_values, int32_t n_values,
+                            const int32_t* nu_index, double* elpd_loo_out, double* pareto_k_out,
+                            double* lppd_out, double* loo_mean_out, double* loo_sd_out,
+                            double* loo_pit_out, double* ess_out);
+int bmc_psis_loo_predict_tv_device(bmc_ctx* ctx, const void* dA, int64_t n_points, int32_t k,
+                                   int64_t lda, int layout, const void* dy, const void* dtheta,
+                                   int64_t n_draws, int64_t ldt, const double* nu_values,
+                                   int32_t n_values, const void* d_nu_index, double* elpd_loo_out,
+                                   double* pareto_k_out, double* lppd_out, double* loo_mean_out,
+                                   double* loo_sd_out, double* loo_pit_out, double* ess_out);
+
 /* ---- exact K-fold / leave-group-out cross-validation, all folds in one call -------------------
  * A (n x k host f64, k <= 64, element (i, j) as in bmc_pointwise_loglik), y [n], fold [n] labels in
  * 0 .. n_folds-1 (2 <= n_folds <= 1024; no fold empty; every training set, the rows of the OTHER

@@ -151,6 +151,17 @@ PROTOTYPES = {
                                        C.c_int64, C.c_int64, _D, _D, _D, _D, _D, _D, _D]),
     "bmc_psis_loo_predict_device": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int, _P,
                                               _P, C.c_int64, C.c_int64, _D, _D, _D, _D, _D, _D, _D]),
+    "bmc_psis_loo_predict_t": (C.c_int, [_P, _D, C.c_int64, C.c_int32, C.c_int64, C.c_int, _D, _D,
+                                         C.c_int64, C.c_int64, C.c_double, _D, _D, _D, _D, _D, _D, _D]),
+    "bmc_psis_loo_predict_t_device": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int, _P,
+                                                _P, C.c_int64, C.c_int64, C.c_double, _D, _D, _D, _D,
+                                                _D, _D, _D]),
+    "bmc_psis_loo_predict_tv": (C.c_int, [_P, _D, C.c_int64, C.c_int32, C.c_int64, C.c_int, _D, _D,
+                                          C.c_int64, C.c_int64, _D, C.c_int32, C.POINTER(C.c_int32),
+                                          _D, _D, _D, _D, _D, _D, _D]),
+    "bmc_psis_loo_predict_tv_device": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int, _P,
+                                                 _P, C.c_int64, C.c_int64, _D, C.c_int32, _P, _D, _D,
+                                                 _D, _D, _D, _D, _D]),
     "bmc_kfold_cv": (C.c_int, [_P, _D, C.c_int64, C.c_int32, C.c_int64, C.c_int, _D,
                                C.POINTER(C.c_int64), C.c_int32, _D, _D, C.c_double, C.c_double,
                                C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_uint64), _D,
@@ -973,6 +984,30 @@ class Context:
         the caller orders its producers before the call."""
         return self._score_call(self._lib.bmc_psis_loo_predict_device, self.LOO_PREDICT_KEYS, _P,
                                 dA, n, k, lda, layout, dy, dtheta, n_draws, ldt)
+
+    def psis_loo_predict_t(self, A, n, k, lda, layout, y, theta, n_draws, ldt, nu):
+        """psis_loo_predict under the Student-t likelihood with `nu` degrees of freedom, 0.06 to 1000
+        (bmc_psis_loo_predict_t)."""
+        return self._score_call(self._lib.bmc_psis_loo_predict_t, self.LOO_PREDICT_KEYS, _dptr,
+                                A, n, k, lda, layout, y, theta, n_draws, ldt, nu)
+
+    def psis_loo_predict_t_device(self, dA, n, k, lda, layout, dy, dtheta, n_draws, ldt, nu):
+        """The same on DEVICE memory (bmc_psis_loo_predict_t_device)."""
+        return self._score_call(self._lib.bmc_psis_loo_predict_t_device, self.LOO_PREDICT_KEYS, _P,
+                                dA, n, k, lda, layout, dy, dtheta, n_draws, ldt, nu)
+
+    def psis_loo_predict_tv(self, A, n, k, lda, layout, y, theta, n_draws, ldt, nu_values, nu_index):
+        """psis_loo_predict under the Student-t likelihood with a nu per draw
+        (bmc_psis_loo_predict_tv)."""
+        return self._score_call_tv(self._lib.bmc_psis_loo_predict_tv, self.LOO_PREDICT_KEYS, _dptr, A,
+                                   n, k, lda, layout, y, theta, n_draws, ldt, nu_values, nu_index)
+
+    def psis_loo_predict_tv_device(self, dA, n, k, lda, layout, dy, dtheta, n_draws, ldt, nu_values,
+                                   d_nu_index):
+        """The same on DEVICE memory, the int32 index included (bmc_psis_loo_predict_tv_device)."""
+        return self._score_call_tv(self._lib.bmc_psis_loo_predict_tv_device, self.LOO_PREDICT_KEYS, _P,
+                                   dA, n, k, lda, layout, dy, dtheta, n_draws, ldt, nu_values,
+                                   d_nu_index)
 
     # -- posterior predictive check ---------------------------------------------------------------
     def _ppc_call(self, fn, ptr, A, n, k, lda, layout, y, theta, n_draws, ldt, offset, seed, *noise):

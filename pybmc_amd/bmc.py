@@ -398,6 +398,39 @@ class BayesianModelCombination:
         out["residual"] = y - out["loo_mean"]
         return out
 
+    def loo_predictions(self, burn=0):
+        """The leave-one-out predictions of the last ``train()`` under the likelihood it sampled
+        from (not in the reference; ``pybmc_amd.scoring.psis_loo_predict``): what ``loo_predict()``
+        returns for a Gaussian fit, and after ``{"sampler": "student_t"}`` the same under the
+        Student-t density with that fit's ``nu`` (every draw's own after ``"nu": "estimate"``) --
+        the leave-one-out method that accepts a Student-t fit, as ``score()`` is the scoring one.
+        Under the t likelihood ``loo_mean`` is the location of the predictive distribution (its mean
+        where ``nu > 1``), ``loo_sd`` carries the t variance and is ``+inf`` when a scored ``nu`` is
+        at most 2, ``loo_pit`` uses the t distribution function, and ``nu`` must lie in 0.06 .. 1000.
+        The rows the robust fit down-weights are the ones to look at first: large ``|residual|``,
+        ``|2 loo_pit - 1|`` near 1.  ``burn`` more draws are dropped from the start of each chain.
+        The result also carries ``likelihood``, ``nu`` and ``nu_estimated`` as ``score()`` sets
+        them."""
+        if self.samples is None or self.U_hat is None:
+            raise ValueError("Must call `orthogonalize()` and `train()` before computing LOO.")
+        nu = self._noise_df()
+        estimated = self._nu_estimated()
+        lik = {"nu_draws": self._nu_chains()} if estimated else {"nu": nu}
+        from .scoring import psis_loo_predict
+        y = np.asarray(self.centered_experiment_train, dtype=np.float64)
+        out = psis_loo_predict(self.U_hat, y, self._chains(), burn=burn, device=self.device, **lik)
+        mu = np.asarray(self._predictions_mean_train, dtype=np.float64)
+        out["predicted"] = out["loo_mean"] + mu
+        out["truth"] = y + mu
+        out["residual"] = y - out["loo_mean"]
+        out["likelihood"] = "gaussian" if nu is None else "student_t"
+        if estimated:    # the mean over the scored draws
+            out["nu"] = float(np.mean(lik["nu_draws"][:, int(burn):]))
+            out["nu_estimated"] = True
+        else:
+            out["nu"] = nu
+        return out
+
     def prior_sensitivity(self, burn=0, alphas=None, training_options=None):
         """Power-scaling sensitivity of the last ``train()`` to its prior and its likelihood (not in
         the reference; ``pybmc_amd.sensitivity.power_scale_sensitivity``): for every coefficient,

@@ -390,13 +390,18 @@ hipError_t launch_score(const ScoreArgs& a, const ScorePlan& p, hipStream_t s);
 struct LooArgs {
     ScoreArgs score;
     void* work;
+    // launch_loo_predict under the t likelihood: some nu in use is <= 2, so loo_sd is +inf wherever
+    // it is not NaN (decided on the host: the device never sums an infinite variance)
+    bool t_sd_inf = false;
 };
 double* loo_out(const LooArgs& a, const LooPlan& p);
 hipError_t launch_loo(const LooArgs& a, const LooPlan& p, hipStream_t s);
 
 // The leave-one-out predictive moments of every point with the same weights.
 // work: loo_predict_buffers(plan, n).total() bytes; at loo_predict_out(): elpd_loo_i, pareto_k,
-// loo_mean, loo_sd, loo_pit, ess, [n] each.  Gaussian only: score.nu != 0 is hipErrorInvalidValue.
+// loo_mean, loo_sd, loo_pit, ess, [n] each.  Under the t likelihood (score.nu > 0 or score.per_draw;
+// the plan made with student = true; nu within STUDENT_T_CDF_NU_MIN .. _MAX of bmc_math.h, which the
+// caller checks) loo_sd carries sigma_s^2 nu_s / (nu_s - 2) and loo_pit the t distribution function.
 double* loo_predict_out(const LooArgs& a, const LooPredictPlan& p);
 hipError_t launch_loo_predict(const LooArgs& a, const LooPredictPlan& p, hipStream_t s);
 

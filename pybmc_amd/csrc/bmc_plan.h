@@ -866,23 +866,36 @@ constexpr int64_t LOO_LDS_BYTES = 160 * 1024;
 constexpr int LOO_PREDICT_OUTS = 6;     // elpd_loo_i, pareto_k, loo_mean, loo_sd, loo_pit, ess
 constexpr int LOO_PREDICT_SUMS = 4;     // per point besides sum w: w r, w (sigma^2 + r^2), w Phi, w^2
 constexpr int LOO_BUCKET_SUMS = 3;      // of a one-value bucket: r, sigma^2 + r^2, Phi
+// Under the Student-t likelihood (student) the append runs in LOO_PREDICT_T_PHASES
+// phases, each one more pass over the matrix: the first sums everything but w F and writes the
+// candidates, the second recomputes the weights and sums w F alone (the t distribution function of
+// bmc_math.h on top of the t density does not fit the registers of one kernel).  Both write the same
+// LOO_PREDICT_SUMS slots.  The passes read LOO_PREDICT_T_ROWS more constants per draw: the variance
+// term sigma_s^2 nu_s / (nu_s - 2) (0 where the call's loo_sd is +inf) and nu_s.
+constexpr int LOO_PREDICT_T_PHASES = 2;
+constexpr int LOO_PREDICT_T_ROWS = 2;
 
 struct LooPredictPlan {
     LooPlan loo;             // the passes both calls share
     int64_t record_bytes;    // global memory per candidate: the value and its draw index
     int64_t fit_lds;         // dynamic LDS of the fit: cap * LOO_PREDICT_SLOT_LDS
     int32_t bucket_pass;     // 1: the one-value-bucket pass is launched
+    int32_t append_phases;   // launches of the append: 1, or LOO_PREDICT_T_PHASES under the t likelihood
+    int64_t draw_rows;       // doubles of further per-draw constants: LOO_PREDICT_T_ROWS * n_draws, or 0
     int32_t matrix_passes;   // all launches that walk the matrix
     bool ok;                 // loo.cap <= LOO_PREDICT_MAX_CAP (LOO_PREDICT_MAX_DRAWS draws)
 };
 
-inline LooPredictPlan plan_loo_predict(int64_t n_points, int64_t n_draws, int32_t k, int n_cu) {
+inline LooPredictPlan plan_loo_predict(int64_t n_points, int64_t n_draws, int32_t k, int n_cu,
+                                       bool student = false) {
     LooPredictPlan p;
     p.loo = plan_loo(n_points, n_draws, k, n_cu);
     p.record_bytes = 8 + 4;
     p.fit_lds = p.loo.cap * LOO_PREDICT_SLOT_LDS;
     p.bucket_pass = p.loo.select_passes > 0 ? 1 : 0;
-    p.matrix_passes = p.loo.matrix_passes + p.bucket_pass;
+    p.append_phases = student ? LOO_PREDICT_T_PHASES : 1;
+    p.draw_rows = student ? (int64_t)LOO_PREDICT_T_ROWS * n_draws : 0;
+    p.matrix_passes = p.loo.matrix_passes + p.bucket_pass + (p.append_phases - 1);
     p.ok = p.loo.cap <= LOO_PREDICT_MAX_CAP;
     return p;
 }
@@ -894,7 +907,8 @@ struct LooPredictBuffers {
     size_t pay;       // [splits][n_pad][4] f64: the payload sums above the bucket
     size_t bucket;    // [splits][n_pad][3] f64: the payload sums of a one-value bucket
     size_t out;       // [6][n_points] f64
-    size_t total() const { return loo.total() + candidx + pay + bucket + out; }
+    size_t tc;        // [LOO_PREDICT_T_ROWS][n_draws] f64: the t passes' further constants (0: Gaussian)
+    size_t total() const { return loo.total() + candidx + pay + bucket + out + tc; }
 };
 inline LooPredictBuffers loo_predict_buffers(const LooPredictPlan& p, int64_t n_points) {
     auto up = [](size_t b) { return (b + 255) / 256 * 256; };
@@ -905,6 +919,7 @@ inline LooPredictBuffers loo_predict_buffers(const LooPredictPlan& p, int64_t n_
     b.pay = up(sp * n_pad * LOO_PREDICT_SUMS * 8);
     b.bucket = up(sp * n_pad * LOO_BUCKET_SUMS * 8);
     b.out = up((size_t)n_points * LOO_PREDICT_OUTS * 8);
+    b.tc = up((size_t)p.draw_rows * 8);
     return b;
 }
 

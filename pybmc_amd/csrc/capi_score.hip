@@ -4,6 +4,7 @@
 // Also the posterior predictive check (kernels_ppc.hip): the same operands and
 // checks, results per draw instead of per point (ppc_entry).
 #include "bmc_ctx.h"
+#include "bmc_math.h"
 
 namespace {
 
@@ -122,9 +123,20 @@ int loo_family(bmc_ctx* c, const ScoreIn& in, const double** src) {
     return BMC_OK;
 }
 
-// elpd_loo, pareto_k, lppd, loo_mean, loo_sd, loo_pit, ess
+// elpd_loo, pareto_k, lppd, loo_mean, loo_sd, loo_pit, ess.  Under the t likelihood every nu in the
+// call (the scalar, or each entry of the table) must lie in the range of student_t_cdf, and one at
+// or below 2 makes loo_sd +inf wherever it is not NaN.
 int loo_predict_family(bmc_ctx* c, const ScoreIn& in, const double** src) {
-    const LooPredictPlan plan = plan_loo_predict(in.n, in.S, in.k, c->n_cu);
+    const bool student = in.nu > 0.0 || in.n_nu > 0;
+    bool sd_inf = false;
+    for (int32_t v = 0; student && v < (in.n_nu > 0 ? in.n_nu : 1); ++v) {
+        const double nu = in.n_nu > 0 ? in.nu_values[v] : in.nu;
+        if (!(nu >= STUDENT_T_CDF_NU_MIN && nu <= STUDENT_T_CDF_NU_MAX))
+            return fail(c, BMC_EINVAL, "nu must be between 0.06 and 1000 for the leave-one-out predictive "
+                                       "distribution (the range of its t distribution function)");
+        sd_inf = sd_inf || nu <= 2.0;
+    }
+    const LooPredictPlan plan = plan_loo_predict(in.n, in.S, in.k, c->n_cu, student);
     if (!plan.ok)
         return fail(c, BMC_EINVAL, "n_draws is too large for the per-point sort of the predictive "
                                    "moments (at most " + std::to_string(LOO_PREDICT_MAX_DRAWS) +
@@ -135,6 +147,7 @@ int loo_predict_family(bmc_ctx* c, const ScoreIn& in, const double** src) {
         (rc = ensure(c, c->looWork, loo_predict_buffers(plan, in.n).total())))
         return rc;
     a.work = c->looWork.p;
+    a.t_sd_inf = sd_inf;
     HIPCHK(c, launch_loo_predict(a, plan, c->stream));
     const double* lo = loo_predict_out(a, plan);
     src[0] = lo, src[1] = lo + in.n, src[2] = a.score.out;
@@ -356,6 +369,50 @@ int bmc_psis_loo_predict_device(bmc_ctx* c, const void* dA, int64_t n_points, in
     return score_entry(c, {dA, dy, dtheta, n_points, lda, n_draws, ldt, k, layout}, false,
                        loo_predict_family, {elpd_loo_out, pareto_k_out, lppd_out, loo_mean_out,
                                             loo_sd_out, loo_pit_out, ess_out});
+}
+
+int bmc_psis_loo_predict_t(bmc_ctx* c, const double* A, int64_t n_points, int32_t k, int64_t lda,
+                           int layout, const double* y, const double* theta, int64_t n_draws,
+                           int64_t ldt, double nu, double* elpd_loo_out, double* pareto_k_out,
+                           double* lppd_out, double* loo_mean_out, double* loo_sd_out,
+                           double* loo_pit_out, double* ess_out) {
+    return score_entry(c, {A, y, theta, n_points, lda, n_draws, ldt, k, layout, t_nu(nu)}, true,
+                       loo_predict_family, {elpd_loo_out, pareto_k_out, lppd_out, loo_mean_out,
+                                            loo_sd_out, loo_pit_out, ess_out});
+}
+
+int bmc_psis_loo_predict_t_device(bmc_ctx* c, const void* dA, int64_t n_points, int32_t k, int64_t lda,
+                                  int layout, const void* dy, const void* dtheta, int64_t n_draws,
+                                  int64_t ldt, double nu, double* elpd_loo_out, double* pareto_k_out,
+                                  double* lppd_out, double* loo_mean_out, double* loo_sd_out,
+                                  double* loo_pit_out, double* ess_out) {
+    return score_entry(c, {dA, dy, dtheta, n_points, lda, n_draws, ldt, k, layout, t_nu(nu)}, false,
+                       loo_predict_family, {elpd_loo_out, pareto_k_out, lppd_out, loo_mean_out,
+                                            loo_sd_out, loo_pit_out, ess_out});
+}
+
+int bmc_psis_loo_predict_tv(bmc_ctx* c, const double* A, int64_t n_points, int32_t k, int64_t lda,
+                            int layout, const double* y, const double* theta, int64_t n_draws,
+                            int64_t ldt, const double* nu_values, int32_t n_values,
+                            const int32_t* nu_index, double* elpd_loo_out, double* pareto_k_out,
+                            double* lppd_out, double* loo_mean_out, double* loo_sd_out,
+                            double* loo_pit_out, double* ess_out) {
+    return score_entry(c, {A, y, theta, n_points, lda, n_draws, ldt, k, layout, 0.0, tv_count(n_values),
+                           nu_values, nu_index}, true, loo_predict_family,
+                       {elpd_loo_out, pareto_k_out, lppd_out, loo_mean_out, loo_sd_out, loo_pit_out,
+                        ess_out});
+}
+
+int bmc_psis_loo_predict_tv_device(bmc_ctx* c, const void* dA, int64_t n_points, int32_t k, int64_t lda,
+                                   int layout, const void* dy, const void* dtheta, int64_t n_draws,
+                                   int64_t ldt, const double* nu_values, int32_t n_values,
+                                   const void* d_nu_index, double* elpd_loo_out, double* pareto_k_out,
+                                   double* lppd_out, double* loo_mean_out, double* loo_sd_out,
+                                   double* loo_pit_out, double* ess_out) {
+    return score_entry(c, {dA, dy, dtheta, n_points, lda, n_draws, ldt, k, layout, 0.0,
+                           tv_count(n_values), nu_values, d_nu_index}, false, loo_predict_family,
+                       {elpd_loo_out, pareto_k_out, lppd_out, loo_mean_out, loo_sd_out, loo_pit_out,
+                        ess_out});
 }
 
 int bmc_ppc(bmc_ctx* c, const double* A, int64_t n_points, int32_t k, int64_t lda, int layout,

@@ -36,7 +36,9 @@
 // (range, select, the non-PREDICT append) are templates <D, L...> on it, TileDraws for the Gaussian
 // density, TileDrawsT with its scalar for the Student-t one (ScoreArgs::nu > 0) and TileDrawsTV for
 // the Student-t one with a nu per draw (ScoreArgs::per_draw); init, scan and
-// fit see values of ll only.  The PREDICT variants and loo_bucket are Gaussian only.
+// fit see values of ll only.  The PREDICT passes of the Student-t likelihood are kernels of their own
+// (loo_append_t_kernel in two phases, loo_bucket_t_kernel, loo_fit_kernel<true, TFit>): the t
+// density and distribution function do not fit the registers of one append.
 #include "bmc_dev.h"
 #include "bmc_launch.h"
 #include "bmc_plan.h"
@@ -419,6 +421,180 @@ __global__ __launch_bounds__(256) void loo_bucket_kernel(PassArgs a,
         }
 }
 
+// ---- the PREDICT passes under the Student-t likelihood ----------------------------
+// tc = [2][S]: v_s = sigma_s^2 nu_s / (nu_s - 2), the variance of draw s's predictive (0 for every
+// draw of a call whose loo_sd is +inf: some nu_s <= 2), and nu_s; staged by loo_t_consts_kernel.
+// F_nu(z) of a pair comes from what the pass has anyway: u = g_s r^2 is the argument of ll's log1p
+// and |z| f_nu(z) = |r| exp(ll) (student_t_cdf_from, bmc_math.h).
+__global__ __launch_bounds__(256) void loo_t_consts_kernel(const double* __restrict__ theta, int64_t S,
+                                                           int64_t ldt, int32_t k, double nu_all,
+                                                           const double* __restrict__ tab, int32_t n_nu,
+                                                           const int32_t* __restrict__ index,
+                                                           int32_t* __restrict__ flag, int32_t sd_inf,
+                                                           double* __restrict__ tc) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= S) return;
+    const double nu = n_nu > 0 ? tab[n_nu + nu_index_clamped(index[s], n_nu, flag)] : nu_all;
+    const double sg = theta[s * ldt + k];
+    tc[s] = sd_inf ? 0.0 : (sg * sg) * (nu / (nu - 2.0));
+    tc[S + s] = nu;
+}
+
+// row `row` of tc for the lane's 4 draws (a draw past S reads draw S - 1, as TileDraws does)
+__device__ __forceinline__ void tile_row(const double* __restrict__ tc, int row, int64_t S, int64_t s0,
+                                         int cl, double (&v)[4]) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const int64_t sd = s0 + cl + 16 * t;
+        v[t] = tc[row * S + (sd < S ? sd : S - 1)];
+    }
+}
+
+// loo_append_kernel<true> in two phases, D = TileDrawsT or TileDrawsTV.  PHASE 0: the candidates
+// with their draw indices, body = sum w, and pay[.][0] = sum w r, pay[.][1] = sum w (v_s + r^2),
+// pay[.][3] = sum w^2 over the keys above the bucket.  PHASE 1: x and w recomputed the same way,
+// pay[.][2] = sum w F_nu(r / sigma) alone.  Every sum in the order of `body`.
+template <int PHASE, class D, class... L>
+__global__ __launch_bounds__(256) void loo_append_t_kernel(PassArgs a,
+                                                           const uint64_t* __restrict__ prefix,
+                                                           const uint64_t* __restrict__ kmin,
+                                                           const uint4* __restrict__ meta,
+                                                           uint32_t cap, uint32_t* __restrict__ count,
+                                                           double* __restrict__ cand,
+                                                           double* __restrict__ body,
+                                                           uint32_t* __restrict__ candidx,
+                                                           double* __restrict__ pay,
+                                                           const double* __restrict__ tc, L... lik) {
+    __shared__ double As[SC_LDS_DOUBLES];
+    __shared__ double Bs[SC_LDS_DOUBLES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, cl = lane & 15, kq = lane >> 4;
+    const TilePos pos(a.point_tiles, a.tiles_per_split, a.draw_tiles);
+    constexpr int N_SUMS = PHASE == 0 ? 4 : 1;   // PHASE 0: w, w r, w (v + r^2), w^2; PHASE 1: w F
+    double yv[4], llmin[4], psum[N_SUMS][4];
+    uint64_t pre[4];
+    uint32_t fixed[4], flags[4];
+    int64_t pi[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        pi[r] = pos.p0 + 16 * wave + kq + 4 * r;
+        const uint4 m = meta[pi[r]];
+        yv[r] = a.yp[pi[r]];
+        pre[r] = prefix[pi[r]];
+        llmin[r] = key_value(kmin[pi[r]]);
+        fixed[r] = m.x;
+        flags[r] = m.w;
+#pragma unroll
+        for (int f = 0; f < N_SUMS; ++f) psum[f][r] = 0.0;
+    }
+    score_tile_loop(a.Ap, a.theta, a.S, a.ldt, a.k, a.k_pad, pos.p0, pos.dt0, pos.dt1, As, Bs,
+                    [&](int64_t s0, const f64x4(&acc)[4]) {
+        const D d(a.ch, a.S, s0, cl, lik...);
+        double row[4];   // PHASE 0: v_s; PHASE 1: nu_s
+        tile_row(tc, PHASE, a.S, s0, cl, row);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            if (flags[r] & LF_BAD) continue;
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+                if (d.ok[t]) {
+                    const double x = d.ll(yv[r], acc[t][r], t);
+                    const uint64_t top = key_top(ord_key(x), fixed[r]);
+                    if ((flags[r] & LF_NOTAIL) || top > pre[r]) {
+                        const double w = exp(llmin[r] - x);
+                        const double res = yv[r] - acc[t][r];
+                        if constexpr (PHASE == 0) {
+                            psum[0][r] += w;
+                            psum[1][r] += w * res;
+                            psum[2][r] += w * (row[t] + res * res);
+                            psum[3][r] += w * w;
+                        } else {
+                            psum[0][r] += w * student_t_cdf_from(res < 0.0, (res * res) * d.hs[t], row[t],
+                                                                 fabs(res) * exp(x));
+                        }
+                    } else if (PHASE == 0 && (top < pre[r] || (flags[r] & LF_APPEND_EQ))) {
+                        const uint32_t slot = atomicAdd(count + pi[r], 1u);
+                        if (slot < cap) {
+                            cand[pi[r] * (int64_t)cap + slot] = x;
+                            candidx[pi[r] * (int64_t)cap + slot] = (uint32_t)(s0 + cl + 16 * t);
+                        }
+                    }
+                }
+        }
+    });
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int64_t o = (int64_t)pos.split * a.n_pad + pi[r];
+#pragma unroll
+        for (int f = 0; f < N_SUMS; ++f) {
+            const double u = lane_sum_ordered<16>(psum[f][r], cl);
+            if (cl != 0) continue;
+            if (PHASE == 1) pay[o * 4 + 2] = u;
+            else if (f == 0) body[o] = u;
+            else pay[o * 4 + (f == 3 ? 3 : f - 1)] = u;
+        }
+    }
+}
+
+// loo_bucket_kernel under the t likelihood: bucket[split][point][3] = sum r, sum (v_s + r^2),
+// sum F_nu(r / sigma) over the draws of a one-value bucket
+template <class D, class... L>
+__global__ __launch_bounds__(256) void loo_bucket_t_kernel(PassArgs a,
+                                                           const uint64_t* __restrict__ prefix,
+                                                           const uint4* __restrict__ meta,
+                                                           double* __restrict__ bucket,
+                                                           const double* __restrict__ tc, L... lik) {
+    __shared__ double As[SC_LDS_DOUBLES];
+    __shared__ double Bs[SC_LDS_DOUBLES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, cl = lane & 15, kq = lane >> 4;
+    const TilePos pos(a.point_tiles, a.tiles_per_split, a.draw_tiles);
+    double yv[4], sum[3][4];
+    uint64_t pre[4];
+    bool live[4];
+    int64_t pi[4];
+    int any = 0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        pi[r] = pos.p0 + 16 * wave + kq + 4 * r;
+        yv[r] = a.yp[pi[r]];
+        pre[r] = prefix[pi[r]];
+        live[r] = (meta[pi[r]].w & (LF_DONE | LF_APPEND_EQ | LF_NOTAIL | LF_BAD)) == LF_DONE;
+        any |= live[r];
+#pragma unroll
+        for (int f = 0; f < 3; ++f) sum[f][r] = 0.0;
+    }
+    if (!__syncthreads_or(any)) return;
+    score_tile_loop(a.Ap, a.theta, a.S, a.ldt, a.k, a.k_pad, pos.p0, pos.dt0, pos.dt1, As, Bs,
+                    [&](int64_t s0, const f64x4(&acc)[4]) {
+        const D d(a.ch, a.S, s0, cl, lik...);
+        double vs[4], nus[4];
+        tile_row(tc, 0, a.S, s0, cl, vs);
+        tile_row(tc, 1, a.S, s0, cl, nus);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            if (!live[r]) continue;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                if (!d.ok[t]) continue;
+                const double x = d.ll(yv[r], acc[t][r], t);
+                if (ord_key(x) == pre[r]) {
+                    const double res = yv[r] - acc[t][r];
+                    sum[0][r] += res;
+                    sum[1][r] += vs[t] + res * res;
+                    sum[2][r] += student_t_cdf_from(res < 0.0, (res * res) * d.hs[t], nus[t],
+                                                    fabs(res) * exp(x));
+                }
+            }
+        }
+    });
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int f = 0; f < 3; ++f) {
+            const double u = lane_sum_ordered<16>(sum[f][r], cl);
+            if (cl == 0 && live[r]) bucket[((int64_t)pos.split * a.n_pad + pi[r]) * 3 + f] = u;
+        }
+}
+
 // What the PREDICT fit reads besides the select state: the padded operands and per-draw constants
 // of the score kernels (a candidate's r and sigma are recomputed from its draw index), the
 // candidates' draw indices and the payload sums of loo_append_kernel<true> and loo_bucket_kernel.
@@ -440,13 +616,26 @@ __device__ __forceinline__ void predict_store(double* __restrict__ out, int64_t 
     out[5 * n + i] = W * (W / t[3]);
 }
 
+// What the fit under the t likelihood takes besides: tc of loo_t_consts_kernel and the call's sd_inf
+struct TFit {
+    const double* tc;
+    int32_t sd_inf;
+};
+__device__ __forceinline__ const double* fit_tc() { return nullptr; }
+__device__ __forceinline__ const double* fit_tc(const TFit& t) { return t.tc; }
+__device__ __forceinline__ bool fit_sd_inf() { return false; }
+__device__ __forceinline__ bool fit_sd_inf(const TFit& t) { return t.sd_inf != 0; }
+
 // One workgroup per point.  buf: `cap` doubles of LDS, cap >= 2 (M + 1): the sorted candidates in
 // buf[0 .. M] and, behind them, M doubles for the tail's x_j and then its smoothed lw.  mg: the
 // grid points of the fit (LooPlan::grid_points).
 // PREDICT: 16 bytes of LDS per slot: every sorted candidate stays in buf[0 .. cap), the tail's M
 // doubles are buf[cap .. cap + cap / 2), then the candidates' draw indices, sorted along as the
 // second key; out is [6][n]: elpd_loo_i, pareto_k, loo_mean, loo_sd, loo_pit, ess.
-template <bool PREDICT>
+// T...: nothing, or one TFit: the fit under the Student-t likelihood (STUDENT; with PREDICT), the
+// payload of a candidate from v_s and nu_s of tc and F_nu from the candidate's own ll.  Without it
+// the kernel has the arguments and the code of the untemplated one.
+template <bool PREDICT, class... T>
 __global__ __launch_bounds__(256) void loo_fit_kernel(const uint64_t* __restrict__ prefix,
                                                       const uint64_t* __restrict__ kmin,
                                                       const uint4* __restrict__ meta,
@@ -455,7 +644,12 @@ __global__ __launch_bounds__(256) void loo_fit_kernel(const uint64_t* __restrict
                                                       const double* __restrict__ body, int64_t n,
                                                       int64_t n_pad, int64_t splits, int64_t S,
                                                       int32_t M, int32_t mg, int32_t cap,
-                                                      double* __restrict__ out, FitPayload pa) {
+                                                      double* __restrict__ out, FitPayload pa,
+                                                      T... tfit) {
+    constexpr bool STUDENT = sizeof...(T) > 0;
+    const double* tc = fit_tc(tfit...);
+    const bool sd_inf = fit_sd_inf(tfit...);
+
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     double* buf = (double*)smem_raw;
     __shared__ double red[256];
@@ -483,6 +677,8 @@ __global__ __launch_bounds__(256) void loo_fit_kernel(const uint64_t* __restrict
             out[i] = (log((double)S) + llmin) - log(B);
             out[n + i] = inf;
             if constexpr (PREDICT) predict_store(out, n, i, pa.yp[i], B, tot);
+            if constexpr (STUDENT)
+                if (sd_inf) out[3 * n + i] = inf;
         }
         return;
     }
@@ -641,10 +837,16 @@ __global__ __launch_bounds__(256) void loo_fit_kernel(const uint64_t* __restrict
             const double* th = pa.theta + sd * pa.ldt;
             double dot = 0.0;
             for (int j = 0; j < pa.k; ++j) dot = fma(arow[j], th[j], dot);
-            const double res = yi - dot, h = pa.ch[S + sd];
+            const double res = yi - dot, h = pa.ch[S + sd];   // (STUDENT: h is g_s)
             part[0] += w * res;
-            part[1] += w * (1.0 / (2.0 * h) + res * res);
-            part[2] += w * draw_phi(res, sqrt(h));
+            if constexpr (STUDENT) {
+                part[1] += w * (tc[sd] + res * res);
+                part[2] += w * student_t_cdf_from(res < 0.0, (res * res) * h, tc[S + sd],
+                                                  fabs(res) * exp(buf[q]));
+            } else {
+                part[1] += w * (1.0 / (2.0 * h) + res * res);
+                part[2] += w * draw_phi(res, sqrt(h));
+            }
             part[3] += w * w;
         }
         for (int f = 0; f < 4; ++f) tot[f] += block_sum(part[f], red);
@@ -657,6 +859,8 @@ __global__ __launch_bounds__(256) void loo_fit_kernel(const uint64_t* __restrict
             tot[3] += (double)m.z * (wb * wb);
         }
         if (tid == 0) predict_store(out, n, i, yi, wsum, tot);
+        if constexpr (STUDENT)   // (some nu_s <= 2: the predictive variance is infinite)
+            if (tid == 0 && sd_inf) out[3 * n + i] = inf;
     }
 }
 
@@ -689,13 +893,14 @@ struct Work {
 // The PREDICT passes' own buffers, behind the ones every call has
 struct PredictWork {
     uint32_t* candidx;
-    double *pay, *bucket, *out;
+    double *pay, *bucket, *out, *tc;
     PredictWork(const Work& w, const LooPredictBuffers& b) {
         char* p = w.end;
         candidx = (uint32_t*)p;
         pay = (double*)(p += b.candidx);
         bucket = (double*)(p += b.pay);
         out = (double*)(p += b.bucket);
+        tc = (double*)(p += b.out);
     }
 };
 
@@ -720,8 +925,7 @@ hipError_t launch_loo_passes(const LooArgs& a, const LooPlan& p, const LooPredic
     const ScorePlan& sp = p.score;
     if (!p.ok || !a.work || sa.S - p.tail < 1 || p.cap < 2 * (p.tail + 1) || p.cap > LOO_MAX_CAP ||
         (p.cap & (p.cap - 1)) != 0 || p.tail != loo_tail(sa.S) || sa.n > 0x7fffffffll ||
-        p.grid_points != (p.tail > 0 ? psis_grid_points(p.tail) : 0) || p.grid_points > LOO_MAX_GRID ||
-        (pp && (sa.nu != 0.0 || sa.per_draw.n_nu != 0)))
+        p.grid_points != (p.tail > 0 ? psis_grid_points(p.tail) : 0) || p.grid_points > LOO_MAX_GRID)
         return hipErrorInvalidValue;   // (the fit's grid is one workgroup per point)
     hipError_t e = launch_score(sa, sp, s);   // (checks the shapes and the split plan)
     if (e != hipSuccess) return e;
@@ -754,6 +958,11 @@ hipError_t launch_loo_passes(const LooArgs& a, const LooPlan& p, const LooPredic
         else hipLaunchKernelGGL(gauss, dim3(groups), dim3(256), lds, s, pa, args...);
     };
 
+    auto pass_t = [&](auto student_t, auto student_tv, auto... args) {   // (the t-only kernels)
+        if (per_draw) hipLaunchKernelGGL(student_tv, dim3(groups), dim3(256), 0, s, pa, args...);
+        else hipLaunchKernelGGL(student_t, dim3(groups), dim3(256), 0, s, pa, args..., hn);
+    };
+
     if ((e = hipMemsetAsync(w.hist, 0, lb.hist, s)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(w.count, 0, lb.count, s)) != hipSuccess) return e;
     pass(loo_range_kernel<TileDraws>, loo_range_kernel<TileDrawsT, double>, loo_range_kernel<TileDrawsTV>, 0,
@@ -773,6 +982,44 @@ hipError_t launch_loo_passes(const LooArgs& a, const LooPlan& p, const LooPredic
             hipLaunchKernelGGL(loo_scan_kernel, dim3(pblocks), dim3(256), 0, s, n_pad, M, cap,
                                w.prefix, w.meta, w.hist);
         }
+    }
+    if (pp && (student || per_draw)) {
+        // the PREDICT passes under the t likelihood: both phases of the append, the bucket, the fit
+        const PredictWork pw(w, loo_predict_buffers(*pp, sa.n));
+        const NuPerDraw& v = sa.per_draw;
+        const int32_t sd_inf = a.t_sd_inf ? 1 : 0;
+        hipLaunchKernelGGL(loo_t_consts_kernel, dim3((unsigned)((sa.S + 255) / 256)), dim3(256), 0, s,
+                           sa.theta, sa.S, sa.ldt, sa.k, sa.nu, v.tab, v.n_nu, v.index, v.flag, sd_inf,
+                           pw.tc);
+        const double* tc = pw.tc;
+        pass_t(loo_append_t_kernel<0, TileDrawsT, double>, loo_append_t_kernel<0, TileDrawsTV>,
+             (const uint64_t*)w.prefix, (const uint64_t*)w.kmin, (const uint4*)w.meta, (uint32_t)cap,
+             w.count, w.cand, w.body, pw.candidx, pw.pay, tc);
+        pass_t(loo_append_t_kernel<1, TileDrawsT, double>, loo_append_t_kernel<1, TileDrawsTV>,
+             (const uint64_t*)w.prefix, (const uint64_t*)w.kmin, (const uint4*)w.meta, (uint32_t)cap,
+             w.count, w.cand, w.body, pw.candidx, pw.pay, tc);
+        if (pp->bucket_pass)
+            pass_t(loo_bucket_t_kernel<TileDrawsT, double>, loo_bucket_t_kernel<TileDrawsTV>,
+                 (const uint64_t*)w.prefix, (const uint4*)w.meta, pw.bucket, tc);
+        FitPayload fp;
+        fp.Ap = sa.Ap;
+        fp.yp = sa.yp;
+        fp.theta = sa.theta;
+        fp.ch = sa.ch;
+        fp.pay = pw.pay;
+        fp.bucket = pw.bucket;
+        fp.candidx = pw.candidx;
+        fp.ldt = sa.ldt;
+        fp.k = sa.k;
+        fp.k_pad = sp.k_pad;
+        e = hipFuncSetAttribute((const void*)loo_fit_kernel<true, TFit>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)pp->fit_lds);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL((loo_fit_kernel<true, TFit>), dim3((unsigned)sa.n), dim3(256), (size_t)pp->fit_lds, s,
+                           (const uint64_t*)w.prefix, (const uint64_t*)w.kmin, (const uint4*)w.meta,
+                           (const uint32_t*)w.count, (const double*)w.cand, (const double*)w.body, sa.n,
+                           n_pad, sp.splits, sa.S, M, p.grid_points, cap, pw.out, fp, TFit{tc, sd_inf});
+        return hipGetLastError();
     }
     if (pp) {
         const PredictWork pw(w, loo_predict_buffers(*pp, sa.n));
@@ -826,7 +1073,10 @@ hipError_t launch_loo(const LooArgs& a, const LooPlan& p, hipStream_t s) {
 }
 
 hipError_t launch_loo_predict(const LooArgs& a, const LooPredictPlan& p, hipStream_t s) {
-    if (!p.ok || p.loo.cap > LOO_PREDICT_MAX_CAP || p.fit_lds != p.loo.cap * LOO_PREDICT_SLOT_LDS)
+    const bool student = a.score.nu != 0.0 || a.score.per_draw.n_nu != 0;
+    if (!p.ok || p.loo.cap > LOO_PREDICT_MAX_CAP || p.fit_lds != p.loo.cap * LOO_PREDICT_SLOT_LDS ||
+        p.append_phases != (student ? LOO_PREDICT_T_PHASES : 1) ||
+        p.draw_rows != (student ? (int64_t)LOO_PREDICT_T_ROWS * a.score.S : 0))
         return hipErrorInvalidValue;
     return launch_loo_passes(a, p.loo, &p, s);
 }

@@ -71,7 +71,25 @@ every output is a function of the draws' values alone.  With ``w_s = W_s / sum_t
   leave-one-out predictive probability of a value at or below the observed one;
 * ``ess_i      = 1 / sum_s w_s^2``, the PSIS effective sample size with r_eff = 1 (1 .. S);
 
-a point with a non-finite ``ll`` gets NaN in each.  On the host ``loo_rmse =
+a point with a non-finite ``ll`` gets NaN in each.  Under the Student-t likelihood (``nu=`` or
+``nu_draws=``; ``nu_s = nu`` for a fixed one) the weights, the tie sharing, ``ess``, the NaN rules
+and the draw limit are these, ``ll`` is the marginal t density above, ``elpd_loo_i``, ``pareto_k``
+and ``lppd`` are bit-equal to ``psis_loo`` under the same likelihood arguments, and with
+``z_s = r_s / sigma_s``:
+
+* ``loo_mean_i = y_i - sum_s w_s r_s``: the location of the predictive distribution, which is its
+  mean where ``nu > 1`` (a t distribution with ``nu <= 1`` has none);
+* ``loo_sd_i   = sqrt(sum_s w_s (sigma_s^2 nu_s / (nu_s - 2) + r_s^2) - (sum_s w_s r_s)^2)`` when
+  every scored ``nu_s > 2``; ``+inf`` at every point with finite ``ll`` when any scored value
+  (``nu``, or any distinct value of the kept ``nu_draws``) is at most 2 -- decided on the host, so
+  the device never sums an infinity (a far draw's weight underflows to 0, and ``0 inf`` is NaN);
+* ``loo_pit_i  = sum_s w_s F_{nu_s}(z_s)``, ``F_nu`` the Student-t distribution function
+  (``student_t_cdf`` of ``bmc_math.h``: the incomplete beta function's continued fraction with the
+  density as its prefactor; within 64 times the error of ``scipy.special.stdtr`` for
+  ``0.06 <= nu <= 1000``, the range the call accepts);
+
+two more passes over the matrix than ``psis_loo`` (the append runs in two phases: the t density
+and distribution function do not fit the registers of one).  On the host ``loo_rmse =
 sqrt(mean_i (y_i - loo_mean_i)^2)``, ``pit_coverage[j]`` = the percentage of points with
 ``|2 loo_pit_i - 1| <= p_j / 100`` for ``p = 0, 5, .., 100`` (the levels and units of
 ``BayesianModelCombination.evaluate``) and ``min_ess``.  At most 1 863 225 pooled draws.
@@ -388,13 +406,32 @@ def loo_predict_summary(y, loo_mean, loo_pit, ess):
             "min_ess": float(np.min(np.asarray(ess, dtype=np.float64)))}
 
 
-def psis_loo_predict(A, y, samples, burn=0, thin=1, device=0):
+LOO_PREDICT_NU_RANGE = (0.06, 1000.0)
+
+
+def _check_predict_nu(values):
+    """The degrees of freedom the leave-one-out predictive distribution takes: the range over which
+    the device's t distribution function is held to its accuracy bar (no GPU needed)."""
+    lo, hi = LOO_PREDICT_NU_RANGE
+    v = np.asarray(values, dtype=np.float64)
+    if not np.all((v >= lo) & (v <= hi)):
+        raise ValueError(f"psis_loo_predict takes degrees of freedom between {lo} and {hi:g}; got "
+                         f"{float(v.min()):g} .. {float(v.max()):g}")
+
+
+def psis_loo_predict(A, y, samples, burn=0, thin=1, device=0, nu=None, nu_draws=None):
     """PSIS-LOO with the leave-one-out predictive distribution of every training point (module
     docstring): everything ``psis_loo`` returns, the pointwise ``loo_mean``, ``loo_sd``,
     ``loo_pit``, ``ess`` and ``loo_rmse``, ``pit_coverage``, ``min_ess``.  Arguments as
-    ``pointwise_log_likelihood``; ``loo_mean`` is in the space of ``A`` and ``y``."""
-    pw = _pointwise_call("psis_loo_predict", "psis_loo_predict_device", A, y, samples, burn, thin,
-                         device)
+    ``pointwise_log_likelihood``, ``nu`` and ``nu_draws`` included; ``loo_mean`` is in the space of
+    ``A`` and ``y``.  Under the Student-t likelihood ``loo_mean`` is the location of the predictive
+    distribution (its mean where ``nu > 1``), ``loo_sd`` is ``+inf`` at every point that is not NaN
+    when a scored ``nu`` is at most 2, and every ``nu`` must lie in 0.06 .. 1000 (``ValueError``)."""
+    host, dev, scalars, held = _likelihood_call("psis_loo_predict", nu, nu_draws, samples, burn, thin)
+    if scalars:
+        _check_predict_nu(scalars[0])
+    pw = _pointwise_call(host, dev, A, y, samples, burn, thin, device, scalars=scalars)
+    del held
     sh = tuple(samples.shape)
     C, T = (1, sh[0]) if len(sh) == 2 else sh[:2]
     out = loo_summary(pw["elpd_loo"], pw["lppd"], pw["pareto_k"], C * kept_draws(T, burn, thin))
